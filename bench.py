@@ -240,7 +240,13 @@ def parse():
     ap.add_argument('--preflight-seconds', type=float, default=45.0, help='N>1: deadline for a candidate layout to create its groups and run its first two steps on every rank')
     ap.add_argument('--no-layout-fallback', action='store_true', help='N>1: fail instead of trying the next layout / independent replicas')
     ap.add_argument('--no-dedup', action='store_true', help='sharded path: exchange one row per occurrence instead of one per distinct item')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='c5, N=1: write what the last timed step computed (each domain step\'s loss vector, the updated table rows of a fixed '
+                         'seeded sample of its batch, a fixed seeded sample of rows of every table) as DIR/<name>.npy, at most 64 MB in all')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def dist_setup(args):
@@ -315,6 +321,42 @@ def xavier_table(rows, D, total_rows, gen, dev):
     t = torch.empty(rows, D, device=dev, dtype=torch.float32)
     t.normal_(0.0, std, generator=gen)
     return t
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 4242
+
+
+def dump_last_step(out_dir, steps, tabs, last, D, B):
+    """--dump-outputs: what the timed path handed its caller in its LAST step, as DIR/<name>.npy.  Per domain: the step's return
+    value (out6: loss, its parts and sums), and the updated user / positive / negative table rows of a fixed seeded sample of that
+    step's triples (with the sampled ids as float64); per table: a fixed seeded sample of rows (ids as float64).  The tables are far
+    larger than the dump may be, so rows are sampled; the sample depends on the arguments only, so two builds compare file by file."""
+    import numpy as np
+    row_b = 4 * D
+    S = max(1, min(B, 8192, (24 << 20) // (6 * row_b)))           # sampled triples of the last batch, per domain
+    R = max(1, min(4096, (8 << 20) // (4 * row_b)))               # uniformly sampled rows, per table
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+    out = {}
+    for dom, (ut, it) in (('source', ('su', 'si')), ('target', ('tu', 'ti'))):
+        u, p, n = last[dom]
+        pick = torch.randperm(u.numel(), generator=gen)[:S].sort().values.to(u.device)
+        ids = [x.index_select(0, pick) for x in (u, p, n)]
+        out[dom + '_step_out'] = steps[dom].out6.detach().cpu().numpy().astype(np.float32)
+        out[dom + '_batch_ids'] = torch.stack(ids, 1).cpu().numpy().astype(np.float64)
+        for what, tab, idx in (('user', ut, ids[0]), ('pos', it, ids[1]), ('neg', it, ids[2])):
+            out['%s_%s_rows' % (dom, what)] = tabs[tab].index_select(0, idx).cpu().numpy().astype(np.float32)
+    for name in ('su', 'si', 'tu', 'ti'):
+        rows = torch.randint(0, tabs[name].shape[0], (R,), generator=gen)
+        out[name + '_sample_ids'] = rows.numpy().astype(np.float64)
+        out[name + '_sample_rows'] = tabs[name].index_select(0, rows.to(tabs[name].device)).cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {'dir': os.path.abspath(out_dir), 'files': len(out), 'bytes': total, 'sampled_triples_per_domain': S, 'sampled_rows_per_table': R,
+            'seed': DUMP_SEED}
 
 
 # ------------------------------------------------------------------------------------------------------ C5 workload
@@ -475,6 +517,9 @@ def run_c5(args, world, rank, dev):
         one_step(i)
     barrier(world)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        # before anything else runs a step on these tables (the single-stream repeat below, the other legs)
+        dumped = dump_last_step(args.dump_outputs, steps, tabs, batches[(args.steps - 1) % pool], D, B)
     single = None
     if two_streams:
         for i in range(2):
@@ -528,6 +573,8 @@ def run_c5(args, world, rank, dev):
                    'row %% %d, user-aligned all-to-all%s, 2-domain pipelined' % (world, '' if args.no_dedup else ' of de-duplicated item rows')},
         'final_loss': loss,
     }
+    if args.dump_outputs:
+        result['dumped_outputs'] = dumped
     if world == 1 and not sharded:
         # the trained tables as exact fp64 sums (after the timed region and its single-stream repeat, before any other leg trains on them):
         # two invocations with the same flags must print the same digits
@@ -2029,6 +2076,8 @@ def main():
         real_stdout = os.dup(1)
         os.dup2(2, 1)
     world, rank, local = dist_setup(args)
+    if args.dump_outputs and (args.workload != 'c5' or world > 1 or args.force_shard or args.only_e2e or args.only_ingest):
+        raise SystemExit('bench: --dump-outputs covers the one-GPU C5 step (--workload c5, --gpus 1, no --force-shard / --only-*)')
     dev = torch.device('cuda', local)
     import recbole_cdr_amd  # noqa: F401  (raises loudly if libcdrhip.so is missing)
     if args.only_e2e:

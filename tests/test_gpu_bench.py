@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,3 +35,34 @@ def test_bench_subprocess_last_stdout_line_is_the_contract_line(tmp_path):
     assert full['value'] == d['value'] and 'kernels' in full and 'e2e' in full
     bad = [l for l in p.stderr.splitlines() if 'Warning' in l or 'Traceback' in l]
     assert not bad, bad[:5]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_bounded_and_repeatable(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float32 / float64 .npy files of at most 64 MB in all, and two runs with the
+    same arguments write the same numbers (the inputs are seeded, the C5 step is deterministic), so two builds compare file by file."""
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--users', '2000001',
+           '--items-per-domain', '1000000', '--batch', '65536', '--no-config-legs', '--no-e2e', '--no-ingest', '--no-fullsort', '--no-map',
+           '--no-cpu-baseline', '--detail-file', str(tmp_path / 'detail.json')]
+    dumps = []
+    for run in ('a', 'b'):
+        out = tmp_path / run
+        p = subprocess.run(cmd + ['--dump-outputs', str(out)], capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+        assert p.returncode == 0, p.stderr[-3000:]
+        d = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+        assert d['steps'] == 3 and d['ms_per_step'] > 0
+        files = sorted(os.listdir(out))
+        assert files and all(f.endswith('.npy') for f in files)
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        arrays = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        dumps.append(arrays)
+    a, b = dumps
+    assert sorted(a) == sorted(b)
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
+    for dom in ('source', 'target'):
+        out6 = a[dom + '_step_out.npy']
+        assert np.isfinite(out6).all() and out6[0] > 0                                   # the last step's total loss
+        ids = a[dom + '_batch_ids.npy']
+        assert ids.shape[1] == 3 and a[dom + '_user_rows.npy'].shape == (ids.shape[0], 128)
