@@ -18,31 +18,14 @@ touched row -- and their moments are compared bit for bit."""
 import pytest
 import torch
 
+from fp64_bounds import U32, apply_fp64, gam
 from helpers import DEV
 
 pytestmark = pytest.mark.gpu
 
-U32 = 2.0 ** -24            # unit roundoff of fp32
 K_COEF = 8                  # ulps of the per-occurrence loss coefficient beyond its score error
-K_SUM = 8                   # the "small constant" of k = D + occurrences + K_SUM (product, subtraction p - n, reg / wd terms)
-K_ADAM = 12                 # ulps of the Adam update term (see the module docstring)
 LOSS_RTOL = 1e-5
 GAMMA = 1e-10               # BPRLoss gamma (recbole): -log(gamma + sigmoid(pos - neg))
-
-
-def gam(k):
-    return k * U32 / (1.0 - k * U32)
-
-
-def f32(x):
-    """A hyper-parameter as the kernel receives it (a float launch argument)."""
-    return float(torch.tensor(x, dtype=torch.float32))
-
-
-def ulp32(x):
-    """One ulp of the fp32 value nearest to x (fp64 tensor), elementwise."""
-    a = x.abs().float()
-    return (torch.nextafter(a, torch.full_like(a, float('inf'))) - a).double()
 
 
 def _occ_sums(n_rows, inv, terms, absum, cerr):
@@ -50,12 +33,6 @@ def _occ_sums(n_rows, inv, terms, absum, cerr):
     A, E = torch.zeros_like(G), torch.zeros_like(G)
     G.index_add_(0, inv, terms); A.index_add_(0, inv, absum); E.index_add_(0, inv, cerr)
     return G, A, E, torch.bincount(inv, minlength=n_rows)
-
-
-def _grad_bound(D, G, A, E, occ):
-    k = (D + occ + K_SUM).double().unsqueeze(1)
-    gk = k * U32 / (1.0 - k * U32)
-    return gk * A + (1.0 + gk) * E
 
 
 # ---------------------------------------------------------------------------------------------------------------------- fp64 reference
@@ -121,37 +98,6 @@ def point_grads_fp64(U, I, uid, iid, label, reg, kind):
     ut = (g1 * i + cu * u, g1.abs() * ia + cu * ua, d1 * ia + gc * cu * ua)
     it = (g1 * u + ci * i, g1.abs() * ua + ci * ia, d1 * ua + gc * ci * ia)
     return float(loss), (ru, *_occ_sums(ru.numel(), inv_u, *ut)), (ri, *_occ_sums(ri.numel(), inv_i, *it))
-
-
-def apply_fp64(state, part, D, opt, lr, wd, t, b1=0.9, b2=0.999, eps=1e-8):
-    """The optimizer on the part's rows in float64 from the device state BEFORE the step; returns {name: (ref, bound)} for the
-    rows' weights (and moments)."""
-    rows, G, A, E, occ = part
-    lr, wd, b1, b2, eps = f32(lr), f32(wd), f32(b1), f32(b2), f32(eps)
-    w = state['w'][rows].double()
-    if wd:
-        G = G + wd * w
-        A = A + wd * w.abs()
-    eg = _grad_bound(D, G, A, E, occ)
-    if opt == 'sgd':
-        wn = w - lr * G
-        return {'w': (wn, lr * eg + 2 * U32 * lr * G.abs() + ulp32(wn))}
-    m0, v0 = state['m'][rows].double(), state['v'][rows].double()
-    m = m0 + (G - m0) * (1 - b1)
-    v = b2 * v0 + (1 - b2) * G * G
-    em = (1 - b1) * eg + 3 * U32 * (m0.abs() + G.abs() + m.abs()) + ulp32(m)
-    ev = (1 - b2) * (2 * G.abs() * eg + eg * eg) + 4 * U32 * (b2 * v0 + (1 - b2) * G * G) + ulp32(v)
-    step_size = lr / (1 - b1 ** t)
-    c2 = 1.0 / (1 - b2 ** t) ** 0.5
-    den = v.sqrt() * c2 + eps
-    T = step_size * m / den
-    den_lo = (v - ev).clamp(min=0).sqrt() * c2 + eps
-    den_hi = (v + ev).sqrt() * c2 + eps
-    hi = step_size * torch.maximum((m + em) / den_lo, (m + em) / den_hi)
-    lo = step_size * torch.minimum((m - em) / den_lo, (m - em) / den_hi)
-    eT = torch.maximum(hi - T, T - lo) + K_ADAM * U32 * torch.maximum(hi.abs(), lo.abs())
-    wn = w - T
-    return {'w': (wn, eT + ulp32(wn)), 'm': (m, em), 'v': (v, ev)}
 
 
 # ---------------------------------------------------------------------------------------------------------------------- checks

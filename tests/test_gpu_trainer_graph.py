@@ -497,6 +497,9 @@ def test_full_c5_size_adam_instantiations(kind):
       * a real first Adam step equals -lr g / (|g| + eps) element by element (g from that SGD run), and twice from the same start is
         bit-identical in weights, both moments and the loss."""
     from recbole_cdr_amd.fused import FusedBPRStep, KMajorBPRStep, RowwiseState, OPT_ADAM
+    # the previous parametrisation leaves ~137 GB in torch's caching allocator: hand it back before measuring, or the check counts this
+    # process's own reusable cache as taken (it passed by 0.8 GB, and skipped as soon as earlier modules left a little more behind)
+    torch.cuda.empty_cache()
     free_b, _ = torch.cuda.mem_get_info()
     if free_b < 170e9:
         pytest.skip('needs ~150 GB of free HBM')
