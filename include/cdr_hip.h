@@ -55,7 +55,7 @@ int cdr_ctx_scrub_next(cdr_ctx* ctx, void* ptr, size_t bytes);
 int cdr_ctx_set_id_counters(cdr_ctx* ctx, uint32_t* user_counts, int64_t user_rows, uint32_t* item_counts, int64_t item_rows,
                             void* list_ws, size_t list_ws_bytes);
 int cdr_id_count_workspace_bytes(int64_t B, size_t* bytes);
-#define CDR_ABI_VERSION 59
+#define CDR_ABI_VERSION 60
 int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the header the library was built from; bumped on any signature change */
 
 /* Optional measurement aid: HIP-event brackets around the hot kernels, recorded on the stream each kernel is launched
@@ -412,6 +412,22 @@ int cdr_lazy_adam_apply(void* stream, int count, int D, float* const* W, float* 
                         int64_t hp_capacity, int64_t* counters);
 int cdr_lazy_adam_flush(void* stream, int D, float* W, float* M, float* V, int32_t* last, int64_t rows, float lr, float beta1,
                         float beta2, float eps, float weight_decay, const void* hp_table, int64_t hp_capacity, const int64_t* counters);
+/* ---- the reference's Adam on the fused row-wise steps (recbole_cdr/properties/overall.yaml:20-21 `learner: adam`, one torch.optim.Adam
+ * over every parameter for the whole schedule, driven by recbole_cdr/trainer/trainer.py:59-73): a row without a gradient in an update still
+ * moves (its momentum decays).  ONE launch in front of a fused step (cdr_bpr_step_fused*, cdr_point_step_fused*, cdr_bpr_step_small,
+ * cdr_map_step_unique, the row-wise applies) makes that step's lazy update exact, per table:
+ *   W, M, V [rows[i], D[i]] (D % 4 == 0, D <= 256), last[i] (int32 [rows], zero-initialised: the update the row reflects),
+ *   hp_table[i] (float2 [hp_capacity], a ring indexed by update & (hp_capacity - 1)), counters[i][0] = updates completed (the step's
+ *   own device count), ids0[i] [n0[i]] and ids1[i] [n1[i]] = the rows the step updates (int64, unsorted, any length, repeats allowed).
+ * With t = counters[i][0] + 1: writes hp[t]; every row of the lists replays its postponed gradient-free updates up to t - 1 and gets
+ * last = t (the step applies update t to it); a window of rows / sweep_period rows of each table (it moves on by its length per update) is
+ * brought to t - 1 (last = t - 1).  sweep_period: 0 = no window (the caller then flushes every table, cdr_lazy_adam_flush with its counters,
+ * at least every hp_capacity / 2 of its updates), else 2 .. hp_capacity / 2.  Reads the counts on the device: capturable.  Every row up to
+ * the count afterwards: cdr_lazy_adam_flush(D[i], W[i], ..., counters[i]). */
+int cdr_rowwise_adam_catch_up(void* stream, int count, const int* D, float* const* W, float* const* M, float* const* V,
+                              int32_t* const* last, const int64_t* rows, void* const* hp_table, int64_t hp_capacity,
+                              const int64_t* const* counters, const int64_t* const* ids0, const int64_t* n0, const int64_t* const* ids1,
+                              const int64_t* n1, float lr, float beta1, float beta2, float eps, float weight_decay, int sweep_period);
 
 /* ---- CoNet towers fused (conet.py:105-203: source_forward + target_forward + BCELoss x2 + reg) -------------------------
  * One stack of R rows -- rows [0, n_source) are the source batch (user_s, item_s, label_s), the rest the target batch (the two

@@ -670,3 +670,153 @@ extern "C" int cdr_lazy_adam_flush(void* stream, int D, float* W, float* M, floa
     CDR_LAUNCH_CHECK();
     return CDR_OK;
 }
+
+namespace {
+
+// ---- per-table catch-up in front of a fused row-wise step (EMCDR, optimizer_mode='rowwise' with rowwise_adam='exact') -----------------
+// The fused steps of cdr_step.hip / cdr_kstep.hip / cdr_mapstep.hip update the rows they gather at update t = count + 1 and leave every
+// other row alone: a lazy Adam.  The reference's Adam moves every row of a table that takes part in the step (the momentum of a row
+// without gradient decays and the weight follows it).  This launch, placed in front of such a step, makes the pair exact: for each of
+// up to four tables -- each with its own update count (count[0] = updates completed: RowwiseState.step_dev), row width, `last` and ring of
+// per-update scalars, so tables that advance in different phases keep their own numbering --
+//   * hp[t] is written (cdr_adam_hp: the expression every dense kernel evaluates),
+//   * every distinct row of the batch's id lists (one or two per table, unsorted, any length) is claimed by atomicMax(last[row], t): the
+//     occurrence that finds last < t - 1 replays updates last+1 .. t-1 in registers; the row is then at t - 1 and last[row] = t, which is
+//     what the step's update t makes true -- the step kernels need no change,
+//   * a moving window of rows / sweep_period rows of each table (the window moves by its length per update) is claimed by
+//     atomicMax(last[row], t - 1) and brought to t - 1: no row is ever more than ~sweep_period updates behind, so the ring never wraps
+//     onto an entry a row still needs.
+// atomicMax for both claims: the value only grows, so whichever claimant comes first, exactly one finds last < t - 1 and replays, and a
+// window claim behind a batch claim cannot pull last[row] back from t to t - 1.  Everything is read on the device (capturable).
+struct ra_table { float* W; float* M; float* V; int32_t* last; float2* hp; const int64_t* count; int64_t rows, chunk; int D; };
+struct ra_seg { const int64_t* ids; int64_t n; unsigned b0, nb; int tab, lanes; };     // ids == nullptr: the table's window
+struct ra_args { ra_table t[kMaxTab]; ra_seg s[3 * kMaxTab]; int ntab, nseg, period; float lr, b1, b2, eps, wd; int64_t hp_mask; };
+
+// updates (from, to] of four elements without gradient: the arithmetic of lz_prepare2_kernel (pairs through lz_elem2_nograd; with weight
+// decay cdr_adam_elem with g = 0), the ring scalars read eight updates at a time
+__device__ __forceinline__ void ra_replay(float4& w, float4& m, float4& v, int64_t from, int64_t to, const float2* __restrict__ hp,
+                                          const ra_args& a) {
+    if (a.wd == 0.f) {
+        // (zero moments without weight decay: a fixed point, as in replay(); a pair with zero moments replays to itself bit for bit)
+        if (m.x == 0.f && m.y == 0.f && m.z == 0.f && m.w == 0.f && v.x == 0.f && v.y == 0.f && v.z == 0.f && v.w == 0.f) return;
+        lz_f2 w0 = {w.x, w.y}, w1 = {w.z, w.w}, m0 = {m.x, m.y}, m1 = {m.z, m.w}, v0 = {v.x, v.y}, v1 = {v.z, v.w};
+        constexpr int CH = 8;
+        int64_t tau = from + 1;
+        for (; tau + CH - 1 <= to; tau += CH) {
+            float2 h[CH];
+#pragma unroll
+            for (int j = 0; j < CH; ++j) h[j] = hp[(tau + j) & a.hp_mask];
+#pragma unroll
+            for (int j = 0; j < CH; ++j) {
+                w0 = lz_elem2_nograd(w0, m0, v0, a.b1, a.b2, a.eps, h[j].x, h[j].y);
+                w1 = lz_elem2_nograd(w1, m1, v1, a.b1, a.b2, a.eps, h[j].x, h[j].y);
+            }
+        }
+        for (; tau <= to; ++tau) {
+            const float2 h = hp[tau & a.hp_mask];
+            w0 = lz_elem2_nograd(w0, m0, v0, a.b1, a.b2, a.eps, h.x, h.y);
+            w1 = lz_elem2_nograd(w1, m1, v1, a.b1, a.b2, a.eps, h.x, h.y);
+        }
+        w = make_float4(w0.x, w0.y, w1.x, w1.y); m = make_float4(m0.x, m0.y, m1.x, m1.y); v = make_float4(v0.x, v0.y, v1.x, v1.y);
+        return;
+    }
+    for (int64_t tau = from + 1; tau <= to; ++tau) {
+        const float2 h = hp[tau & a.hp_mask];
+        w.x = cdr_adam_elem(w.x, 0.f, m.x, v.x, a.b1, a.b2, a.eps, a.wd, h.x, h.y);
+        w.y = cdr_adam_elem(w.y, 0.f, m.y, v.y, a.b1, a.b2, a.eps, a.wd, h.x, h.y);
+        w.z = cdr_adam_elem(w.z, 0.f, m.z, v.z, a.b1, a.b2, a.eps, a.wd, h.x, h.y);
+        w.w = cdr_adam_elem(w.w, 0.f, m.w, v.w, a.b1, a.b2, a.eps, a.wd, h.x, h.y);
+    }
+}
+
+// 1-D grid: workgroup b serves segment s with s.b0 <= b < s.b0 + s.nb (a table's window, or one id list of a table).  A row is one lane
+// group of `lanes` (a power of two >= D / 4, <= 64: always inside one wave) holding a float4 per lane; the group's first lane claims it
+// and hands the old update number to the others by a shuffle -- no barrier, no LDS.
+__global__ __launch_bounds__(kBlock) void ra_catch_up_kernel(ra_args a) {
+    if (blockIdx.x == 0 && threadIdx.x < (unsigned)a.ntab) {
+        const ra_table& tb = a.t[threadIdx.x];
+        const int64_t t = tb.count[0] + 1;
+        float ss, bc;
+        cdr_adam_hp((double)t, a.lr, a.b1, a.b2, ss, bc);               // read by later launches only (this one replays up to t - 1)
+        tb.hp[t & a.hp_mask] = make_float2(ss, bc);
+    }
+    int si = 0;
+    for (int i = 1; i < a.nseg; ++i) if (blockIdx.x >= a.s[i].b0) si = i;
+    const ra_seg sg = a.s[si];
+    const ra_table tb = a.t[sg.tab];
+    const int64_t t = tb.count[0] + 1, to = t - 1;
+    const bool window = sg.ids == nullptr;
+    const int claim = (int)(window ? to : t);
+    int64_t first = 0, n = sg.n;
+    if (window) {
+        first = (to % a.period) * tb.chunk;
+        n = tb.rows - first < tb.chunk ? tb.rows - first : tb.chunk;
+    }
+    const int L = sg.lanes, gpb = kBlock / L;
+    const int sub = threadIdx.x % L, grp = threadIdx.x / L;
+    const int gbase = (int)(threadIdx.x & 63) / L * L;                  // the group's first lane inside its wave
+    const int D4 = tb.D >> 2;
+    for (int64_t base = (int64_t)(blockIdx.x - sg.b0) * gpb; base < n; base += (int64_t)sg.nb * gpb) {   // block-uniform
+        const int64_t q = base + grp;
+        int64_t row = -1;
+        if (q < n) row = window ? first + q : sg.ids[q];
+        const bool ok = row >= 0 && row < tb.rows;                      // (an id outside the table is no row of it)
+        int old = claim;
+        if (ok && sub == 0) old = atomicMax(&tb.last[row], claim);
+        const int64_t from = __shfl(old, gbase);
+        if (ok && from < to && sub < D4) {
+            const int64_t o = row * tb.D + 4 * sub;
+            float4 w = ld4(tb.W + o), m = ld4(tb.M + o), v = ld4(tb.V + o);
+            ra_replay(w, m, v, from, to, tb.hp, a);
+            st4(tb.W + o, w); st4(tb.M + o, m); st4(tb.V + o, v);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int cdr_rowwise_adam_catch_up(void* stream, int count, const int* D, float* const* W, float* const* M, float* const* V,
+                                         int32_t* const* last, const int64_t* rows, void* const* hp_table, int64_t hp_capacity,
+                                         const int64_t* const* counters, const int64_t* const* ids0, const int64_t* n0,
+                                         const int64_t* const* ids1, const int64_t* n1, float lr, float beta1, float beta2, float eps,
+                                         float weight_decay, int sweep_period) {
+    CDR_CHECK_ARG(count >= 1 && count <= kMaxTab && D && W && M && V && last && rows && hp_table && counters && n0 && n1);
+    CDR_CHECK_ARG(hp_capacity >= 2 && (hp_capacity & (hp_capacity - 1)) == 0);
+    CDR_CHECK_ARG(sweep_period == 0 || (sweep_period >= 2 && sweep_period <= hp_capacity / 2));
+    ra_args a{};
+    a.ntab = count; a.period = sweep_period > 0 ? sweep_period : 1;
+    a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.hp_mask = hp_capacity - 1;
+    const int64_t cap = CDR_NUM_CU * 16;
+    unsigned blocks = 0;
+    auto add_seg = [&](int tab, const int64_t* ids, int64_t n) {
+        ra_seg& s = a.s[a.nseg++];
+        int lanes = 1;
+        while (lanes < (a.t[tab].D >> 2)) lanes *= 2;
+        int64_t nb = (n + kBlock / lanes - 1) / (kBlock / lanes);
+        nb = nb < 1 ? 1 : nb > cap ? cap : nb;
+        s.ids = ids; s.n = n; s.tab = tab; s.lanes = lanes; s.b0 = blocks; s.nb = (unsigned)nb;
+        blocks += s.nb;
+    };
+    for (int i = 0; i < count; ++i) {
+        if (D[i] <= 0 || D[i] > 256 || (D[i] & 3) || !W[i] || !M[i] || !V[i] || !last[i] || rows[i] <= 0 || !hp_table[i] || !counters[i]
+            || n0[i] < 0 || n1[i] < 0 || (n0[i] > 0 && !(ids0 && ids0[i])) || (n1[i] > 0 && !(ids1 && ids1[i]))) {
+            cdr_set_error("cdr_rowwise_adam_catch_up: bad table description (D % 4 == 0, 0 < D <= 256, every pointer set, rows > 0)");
+            return CDR_EINVAL;
+        }
+        if (rows[i] > INT32_MAX) { cdr_set_error("cdr_rowwise_adam_catch_up: more than 2^31 - 1 rows"); return CDR_EINVAL; }
+        ra_table& tb = a.t[i];
+        tb.W = W[i]; tb.M = M[i]; tb.V = V[i]; tb.last = last[i]; tb.hp = (float2*)hp_table[i]; tb.count = counters[i];
+        tb.rows = rows[i]; tb.D = D[i];
+        tb.chunk = sweep_period > 0 ? (rows[i] + sweep_period - 1) / sweep_period : 0;
+    }
+    // the windows first (they start first: every row of them is ~sweep_period updates behind), then the batch's lists
+    for (int i = 0; i < count; ++i) if (sweep_period > 0) add_seg(i, nullptr, a.t[i].chunk);
+    for (int i = 0; i < count; ++i) {
+        if (n0[i] > 0) add_seg(i, ids0[i], n0[i]);
+        if (n1[i] > 0) add_seg(i, ids1[i], n1[i]);
+    }
+    if (a.nseg == 0) add_seg(0, nullptr, 0);                            // nothing to claim (no window, empty lists): hp[t] is still written
+    ra_catch_up_kernel<<<dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream>>>(a);
+    CDR_LAUNCH_CHECK();
+    return CDR_OK;
+}

@@ -19,16 +19,32 @@ OPT_SGD, OPT_ADAM = 0, 1
 class RowwiseState:
     """Per-table optimizer state for the row-wise Adam (SGD needs no moments).  ``step`` counts the updates this TABLE
     has received -- like torch.optim.Adam's per-parameter ``state['step']`` -- so one state object can be shared by the
-    step objects of several phases (SOURCE / TARGET BPR steps and the OVERLAP map step touch the same user tables)."""
+    step objects of several phases (SOURCE / TARGET BPR steps and the OVERLAP map step touch the same user tables).
+
+    ``exact=True``: the reference's dense Adam instead of the lazy one (``rowwise_catch_up`` in front of every step on the table).
+    The state then also holds ``last`` (int32 [rows]: the update each row reflects) and its own ring of per-update scalars, so that
+    tables stepped on different streams (parallel domains) share nothing mutable; ``flush()`` brings every row to ``step``."""
     _step = 0                 # class-level defaults: objects built with __new__ (layout transposes in dimshard.py) start consistent
     _step_dev = None
+    exact = False
 
-    def __init__(self, table, opt):
+    HP_CAPACITY = 1 << 12     # ring entries: with the moving window (period <= capacity / 2) no row falls a ring behind
+
+    def __init__(self, table, opt, exact=False):
         self.table = table
         self._step = 0
         self.exp_avg = torch.zeros_like(table) if opt == OPT_ADAM else None
         self.exp_avg_sq = torch.zeros_like(table) if opt == OPT_ADAM else None
         self._step_dev = None
+        self.exact = bool(exact)
+        if self.exact:
+            if opt != OPT_ADAM:
+                raise ValueError('RowwiseState(exact=True) is the dense Adam: it needs opt=adam')
+            self.last = torch.zeros(table.shape[0], device=table.device, dtype=torch.int32)
+            self.hp = torch.zeros(self.HP_CAPACITY, 2, device=table.device, dtype=torch.float32)
+            self.hparams = None       # (lr, beta1, beta2, eps, weight_decay) of the catch-ups: the flush replays with the same
+            self._flushed_at = 0
+            self.sweep_period = rowwise_sweep_period()     # fixed for the table's life: the lag bound rests on it
 
     @property
     def step(self):
@@ -52,6 +68,76 @@ class RowwiseState:
         self._step += 1
         if self._step_dev is not None and not device_bumped:
             B_.call('cdr_inc_i64', B_.stream(), B_.i64(self._step_dev))
+
+    @torch.no_grad()
+    def flush(self):
+        """Exact mode: every row of the table up to ``step`` -- what the dense sweep would have left in memory (evaluation, checkpoint).
+        Reads the device count (``step_dev``), as the catch-ups do."""
+        if not self.exact or self.hparams is None:
+            return
+        lr, b1, b2, eps, wd = self.hparams
+        B_.call('cdr_lazy_adam_flush', B_.stream(), self.table.shape[1], B_.f32(self.table), B_.f32(self.exp_avg), B_.f32(self.exp_avg_sq),
+                B_.raw(self.last), self.table.shape[0], lr, b1, b2, eps, wd, B_.raw(self.hp), self.HP_CAPACITY, B_.i64(self.step_dev))
+        self._flushed_at = self._step
+
+    def restored(self):
+        """Exact mode, after the table, moments and ``step`` were loaded: every row is current at ``step``."""
+        if self.exact:
+            self.last.fill_(self._step)
+            self._flushed_at = self._step
+
+
+def rowwise_sweep_period():
+    """Updates after which the catch-up's moving window has visited every row of a table: 256, at most half the ring.
+    CDR_ROWWISE_SWEEP=0 switches the window off (A/B runs: ``rowwise_catch_up`` then flushes each table every half ring of updates)."""
+    p = int(os.environ.get('CDR_ROWWISE_SWEEP', '256'))
+    return 0 if p <= 0 else max(2, min(p, RowwiseState.HP_CAPACITY // 2))
+
+
+def rowwise_bound_lag(state):
+    """Without the window: keep every row of an exact table less than a ring behind by a flush every half ring of its updates."""
+    if state.exact and state.sweep_period == 0 and state.step - state._flushed_at >= RowwiseState.HP_CAPACITY // 2:
+        state.flush()
+
+
+@torch.no_grad()
+def rowwise_catch_up(tables, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    """ONE launch in front of a fused step that makes its row-wise Adam the reference's dense one (cdr_rowwise_adam_catch_up).
+    ``tables``: [(RowwiseState with exact=True, [int64 id tensors: the rows the step updates in this table, one or two lists])], one to
+    four tables.  Every listed row replays its postponed gradient-free updates and is then exactly where the dense sweep would have left
+    it before the step's update; the step itself is unchanged.  Issue it BEFORE the step advances the counts; capturable."""
+    n = len(tables)
+    assert 1 <= n <= 4
+    hp = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
+    capturing = torch.cuda.is_current_stream_capturing()
+    period = tables[0][0].sweep_period if tables[0][0].exact else 0
+    for st, ids in tables:
+        if not st.exact:
+            raise ValueError('rowwise_catch_up needs RowwiseState(..., exact=True)')
+        if st.sweep_period != period:
+            raise ValueError(f'rowwise_catch_up: tables with different window periods in one launch ({st.sweep_period} vs {period})')
+        if not 1 <= len(ids) <= 2:
+            raise ValueError('rowwise_catch_up: one or two id lists per table')
+        for x in ids:                 # (the launch reads raw pointers and moves `last` of the rows it reads: check before, not after)
+            if x.dtype != torch.int64 or x.device != st.table.device:
+                raise ValueError(f'rowwise_catch_up: ids must be int64 on {st.table.device}, got {x.dtype} on {x.device}')
+        if st.hparams is not None and st.hparams != hp:
+            raise ValueError(f'exact row-wise Adam: one table stepped with two sets of hyperparameters ({st.hparams} vs {hp})')
+        st.hparams = hp
+        if not capturing:
+            rowwise_bound_lag(st)
+    lists = [[x.reshape(-1).contiguous() for x in ids] + [None] * (2 - len(ids)) for _, ids in tables]
+    arr = lambda xs: (ctypes.c_void_p * n)(*xs)
+    i64s = lambda xs: (ctypes.c_int64 * n)(*xs)
+    ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()
+    keep = [[st.step_dev for st, _ in tables], lists]              # (step_dev: created here on first use)
+    B_.call('cdr_rowwise_adam_catch_up', B_.stream(), n, (ctypes.c_int * n)(*[st.table.shape[1] for st, _ in tables]),
+            arr([st.table.data_ptr() for st, _ in tables]), arr([st.exp_avg.data_ptr() for st, _ in tables]),
+            arr([st.exp_avg_sq.data_ptr() for st, _ in tables]), arr([st.last.data_ptr() for st, _ in tables]),
+            i64s([st.table.shape[0] for st, _ in tables]), arr([st.hp.data_ptr() for st, _ in tables]), RowwiseState.HP_CAPACITY,
+            arr([c.data_ptr() for c in keep[0]]), arr([ptr(l[0]) for l in lists]), i64s([0 if l[0] is None else l[0].numel() for l in lists]),
+            arr([ptr(l[1]) for l in lists]), i64s([0 if l[1] is None else l[1].numel() for l in lists]), *hp, period)
+    del keep
 
 
 class FusedBPRStep:

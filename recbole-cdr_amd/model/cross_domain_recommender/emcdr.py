@@ -121,22 +121,42 @@ class EMCDR(CrossDomainRecommender):
             return self.calculate_target_loss(interaction)
 
     # ---- O(batch) training step (large tables) ------------------------------------------------------------------
-    def fused_train_step(self, interaction, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def fused_train_step(self, interaction, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam='lazy'):
         """``calculate_loss -> backward -> optimizer.step`` of the current phase without table-sized gradients or a dense
         optimizer sweep (fused.FusedBPRStep / fused.FusedMapStep on this model's own tables): what
         ``CrossDomainTrainer`` runs when ``config['optimizer_mode'] == 'rowwise'``.  Same loss and per-row gradients as
-        ``calculate_loss``; the embedding tables take the row-wise (lazy) Adam, the mapping function the exact dense one.
-        One optimizer state per table, shared by the phases.  Both latent factor models (MF: pointwise MSE; BPR)."""
-        from ...fused import FusedBPRStep, FusedPointStep, FusedMapStep, RowwiseState, OPT_ADAM, OPT_SGD
+        ``calculate_loss``; the embedding tables take the row-wise Adam, the mapping function the exact dense one.
+        One optimizer state per table, shared by the phases.  Both latent factor models (MF: pointwise MSE; BPR).
+
+        ``adam='lazy'`` (default): rows the batch does not touch do not move.  ``adam='exact'``: the reference's dense Adam -- one
+        catch-up launch in front of every step (fused.rowwise_catch_up) replays the gradient-free updates the step's rows missed, so
+        the tables hold what ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run (evaluation,
+        checkpoints; the trainer calls it).  One mode per model."""
+        from ...fused import FusedBPRStep, FusedPointStep, FusedMapStep, RowwiseState, OPT_ADAM, OPT_SGD, rowwise_catch_up
+        if adam not in ('lazy', 'exact'):
+            raise ValueError(f"adam must be 'lazy' or 'exact', got {adam!r}")
+        exact = adam == 'exact'
+        if exact and opt != 'adam':
+            raise ValueError(f"adam='exact' is the reference's dense Adam: it needs opt='adam', got {opt!r}")
+        if exact and self._dist_group() is not None:
+            raise ValueError("adam='exact' is not available with config['dist_group'] (sharded tables): use adam='lazy' or one GPU")
         code = OPT_ADAM if opt == 'adam' else OPT_SGD
         cache = self.__dict__.setdefault('_fused', {'states': {}, 'steps': {}})
         if self._dist_group() is not None:
             return self._dist_train_step(interaction, code, dict(opt=opt, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
 
+        for name, st in cache['states'].items():
+            if st.exact != exact:
+                raise ValueError(f"{name} was trained with adam={'exact' if st.exact else 'lazy'!r}; one row-wise Adam mode per model")
+
         def state(name):
             if name not in cache['states']:
-                cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code)
+                cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code, exact=exact)
             return cache['states'][name]
+
+        def catch_up(*tables):
+            if exact:
+                rowwise_catch_up(tables, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
 
         hp = dict(opt=opt, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         if self.phase == 'OVERLAP':
@@ -151,6 +171,8 @@ class EMCDR(CrossDomainRecommender):
                 pending = self.__dict__.get('_pending_map_state', {}).pop(kind, None)
                 if pending is not None and cache['steps'][key].map_opt is not None:
                     cache['steps'][key].map_opt.load_state_dict(pending)
+            if idx.numel() > 0:                                  # (an empty batch is a no-op: no table advances)
+                catch_up((state(f'source_{kind}_embedding'), [idx]), (state(f'target_{kind}_embedding'), [idx]))
             # the reference's OverlapDataloader yields slices of a shuffled arange (data/dataloader.py:37-52): distinct ids, which
             # the two-launch step relies on.  A caller feeding its own, possibly repeated ids sets model.overlap_ids_unique = False.
             return cache['steps'][key].step(idx, unique=getattr(self, 'overlap_ids_unique', True))
@@ -174,6 +196,7 @@ class EMCDR(CrossDomainRecommender):
                                            reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'),
                                            item_state=state(f'{domain}_item_embedding'), **hp)
                     cache['steps'][key] = step
+                catch_up((step.ustate, [user[:rows // (1 + pk)]]), (step.istate, [item]))
                 return step.step(user, item, label)[0]
             key = ('mf', domain)
             step = cache['steps'].get(key)
@@ -183,6 +206,7 @@ class EMCDR(CrossDomainRecommender):
                                       reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'),
                                       item_state=state(f'{domain}_item_embedding'), **hp)
                 cache['steps'][key] = step
+            catch_up((step.ustate, [user]), (step.istate, [item]))
             return step.step(user, item, label)[0]
         neg = interaction[getattr(self, f'{domain.upper()}_NEG_ITEM_ID')].reshape(-1)
         # recbole's pairwise batches tile S positives k times with k-major negatives (crossdomain_sampler.py:148-152); the loader
@@ -201,6 +225,7 @@ class EMCDR(CrossDomainRecommender):
                                      reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'),
                                      item_state=state(f'{domain}_item_embedding'), **hp)
                 cache['steps'][key] = step
+            catch_up((step.ustate, [user[:rows // k]]), (step.istate, [item[:rows // k], neg]))
             return step.step(user, item, neg)[0]
         key = ('bpr', domain)
         step = cache['steps'].get(key)
@@ -210,16 +235,18 @@ class EMCDR(CrossDomainRecommender):
                                 reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'),
                                 item_state=state(f'{domain}_item_embedding'), **hp)
             cache['steps'][key] = step
+        catch_up((step.ustate, [user]), (step.istate, [item, neg]))
         return step.step(user, item, neg)[0]
 
-    def fused_graph_key(self, interaction):
+    def fused_graph_key(self, interaction, adam='lazy'):
         """Hashable tag of the launches ``fused_train_step(interaction)`` would make, or None when they must not be captured in a
         hipGraph: capturable are the per-triple BPR step (update counts on the device: cdr_bpr_step_fused_dev) and the distinct-id
-        OVERLAP step; the MF steps and the per-positive forms read host-side update counts."""
+        OVERLAP step; the MF steps and the per-positive forms read host-side update counts.  ``adam``: the row-wise Adam mode of
+        ``fused_train_step`` (the exact mode's catch-up launch is captured with the step)."""
         if self._dist_group() is not None:
             return None
         if self.phase == 'OVERLAP':
-            return ('map', self.mode) if getattr(self, 'overlap_ids_unique', True) and self.map_func in ('linear', 'non_linear') else None
+            return ('map', self.mode, adam) if getattr(self, 'overlap_ids_unique', True) and self.map_func in ('linear', 'non_linear') else None
         if self.latent_factor_model == 'MF':
             return None
         domain = 'source' if self.phase == 'SOURCE' else 'target'
@@ -233,7 +260,7 @@ class EMCDR(CrossDomainRecommender):
             # hands the applies garbage positions -- an illegal access at B = 1,048,576, found by bench.py --only-e2e.  Nothing is lost:
             # at these sizes the step is the sum of its kernels, a replay saves no time.
             return None
-        return ('bpr', domain, rows)
+        return ('bpr', domain, rows, adam)
 
     def fused_replayed(self, n=1):
         """Host bookkeeping of ``n`` hipGraph replays of the current phase's ``fused_train_step`` (the update counts' host mirrors)."""
@@ -244,9 +271,24 @@ class EMCDR(CrossDomainRecommender):
             for _ in range(n):
                 st.sstate.advance(device_bumped=True)
                 st.tstate.advance(device_bumped=True)
-            return
-        domain = 'source' if self.phase == 'SOURCE' else 'target'
-        cache['steps'][('bpr', domain)].replayed(n)
+            states = (st.sstate, st.tstate)
+        else:
+            domain = 'source' if self.phase == 'SOURCE' else 'target'
+            st = cache['steps'][('bpr', domain)]
+            st.replayed(n)
+            states = (st.ustate, st.istate)
+        from ...fused import rowwise_bound_lag
+        for s_ in states:
+            rowwise_bound_lag(s_)                               # (exact mode without the moving window only)
+
+    def fused_sync(self):
+        """``fused_train_step(adam='exact')``: bring every row of every table to its update count -- the tables and moments then equal
+        the reference's dense Adam (before evaluation, checkpoints, the end of training).  Lazy mode: nothing to do."""
+        cache = self.__dict__.get('_fused')
+        if cache:
+            for st in cache['states'].values():
+                if st.exact:
+                    st.flush()
 
     # ---- the same step over the GPUs of a node (config['dist_group']: a torch.distributed group, or True for WORLD) ----------
     _TABLES = ('source_user_embedding', 'source_item_embedding', 'target_user_embedding', 'target_item_embedding')
@@ -451,24 +493,27 @@ class EMCDR(CrossDomainRecommender):
         cache = self.__dict__.get('_fused')
         if not cache:
             return {}
+        self.fused_sync()
         out = {'tables': {k: {'step': st.step, 'exp_avg': st.exp_avg, 'exp_avg_sq': st.exp_avg_sq} for k, st in cache['states'].items()}}
         for key, step in cache['steps'].items():
             if key[0] == 'map' and step.map_opt is not None:
                 out.setdefault('mapping', {})[key[1]] = step.map_opt.state_dict()
         return out
 
-    def load_fused_optimizer_state(self, state, opt='adam'):
-        """Restore what ``fused_optimizer_state`` returned (before the next ``fused_train_step``)."""
+    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
+        """Restore what ``fused_optimizer_state`` returned (before the next ``fused_train_step``).  ``adam``: the mode training
+        goes on with; in exact mode every row is current at its table's update count (the checkpoint was written flushed)."""
         from ...fused import RowwiseState, OPT_ADAM, OPT_SGD
         cache = self.__dict__.setdefault('_fused', {'states': {}, 'steps': {}})
         code = OPT_ADAM if opt == 'adam' else OPT_SGD
         for name, rec in state.get('tables', {}).items():
             st = cache['states'].get(name)
             if st is None:
-                st = cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code)
+                st = cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code, exact=adam == 'exact')
             st.step = int(rec['step'])
             if rec['exp_avg'] is not None:
                 st.exp_avg.copy_(rec['exp_avg']); st.exp_avg_sq.copy_(rec['exp_avg_sq'])
+            st.restored()
         self._pending_map_state = state.get('mapping', {})
 
     # ---- scoring ------------------------------------------------------------------------------------------------

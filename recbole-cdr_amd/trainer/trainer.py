@@ -161,6 +161,8 @@ def early_stopping(value, best, cur_step, max_step, bigger=True):
 
 
 class Trainer:
+    rowwise_adam = 'lazy'             # (class default: loops driven on objects built without __init__ keep the lazy row-wise Adam)
+
     def __init__(self, config, model):
         self.config, self.model = config, model
         self.learning_rate = config['learning_rate'] if 'learning_rate' in config else 1e-3
@@ -227,6 +229,19 @@ class Trainer:
             raise ValueError(f"optimizer_mode must be 'dense' or 'rowwise', got {self.optimizer_mode!r}")
         if self.optimizer_mode == 'rowwise' and not hasattr(self.model, 'fused_train_step'):
             raise NotImplementedError(f'{type(self.model).__name__} has no fused_train_step; use optimizer_mode=dense')
+        # config['rowwise_adam'] with optimizer_mode='rowwise': 'lazy' (default) -- rows a batch does not touch keep their state -- or
+        # 'exact': the reference's Adam over whole tables (recbole_cdr/properties/overall.yaml:20-21), evaluated per row by a catch-up launch
+        # in front of every fused step; the tables are brought up to date (model.fused_sync) before evaluation, checkpoints and the end of fit
+        self.rowwise_adam = config['rowwise_adam'] if 'rowwise_adam' in config and config['rowwise_adam'] is not None else 'lazy'
+        if self.rowwise_adam not in ('lazy', 'exact'):
+            raise ValueError(f"rowwise_adam must be 'lazy' or 'exact', got {self.rowwise_adam!r}")
+        if self.rowwise_adam == 'exact':
+            if self.optimizer_mode != 'rowwise':
+                raise ValueError("rowwise_adam='exact' applies to optimizer_mode='rowwise' (optimizer_mode='dense' already runs the dense Adam)")
+            if self.dist_group is not None:
+                raise ValueError("rowwise_adam='exact' is not available with dist_group (sharded tables)")
+            if not hasattr(self.model, 'fused_sync'):
+                raise NotImplementedError(f"{type(self.model).__name__}.fused_train_step has no rowwise_adam='exact' mode")
         if self.optimizer_mode == 'rowwise' and self.clip_grad_norm:
             # the fused step never materialises the gradient, so there is no norm to clip: refuse rather than ignore silently
             raise ValueError("clip_grad_norm is not supported with optimizer_mode='rowwise' (the fused step applies per-row updates "
@@ -345,7 +360,7 @@ class Trainer:
             if self.dist_group is not None:
                 interaction = self._my_rows(interaction)
             if self.optimizer_mode == 'rowwise':
-                loss = self.model.fused_train_step(interaction, lr=self.learning_rate, weight_decay=self.weight_decay)
+                loss = self.model.fused_train_step(interaction, **self._fused_kw())
                 total = loss.detach().clone() if total is None else total + loss.detach()
                 continue
             self.optimizer.zero_grad()
@@ -374,15 +389,15 @@ class Trainer:
         prod.resync()
         # full batches of a capturable phase (model.fused_graph_key): the first two run eagerly on the capture stream -- real steps, they
         # create every buffer and context the capture needs -- then {producer -> fused step -> loss total} is replayed, 4 steps per launch
-        gkey = self.model.fused_graph_key(prod.fields) if (self.graph_step_rowwise and hasattr(self.model, 'fused_graph_key')) else None
+        gkw = {'adam': 'exact'} if self.rowwise_adam == 'exact' else {}
+        gkey = self.model.fused_graph_key(prod.fields, **gkw) if (self.graph_step_rowwise and hasattr(self.model, 'fused_graph_key')) else None
         gs = None
         if gkey is not None:
             gkey = (gkey, getattr(train_data, 'state', None), id(prod))
             gs = self._graphs.get(gkey)
             if gs is None:
                 from ..graph_step import GraphedRowwiseStep
-                gs = self._graphs[gkey] = GraphedRowwiseStep(self.model, prod, self._loss_sum,
-                                                             dict(lr=self.learning_rate, weight_decay=self.weight_decay), unroll=4)
+                gs = self._graphs[gkey] = GraphedRowwiseStep(self.model, prod, self._loss_sum, self._fused_kw(), unroll=4)
         while True:
             if gs is not None and gs is not False and prod.full_ahead():
                 if gs.graph is None:
@@ -413,7 +428,7 @@ class Trainer:
                 except StopIteration:
                     break
                 prod.resync()
-            loss = self.model.fused_train_step(interaction, lr=self.learning_rate, weight_decay=self.weight_decay)
+            loss = self.model.fused_train_step(interaction, **self._fused_kw())
             self._loss_sum.add_(loss.detach().reshape(()))
         value = float(self._loss_sum)
         if value != value:
@@ -464,6 +479,7 @@ class Trainer:
     def evaluate(self, eval_data):
         """eval_data yields (interaction, history_index (rows, cols) or None, positive_u, positive_i) like recbole's
         FullSortEvalDataLoader; returns {metric@k: value} for recall / mrr / ndcg / hit / precision."""
+        self._fused_sync()
         self.model.eval()
         kmax = max(self.topk)
         fused = self.fused_topk and hasattr(self.model, 'full_sort_topk')
@@ -527,6 +543,7 @@ class Trainer:
         """recbole ``Trainer._save_checkpoint``: config-free subset -- epoch, early-stopping state, model ``state_dict``,
         ``other_parameter`` and the optimizer state (dense: ``DenseAdam.state_dict()``; rowwise: the model's per-table
         moments and update counts).  With a ``dist_group``: one file per rank, ``<path>.rank<r>``."""
+        self._fused_sync()
         if self.dist_group is not None:
             # a sharded model: every rank writes ITS shards (tables + moments in their current layout) next to the replicated parts
             import torch.distributed as dist
@@ -563,7 +580,10 @@ class Trainer:
             self.model.set_phase(state['phase'])
         self.optimizer.load_state_dict(state['optimizer'])
         if 'rowwise' in state and hasattr(self.model, 'load_fused_optimizer_state'):
-            self.model.load_fused_optimizer_state(state['rowwise'])
+            if self.rowwise_adam == 'exact':
+                self.model.load_fused_optimizer_state(state['rowwise'], adam='exact')
+            else:
+                self.model.load_fused_optimizer_state(state['rowwise'])
 
     def fit(self, train_data, valid_data=None, verbose=True, saved=True, show_progress=False, callback_fn=None):
         for epoch_idx in range(self.start_epoch, self.epochs):
@@ -583,7 +603,20 @@ class Trainer:
                     callback_fn(epoch_idx, valid_score)
                 if stop_flag:
                     break
+        self._fused_sync()
         return self.best_valid_score, self.best_valid_result
+
+    def _fused_kw(self):
+        """Keyword arguments of ``model.fused_train_step`` (optimizer_mode='rowwise')."""
+        kw = {'lr': self.learning_rate, 'weight_decay': self.weight_decay}
+        if self.rowwise_adam == 'exact':
+            kw['adam'] = 'exact'
+        return kw
+
+    def _fused_sync(self):
+        """rowwise_adam='exact': every row of the model's tables at its update count (the reference's dense-Adam state)."""
+        if self.rowwise_adam == 'exact':
+            self.model.fused_sync()
 
 
 class CrossDomainTrainer(Trainer):
@@ -682,7 +715,7 @@ class CrossDomainTrainer(Trainer):
                             if pr is not None:
                                 pr.resync()
                         self.model.set_phase(sc)                          # (host-side switch: which tables the fused step takes)
-                        loss = self.model.fused_train_step(batch, lr=self.learning_rate, weight_decay=self.weight_decay)
+                        loss = self.model.fused_train_step(batch, **self._fused_kw())
                         sums[sc].add_(loss.detach().reshape(()))
             for sc in active:
                 cur.wait_stream(streams[sc])
@@ -733,6 +766,7 @@ class CrossDomainTrainer(Trainer):
                     super().fit(train_data, target_valid_data, verbose, saved, show_progress, callback_fn)
             else:
                 super().fit(train_data, valid_data, verbose, saved, show_progress, callback_fn)
+        self._fused_sync()
         self.model.set_phase('OVERLAP')
         return self.best_valid_score, self.best_valid_result
 
