@@ -55,7 +55,7 @@ int cdr_ctx_scrub_next(cdr_ctx* ctx, void* ptr, size_t bytes);
 int cdr_ctx_set_id_counters(cdr_ctx* ctx, uint32_t* user_counts, int64_t user_rows, uint32_t* item_counts, int64_t item_rows,
                             void* list_ws, size_t list_ws_bytes);
 int cdr_id_count_workspace_bytes(int64_t B, size_t* bytes);
-#define CDR_ABI_VERSION 60
+#define CDR_ABI_VERSION 61
 int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the header the library was built from; bumped on any signature change */
 
 /* Optional measurement aid: HIP-event brackets around the hot kernels, recorded on the stream each kernel is launched
@@ -690,6 +690,27 @@ int cdr_point_step_fused(cdr_ctx* ctx, void* stream, int loss_kind, int opt, flo
                          const float* label, int64_t B, float reg_weight, float lr, float beta1, float beta2, float eps, float weight_decay,
                          int64_t step_user, int64_t step_item, float* out9, float* GU, float* GI, uint32_t* keys, uint32_t* perm,
                          uint8_t* flags, uint32_t* heads, void* sort_ws, size_t sort_ws_bytes);
+
+/* CMF's step on its two domains (cmf.py:75-99): both batches train ONE user and ONE item table, and the loss
+ *   alpha (BCE(sigmoid(<U[su], I[si]>), ys) + reg_s EmbLoss(U[su], I[si])) + (1 - alpha) (BCE(sigmoid(<U[tu], I[ti]>), yt) + reg_t EmbLoss(U[tu], I[ti]))
+ * takes ONE optimizer update per touched row, from the sum of its source and target contributions (the reference's single
+ * torch.optim.Adam step; two cdr_point_step_fused calls would update a row named by both batches twice).  The step of
+ * cdr_point_step_fused over the joint occurrence list [source rows | target rows] (B_s != B_t allowed): EmbLoss norms (skipped when
+ * alpha reg_s = (1 - alpha) reg_t = 0) -> per-domain coefficients, ONE sort of the user keys [su | tu] and the item keys [si | ti], a row
+ * that occurs once across BOTH lists updated in place by the forward with its own domain's gradient, every other row once by the
+ * segmented applies.  Update counts in DEVICE memory as cdr_bpr_step_fused_dev's (*step_*_dev: the counts before the call, advanced by
+ * it; hp_dev: 4 floats of scratch): capturable.  opt = 1 (Adam) needs the moments, both counts and hp_dev; opt = 0 (SGD) takes NULL
+ * counts (given, they are advanced).  loss_kind: CDR_LOSS_BCE (CMF) or CDR_LOSS_MSE.  With N = B_s + B_t: keys / perm [2 N], flags [4 N]
+ * (4-byte aligned, zeroed once), heads cdr_bpr_step_fused_heads_words(N) words, GU / GI [N, D], sort workspace cdr_sort_workspace_bytes(2 N,
+ * 2 * next power of two of the larger row count).  out16: {total, BCE_s, BCE_t, EmbLoss_s, EmbLoss_t, ||U_s||, ||I_s||, ||U_t||, ||I_t||,
+ * the four coefficients (scratch), -, -, -} -- BCE_d the mean over the domain's rows, EmbLoss_d = (||U_d|| + ||I_d||) / B_d. */
+int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int loss_kind, int opt, float* user_tab, float* user_m, float* user_v,
+                                  int64_t user_rows, float* item_tab, float* item_m, float* item_v, int64_t item_rows, int D,
+                                  const int64_t* su, const int64_t* si, const float* ys, int64_t B_s, const int64_t* tu, const int64_t* ti,
+                                  const float* yt, int64_t B_t, float alpha, float reg_s, float reg_t, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int64_t* step_user_dev, int64_t* step_item_dev, float* hp_dev, float* out16,
+                                  float* GU, float* GI, uint32_t* keys, uint32_t* perm, uint8_t* flags, uint32_t* heads, void* sort_ws,
+                                  size_t sort_ws_bytes);
 
 /* The same step per POSITIVE, for recbole's pointwise batch layout (TrainDataLoader._neg_sampling under data/dataloader.py:114-162): uid [S]
  * (the first S entries of the user column tiled 1 + k times), iid [S + S k] = [positives | k-major negatives], label [S + S k].  In that

@@ -2950,3 +2950,313 @@ extern "C" int cdr_bpr_step_fused_kmajor(cdr_ctx* ctx, void* stream, int opt, fl
     CDR_LAUNCH_CHECK();
     return apply_dups_pair(ctx, s, opt, D, pl);
 }
+
+
+// ================================================================================================ CMF's two-domain step on shared tables
+// cmf.py:75-99: both domains' batches train ONE user and ONE item table, and the reference takes one torch.optim.Adam step on the summed
+// loss  alpha (BCE_s + lambda EmbLoss_s) + (1 - alpha) (BCE_t + gamma EmbLoss_t).  A row named by both domains' batches (an overlapped user,
+// an item in both lists) gets ONE update from the sum of its contributions, so the step is cdr_point_step_fused over the JOINT occurrence
+// list [source rows | target rows] -- occurrence o < B_s is source row o, o >= B_s target row o - B_s -- with per-domain weights:
+//   pair_norms_kernel        the four EmbLoss sums ||U_s||^2, ||I_s||^2, ||U_t||^2, ||I_t||^2 (skipped when lambda = gamma = 0)
+//   pair_coef_kernel         -> the per-domain coefficients c = w_d reg_d / (B_d ||.||); the update counts bumped on the device
+//   one two-table sort       user keys [su | tu], item keys [si | ti] (make_keys_pair_kernel reads the four lists in place)
+//   occ_flags_kernel         "only occurrence of its row across BOTH domains" per joint occurrence
+//   point_pair_fwd_apply     single rows updated in place with their own domain's gradient and EmbLoss coefficient; every other occurrence
+//                            writes its FULL gradient row (loss term + its domain's EmbLoss term), so the duplicate apply sums rows with no
+//                            coefficient of its own (reg_coef = nullptr)
+//   pair_finish_kernel       the loss vector; the duplicate applies (apply_dups_pair) give every other row exactly one update.
+namespace {
+
+__global__ __launch_bounds__(kBlock) void make_keys_pair_kernel(const int64_t* __restrict__ a0, int64_t na0, const int64_t* __restrict__ a1,
+                                                                int64_t na1, const int64_t* __restrict__ b0, int64_t nb0,
+                                                                const int64_t* __restrict__ b1, int64_t nb1, uint32_t key_base,
+                                                                uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const int64_t na = na0 + na1, n = na + nb0 + nb1, stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride) {
+        if (e < na) { keys[e] = (uint32_t)(e < na0 ? a0[e] : a1[e - na0]); vals[e] = (uint32_t)e; }
+        else {
+            const int64_t o = e - na;
+            keys[e] = key_base + (uint32_t)(o < nb0 ? b0[o] : b1[o - nb0]);
+            vals[e] = (uint32_t)o;                               // joint occurrence index inside the item lists
+        }
+    }
+}
+
+// partials[block] = {sum ||U[su]||^2, sum ||I[si]||^2, sum ||U[tu]||^2, sum ||I[ti]||^2} over the joint occurrence list
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void pair_norms_kernel(const float* __restrict__ U, const float* __restrict__ I, int D,
+                                                            const int64_t* __restrict__ su, const int64_t* __restrict__ si, int64_t Bs,
+                                                            const int64_t* __restrict__ tu, const int64_t* __restrict__ ti, int64_t Bt,
+                                                            double* __restrict__ partials) {
+    constexpr int GPB = kBlock / LPR;
+    constexpr int UNR = 8;
+    __shared__ double smem[4 * (kBlock / 64)];
+    const int sub = threadIdx.x % LPR;
+    const int64_t gg = (int64_t)blockIdx.x * GPB + threadIdx.x / LPR;
+    const int64_t TG = (int64_t)gridDim.x * GPB;
+    const int64_t N = Bs + Bt;
+    const bool live = sub < (D >> 2);
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t base = gg; base < N; base += TG * UNR) {
+        int64_t iu[UNR], ii[UNR];
+        float4 u[UNR], v[UNR];
+#pragma unroll
+        for (int r = 0; r < UNR; ++r) {
+            const int64_t t = base + (int64_t)r * TG;
+            const int64_t tc = t < N ? t : N - 1;
+            iu[r] = tc < Bs ? su[tc] : tu[tc - Bs]; ii[r] = tc < Bs ? si[tc] : ti[tc - Bs];
+        }
+#pragma unroll
+        for (int r = 0; r < UNR; ++r) {
+            const int64_t t = base + (int64_t)r * TG;
+            u[r] = v[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (t < N && live) { u[r] = ld4n<(LPR >= 32)>(U + iu[r] * D + 4 * sub); v[r] = ld4n<(LPR >= 32)>(I + ii[r] * D + 4 * sub); }
+        }
+#pragma unroll
+        for (int r = 0; r < UNR; ++r) {
+            const int64_t t = base + (int64_t)r * TG;
+            const float s_u = group_sum<LPR>(dot4(u[r], u[r])), s_i = group_sum<LPR>(dot4(v[r], v[r]));
+            if (sub == 0) {
+                if (t < Bs) { acc[0] += (double)s_u; acc[1] += (double)s_i; }
+                else { acc[2] += (double)s_u; acc[3] += (double)s_i; }          // (t >= N: zero rows)
+            }
+        }
+    }
+    block_sum_d<4>(acc, smem);
+    if (threadIdx.x == 0) {
+        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
+        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3];
+    }
+}
+
+// out[9..12] = {c_u_s, c_i_s, c_u_t, c_i_t}: c = w_d reg_d / (B_d ||rows||) (0 without EmbLoss or for a zero norm), w_s = alpha, w_t = 1 - alpha.
+// As coef_finish_kernel: the update counts (when given) advanced here with the Adam scalars of the new counts in hp_dev[0..3]; zero4 = the
+// head lists' counters of occ_flags_kernel.
+__global__ __launch_bounds__(kBlock) void pair_coef_kernel(const double* __restrict__ partials, int nblocks, int64_t Bs, int64_t Bt,
+                                                           float wreg_s, float wreg_t, float* __restrict__ out, int64_t* __restrict__ step_u_dev,
+                                                           int64_t* __restrict__ step_i_dev, float* __restrict__ hp_dev, float lr, float b1,
+                                                           float b2, unsigned* __restrict__ zero4) {
+    __shared__ double smem[4 * (kBlock / 64)];
+    if (threadIdx.x >= 64 && threadIdx.x < 68) zero4[threadIdx.x - 64] = 0u;
+    if (step_u_dev && threadIdx.x < 2) {
+        int64_t* c = threadIdx.x == 0 ? step_u_dev : step_i_dev;
+        const int64_t st = c[0] + 1;
+        c[0] = st;
+        if (hp_dev) cdr_adam_hp((double)st, lr, b1, b2, hp_dev[2 * threadIdx.x], hp_dev[2 * threadIdx.x + 1]);
+    }
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
+        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
+        acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2]; acc[3] += o[3];
+    }
+    block_sum_d<4>(acc, smem);
+    if (threadIdx.x == 0) {
+        const float n[4] = {(float)sqrt(acc[0]), (float)sqrt(acc[1]), (float)sqrt(acc[2]), (float)sqrt(acc[3])};
+        for (int j = 0; j < 4; ++j) {
+            const float wr = j < 2 ? wreg_s : wreg_t;
+            const float B = (float)(j < 2 ? Bs : Bt);
+            out[9 + j] = (wr != 0.f && n[j] > 0.f) ? wr / (B * n[j]) : 0.f;
+        }
+    }
+}
+
+// point_fwd_apply_kernel over the joint occurrence list: row t < Bs is source row t (weight invB_s = alpha / B_s, coefficients coef[0..1]),
+// row t >= Bs target row t - Bs (invB_t = (1 - alpha) / B_t, coef[2..3]).  flags4[t] byte 0 / 1: its user / item occurs once in BOTH lists.
+// partials[block] = {BCE sum_s, BCE sum_t, sum u_s^2, sum i_s^2, sum u_t^2, sum i_t^2} (pre-step rows).
+template <int LPR, int OPT>
+__global__ __launch_bounds__(kBlock) void point_pair_fwd_apply_kernel(int loss_kind, tab_ptrs TU, tab_ptrs TI, int D,
+                                                                      const int64_t* __restrict__ su, const int64_t* __restrict__ si,
+                                                                      const float* __restrict__ ys, int64_t Bs, const int64_t* __restrict__ tu,
+                                                                      const int64_t* __restrict__ ti, const float* __restrict__ yt, int64_t Bt,
+                                                                      const uint32_t* __restrict__ flags4, float invB_s, float invB_t,
+                                                                      const float* __restrict__ coef, apply_hp hu, apply_hp hi,
+                                                                      float* __restrict__ GU, float* __restrict__ GI, double* __restrict__ partials) {
+    HP_FROM_DEV(hu); HP_FROM_DEV(hi);
+    constexpr int GPB = kBlock / LPR;
+    __shared__ double smem[6 * (kBlock / 64)];
+    const int sub = threadIdx.x % LPR;
+    const int64_t gg = (int64_t)blockIdx.x * GPB + threadIdx.x / LPR;
+    const int64_t TG = (int64_t)gridDim.x * GPB;
+    const int64_t N = Bs + Bt;
+    const bool live = sub < (D >> 2);
+    const float cus = coef[0], cis = coef[1], cut = coef[2], cit = coef[3];
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    uint32_t iu, ii, fl; float yl;
+    {
+        const int64_t tc = gg < N ? gg : N - 1;
+        const bool src = tc < Bs;
+        iu = (uint32_t)(src ? su[tc] : tu[tc - Bs]); ii = (uint32_t)(src ? si[tc] : ti[tc - Bs]); yl = src ? ys[tc] : yt[tc - Bs];
+        fl = flags4[tc];
+    }
+    asm volatile("" : "+v"(iu), "+v"(ii), "+v"(fl), "+v"(yl));
+    for (int64_t t = gg; t < N; t += TG) {
+        const bool src = t < Bs;
+        const bool fu = (fl & 0xFFu) != 0, fi = (fl & 0xFF00u) != 0;
+        const int64_t ou = (int64_t)iu * D + 4 * sub, oi = (int64_t)ii * D + 4 * sub;
+        float4 u = live ? ld4n<(LPR >= 32)>(TU.W + ou) : z4, v = live ? ld4n<(LPR >= 32)>(TI.W + oi) : z4;
+        float4 um = z4, uv = z4, im = z4, iv = z4;
+        if (OPT == 1) {
+            if (live && fu) { um = ld4n<(LPR >= 32)>(TU.M + ou); uv = ld4n<(LPR >= 32)>(TU.V + ou); }
+            if (live && fi) { im = ld4n<(LPR >= 32)>(TI.M + oi); iv = ld4n<(LPR >= 32)>(TI.V + oi); }
+        }
+        uint32_t ju, ji, gl; float yn;
+        {
+            const int64_t tn = t + TG, tc = tn < N ? tn : N - 1;
+            const bool sn = tc < Bs;
+            ju = (uint32_t)(sn ? su[tc] : tu[tc - Bs]); ji = (uint32_t)(sn ? si[tc] : ti[tc - Bs]); yn = sn ? ys[tc] : yt[tc - Bs];
+            gl = flags4[tc];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const float dx = group_sum<LPR>(dot4(u, v));
+        const float s_u = group_sum<LPR>(dot4(u, u));
+        const float s_i = group_sum<LPR>(dot4(v, v));
+        const float invB = src ? invB_s : invB_t;
+        float l, g;
+        if (loss_kind == CDR_LOSS_MSE) {
+            const float d = dx - yl;
+            l = d * d; g = 2.0f * d * invB;
+        } else {                                               // torch BCELoss on sigmoid(dot): -100 log clamp, 1e-12 backward clamp
+            const float p = sigmoidf_(dx);
+            l = (yl - 1.0f) * fmaxf(logf(1.0f - p), -100.0f) - yl * fmaxf(logf(p), -100.0f);
+            const float pq = (1.0f - p) * p;
+            g = (p - yl) / fmaxf(pq, 1e-12f) * invB * pq;
+        }
+        asm volatile("" : "+v"(ju), "+v"(ji), "+v"(gl), "+v"(yn));        // every request of this iteration has returned
+        __builtin_amdgcn_sched_barrier(0);
+        const float cu = src ? cus : cut, ci = src ? cis : cit;
+        const float4 gu = make_float4(g * v.x, g * v.y, g * v.z, g * v.w);
+        const float4 gi = make_float4(g * u.x, g * u.y, g * u.z, g * u.w);
+        if (fu) {
+            const float4 wu = upd_math<OPT>(u, um, uv, gu, cu, hu);
+            if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TU.M + ou, um); st4n<(LPR >= 32)>(TU.V + ou, uv); } st4n<(LPR >= 32)>(TU.W + ou, wu); }
+        } else if (live) {
+            st4n<(LPR >= 32)>(GU + t * D + 4 * sub, make_float4(gu.x + cu * u.x, gu.y + cu * u.y, gu.z + cu * u.z, gu.w + cu * u.w));
+        }
+        if (fi) {
+            const float4 wi = upd_math<OPT>(v, im, iv, gi, ci, hi);
+            if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + oi, im); st4n<(LPR >= 32)>(TI.V + oi, iv); } st4n<(LPR >= 32)>(TI.W + oi, wi); }
+        } else if (live) {
+            st4n<(LPR >= 32)>(GI + t * D + 4 * sub, make_float4(gi.x + ci * v.x, gi.y + ci * v.y, gi.z + ci * v.z, gi.w + ci * v.w));
+        }
+        if (sub == 0) {
+            if (src) { acc[0] += (double)l; acc[2] += (double)s_u; acc[3] += (double)s_i; }
+            else { acc[1] += (double)l; acc[4] += (double)s_u; acc[5] += (double)s_i; }
+        }
+        iu = ju; ii = ji; fl = gl; yl = yn;
+    }
+    block_sum_d<6>(acc, smem);
+    if (threadIdx.x == 0) {
+        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
+        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3]; o[4] = acc[4]; o[5] = acc[5];
+    }
+}
+
+// out[0..8] = {total, BCE_s, BCE_t, EmbLoss_s, EmbLoss_t, ||U_s||, ||I_s||, ||U_t||, ||I_t||} from the forward's partials (BCE: the mean over
+// the domain's rows; EmbLoss = (||U_d|| + ||I_d||) / B_d, recbole's EmbLoss over the gathered rows); out[9..12] (the coefficients) stay.
+// zero_a / zero_b: the long-segment counters of the duplicate applies behind this launch.
+__global__ __launch_bounds__(kBlock) void pair_finish_kernel(const double* __restrict__ partials, int nblocks, int64_t Bs, int64_t Bt,
+                                                             float alpha, float reg_s, float reg_t, float* __restrict__ out,
+                                                             unsigned* __restrict__ zero_a, unsigned* __restrict__ zero_b) {
+    __shared__ double smem[6 * (kBlock / 64)];
+    if (zero_a && threadIdx.x >= 64 && threadIdx.x < 68) zero_a[threadIdx.x - 64] = 0u;
+    if (zero_b && threadIdx.x >= 128 && threadIdx.x < 132) zero_b[threadIdx.x - 128] = 0u;
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
+        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) acc[j] += o[j];
+    }
+    block_sum_d<6>(acc, smem);
+    if (threadIdx.x == 0) {
+        const float bce_s = (float)(acc[0] / (double)Bs), bce_t = (float)(acc[1] / (double)Bt);
+        const float nus = (float)sqrt(acc[2]), nis = (float)sqrt(acc[3]), nut = (float)sqrt(acc[4]), nit = (float)sqrt(acc[5]);
+        const float emb_s = (nus + nis) / (float)Bs, emb_t = (nut + nit) / (float)Bt;
+        out[0] = alpha * (bce_s + reg_s * emb_s) + (1.0f - alpha) * (bce_t + reg_t * emb_t);
+        out[1] = bce_s; out[2] = bce_t; out[3] = emb_s; out[4] = emb_t;
+        out[5] = nus; out[6] = nis; out[7] = nut; out[8] = nit;
+    }
+}
+
+}  // namespace
+
+extern "C" int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int loss_kind, int opt, float* user_tab, float* user_m, float* user_v,
+                                             int64_t user_rows, float* item_tab, float* item_m, float* item_v, int64_t item_rows, int D,
+                                             const int64_t* su, const int64_t* si, const float* ys, int64_t B_s, const int64_t* tu,
+                                             const int64_t* ti, const float* yt, int64_t B_t, float alpha, float reg_s, float reg_t, float lr,
+                                             float beta1, float beta2, float eps, float weight_decay, int64_t* step_user_dev,
+                                             int64_t* step_item_dev, float* hp_dev, float* out16, float* GU, float* GI, uint32_t* keys,
+                                             uint32_t* perm, uint8_t* flags, uint32_t* heads, void* sort_ws, size_t sort_ws_bytes) {
+    CDR_CHECK_ARG(ctx && user_tab && item_tab && su && si && ys && tu && ti && yt && out16 && GU && GI && keys && perm && flags && heads && sort_ws);
+    CDR_CHECK_ARG((loss_kind == CDR_LOSS_MSE || loss_kind == CDR_LOSS_BCE) && D > 0 && (D & 3) == 0 && D <= 256 && B_s >= 1 && B_t >= 1);
+    CDR_CHECK_ARG(2 * (B_s + B_t) <= (int64_t)0x7FFFFFFF && user_rows > 0 && item_rows > 0);
+    CDR_CHECK_ARG((step_user_dev == nullptr) == (step_item_dev == nullptr));
+    CDR_CHECK_ARG(opt == 0 || (opt == 1 && user_m && user_v && item_m && item_v && step_user_dev && hp_dev));
+    CDR_CHECK_ARG(((uintptr_t)flags & 3) == 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t N = B_s + B_t;
+    const int lpr = cdr_lpr_for(D);
+    const float wreg_s = alpha * reg_s, wreg_t = (1.0f - alpha) * reg_t;
+    unsigned* cnt = (unsigned*)heads;
+    uint32_t* headsA = heads + 4;
+    uint32_t* headsB = headsA + (N / 2 + 1);           // (cnt[0..3] are cleared by pair_coef_kernel)
+    // ---- EmbLoss coefficients first (they do not need the sort) + the device-resident update counts
+    int ngrid = 0;
+    if (wreg_s != 0.f || wreg_t != 0.f) {
+        ngrid = grid_for((N + 7) / 8, kBlock / lpr);
+        cdr_time_scope ts(ctx, CDR_TAG_BATCH_NORMS, s);
+        DISPATCH_LPR(lpr, pair_norms_kernel<L><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, su, si, B_s, tu, ti, B_t, ctx->partials));
+        CDR_LAUNCH_CHECK();
+    }
+    pair_coef_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B_s, B_t, wreg_s, wreg_t, out16, step_user_dev, step_item_dev,
+                                                      opt == 1 ? hp_dev : nullptr, lr, beta1, beta2, cnt);
+    CDR_LAUNCH_CHECK();
+    // ---- one sort of both tables' keys: [su | tu] and key_base + [si | ti]
+    const unsigned hb = bits_for(user_rows) > bits_for(item_rows) ? bits_for(user_rows) : bits_for(item_rows);
+    CDR_CHECK_ARG(hb < 31);
+    const uint32_t key_base = 1u << hb;
+    {
+        size_t need = 0;
+        int rc = cdr_sort_workspace_bytes(2 * N, (int64_t)key_base * 2, &need);
+        if (rc) return rc;
+        CDR_CHECK_ARG(sort_ws_bytes >= need);
+        const size_t arr = ((size_t)(2 * N) * sizeof(uint32_t) + 255) & ~(size_t)255;
+        uint32_t* keys_in = (uint32_t*)sort_ws;
+        uint32_t* vals_in = (uint32_t*)((char*)sort_ws + arr);
+        void* tmp = (char*)sort_ws + 2 * arr;
+        size_t tmp_bytes = sort_ws_bytes - 2 * arr;
+        cdr_time_scope ts(ctx, CDR_TAG_SORT, s);
+        make_keys_pair_kernel<<<dim3(grid_for(2 * N, kBlock)), dim3(kBlock), 0, s>>>(su, B_s, tu, B_t, si, B_s, ti, B_t, key_base, keys_in, vals_in);
+        CDR_LAUNCH_CHECK();
+        CDR_HIP(sort_pairs(tmp, tmp_bytes, keys_in, keys, vals_in, perm, (size_t)(2 * N), hb + 1, s));
+    }
+    {
+        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
+        occ_flags_kernel<<<dim3(grid_for(2 * N, kBlock * kFlagIT)), dim3(kBlock), 0, s>>>(keys, perm, N, 2 * N, 4, flags, headsA, headsB, cnt);
+    }
+    CDR_LAUNCH_CHECK();
+    // ---- forward + single rows in place; the Adam scalars of the new counts come from hp_dev (apply_hp::dev)
+    apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, 1), hi = hu;
+    if (opt == 1) { hu.dev = hp_dev; hi.dev = hp_dev + 2; }
+    const tab_ptrs TU{user_tab, user_m, user_v}, TI{item_tab, item_m, item_v};
+    const int grid = grid_for(N, kBlock / lpr);
+    {
+        cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
+#define PP_ARGS loss_kind, TU, TI, D, su, si, ys, B_s, tu, ti, yt, B_t, (const uint32_t*)flags, alpha / (float)B_s, (1.0f - alpha) / (float)B_t, \
+                out16 + 9, hu, hi, GU, GI, ctx->partials
+        if (opt == 0) { DISPATCH_LPR(lpr, point_pair_fwd_apply_kernel<L, 0><<<dim3(grid), dim3(kBlock), 0, s>>>(PP_ARGS)); }
+        else { DISPATCH_LPR(lpr, point_pair_fwd_apply_kernel<L, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(PP_ARGS)); }
+#undef PP_ARGS
+    }
+    CDR_LAUNCH_CHECK();
+    // ---- every row with more than one occurrence: one update from the sum of its (complete) gradient rows
+    const dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, N, headsA, cnt, GU, N, N, nullptr, hu, 0},
+                               {item_tab, item_m, item_v, keys + N, perm + N, N, headsB, cnt + 1, GI, N, N, nullptr, hi, key_base}};
+    dups_plan pl;
+    int rc = dups_plan_make(ctx, D, sides, pl);
+    if (rc) return rc;
+    pair_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B_s, B_t, alpha, reg_s, reg_t, out16, pl.side[0].counters,
+                                                        pl.side[1].counters);
+    CDR_LAUNCH_CHECK();
+    return apply_dups_pair(ctx, s, opt, D, pl);
+}

@@ -1,5 +1,6 @@
 """Fused row-wise training steps: forward + backward + optimizer for one batch without table-sized gradients
-(FusedBPRStep: pairwise BPR; FusedPointStep: pointwise MSE / BCE; FusedMapStep: EMCDR's OVERLAP-phase mapping loss).
+(FusedBPRStep: pairwise BPR; FusedPointStep: pointwise MSE / BCE; FusedPointPairStep: CMF's two domains on shared tables;
+FusedMapStep: EMCDR's OVERLAP-phase mapping loss).
 
 This is the large-table counterpart of ``loss.backward(); optimizer.step()`` in the reference's loop
 (recbole_cdr/trainer/trainer.py:59-73 -> recbole ``Trainer._train_epoch``): dense ``[rows, D]`` gradients and a dense
@@ -562,6 +563,77 @@ class FusedPointStep:
                     B_.raw(self.keys[lo:lo + B]), B_.raw(self.perm[lo:lo + B]), B, B_.f32(G), B, B, B_.f32(coef), float(self.lr),
                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), st.step, None, int(base))
         return self.out6
+
+
+class FusedPointPairStep:
+    """CMF's BOTH-phase step (cmf.py:75-99): a source and a target pointwise batch on ONE user and ONE item table,
+    loss = alpha (BCE_s + reg_source EmbLoss_s) + (1 - alpha) (BCE_t + reg_target EmbLoss_t), and ONE update per touched row from the
+    sum of its two domains' contributions -- the reference's single Adam step (two FusedPointStep calls would update a row named by both
+    batches twice and advance each table twice).  One native call (cdr_point_step_fused_pair_dev) with the update counts on the device:
+    capturable in a hipGraph (``replayed`` keeps the host mirrors in step)."""
+
+    def __init__(self, user_table, item_table, max_source, max_target, alpha, reg_source, reg_target, opt='adam', lr=1e-3,
+                 betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, user_state=None, item_state=None, loss='bce'):
+        assert user_table.is_cuda and item_table.is_cuda, 'FusedPointPairStep needs ROCm device tensors'
+        assert user_table.shape[1] == item_table.shape[1]
+        self.U, self.I = user_table, item_table
+        self.D = user_table.shape[1]
+        if self.D % 4 != 0 or self.D > 256:
+            raise ValueError(f'FusedPointPairStep: D must be a multiple of 4 and <= 256, got {self.D}')
+        self.kind = B_.CDR_LOSS_MSE if loss == 'mse' else B_.CDR_LOSS_BCE
+        self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
+        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        self.alpha, self.reg_source, self.reg_target = float(alpha), float(reg_source), float(reg_target)
+        self.ustate = user_state if user_state is not None else RowwiseState(user_table, self.opt)
+        self.istate = item_state if item_state is not None else RowwiseState(item_table, self.opt)
+        dev = user_table.device
+        self.max_source, self.max_target = int(max_source), int(max_target)
+        Nm = self.max_source + self.max_target
+        self.GU = torch.empty(Nm, self.D, device=dev, dtype=torch.float32)
+        self.GI = torch.empty(Nm, self.D, device=dev, dtype=torch.float32)
+        self.out16 = torch.zeros(16, device=dev, dtype=torch.float32)
+        self.keys = torch.empty(2 * Nm, device=dev, dtype=torch.int32)       # one sort: user keys [su | tu], item keys [si | ti]
+        self.perm = torch.empty(2 * Nm, device=dev, dtype=torch.int32)
+        self.flags = torch.zeros(4 * Nm, device=dev, dtype=torch.uint8)      # {user, item, -, -} per joint row
+        words = ctypes.c_int64(0)
+        B_._check(B_.load().cdr_bpr_step_fused_heads_words(Nm, ctypes.byref(words)), 'cdr_bpr_step_fused_heads_words')
+        self.heads = torch.empty(int(words.value), device=dev, dtype=torch.int32)
+        rows = 2 << (max(user_table.shape[0], item_table.shape[0]) - 1).bit_length()
+        need = 0
+        # (the sort switches configuration at 2^18 keys: a short tail batch may need more scratch than a full one)
+        for n in {2 * Nm, min(2 * Nm, (1 << 18) - 1)}:
+            b = ctypes.c_size_t(0)
+            B_._check(B_.load().cdr_sort_workspace_bytes(n, rows, ctypes.byref(b)), 'cdr_sort_workspace_bytes')
+            need = max(need, int(b.value))
+        self.ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        self._hp_dev = torch.zeros(4, device=dev, dtype=torch.float32)
+
+    def step(self, su, si, ys, tu, ti, yt):
+        """su / si int64 [B_s], ys fp32 [B_s] (source rows); tu / ti int64 [B_t], yt fp32 [B_t] (target rows).  Returns out16 (view):
+        [0] total, [1] BCE_s, [2] BCE_t, [3] EmbLoss_s, [4] EmbLoss_t (unweighted parts), [5:9] the four batch norms."""
+        Bs, Bt = su.numel(), tu.numel()
+        if not (1 <= Bs <= self.max_source and 1 <= Bt <= self.max_target):
+            raise ValueError(f'FusedPointPairStep: batches of {Bs} + {Bt} rows, sized for 1..{self.max_source} + 1..{self.max_target}')
+        if si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
+            raise ValueError('FusedPointPairStep: ids and labels of a domain must have the same length')
+        us, its = self.ustate, self.istate
+        adam = self.opt == OPT_ADAM
+        B_.call('cdr_point_step_fused_pair_dev', B_.ctx(self.U.device), B_.stream(), self.kind, self.opt, B_.f32(us.table), B_.f32(us.exp_avg),
+                B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq), its.table.shape[0],
+                self.D, B_.i64(su), B_.i64(si), B_.f32(ys), Bs, B_.i64(tu), B_.i64(ti), B_.f32(yt), Bt, self.alpha, self.reg_source,
+                self.reg_target, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd),
+                B_.i64(us.step_dev), B_.i64(its.step_dev), B_.f32(self._hp_dev) if adam else None, B_.f32(self.out16), B_.f32(self.GU),
+                B_.f32(self.GI), B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws.numel())
+        if not torch.cuda.is_current_stream_capturing():       # (a capture enqueues nothing: the host counts advance per replay)
+            us.advance(device_bumped=True)
+            its.advance(device_bumped=True)
+        return self.out16
+
+    def replayed(self, n=1):
+        """Host bookkeeping of ``n`` hipGraph replays of ``step``: the update counts' host mirrors."""
+        for _ in range(n):
+            self.ustate.advance(device_bumped=True)
+            self.istate.advance(device_bumped=True)
 
 
 class KMajorPointStep:

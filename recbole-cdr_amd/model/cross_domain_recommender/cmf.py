@@ -1,6 +1,10 @@
 """CMF on libcdrhip -- same class contract as recbole_cdr/model/cross_domain_recommender/cmf.py:23-112.
 Both domains share one user and one item table; each domain's loss is one fused gather-dot-sigmoid-BCE(+EmbLoss)
-launch; scoring is the fp32-MFMA contraction over item rows [0, target_num_items)."""
+launch; scoring is the fp32-MFMA contraction over item rows [0, target_num_items).
+
+``fused_train_step`` (``optimizer_mode='rowwise'``): the BOTH-phase step without table-sized gradients -- fused.FusedPointPairStep, one
+update per touched row from the sum of both domains' contributions; ``adam='exact'`` puts the catch-up of the reference's dense Adam in
+front of it (fused.rowwise_catch_up)."""
 import torch
 import torch.nn as nn
 
@@ -24,6 +28,11 @@ class CMF(CrossDomainRecommender):
         self.user_embedding = nn.Embedding(self.total_num_users, self.embedding_size)
         self.item_embedding = nn.Embedding(self.total_num_items, self.embedding_size)
         self.apply(xavier_normal_initialization)
+        self.phase = 'BOTH'
+        self.__dict__['_dist_cfg'] = config['dist_group'] if 'dist_group' in config else None
+
+    def set_phase(self, phase):
+        self.phase = phase
 
     def _loss_and_prob(self, user, item, label, reg):
         return F_.PointGatherLoss.apply(B_.CDR_LOSS_BCE, self.user_embedding.weight, self.item_embedding.weight,
@@ -46,6 +55,113 @@ class CMF(CrossDomainRecommender):
             interaction[self.SOURCE_USER_ID], interaction[self.SOURCE_ITEM_ID], interaction[self.SOURCE_LABEL], self.lamda,
             interaction[self.TARGET_USER_ID], interaction[self.TARGET_ITEM_ID], interaction[self.TARGET_LABEL], self.gamma, self.alpha)
         return total
+
+    # ---- O(batch) training step (large tables) ------------------------------------------------------------------
+    _TABLES = ('user_embedding', 'item_embedding')
+
+    def _pair_fields(self, interaction):
+        fields = (self.SOURCE_USER_ID, self.SOURCE_ITEM_ID, self.SOURCE_LABEL, self.TARGET_USER_ID, self.TARGET_ITEM_ID, self.TARGET_LABEL)
+        missing = [f for f in fields if f not in interaction]
+        if missing:
+            raise ValueError(f'CMF.fused_train_step trains on BOTH-phase batches (source and target rows); the {self.phase} batch '
+                             f'has no {", ".join(missing)}')
+        return [interaction[f].reshape(-1) for f in fields]
+
+    def fused_train_step(self, interaction, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam='lazy'):
+        """``calculate_loss -> backward -> optimizer.step`` on a BOTH-phase batch without table-sized gradients or a dense optimizer
+        sweep (fused.FusedPointPairStep on the shared tables): what ``CrossDomainTrainer`` runs when ``config['optimizer_mode'] ==
+        'rowwise'``.  Same loss and per-row gradients as ``calculate_loss``; a row named by both domains' batches gets ONE update from
+        their sum, and each table advances once per step, as under the reference's single Adam.  Returns the total loss (device [1]).
+
+        ``adam='lazy'`` (default): rows the batch does not touch do not move.  ``adam='exact'``: the reference's dense Adam -- one catch-up
+        launch in front of every step (fused.rowwise_catch_up) replays the gradient-free updates the step's rows missed; the tables hold
+        what ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run.  One mode per model."""
+        from ...fused import FusedPointPairStep, RowwiseState, OPT_ADAM, OPT_SGD, rowwise_catch_up
+        if adam not in ('lazy', 'exact'):
+            raise ValueError(f"adam must be 'lazy' or 'exact', got {adam!r}")
+        exact = adam == 'exact'
+        if exact and opt != 'adam':
+            raise ValueError(f"adam='exact' is the reference's dense Adam: it needs opt='adam', got {opt!r}")
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            raise ValueError("CMF.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
+        su, si, ys, tu, ti, yt = self._pair_fields(interaction)
+        cache = self.__dict__.setdefault('_fused', {'states': {}, 'steps': {}})
+        for name, st in cache['states'].items():
+            if st.exact != exact:
+                raise ValueError(f"{name} was trained with adam={'exact' if st.exact else 'lazy'!r}; one row-wise Adam mode per model")
+        code = OPT_ADAM if opt == 'adam' else OPT_SGD
+        for name in self._TABLES:
+            if name not in cache['states']:
+                cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code, exact=exact)
+        us, its = cache['states']['user_embedding'], cache['states']['item_embedding']
+        Bs, Bt = su.numel(), tu.numel()
+        step = cache['steps'].get('pair')
+        hp = dict(opt=opt, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if step is None or step.max_source < Bs or step.max_target < Bt or step.hp != hp:
+            ms, mt = (Bs, Bt) if step is None else (max(Bs, step.max_source), max(Bt, step.max_target))
+            step = FusedPointPairStep(self.user_embedding.weight.data, self.item_embedding.weight.data, ms, mt, self.alpha, self.lamda,
+                                      self.gamma, user_state=us, item_state=its, **hp)
+            step.hp = hp
+            cache['steps']['pair'] = step
+        ys = ys if ys.dtype == torch.float32 else ys.float()
+        yt = yt if yt.dtype == torch.float32 else yt.float()
+        if exact:
+            rowwise_catch_up([(us, [su, tu]), (its, [si, ti])], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        return step.step(su, si, ys, tu, ti, yt)[:1]
+
+    def fused_graph_key(self, interaction, adam='lazy'):
+        """Hashable tag of the launches ``fused_train_step(interaction)`` would make, or None when they must not be captured in a hipGraph.
+        The step keeps its update counts on the device, so it is capturable while its two-table sort (2 (B_s + B_t) keys) stays below the
+        size EMCDR.fused_graph_key refuses to capture (rocPRIM's Onesweep configuration: its temporary-storage resets do not survive a
+        replay)."""
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            return None
+        if self.SOURCE_USER_ID not in interaction or self.TARGET_USER_ID not in interaction:
+            return None
+        Bs, Bt = interaction[self.SOURCE_USER_ID].numel(), interaction[self.TARGET_USER_ID].numel()
+        if 2 * (Bs + Bt) > 3 * 65536:
+            return None
+        return ('cmf', Bs, Bt, adam)
+
+    def fused_replayed(self, n=1):
+        """Host bookkeeping of ``n`` hipGraph replays of ``fused_train_step`` (the update counts' host mirrors)."""
+        from ...fused import rowwise_bound_lag
+        st = self.__dict__['_fused']['steps']['pair']
+        st.replayed(n)
+        for s_ in (st.ustate, st.istate):
+            rowwise_bound_lag(s_)                               # (exact mode without the moving window only)
+
+    def fused_sync(self):
+        """``fused_train_step(adam='exact')``: bring every row of both tables to its update count -- the tables and moments then equal
+        the reference's dense Adam (before evaluation, checkpoints, the end of training).  Lazy mode: nothing to do."""
+        cache = self.__dict__.get('_fused')
+        if cache:
+            for st in cache['states'].values():
+                if st.exact:
+                    st.flush()
+
+    def fused_optimizer_state(self):
+        """Row-wise optimizer state of ``fused_train_step`` for a checkpoint: per table the moments and the update count."""
+        cache = self.__dict__.get('_fused')
+        if not cache:
+            return {}
+        self.fused_sync()
+        return {'tables': {k: {'step': st.step, 'exp_avg': st.exp_avg, 'exp_avg_sq': st.exp_avg_sq} for k, st in cache['states'].items()}}
+
+    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
+        """Restore what ``fused_optimizer_state`` returned (before the next ``fused_train_step``).  ``adam``: the mode training goes on
+        with; in exact mode every row is current at its table's update count (the checkpoint was written flushed)."""
+        from ...fused import RowwiseState, OPT_ADAM, OPT_SGD
+        cache = self.__dict__.setdefault('_fused', {'states': {}, 'steps': {}})
+        code = OPT_ADAM if opt == 'adam' else OPT_SGD
+        for name, rec in state.get('tables', {}).items():
+            st = cache['states'].get(name)
+            if st is None:
+                st = cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code, exact=adam == 'exact')
+            st.step = int(rec['step'])
+            if rec['exp_avg'] is not None:
+                st.exp_avg.copy_(rec['exp_avg']); st.exp_avg_sq.copy_(rec['exp_avg_sq'])
+            st.restored()
 
     @torch.no_grad()
     def predict(self, interaction):
