@@ -15,6 +15,12 @@ region.  With N>1 the tables are row-sharded (row r on rank r % N) and every ran
 
 `--workload c1|c2|c3|c4` run BASELINE configs[0..3] (CMF and EMCDR at ml-1m->ml-100k sizes, CoNet Amazon sizes, BiTGCF Douban sizes)
 through the drop-in class contract (autograd + dense Adam in torch.optim.Adam's semantics), the whole step replayed as one hipGraph.
+
+A plain run does what its headline figure needs and nothing else: set-up, the warm-up steps, the timed steps, `--dump-outputs`, the
+line.  `--full` adds everything else bench.py measures or checks: the kernel brackets and rooflines (single-stream repeat of the timed
+steps, gather leg), the trained-state checksums, the OVERLAP / per-positive / synthetic-grid / full-sort legs, the C1-C4 legs, the
+end-to-end and ingest legs, the CPU baselines and, with N > 1, the relayout and the second C5 layout.  The `--no-*` options below
+leave legs out of a `--full` run.
 """
 import argparse
 import json
@@ -197,6 +203,8 @@ def parse():
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--workload', default='c5', choices=['c5', 'c1', 'c2', 'c3', 'c4'])
+    ap.add_argument('--full', action='store_true', help='also run every leg, baseline, roofline and check behind the headline (module docstring); '
+                                                        'without it the run times the headline steps alone')
     ap.add_argument('--dense-adam', action='store_true', help='c3: the literal O(table) dense Adam sweep instead of its deferred row-wise form')
     ap.add_argument('--batch', type=int, default=1 << 20, help='triples per domain per rank per step (c5)')
     ap.add_argument('--opt', default='adam', choices=['adam', 'sgd'])
@@ -521,7 +529,7 @@ def run_c5(args, world, rank, dev):
         # before anything else runs a step on these tables (the single-stream repeat below, the other legs)
         dumped = dump_last_step(args.dump_outputs, steps, tabs, batches[(args.steps - 1) % pool], D, B)
     single = None
-    if two_streams:
+    if two_streams and args.full:
         for i in range(2):
             one_step(i, serial=True)
         B_.timing_enable(dev, args.steps * 2 * 5 + 16)
@@ -532,7 +540,7 @@ def run_c5(args, world, rank, dev):
         single = (time.perf_counter() - t1) / args.steps
     timings = {}
     collected = B_.timing_collect(dev)
-    if dim_mode and not dom_groups and not args.no_pipeline:
+    if dim_mode and not dom_groups and not args.no_pipeline and args.full:
         # the two domain streams ran side by side in the timed region, so its per-kernel event times include sharing the
         # GPU with the other domain's kernels; the roofline figures come from two extra steps with the domains serialised
         prof = {d: st._prof for d, st in steps.items()}
@@ -575,12 +583,14 @@ def run_c5(args, world, rank, dev):
     }
     if args.dump_outputs:
         result['dumped_outputs'] = dumped
-    if world == 1 and not sharded:
+    if world == 1 and not sharded and args.full:
         # the trained tables as exact fp64 sums (after the timed region and its single-stream repeat, before any other leg trains on them):
         # two invocations with the same flags must print the same digits
         result['state_checksum'] = {k_: repr(exact_sum(v_)) for k_, v_ in tabs.items()}
+    if two_streams:
+        result['config']['streams'] = 'the two domain steps of a step on two HIP streams (CrossDomainTrainer parallel_domains)' + \
+                                      ('; kernel brackets / roofline from single-stream steps' if single is not None else '')
     if single is not None:
-        result['config']['streams'] = 'the two domain steps of a step on two HIP streams (CrossDomainTrainer parallel_domains); kernel brackets / roofline from single-stream steps'
         result['single_stream'] = {'ms_per_step': single * 1e3, 'value': 2 * B / single, 'unit': 'interactions/s', 'steps': args.steps,
                                    'what': 'the same steps with the TARGET domain step enqueued behind the SOURCE domain step on one stream, right after the '
                                            'timed region: the per-kernel HIP-event brackets (kernels, roofline) are taken here, with every kernel running alone'}
@@ -619,7 +629,9 @@ def run_c5(args, world, rank, dev):
                               'note': 'bytes: everything the data path sends; ms: HIP-event time of the collectives that are bracketed (dim: the id '
                                       'all-gather, which runs prefetched on a side stream -- the score all-reduce is asynchronous under the id sort and '
                                       'not bracketed; row: the 4 all-to-alls per domain, both domain streams summed)'}
-    if rank == 0 and dim_mode:
+    if sharded and int(os.environ.get('CDR_BENCH_SHARED_GPU', '0')):
+        result['data'] = 'synthetic; FUNCTIONAL CHECK ONLY: all ranks share cuda:0 over gloo'
+    if rank == 0 and dim_mode and args.full:
         # every rank walks its group's GLOBAL batch on [rows, Ds] tables: the kernels are the single-GPU ones at width Ds
         st0 = steps['source']
         gsz = (world // 2) if dom_groups else world
@@ -651,9 +663,7 @@ def run_c5(args, world, rank, dev):
         result['kernels'] = [{'kernel': k, 'avg_ms': mean_ms(k)} for k in
                              ('bpr_fwd_apply_kernel', 'batch_norms_kernel', 'occ_flags_kernel', 'bpr_fwd_grad_kernel', 'bpr_partial_diff_kernel',
                               'bpr_grad_from_diff_kernel', 'sort_ids', 'rowwise_apply_kernel(users)', 'rowwise_apply_kernel(items)') if timings.get(k)]
-        if int(os.environ.get('CDR_BENCH_SHARED_GPU', '0')):
-            result['data'] = 'synthetic; FUNCTIONAL CHECK ONLY: all ranks share cuda:0 over gloo'
-    if rank == 0 and sharded and not dim_mode:
+    if rank == 0 and sharded and not dim_mode and args.full:
         # N > 1: the exchange adds all-to-alls between the kernels; the kernels themselves are the 1-GPU ones.  Buckets
         # are balanced in expectation (uniform ids), so one fwd_grad launch sees ~B triples: 3 rows read, GU + 2 GI rows
         # written (scatter mode).  Rank 0's own HIP-event durations.
@@ -677,11 +687,9 @@ def run_c5(args, world, rank, dev):
         result['kernels'] = [{'kernel': k, 'avg_ms': mean_ms(k)} for k in
                              (kname, 'batch_norms_kernel', 'occ_flags_kernel', 'rowwise_apply_kernel(users)', 'rowwise_apply_kernel(items)', 'sort_ids')
                              if timings.get(k)]
-        if int(os.environ.get('CDR_BENCH_SHARED_GPU', '0')):
-            result['data'] = 'synthetic; FUNCTIONAL CHECK ONLY: all ranks share cuda:0 over gloo'
 
     try:                                          # a failure in this extra leg must not cost the headline measurement
-        if dim_mode:
+        if dim_mode and args.full:
             # phase switch: the OVERLAP step and the full-sort run on ROW shards (ids / k candidates are all they exchange there),
             # so the user tables with their Adam moments and the target item table are transposed once (one all-to-all each)
             from types import SimpleNamespace
@@ -801,7 +809,7 @@ def run_c5(args, world, rank, dev):
         result.setdefault('leg_errors', {})['relayout_overlap'] = repr(e)[:500]
         print('bench: relayout_overlap leg failed: %r' % (e,), file=sys.stderr)
     # ---- roofline of the dominant kernel(s): algorithmic bytes / HIP-event time of each native call --------------
-    if rank == 0 and not sharded:
+    if rank == 0 and not sharded and args.full:
         med_ms = lambda k: (sorted(timings[k])[len(timings[k]) // 2]) if timings.get(k) else 0.0
         fused = bool(getattr(steps['source'], 'fuse_singles', False))
         nmom = 6 if args.opt == 'adam' else 2
@@ -861,7 +869,7 @@ def run_c5(args, world, rank, dev):
                               'design_frac': dom_k['design_GBps'] / HBM_PEAK_GBS,
                               'traffic': pmc_traffic(dom_k['kernel'].split(' ')[0]),
                               'rocprof': 'profiles/r05_bench_c5_headline_kernel_stats.csv = rocprofv3 --kernel-trace --stats of `python bench.py --headline-only` '
-                                         '(single stream, this kernel on the headline batch only; the default command also launches it on the k = 4 and synthetic-grid '
+                                         '(single stream, this kernel on the headline batch only; a --full run also launches it on the k = 4 and synthetic-grid '
                                          'batches and beside the other domain\'s kernels, so ITS stats file averages over several situations)'}
         result['kernels'] = kernels
         result['batch_occupancy'] = {'triples': B, 'distinct_user_rows': du, 'distinct_item_rows': di, 'single_user_rows': su_, 'single_item_rows': si_}
@@ -1178,7 +1186,7 @@ def run_c5(args, world, rank, dev):
     except Exception as e:  # noqa: BLE001
         result.setdefault('leg_errors', {})['fullsort'] = repr(e)[:500]
         print('bench: fullsort leg failed: %r' % (e,), file=sys.stderr)
-    if world == 1 and not sharded:
+    if world == 1 and not sharded and args.full:
         # ... and once more after every other leg has trained on the same tables (OVERLAP steps, k-major, Zipf and small batches, graphs):
         # all of them run a fixed number of steps, so this too is the same in every invocation with the same flags
         result['state_checksum_after_all_legs'] = {k_: repr(exact_sum(v_)) for k_, v_ in tabs.items()}
@@ -1462,7 +1470,7 @@ def run_model_workload(args, world, rank, dev):
                          'trainer_steps': None if trainer is None else dict(stats, warmup_steps_run=args.steps, optimizer=type(opt).__name__,
                                                                             timed='one fit() = one shuffled epoch of exactly --steps full batches, sampler + loader + step + loss read-back')},
               'final_loss': float(loss.sum())}
-    if world == 1 and trainer is not None:
+    if world == 1 and trainer is not None and args.full:
         # the trained state as exact fp64 sums (after the timed region): two invocations with the same flags must print the same digits
         if hasattr(model, 'sync_tables'):
             model.sync_tables()
@@ -1476,7 +1484,9 @@ def run_model_workload(args, world, rank, dev):
     step_s = dt / args.steps
     D = cfg['embedding_size'] if 'embedding_size' in cfg else cfg['source_embedding_size']
     nu, ni = ds.num_total_user, ds.num_total_item
-    if args.workload == 'c3':
+    if not args.full:
+        roof = None                        # (the rooflines, their kernel brackets and cache-rate measurements are --full's)
+    elif args.workload == 'c3':
         dims = [2 * D] + list(cfg['mlp_hidden_size'])
         fwd_flop_row = 8 * sum(a * b for a, b in zip(dims[:-1], dims[1:]))          # 4 products per cross unit, 2 flop per MAC
         flops = 3.0 * fwd_flop_row * rows_per_step                                   # forward + data gradient + weight gradient
@@ -1556,7 +1566,8 @@ def run_model_workload(args, world, rank, dev):
                 'cache_roof_record': roof_rec, 'product_gather_kernel_GBs_measured_in_run': gather_bw, 'launches_per_step': n_launch,
                 'frac_of_hbm_peak_nominal': gbs / HBM_PEAK_GBS,
                 'what': 'gather (%d B per row) + dense Adam over the parameters that received a gradient (7 x 4 B per element)' % per_row, 'traffic': None}
-    result['roofline'] = roof
+    if roof is not None:
+        result['roofline'] = roof
     if rowshard is not None:
         p_ = rowshard.part
         D_, L_ = cfg['embedding_size'], cfg['n_layers']
@@ -2066,7 +2077,7 @@ def run_replicas(args, world, rank, dev, attempts):
 
 def main():
     args = parse()
-    if args.headline_only:
+    if args.headline_only or not args.full:
         args.no_map = args.no_extra_legs = args.no_fullsort = args.no_config_legs = args.no_cpu_baseline = args.no_e2e = args.no_ingest = True
     # the contract is ONE JSON line on stdout; RCCL and gloo print banners through C stdio (some only when the process exits),
     # so with a process group everything else written to fd 1 is sent to stderr and the line goes to the saved descriptor
@@ -2086,7 +2097,7 @@ def main():
     if args.only_ingest:
         print(json.dumps({'ingest': ingest_leg(args, dev)}), flush=True)
         return
-    if args.workload == 'c5' and (world > 1 or args.force_shard) and not args.single_layout:
+    if args.workload == 'c5' and (world > 1 or args.force_shard) and not args.single_layout and args.full:
         # N > 1: BOTH layouts of the C5 tables in one record -- north_star's row shard (rows r % N, row / gradient-row all-to-all)
         # and the dimension shard (D/N columns of every row, ids all-gathered, one partial score per triple all-reduced) -- so
         # that one hardware run shows them side by side.  The headline fields are those of --shard (default row: north_star's).
@@ -2119,7 +2130,7 @@ def main():
         except LayoutUnavailable as e:
             result = run_replicas(args, world, rank, dev, e.attempts)
         if world == 1 and not args.no_config_legs:
-            # BASELINE configs[0..3] behind the headline, compact: so that ONE default invocation covers all five configurations.
+            # BASELINE configs[0..3] behind the headline, compact: so that ONE --full invocation covers all five configurations.
             # Each leg is the full `--workload cN` measurement at 200 steps (they take 0.03-1 ms each) with a 3-second CPU sample.
             import copy
             import gc
@@ -2190,7 +2201,7 @@ def main():
             result['cpu_baseline'] = cpu_baseline(args)
         from recbole_cdr_amd import functional as F_
         result['deterministic_backward'] = bool(F_.deterministic())      # CDR_DETERMINISTIC=1: the drop-in losses' dense gradients without float atomics
-        if not result['deterministic_backward']:
+        if not result['deterministic_backward'] and args.full:
             # which legs of THIS line are not bit-reproducible run to run: only the drop-in dense backward of the small configurations (fp32
             # atomics into dense gradients, as torch's own embedding backward); every O(batch) step (the headline, the sharded layouts, the
             # medium / k-major / pointwise steps, the OVERLAP step), the full-sort legs and the ingest sum in a fixed order

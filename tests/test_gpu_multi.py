@@ -584,7 +584,7 @@ def _bench_line_and_detail(p, tmp_path):
 def test_bench_multi_rank_line_contract(world, extra, tmp_path):
     """`bench.py --gpus N` as the driver launches it (torch.distributed.run, one rank per process) -- here with every rank on
     cuda:0 over gloo (CDR_BENCH_SHARED_GPU=1, small tables): stdout is exactly ONE JSON line from rank 0 with the contract's
-    keys, the whole-job value, a roofline and an exchange object; the other legs (OVERLAP step, sharded full-sort) ran."""
+    keys, the whole-job value, a roofline and an exchange object; with --full the other legs (OVERLAP step, sharded full-sort) ran."""
     import json
     import os
     import socket
@@ -595,7 +595,7 @@ def test_bench_multi_rank_line_contract(world, extra, tmp_path):
     env = dict(os.environ, CDR_BENCH_SHARED_GPU='1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={world}', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '3', '--warmup', '2',
-           '--users', '400001', '--items-per-domain', '100000', '--batch', '8192', '--detail-file', str(tmp_path / 'detail.json')] + extra
+           '--users', '400001', '--items-per-domain', '100000', '--batch', '8192', '--full', '--detail-file', str(tmp_path / 'detail.json')] + extra
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line, d = _bench_line_and_detail(p, tmp_path)

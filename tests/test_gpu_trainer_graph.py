@@ -690,8 +690,8 @@ def _bench_c3_state(extra=(), env=None):
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         detail = os.path.join(tmp, 'detail.json')
-        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--workload', 'c3', '--no-cpu-baseline', '--no-fullsort', '--steps', '40', '--warmup', '4',
-               '--detail-file', detail] + list(extra)
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--workload', 'c3', '--full', '--no-cpu-baseline', '--no-fullsort', '--steps', '40',
+               '--warmup', '4', '--detail-file', detail] + list(extra)
         p = subprocess.run(cmd, cwd=root, env=dict(os.environ, **(env or {})), capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-3000:]
         line = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])          # the bounded contract line ...
@@ -732,7 +732,7 @@ def test_headline_step_trains_the_same_tables_in_every_process_and_stream_layout
     for extra in ([], [], ['--single-stream']):
         with tempfile.TemporaryDirectory() as tmp:
             detail = os.path.join(tmp, 'detail.json')
-            cmd = [sys.executable, os.path.join(root, 'bench.py'), '--headline-only', '--steps', '6', '--warmup', '2', '--users', '2000001',
+            cmd = [sys.executable, os.path.join(root, 'bench.py'), '--headline-only', '--full', '--steps', '6', '--warmup', '2', '--users', '2000001',
                    '--items-per-domain', '300000', '--batch', '262144', '--detail-file', detail] + extra
             p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
             assert p.returncode == 0, p.stderr[-3000:]

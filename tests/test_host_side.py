@@ -302,6 +302,30 @@ def test_bench_line_builder_keeps_the_driver_contract(bloat, tmp_path, capsys):
     assert full['configs']['c3']['ms_per_step'] == 0.177 and len(full['synthetic_grid']) == 6 and full['roofline']['traffic']['bytes'] > 0
 
 
+def test_bench_line_builder_takes_a_plain_run(tmp_path, capsys, monkeypatch):
+    """A plain bench.py run (no --full, the default) has the contract keys and none of the legs, rooflines or baselines: the line and the
+    detail file carry it as it is."""
+    import json
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1'])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--full'])
+    assert bench.parse().full is True
+    res = {k: v for k, v in _fake_bench_result(1).items() if k in bench.CONTRACT_KEYS + ('config', 'final_loss', 'bench_wall_s')}
+    bench.emit(res, detail_dir=str(tmp_path))
+    out = capsys.readouterr()
+    assert out.err == '' and len(out.out.splitlines()) == 1
+    d = json.loads(out.out)
+    for k in bench.CONTRACT_KEYS:
+        assert d[k] == res[k], k
+    assert 'roofline' not in d and 'cpu_baseline' not in d and 'vs_cpu' not in d and d['bench_wall_s'] == res['bench_wall_s']
+    assert json.load(open(tmp_path / bench.DETAIL_FILE)) == res
+
+
 def test_filed_bench_lines_of_this_round_parse():
     """Every `profiles/r05_bench*_line.json` (the last stdout line of a bench.py run on the GPU box, filed as printed) is one bounded
     JSON object with the contract's keys."""

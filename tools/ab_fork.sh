@@ -2,8 +2,8 @@ ulimit -c 0
 cd /root/repo
 O=gpurun_out/fork; mkdir -p $O
 for f in 1 0; do
-  CDR_STEP_FORK=$f python bench.py --no-cpu-baseline --no-fullsort --no-config-legs --no-e2e --steps 30 --warmup 5 > $O/two_$f.json 2> $O/two_$f.err
-  CDR_STEP_FORK=$f python bench.py --no-cpu-baseline --no-fullsort --no-config-legs --no-e2e --single-stream --steps 30 --warmup 5 > $O/one_$f.json 2> $O/one_$f.err
+  CDR_STEP_FORK=$f python bench.py --full --no-cpu-baseline --no-fullsort --no-config-legs --no-e2e --steps 30 --warmup 5 > $O/two_$f.json 2> $O/two_$f.err
+  CDR_STEP_FORK=$f python bench.py --full --no-cpu-baseline --no-fullsort --no-config-legs --no-e2e --single-stream --steps 30 --warmup 5 > $O/one_$f.json 2> $O/one_$f.err
 done
 python - <<'PY'
 import json
