@@ -60,3 +60,40 @@ def apply_fp64(state, part, D, opt, lr, wd, t, b1=0.9, b2=0.999, eps=1e-8):
     eT = torch.maximum(hi - T, T - lo) + K_ADAM * U32 * torch.maximum(hi.abs(), lo.abs())
     wn = w - T
     return {'w': (wn, eT + ulp32(wn)), 'm': (m, em), 'v': (v, ev)}
+
+
+def adam_idle_fp64(state, err, t, lr, wd=0.0, b1=0.9, b2=0.999, eps=1e-8):
+    """One gradient-free update (number t) of torch.optim.Adam in float64 -- what a row without a gradient goes through in the dense
+    sweep and in the deferred form's replay -- from a REFERENCE state that already carries first-order bounds.  ``state`` / ``err``:
+    {'w', 'm', 'v'} float64 tensors and their bounds.  The per-update terms are those of apply_fp64 with G = 0 (G = wd w when wd != 0),
+    the input bounds propagated: e_m <- b1 e_m + ..., e_v <- b2 e_v + ..., e_w <- e_w + (the update term's bound) + ulp."""
+    lr, wd, b1, b2, eps = f32(lr), f32(wd), f32(b1), f32(b2), f32(eps)
+    w, m0, v0 = state['w'], state['m'], state['v']
+    ew, em0, ev0 = err['w'], err['m'], err['v']
+    if wd:
+        G = wd * w
+        eg = wd * ew + U32 * G.abs()
+    else:
+        G = torch.zeros_like(w)
+        eg = torch.zeros_like(w)
+    m = b1 * m0 + (1 - b1) * G
+    v = b2 * v0 + (1 - b2) * G * G
+    em = b1 * em0 + (1 - b1) * eg + 3 * U32 * (m0.abs() + G.abs() + m.abs()) + ulp32(m)
+    ev = b2 * ev0 + (1 - b2) * (2 * G.abs() * eg + eg * eg) + 4 * U32 * v + ulp32(v)
+    step_size = lr / (1 - b1 ** t)
+    c2 = 1.0 / (1 - b2 ** t) ** 0.5
+    T = step_size * m / (v.sqrt() * c2 + eps)
+    den_lo = (v - ev).clamp(min=0).sqrt() * c2 + eps
+    den_hi = (v + ev).sqrt() * c2 + eps
+    hi = step_size * torch.maximum((m + em) / den_lo, (m + em) / den_hi)
+    lo = step_size * torch.minimum((m - em) / den_lo, (m - em) / den_hi)
+    eT = torch.maximum(hi - T, T - lo) + K_ADAM * U32 * torch.maximum(hi.abs(), lo.abs())
+    wn = w - T
+    return {'w': wn, 'm': m, 'v': v}, {'w': ew + eT + ulp32(wn), 'm': em, 'v': ev}
+
+
+def adam_replay_fp64(state, err, t_from, n, lr, wd=0.0, b1=0.9, b2=0.999, eps=1e-8):
+    """adam_idle_fp64 over updates t_from + 1 .. t_from + n, each with its own bias corrections."""
+    for t in range(t_from + 1, t_from + n + 1):
+        state, err = adam_idle_fp64(state, err, t, lr, wd, b1, b2, eps)
+    return state, err
