@@ -316,9 +316,8 @@ class NativeDimOps:
             us.advance(); its.advance()
             B_.call('cdr_bpr_step_from_diff', B_.ctx(fs.U.device), B_.stream(), fs.opt, B_.f32(us.table), B_.f32(us.exp_avg), B_.f32(us.exp_avg_sq),
                     B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq), fs.D, B_.i64(uid), B_.i64(pid), B_.i64(nid), uid.numel(),
-                    float(fs.gamma), float(fs.reg_weight), float(fs.lr), float(fs.betas[0]), float(fs.betas[1]), float(fs.eps), float(fs.wd),
-                    us.step, its.step, B_.f32(diff), int(fs._key_base.value), B_.f32(fs.out6), B_.f32(fs.GU), B_.f32(fs.GP), B_.raw(fs.keys),
-                    B_.raw(fs.perm), B_.raw(fs.flags), B_.raw(fs.heads))
+                    float(fs.gamma), float(fs.reg_weight), *fs._hp(), us.step, its.step, B_.f32(diff), int(fs._key_base.value), B_.f32(fs.out6),
+                    B_.f32(fs.GU), B_.f32(fs.GP), B_.raw(fs.keys), B_.raw(fs.perm), B_.raw(fs.flags), B_.raw(fs.heads))
             return fs.out6
         B_.call('cdr_bpr_grad_from_diff', B_.ctx(fs.U.device), B_.stream(), B_.f32(fs.U), B_.f32(fs.I), fs.D, B_.i64(uid),
                 B_.i64(pid), B_.i64(nid), uid.numel(), float(fs.gamma), float(fs.reg_weight), B_.f32(diff), B_.f32(fs.out6),
@@ -363,9 +362,8 @@ class NativePointDimOps(NativeDimOps):
             us.advance(); its.advance()
             B_.call('cdr_point_step_from_dot', B_.ctx(fs.U.device), B_.stream(), fs.kind, fs.opt, B_.f32(us.table), B_.f32(us.exp_avg),
                     B_.f32(us.exp_avg_sq), B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq), fs.D, B_.i64(uid), B_.i64(iid),
-                    B_.f32(label), uid.numel(), float(fs.reg_weight), float(fs.lr), float(fs.betas[0]), float(fs.betas[1]), float(fs.eps),
-                    float(fs.wd), us.step, its.step, B_.f32(dot), int(fs._key_base.value), B_.f32(fs.out6), B_.f32(fs.GU), B_.f32(fs.GI),
-                    B_.raw(fs.keys), B_.raw(fs.perm), B_.raw(fs.flags), B_.raw(fs.heads))
+                    B_.f32(label), uid.numel(), float(fs.reg_weight), *fs._hp(), us.step, its.step, B_.f32(dot), int(fs._key_base.value),
+                    B_.f32(fs.out6), B_.f32(fs.GU), B_.f32(fs.GI), B_.raw(fs.keys), B_.raw(fs.perm), B_.raw(fs.flags), B_.raw(fs.heads))
             return fs.out6
         B_.call('cdr_point_grad_from_dot', B_.ctx(fs.U.device), B_.stream(), fs.kind, B_.f32(fs.U), B_.f32(fs.I), fs.D, B_.i64(uid),
                 B_.i64(iid), B_.f32(label), uid.numel(), float(fs.reg_weight), B_.f32(dot), B_.f32(fs.out6), B_.f32(fs.GU), B_.f32(fs.GI))

@@ -141,21 +141,68 @@ def rowwise_catch_up(tables, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay
     del keep
 
 
-class FusedBPRStep:
+def _sort_workspace_bytes(n_keys, rows):
+    need = ctypes.c_size_t(0)
+    B_._check(B_.load().cdr_sort_workspace_bytes(n_keys, rows, ctypes.byref(need)), 'cdr_sort_workspace_bytes')
+    return int(need.value)
+
+
+class _Step:
+    """What every step class keeps: the optimizer settings (and their native-call form) and the host side of a hipGraph replay."""
+
+    def __init__(self, opt, lr, betas, eps, weight_decay):
+        self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
+        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+
+    def _hp(self):
+        """(lr, beta1, beta2, eps, weight_decay) in the order the native calls take them."""
+        return tuple(map(float, (self.lr, self.betas[0], self.betas[1], self.eps, self.wd)))
+
+    def replayed(self, n=1):
+        """Host bookkeeping of ``n`` hipGraph replays of a step whose update counts live on the device: their host mirrors."""
+        for _ in range(n):
+            for st in self._states():
+                st.advance(device_bumped=True)
+
+
+class _TwoTableStep(_Step):
+    """What the steps on one (user table, item table) pair share: the tables, one ``RowwiseState`` per table (the caller's, or a fresh
+    one) and the sizing of the scratch buffers."""
+
+    def __init__(self, user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state):
+        assert user_table.is_cuda and item_table.is_cuda, f'{type(self).__name__} needs ROCm device tensors'
+        assert user_table.shape[1] == item_table.shape[1]
+        super().__init__(opt, lr, betas, eps, weight_decay)
+        self.U, self.I = user_table, item_table
+        self.D = user_table.shape[1]
+        self.ustate = user_state if user_state is not None else RowwiseState(user_table, self.opt)
+        self.istate = item_state if item_state is not None else RowwiseState(item_table, self.opt)
+        self._sort_rows = 2 << (max(user_table.shape[0], item_table.shape[0]) - 1).bit_length()
+
+    def _states(self):
+        return self.ustate, self.istate
+
+    def _sort_workspace(self, *n_keys):
+        """(uint8 scratch, its size in bytes) of the two-table id sort: enough for each of the key counts given."""
+        need = max(_sort_workspace_bytes(n, self._sort_rows) for n in n_keys)
+        return torch.empty(need, device=self.U.device, dtype=torch.uint8), need
+
+    def _single_row_buffers(self, n):
+        """(flags, heads) of the forward kernels that update single-occurrence rows themselves: four flag bytes per batch row."""
+        words = ctypes.c_int64(0)
+        B_._check(B_.load().cdr_bpr_step_fused_heads_words(n, ctypes.byref(words)), 'cdr_bpr_step_fused_heads_words')
+        return (torch.zeros(4 * n, device=self.U.device, dtype=torch.uint8),
+                torch.empty(int(words.value), device=self.U.device, dtype=torch.int32))
+
+
+class FusedBPRStep(_TwoTableStep):
     """One object per (user table, item table) pair; buffers are sized for ``max_batch`` triples and reused."""
 
     def __init__(self, user_table, item_table, max_batch, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, gamma=1e-10, reg_weight=0.0, user_state=None, item_state=None, fuse_singles=True, device_counts=True,
                  id_path='auto'):
-        assert user_table.is_cuda and item_table.is_cuda, 'FusedBPRStep needs ROCm device tensors'
-        assert user_table.shape[1] == item_table.shape[1]
-        self.U, self.I = user_table, item_table
-        self.D = user_table.shape[1]
-        self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        super().__init__(user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state)
         self.gamma, self.reg_weight = gamma, reg_weight
-        self.ustate = user_state if user_state is not None else RowwiseState(user_table, self.opt)
-        self.istate = item_state if item_state is not None else RowwiseState(item_table, self.opt)
         dev = user_table.device
         Bm = int(max_batch)
         self.max_batch = Bm
@@ -166,12 +213,7 @@ class FusedBPRStep:
         # come out first, the item keys behind them with a table bit (key_base) the apply kernel subtracts again
         self.keys = torch.empty(3 * Bm, device=dev, dtype=torch.int32)
         self.perm = torch.empty(3 * Bm, device=dev, dtype=torch.int32)
-        rows = max(user_table.shape[0], item_table.shape[0])
-        self._sort_rows = 2 << (rows - 1).bit_length()
-        need = ctypes.c_size_t(0)
-        B_._check(B_.load().cdr_sort_workspace_bytes(3 * Bm, self._sort_rows, ctypes.byref(need)), 'cdr_sort_workspace_bytes')
-        self.ws_bytes = int(need.value)
-        self.ws = torch.empty(self.ws_bytes, device=dev, dtype=torch.uint8)
+        self.ws, self.ws_bytes = self._sort_workspace(3 * Bm)
         self._key_base = ctypes.c_uint32(0)
         # single-occurrence rows updated by the forward kernel (cdr_bpr_step_fused): D <= 256 like cdr_bpr_fwd_grad
         self.fuse_singles = bool(fuse_singles) and self.D % 4 == 0 and self.D <= 256 and os.environ.get('CDR_FUSE_SINGLES', '1') != '0'   # env: A/B runs
@@ -180,10 +222,7 @@ class FusedBPRStep:
         self.device_counts = bool(device_counts) and self.fuse_singles
         self._hp_dev = None
         if self.fuse_singles:
-            words = ctypes.c_int64(0)
-            B_._check(B_.load().cdr_bpr_step_fused_heads_words(Bm, ctypes.byref(words)), 'cdr_bpr_step_fused_heads_words')
-            self.flags = torch.zeros(4 * Bm, device=dev, dtype=torch.uint8)      # {user, positive, negative, -} per triple
-            self.heads = torch.empty(int(words.value), device=dev, dtype=torch.int32)
+            self.flags, self.heads = self._single_row_buffers(Bm)               # flags: {user, positive, negative, -} per triple
         # Ids without a sort (round 6, csrc/cdr_step.hip): batches of 16,448 ... 131,072 triples take their single-occurrence flags from one
         # counter per table row and sort only the duplicate occurrences.  'auto': on, and moved to the sorted path (and back) by the
         # duplicate statistics the step leaves in heads[2:4] -- read back asynchronously, one step late, never waited for; 'count' / 'sort' pin it.
@@ -269,9 +308,8 @@ class FusedBPRStep:
             B_.call('cdr_bpr_step_fused_dev', B_.ctx(self.U.device), B_.stream(), self.opt, B_.f32(us.table), B_.f32(us.exp_avg),
                     B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq),
                     its.table.shape[0], self.D, B_.i64(uid), B_.i64(pid), B_.i64(nid), B, float(self.gamma),
-                    float(self.reg_weight), float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd),
-                    B_.i64(su), B_.i64(si), B_.f32(self._hp_dev), B_.f32(self.out6), B_.f32(self.GU), B_.f32(self.GP), B_.raw(self.keys),
-                    B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws_bytes)
+                    float(self.reg_weight), *self._hp(), B_.i64(su), B_.i64(si), B_.f32(self._hp_dev), B_.f32(self.out6), B_.f32(self.GU),
+                    B_.f32(self.GP), B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws_bytes)
             if not torch.cuda.is_current_stream_capturing():
                 us.advance(device_bumped=True)
                 its.advance(device_bumped=True)
@@ -281,16 +319,9 @@ class FusedBPRStep:
         B_.call('cdr_bpr_step_fused', B_.ctx(self.U.device), B_.stream(), self.opt, B_.f32(us.table), B_.f32(us.exp_avg),
                 B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq),
                 its.table.shape[0], self.D, B_.i64(uid), B_.i64(pid), B_.i64(nid), B, float(self.gamma),
-                float(self.reg_weight), float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd),
-                us.step, its.step, B_.f32(self.out6), B_.f32(self.GU), B_.f32(self.GP), B_.raw(self.keys), B_.raw(self.perm),
-                B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws_bytes)
+                float(self.reg_weight), *self._hp(), us.step, its.step, B_.f32(self.out6), B_.f32(self.GU), B_.f32(self.GP), B_.raw(self.keys),
+                B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws_bytes)
         return self.out6
-
-    def replayed(self, n=1):
-        """Host bookkeeping of ``n`` hipGraph replays of ``step`` (device_counts form): the update counts' host mirrors."""
-        for _ in range(n):
-            self.ustate.advance(device_bumped=True)
-            self.istate.advance(device_bumped=True)
 
     def sort_apply(self, uid, pid, nid):
         """Second half of the step: GU / GP / out6[4:6] are in place (written by the forward kernel); one sort for both tables,
@@ -316,11 +347,10 @@ class FusedBPRStep:
         st.advance()
         B_.call('cdr_rowwise_apply', ctxh, B_.stream(), self.opt, B_.f32(st.table), B_.f32(st.exp_avg),
                 B_.f32(st.exp_avg_sq), self.D, B_.raw(keys), B_.raw(perm), n, B_.f32(G), neg_start, reg_limit,
-                B_.f32(coef), float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                float(self.wd), st.step, None, int(key_base))
+                B_.f32(coef), *self._hp(), st.step, None, int(key_base))
 
 
-class KMajorBPRStep:
+class KMajorBPRStep(_TwoTableStep):
     """The fused BPR step cut along recbole's pairwise batch layout (crossdomain_sampler.py:148-152; emcdr.py:123-131): S positives
     tiled k times with k-major negatives.  One lane group per POSITIVE in the forward (u, p gathered once, not k times), one
     gradient row per positive for the user table, and no item gradient rows at all: the item apply rebuilds each occurrence's
@@ -330,16 +360,9 @@ class KMajorBPRStep:
 
     def __init__(self, user_table, item_table, max_positives, k=1, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, gamma=1e-10, reg_weight=0.0, user_state=None, item_state=None, fuse_singles=True):
-        assert user_table.is_cuda and item_table.is_cuda, 'KMajorBPRStep needs ROCm device tensors'
-        assert user_table.shape[1] == item_table.shape[1]
-        self.U, self.I = user_table, item_table
-        self.D = user_table.shape[1]
+        super().__init__(user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state)
         self.k = int(k)
-        self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.gamma, self.reg_weight = gamma, reg_weight
-        self.ustate = user_state if user_state is not None else RowwiseState(user_table, self.opt)
-        self.istate = item_state if item_state is not None else RowwiseState(item_table, self.opt)
         dev = user_table.device
         Sm = int(max_positives)
         Bm = Sm * self.k
@@ -367,11 +390,7 @@ class KMajorBPRStep:
         self.ws = None
         self._key_base = ctypes.c_uint32(0)
         if not self.small:
-            rows = max(user_table.shape[0], item_table.shape[0])
-            need = ctypes.c_size_t(0)
-            B_._check(B_.load().cdr_sort_workspace_bytes(n_all, 2 << (rows - 1).bit_length(), ctypes.byref(need)),
-                      'cdr_sort_workspace_bytes')
-            self.ws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+            self.ws, _ = self._sort_workspace(n_all)
         self._graph = None
 
     def step(self, uid, pid, nid):
@@ -386,9 +405,8 @@ class KMajorBPRStep:
             B_.call('cdr_bpr_step_fused_kmajor', B_.ctx(self.U.device), B_.stream(), self.opt, B_.f32(us.table), B_.f32(us.exp_avg),
                     B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq),
                     its.table.shape[0], self.D, B_.i64(uid), B_.i64(pid), B_.i64(nid), S, self.k, float(self.gamma), float(self.reg_weight),
-                    float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), us.step, its.step,
-                    B_.f32(self.out6), B_.f32(self.GU), B_.f32(self.GI), B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags),
-                    B_.raw(self.heads), B_.raw(self.ws), self.ws.numel())
+                    *self._hp(), us.step, its.step, B_.f32(self.out6), B_.f32(self.GU), B_.f32(self.GI), B_.raw(self.keys), B_.raw(self.perm),
+                    B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws.numel())
             return self.out6
         self._enqueue(uid, pid, nid, S)
         self.ustate.advance(device_bumped=True)
@@ -401,7 +419,7 @@ class KMajorBPRStep:
         B = S * self.k
         adam = self.opt == OPT_ADAM
         ud, idv = (self.ustate.step_dev, self.istate.step_dev) if adam else (None, None)
-        hp = (float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd))
+        hp = self._hp()
         if self.small:
             # four launches behind one call: {forward || rank count}, {scatter || loss finish}, item apply, user apply
             us, its = self.ustate, self.istate
@@ -481,28 +499,20 @@ class KMajorBPRStep:
         if uid is not None:
             self._ids[0].copy_(uid[:S]); self._ids[1].copy_(pid[:S]); self._ids[2].copy_(nid)
         self._graph.replay()
-        self.ustate.advance(device_bumped=True)
-        self.istate.advance(device_bumped=True)
+        self.replayed()
         return self.out6
 
 
-class FusedPointStep:
+class FusedPointStep(_TwoTableStep):
     """Pointwise counterpart of FusedBPRStep: rows (user, item, label) -- recbole's pointwise layout, sampled negatives stacked
     behind the positives with label 0 -- MSE on the raw dot (EMCDR's default MF latent factor model, emcdr.py:111-122) or BCE
     on sigmoid(dot), plus ``reg_weight * EmbLoss(u_rows, i_rows)``; both tables updated row-wise on the batch's rows."""
 
     def __init__(self, user_table, item_table, max_batch, loss='mse', opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, reg_weight=0.0, user_state=None, item_state=None, fuse_singles=True):
-        assert user_table.is_cuda and item_table.is_cuda, 'FusedPointStep needs ROCm device tensors'
-        assert user_table.shape[1] == item_table.shape[1]
-        self.U, self.I = user_table, item_table
-        self.D = user_table.shape[1]
+        super().__init__(user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state)
         self.kind = B_.CDR_LOSS_MSE if loss == 'mse' else B_.CDR_LOSS_BCE
-        self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.reg_weight = reg_weight
-        self.ustate = user_state if user_state is not None else RowwiseState(user_table, self.opt)
-        self.istate = item_state if item_state is not None else RowwiseState(item_table, self.opt)
         dev = user_table.device
         Bm = int(max_batch)
         self.max_batch = Bm
@@ -511,20 +521,13 @@ class FusedPointStep:
         self.out6 = torch.zeros(12, device=dev, dtype=torch.float32)
         self.keys = torch.empty(2 * Bm, device=dev, dtype=torch.int32)        # one sort for both tables (see FusedBPRStep)
         self.perm = torch.empty(2 * Bm, device=dev, dtype=torch.int32)
-        rows = max(user_table.shape[0], item_table.shape[0])
-        need = ctypes.c_size_t(0)
-        B_._check(B_.load().cdr_sort_workspace_bytes(2 * Bm, 2 << (rows - 1).bit_length(), ctypes.byref(need)),
-                  'cdr_sort_workspace_bytes')
-        self.ws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+        self.ws, _ = self._sort_workspace(2 * Bm)
         self._key_base = ctypes.c_uint32(0)
         # round 5: rows that occur once in the batch are updated by the forward kernel itself (cdr_point_step_fused), as in FusedBPRStep;
         # fuse_singles=False (or CDR_FUSE_SINGLES=0) keeps the two-pass form (the dimension-sharded step drives its halves)
         self.fuse_singles = bool(fuse_singles) and self.D % 4 == 0 and self.D <= 256 and os.environ.get('CDR_FUSE_SINGLES', '1') != '0'
         if self.fuse_singles:
-            words = ctypes.c_int64(0)
-            B_._check(B_.load().cdr_bpr_step_fused_heads_words(Bm, ctypes.byref(words)), 'cdr_bpr_step_fused_heads_words')
-            self.flags = torch.zeros(4 * Bm, device=dev, dtype=torch.uint8)      # {user, item, -, -} per row
-            self.heads = torch.empty(int(words.value), device=dev, dtype=torch.int32)
+            self.flags, self.heads = self._single_row_buffers(Bm)               # flags: {user, item, -, -} per row
 
     def step(self, uid, iid, label):
         """uid / iid int64 [B], label fp32 [B].  Returns out6 (view; [0] = total loss)."""
@@ -535,9 +538,9 @@ class FusedPointStep:
             us.advance(); its.advance()
             B_.call('cdr_point_step_fused', B_.ctx(self.U.device), B_.stream(), self.kind, self.opt, B_.f32(us.table), B_.f32(us.exp_avg),
                     B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq), its.table.shape[0],
-                    self.D, B_.i64(uid), B_.i64(iid), B_.f32(label), B, float(self.reg_weight), float(self.lr), float(self.betas[0]),
-                    float(self.betas[1]), float(self.eps), float(self.wd), us.step, its.step, B_.f32(self.out6), B_.f32(self.GU), B_.f32(self.GI),
-                    B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws.numel())
+                    self.D, B_.i64(uid), B_.i64(iid), B_.f32(label), B, float(self.reg_weight), *self._hp(), us.step, its.step, B_.f32(self.out6),
+                    B_.f32(self.GU), B_.f32(self.GI), B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws),
+                    self.ws.numel())
             return self.out6
         B_.call('cdr_point_fwd_grad', B_.ctx(self.U.device), B_.stream(), self.kind, B_.f32(self.U), B_.f32(self.I), self.D, B_.i64(uid),
                 B_.i64(iid), B_.f32(label), B, float(self.reg_weight), B_.f32(self.out6), B_.f32(self.GU), B_.f32(self.GI))
@@ -560,12 +563,12 @@ class FusedPointStep:
                                       (self.istate, B, self.GI, self.out6[5:6], self._key_base.value)):
             st.advance()
             B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
-                    B_.raw(self.keys[lo:lo + B]), B_.raw(self.perm[lo:lo + B]), B, B_.f32(G), B, B, B_.f32(coef), float(self.lr),
-                    float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), st.step, None, int(base))
+                    B_.raw(self.keys[lo:lo + B]), B_.raw(self.perm[lo:lo + B]), B, B_.f32(G), B, B, B_.f32(coef), *self._hp(), st.step, None,
+                    int(base))
         return self.out6
 
 
-class FusedPointPairStep:
+class FusedPointPairStep(_TwoTableStep):
     """CMF's BOTH-phase step (cmf.py:75-99): a source and a target pointwise batch on ONE user and ONE item table,
     loss = alpha (BCE_s + reg_source EmbLoss_s) + (1 - alpha) (BCE_t + reg_target EmbLoss_t), and ONE update per touched row from the
     sum of its two domains' contributions -- the reference's single Adam step (two FusedPointStep calls would update a row named by both
@@ -574,18 +577,11 @@ class FusedPointPairStep:
 
     def __init__(self, user_table, item_table, max_source, max_target, alpha, reg_source, reg_target, opt='adam', lr=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, user_state=None, item_state=None, loss='bce'):
-        assert user_table.is_cuda and item_table.is_cuda, 'FusedPointPairStep needs ROCm device tensors'
-        assert user_table.shape[1] == item_table.shape[1]
-        self.U, self.I = user_table, item_table
-        self.D = user_table.shape[1]
-        if self.D % 4 != 0 or self.D > 256:
-            raise ValueError(f'FusedPointPairStep: D must be a multiple of 4 and <= 256, got {self.D}')
+        if user_table.shape[1] % 4 != 0 or user_table.shape[1] > 256:            # (before the base allocates any optimizer state)
+            raise ValueError(f'FusedPointPairStep: D must be a multiple of 4 and <= 256, got {user_table.shape[1]}')
+        super().__init__(user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state)
         self.kind = B_.CDR_LOSS_MSE if loss == 'mse' else B_.CDR_LOSS_BCE
-        self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.alpha, self.reg_source, self.reg_target = float(alpha), float(reg_source), float(reg_target)
-        self.ustate = user_state if user_state is not None else RowwiseState(user_table, self.opt)
-        self.istate = item_state if item_state is not None else RowwiseState(item_table, self.opt)
         dev = user_table.device
         self.max_source, self.max_target = int(max_source), int(max_target)
         Nm = self.max_source + self.max_target
@@ -594,18 +590,9 @@ class FusedPointPairStep:
         self.out16 = torch.zeros(16, device=dev, dtype=torch.float32)
         self.keys = torch.empty(2 * Nm, device=dev, dtype=torch.int32)       # one sort: user keys [su | tu], item keys [si | ti]
         self.perm = torch.empty(2 * Nm, device=dev, dtype=torch.int32)
-        self.flags = torch.zeros(4 * Nm, device=dev, dtype=torch.uint8)      # {user, item, -, -} per joint row
-        words = ctypes.c_int64(0)
-        B_._check(B_.load().cdr_bpr_step_fused_heads_words(Nm, ctypes.byref(words)), 'cdr_bpr_step_fused_heads_words')
-        self.heads = torch.empty(int(words.value), device=dev, dtype=torch.int32)
-        rows = 2 << (max(user_table.shape[0], item_table.shape[0]) - 1).bit_length()
-        need = 0
+        self.flags, self.heads = self._single_row_buffers(Nm)                # flags: {user, item, -, -} per joint row
         # (the sort switches configuration at 2^18 keys: a short tail batch may need more scratch than a full one)
-        for n in {2 * Nm, min(2 * Nm, (1 << 18) - 1)}:
-            b = ctypes.c_size_t(0)
-            B_._check(B_.load().cdr_sort_workspace_bytes(n, rows, ctypes.byref(b)), 'cdr_sort_workspace_bytes')
-            need = max(need, int(b.value))
-        self.ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        self.ws, _ = self._sort_workspace(2 * Nm, min(2 * Nm, (1 << 18) - 1))
         self._hp_dev = torch.zeros(4, device=dev, dtype=torch.float32)
 
     def step(self, su, si, ys, tu, ti, yt):
@@ -621,22 +608,15 @@ class FusedPointPairStep:
         B_.call('cdr_point_step_fused_pair_dev', B_.ctx(self.U.device), B_.stream(), self.kind, self.opt, B_.f32(us.table), B_.f32(us.exp_avg),
                 B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq), its.table.shape[0],
                 self.D, B_.i64(su), B_.i64(si), B_.f32(ys), Bs, B_.i64(tu), B_.i64(ti), B_.f32(yt), Bt, self.alpha, self.reg_source,
-                self.reg_target, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd),
-                B_.i64(us.step_dev), B_.i64(its.step_dev), B_.f32(self._hp_dev) if adam else None, B_.f32(self.out16), B_.f32(self.GU),
-                B_.f32(self.GI), B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws.numel())
+                self.reg_target, *self._hp(), B_.i64(us.step_dev), B_.i64(its.step_dev), B_.f32(self._hp_dev) if adam else None,
+                B_.f32(self.out16), B_.f32(self.GU), B_.f32(self.GI), B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws.numel())
         if not torch.cuda.is_current_stream_capturing():       # (a capture enqueues nothing: the host counts advance per replay)
             us.advance(device_bumped=True)
             its.advance(device_bumped=True)
         return self.out16
 
-    def replayed(self, n=1):
-        """Host bookkeeping of ``n`` hipGraph replays of ``step``: the update counts' host mirrors."""
-        for _ in range(n):
-            self.ustate.advance(device_bumped=True)
-            self.istate.advance(device_bumped=True)
 
-
-class KMajorPointStep:
+class KMajorPointStep(_TwoTableStep):
     """``FusedPointStep`` cut along recbole's pointwise batch layout: S positives, the user column tiled 1 + k times, items =
     [positives | k-major negatives], labels [1] * S + [0] * S k (TrainDataLoader._neg_sampling).  One lane group per POSITIVE gathers
     the user row once and sums its gradient over the 1 + k rows in registers; users that occur in one positive and item rows that occur
@@ -645,15 +625,11 @@ class KMajorPointStep:
 
     def __init__(self, user_table, item_table, max_positives, k=1, loss='mse', opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, reg_weight=0.0, user_state=None, item_state=None):
-        assert user_table.is_cuda and item_table.is_cuda, 'KMajorPointStep needs ROCm device tensors'
-        assert user_table.shape[1] == item_table.shape[1] and user_table.shape[1] % 4 == 0 and user_table.shape[1] <= 256 and 1 <= int(k) <= 64
-        self.U, self.I = user_table, item_table
-        self.D, self.k = user_table.shape[1], int(k)
+        assert user_table.shape[1] % 4 == 0 and user_table.shape[1] <= 256 and 1 <= int(k) <= 64
+        super().__init__(user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state)
+        self.k = int(k)
         self.kind = B_.CDR_LOSS_MSE if loss == 'mse' else B_.CDR_LOSS_BCE
-        self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
-        self.lr, self.betas, self.eps, self.wd, self.reg_weight = lr, betas, eps, weight_decay, reg_weight
-        self.ustate = user_state if user_state is not None else RowwiseState(user_table, self.opt)
-        self.istate = item_state if item_state is not None else RowwiseState(item_table, self.opt)
+        self.reg_weight = reg_weight
         dev = user_table.device
         Sm = int(max_positives)
         nI = Sm * (1 + self.k)
@@ -668,10 +644,7 @@ class KMajorPointStep:
         self.out6 = torch.zeros(12, device=dev, dtype=torch.float32)
         self.keys = torch.empty(Sm + nI, device=dev, dtype=torch.int32)
         self.perm = torch.empty(Sm + nI, device=dev, dtype=torch.int32)
-        rows = max(user_table.shape[0], item_table.shape[0])
-        need = ctypes.c_size_t(0)
-        B_._check(B_.load().cdr_sort_workspace_bytes(Sm + nI, 2 << (rows - 1).bit_length(), ctypes.byref(need)), 'cdr_sort_workspace_bytes')
-        self.ws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+        self.ws, _ = self._sort_workspace(Sm + nI)
 
     def step(self, uid, iid, label):
         """uid int64 [S (1 + k)] tiled (or [S]: the first S entries are read), iid int64 [S (1 + k)], label fp32 [S (1 + k)].
@@ -683,13 +656,13 @@ class KMajorPointStep:
         us.advance(); its.advance()
         B_.call('cdr_point_step_fused_kmajor', B_.ctx(self.U.device), B_.stream(), self.kind, self.opt, B_.f32(us.table), B_.f32(us.exp_avg),
                 B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq), its.table.shape[0],
-                self.D, B_.i64(uid), B_.i64(iid), B_.f32(label), S, self.k, float(self.reg_weight), float(self.lr), float(self.betas[0]),
-                float(self.betas[1]), float(self.eps), float(self.wd), us.step, its.step, B_.f32(self.out6), B_.f32(self.GU), B_.f32(self.GI),
-                B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws.numel())
+                self.D, B_.i64(uid), B_.i64(iid), B_.f32(label), S, self.k, float(self.reg_weight), *self._hp(), us.step, its.step, B_.f32(self.out6),
+                B_.f32(self.GU), B_.f32(self.GI), B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws),
+                self.ws.numel())
         return self.out6
 
 
-class FusedMapStep:
+class FusedMapStep(_Step):
     """EMCDR's OVERLAP phase (emcdr.py:133-137 ``calculate_map_loss``: MSE(mapping(source_e[idx]), target_e[idx])) as an
     O(batch) step: the two embedding tables are updated row-wise on the overlapped ids only; the mapping function's own
     parameters (a few hundred KB) keep the exact dense Adam.
@@ -710,8 +683,7 @@ class FusedMapStep:
         self.S, self.T = source_table, target_table
         self.mapping_fn = mapping_fn
         self.mapping_params = list(mapping_params)
-        self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        super().__init__(opt, lr, betas, eps, weight_decay)
         # the row-wise moments may be shared with the FusedBPRStep objects of the SOURCE / TARGET phases (one optimizer
         # state per table across phases, like the reference's single Adam instance: trainer.py:30-41)
         self.sstate = source_state if source_state is not None else RowwiseState(source_table, self.opt)
@@ -734,6 +706,9 @@ class FusedMapStep:
                                                        max(int(max_batch), 1), ctypes.byref(need)) == 0:
                 self.layers, self._dims = list(layers), dims
                 self._loss1 = torch.zeros(1, device=source_table.device, dtype=torch.float32)
+
+    def _states(self):
+        return self.sstate, self.tstate
 
     def _step_unique(self, idx):
         """Two launches: gather + mapping + MSE + backward + in-place row updates + gradient partials, then reduction + dense Adam on
@@ -769,8 +744,8 @@ class FusedMapStep:
         B_.call('cdr_map_step_unique', B_.ctx(dev), B_.stream(), self.opt, B_.f32(self.S), B_.f32(self.sstate.exp_avg),
                 B_.f32(self.sstate.exp_avg_sq), B_.f32(self.T), B_.f32(self.tstate.exp_avg), B_.f32(self.tstate.exp_avg_sq), B_.i64(idx), n,
                 L, dims_c, (ctypes.c_int * L)(*[int(a) for _, _, a in self.layers]), ptrs(Ws), ptrs(bs), ptrs(mW), ptrs(vW), ptrs(mb),
-                ptrs(vb), ptrs(sW), ptrs(sb), B_.i64(ss), B_.i64(ts_), float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                float(self.eps), float(self.wd), B_.f32(self._loss1), B_.raw(self._uws), self._uws.numel())
+                ptrs(vb), ptrs(sW), ptrs(sb), B_.i64(ss), B_.i64(ts_), *self._hp(), B_.f32(self._loss1), B_.raw(self._uws),
+                self._uws.numel())
         del keep
         if not torch.cuda.is_current_stream_capturing():       # (a capture enqueues nothing: the host counts advance per replay)
             self.sstate.advance(device_bumped=True)
@@ -818,8 +793,7 @@ class FusedMapStep:
         if idx is not None:
             self._idx.copy_(idx.reshape(-1)[:self._OB])
         self._graph.replay()
-        self.sstate.advance(device_bumped=True)
-        self.tstate.advance(device_bumped=True)
+        self.replayed()
         self.loss = self._loss1[0]
         return self.loss
 
@@ -886,10 +860,9 @@ class FusedMapStep:
         self.tstate.advance()
         if n:
             ctxh = B_.ctx(dev)
-            need = ctypes.c_size_t(0)
-            B_._check(B_.load().cdr_sort_workspace_bytes(n, self.S.shape[0], ctypes.byref(need)), 'cdr_sort_workspace_bytes')
-            if self._ws is None or self._ws.numel() < need.value:
-                self._ws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+            need = _sort_workspace_bytes(n, self.S.shape[0])
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, device=dev, dtype=torch.uint8)
             keys = torch.empty(n, device=dev, dtype=torch.int32)
             perm = torch.empty(n, device=dev, dtype=torch.int32)
             # the same ids index both tables: one sort serves both applies
@@ -897,8 +870,7 @@ class FusedMapStep:
                     B_.raw(self._ws), self._ws.numel())
             for st, g in ((self.sstate, src.grad), (self.tstate, tgt.grad)):
                 B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq),
-                        st.table.shape[1], B_.raw(keys), B_.raw(perm), n, B_.f32(g), n, 0, None, float(self.lr),
-                        float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), st.step, None, 0)
+                        st.table.shape[1], B_.raw(keys), B_.raw(perm), n, B_.f32(g), n, 0, None, *self._hp(), st.step, None, 0)
         if self.map_opt is not None:
             self.map_opt.step()
         else:

@@ -10,11 +10,13 @@ import torch.nn as nn
 
 from ... import binding as B_
 from ... import functional as F_
+from ...fused import FusedPointPairStep, rowwise_catch_up
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
+from ..rowwise import RowwiseTraining
 
 
-class CMF(CrossDomainRecommender):
+class CMF(RowwiseTraining, CrossDomainRecommender):
     input_type = InputType.POINTWISE
 
     def __init__(self, config, dataset):
@@ -57,8 +59,6 @@ class CMF(CrossDomainRecommender):
         return total
 
     # ---- O(batch) training step (large tables) ------------------------------------------------------------------
-    _TABLES = ('user_embedding', 'item_embedding')
-
     def _pair_fields(self, interaction):
         fields = (self.SOURCE_USER_ID, self.SOURCE_ITEM_ID, self.SOURCE_LABEL, self.TARGET_USER_ID, self.TARGET_ITEM_ID, self.TARGET_LABEL)
         missing = [f for f in fields if f not in interaction]
@@ -76,33 +76,18 @@ class CMF(CrossDomainRecommender):
         ``adam='lazy'`` (default): rows the batch does not touch do not move.  ``adam='exact'``: the reference's dense Adam -- one catch-up
         launch in front of every step (fused.rowwise_catch_up) replays the gradient-free updates the step's rows missed; the tables hold
         what ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run.  One mode per model."""
-        from ...fused import FusedPointPairStep, RowwiseState, OPT_ADAM, OPT_SGD, rowwise_catch_up
-        if adam not in ('lazy', 'exact'):
-            raise ValueError(f"adam must be 'lazy' or 'exact', got {adam!r}")
-        exact = adam == 'exact'
-        if exact and opt != 'adam':
-            raise ValueError(f"adam='exact' is the reference's dense Adam: it needs opt='adam', got {opt!r}")
+        exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
         if self.__dict__.get('_dist_cfg') not in (None, False):
             raise ValueError("CMF.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
         su, si, ys, tu, ti, yt = self._pair_fields(interaction)
-        cache = self.__dict__.setdefault('_fused', {'states': {}, 'steps': {}})
-        for name, st in cache['states'].items():
-            if st.exact != exact:
-                raise ValueError(f"{name} was trained with adam={'exact' if st.exact else 'lazy'!r}; one row-wise Adam mode per model")
-        code = OPT_ADAM if opt == 'adam' else OPT_SGD
-        for name in self._TABLES:
-            if name not in cache['states']:
-                cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code, exact=exact)
-        us, its = cache['states']['user_embedding'], cache['states']['item_embedding']
+        old = self._fused_cache(exact)['steps'].get('pair')
+        us, its = self._fused_state('user_embedding', code, exact), self._fused_state('item_embedding', code, exact)
         Bs, Bt = su.numel(), tu.numel()
-        step = cache['steps'].get('pair')
-        hp = dict(opt=opt, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        if step is None or step.max_source < Bs or step.max_target < Bt or step.hp != hp:
-            ms, mt = (Bs, Bt) if step is None else (max(Bs, step.max_source), max(Bt, step.max_target))
-            step = FusedPointPairStep(self.user_embedding.weight.data, self.item_embedding.weight.data, ms, mt, self.alpha, self.lamda,
-                                      self.gamma, user_state=us, item_state=its, **hp)
-            step.hp = hp
-            cache['steps']['pair'] = step
+        ms, mt = (Bs, Bt) if old is None else (max(Bs, old.max_source), max(Bt, old.max_target))
+        step = self._fused_step('pair', lambda s: s.max_source >= Bs and s.max_target >= Bt and s.hp == hp,
+                                lambda: FusedPointPairStep(self.user_embedding.weight.data, self.item_embedding.weight.data, ms, mt, self.alpha,
+                                                           self.lamda, self.gamma, user_state=us, item_state=its, **hp))
+        step.hp = hp
         ys = ys if ys.dtype == torch.float32 else ys.float()
         yt = yt if yt.dtype == torch.float32 else yt.float()
         if exact:
@@ -123,45 +108,8 @@ class CMF(CrossDomainRecommender):
             return None
         return ('cmf', Bs, Bt, adam)
 
-    def fused_replayed(self, n=1):
-        """Host bookkeeping of ``n`` hipGraph replays of ``fused_train_step`` (the update counts' host mirrors)."""
-        from ...fused import rowwise_bound_lag
-        st = self.__dict__['_fused']['steps']['pair']
-        st.replayed(n)
-        for s_ in (st.ustate, st.istate):
-            rowwise_bound_lag(s_)                               # (exact mode without the moving window only)
-
-    def fused_sync(self):
-        """``fused_train_step(adam='exact')``: bring every row of both tables to its update count -- the tables and moments then equal
-        the reference's dense Adam (before evaluation, checkpoints, the end of training).  Lazy mode: nothing to do."""
-        cache = self.__dict__.get('_fused')
-        if cache:
-            for st in cache['states'].values():
-                if st.exact:
-                    st.flush()
-
-    def fused_optimizer_state(self):
-        """Row-wise optimizer state of ``fused_train_step`` for a checkpoint: per table the moments and the update count."""
-        cache = self.__dict__.get('_fused')
-        if not cache:
-            return {}
-        self.fused_sync()
-        return {'tables': {k: {'step': st.step, 'exp_avg': st.exp_avg, 'exp_avg_sq': st.exp_avg_sq} for k, st in cache['states'].items()}}
-
-    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
-        """Restore what ``fused_optimizer_state`` returned (before the next ``fused_train_step``).  ``adam``: the mode training goes on
-        with; in exact mode every row is current at its table's update count (the checkpoint was written flushed)."""
-        from ...fused import RowwiseState, OPT_ADAM, OPT_SGD
-        cache = self.__dict__.setdefault('_fused', {'states': {}, 'steps': {}})
-        code = OPT_ADAM if opt == 'adam' else OPT_SGD
-        for name, rec in state.get('tables', {}).items():
-            st = cache['states'].get(name)
-            if st is None:
-                st = cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code, exact=adam == 'exact')
-            st.step = int(rec['step'])
-            if rec['exp_avg'] is not None:
-                st.exp_avg.copy_(rec['exp_avg']); st.exp_avg_sq.copy_(rec['exp_avg_sq'])
-            st.restored()
+    def _fused_phase_step(self):
+        return self._fused['steps']['pair']
 
     @torch.no_grad()
     def predict(self, interaction):

@@ -12,11 +12,13 @@ import torch.nn as nn
 
 from ... import binding as B_
 from ... import functional as F_
+from ...fused import FusedBPRStep, FusedMapStep, FusedPointStep, KMajorBPRStep, KMajorPointStep, rowwise_catch_up
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
+from ..rowwise import RowwiseTraining
 
 
-class EMCDR(CrossDomainRecommender):
+class EMCDR(RowwiseTraining, CrossDomainRecommender):
 
     def __init__(self, config, dataset):
         super().__init__(config, dataset)
@@ -132,53 +134,52 @@ class EMCDR(CrossDomainRecommender):
         catch-up launch in front of every step (fused.rowwise_catch_up) replays the gradient-free updates the step's rows missed, so
         the tables hold what ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run (evaluation,
         checkpoints; the trainer calls it).  One mode per model."""
-        from ...fused import FusedBPRStep, FusedPointStep, FusedMapStep, RowwiseState, OPT_ADAM, OPT_SGD, rowwise_catch_up
-        if adam not in ('lazy', 'exact'):
-            raise ValueError(f"adam must be 'lazy' or 'exact', got {adam!r}")
-        exact = adam == 'exact'
-        if exact and opt != 'adam':
-            raise ValueError(f"adam='exact' is the reference's dense Adam: it needs opt='adam', got {opt!r}")
+        exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
         if exact and self._dist_group() is not None:
             raise ValueError("adam='exact' is not available with config['dist_group'] (sharded tables): use adam='lazy' or one GPU")
-        code = OPT_ADAM if opt == 'adam' else OPT_SGD
-        cache = self.__dict__.setdefault('_fused', {'states': {}, 'steps': {}})
         if self._dist_group() is not None:
-            return self._dist_train_step(interaction, code, dict(opt=opt, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-
-        for name, st in cache['states'].items():
-            if st.exact != exact:
-                raise ValueError(f"{name} was trained with adam={'exact' if st.exact else 'lazy'!r}; one row-wise Adam mode per model")
+            self._fused_cache()
+            return self._dist_train_step(interaction, code, hp)
+        self._fused_cache(exact)
 
         def state(name):
-            if name not in cache['states']:
-                cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code, exact=exact)
-            return cache['states'][name]
+            return self._fused_state(name, code, exact)
 
         def catch_up(*tables):
             if exact:
                 rowwise_catch_up(tables, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
 
-        hp = dict(opt=opt, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         if self.phase == 'OVERLAP':
             kind = 'user' if self.mode == 'overlap_users' else 'item'
             idx = interaction[self.OVERLAP_ID]
-            key = ('map', kind)
-            if key not in cache['steps']:
-                cache['steps'][key] = FusedMapStep(
+
+            def build_map_step():
+                step = FusedMapStep(
                     getattr(self, f'source_{kind}_embedding').weight.data, getattr(self, f'target_{kind}_embedding').weight.data,
                     self.apply_mapping, list(self.mapping.parameters()), idx.numel(), layers=self.mapping_layers(),
                     source_state=state(f'source_{kind}_embedding'), target_state=state(f'target_{kind}_embedding'), **hp)
                 pending = self.__dict__.get('_pending_map_state', {}).pop(kind, None)
-                if pending is not None and cache['steps'][key].map_opt is not None:
-                    cache['steps'][key].map_opt.load_state_dict(pending)
+                if pending is not None and step.map_opt is not None:
+                    step.map_opt.load_state_dict(pending)
+                return step
+
+            step = self._fused_step(('map', kind), lambda s: True, build_map_step)
             if idx.numel() > 0:                                  # (an empty batch is a no-op: no table advances)
-                catch_up((state(f'source_{kind}_embedding'), [idx]), (state(f'target_{kind}_embedding'), [idx]))
+                catch_up((step.sstate, [idx]), (step.tstate, [idx]))
             # the reference's OverlapDataloader yields slices of a shuffled arange (data/dataloader.py:37-52): distinct ids, which
             # the two-launch step relies on.  A caller feeding its own, possibly repeated ids sets model.overlap_ids_unique = False.
-            return cache['steps'][key].step(idx, unique=getattr(self, 'overlap_ids_unique', True))
+            return step.step(idx, unique=getattr(self, 'overlap_ids_unique', True))
         domain = 'source' if self.phase == 'SOURCE' else 'target'
         user = interaction[getattr(self, f'{domain.upper()}_USER_ID')].reshape(-1)
         item = interaction[getattr(self, f'{domain.upper()}_ITEM_ID')].reshape(-1)
+
+        def domain_step(key, cls, size, sized_by, **kw):
+            # this domain's ``cls`` object for ``size`` rows or positives, rebuilt when its ``sized_by`` attribute says it is too small
+            return self._fused_step(key, lambda s: getattr(s, sized_by) >= size, lambda: cls(
+                getattr(self, f'{domain}_user_embedding').weight.data, getattr(self, f'{domain}_item_embedding').weight.data, size,
+                reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'), item_state=state(f'{domain}_item_embedding'),
+                **kw, **hp))
+
         if self.latent_factor_model == 'MF':
             label = interaction[getattr(self, f'{domain.upper()}_LABEL')].reshape(-1).float()
             # recbole's pointwise batches tile S positives 1 + k times (Interaction.point_k, set by the loader): at large batches the
@@ -187,25 +188,10 @@ class EMCDR(CrossDomainRecommender):
             rows = user.numel()
             D_ = getattr(self, f'{domain}_user_embedding').weight.shape[1]
             if pk is not None and 1 <= pk <= 64 and rows % (1 + pk) == 0 and rows > 8192 and D_ % 4 == 0 and D_ <= 256:
-                from ...fused import KMajorPointStep
-                key = ('mfk', domain, pk)
-                step = cache['steps'].get(key)
-                if step is None or step.max_positives < rows // (1 + pk):
-                    step = KMajorPointStep(getattr(self, f'{domain}_user_embedding').weight.data,
-                                           getattr(self, f'{domain}_item_embedding').weight.data, rows // (1 + pk), k=pk, loss='mse',
-                                           reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'),
-                                           item_state=state(f'{domain}_item_embedding'), **hp)
-                    cache['steps'][key] = step
+                step = domain_step(('mfk', domain, pk), KMajorPointStep, rows // (1 + pk), 'max_positives', k=pk, loss='mse')
                 catch_up((step.ustate, [user[:rows // (1 + pk)]]), (step.istate, [item]))
                 return step.step(user, item, label)[0]
-            key = ('mf', domain)
-            step = cache['steps'].get(key)
-            if step is None or step.max_batch < user.numel():
-                step = FusedPointStep(getattr(self, f'{domain}_user_embedding').weight.data,
-                                      getattr(self, f'{domain}_item_embedding').weight.data, user.numel(), loss='mse',
-                                      reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'),
-                                      item_state=state(f'{domain}_item_embedding'), **hp)
-                cache['steps'][key] = step
+            step = domain_step(('mf', domain), FusedPointStep, rows, 'max_batch', loss='mse')
             catch_up((step.ustate, [user]), (step.istate, [item]))
             return step.step(user, item, label)[0]
         neg = interaction[getattr(self, f'{domain.upper()}_NEG_ITEM_ID')].reshape(-1)
@@ -216,25 +202,10 @@ class EMCDR(CrossDomainRecommender):
         k = getattr(interaction, 'k_major', None)
         rows = user.numel()
         if k is not None and rows % k == 0 and (k >= 2 or rows + rows // k <= 8192):
-            from ...fused import KMajorBPRStep
-            key = ('bprk', domain, k)
-            step = cache['steps'].get(key)
-            if step is None or step.max_positives < rows // k:
-                step = KMajorBPRStep(getattr(self, f'{domain}_user_embedding').weight.data,
-                                     getattr(self, f'{domain}_item_embedding').weight.data, rows // k, k=k, gamma=self.bpr_gamma,
-                                     reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'),
-                                     item_state=state(f'{domain}_item_embedding'), **hp)
-                cache['steps'][key] = step
+            step = domain_step(('bprk', domain, k), KMajorBPRStep, rows // k, 'max_positives', k=k, gamma=self.bpr_gamma)
             catch_up((step.ustate, [user[:rows // k]]), (step.istate, [item[:rows // k], neg]))
             return step.step(user, item, neg)[0]
-        key = ('bpr', domain)
-        step = cache['steps'].get(key)
-        if step is None or step.max_batch < user.numel():
-            step = FusedBPRStep(getattr(self, f'{domain}_user_embedding').weight.data,
-                                getattr(self, f'{domain}_item_embedding').weight.data, user.numel(), gamma=self.bpr_gamma,
-                                reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'),
-                                item_state=state(f'{domain}_item_embedding'), **hp)
-            cache['steps'][key] = step
+        step = domain_step(('bpr', domain), FusedBPRStep, rows, 'max_batch', gamma=self.bpr_gamma)
         catch_up((step.ustate, [user]), (step.istate, [item, neg]))
         return step.step(user, item, neg)[0]
 
@@ -262,33 +233,10 @@ class EMCDR(CrossDomainRecommender):
             return None
         return ('bpr', domain, rows, adam)
 
-    def fused_replayed(self, n=1):
-        """Host bookkeeping of ``n`` hipGraph replays of the current phase's ``fused_train_step`` (the update counts' host mirrors)."""
-        cache = self.__dict__.get('_fused', {'steps': {}})
+    def _fused_phase_step(self):
         if self.phase == 'OVERLAP':
-            kind = 'user' if self.mode == 'overlap_users' else 'item'
-            st = cache['steps'].get(('map', kind))
-            for _ in range(n):
-                st.sstate.advance(device_bumped=True)
-                st.tstate.advance(device_bumped=True)
-            states = (st.sstate, st.tstate)
-        else:
-            domain = 'source' if self.phase == 'SOURCE' else 'target'
-            st = cache['steps'][('bpr', domain)]
-            st.replayed(n)
-            states = (st.ustate, st.istate)
-        from ...fused import rowwise_bound_lag
-        for s_ in states:
-            rowwise_bound_lag(s_)                               # (exact mode without the moving window only)
-
-    def fused_sync(self):
-        """``fused_train_step(adam='exact')``: bring every row of every table to its update count -- the tables and moments then equal
-        the reference's dense Adam (before evaluation, checkpoints, the end of training).  Lazy mode: nothing to do."""
-        cache = self.__dict__.get('_fused')
-        if cache:
-            for st in cache['states'].values():
-                if st.exact:
-                    st.flush()
+            return self._fused['steps'][('map', 'user' if self.mode == 'overlap_users' else 'item')]
+        return self._fused['steps'][('bpr', 'source' if self.phase == 'SOURCE' else 'target')]
 
     # ---- the same step over the GPUs of a node (config['dist_group']: a torch.distributed group, or True for WORLD) ----------
     _TABLES = ('source_user_embedding', 'source_item_embedding', 'target_user_embedding', 'target_item_embedding')
@@ -487,33 +435,16 @@ class EMCDR(CrossDomainRecommender):
         return {n: T.full(n) for n in self._TABLES} if T is not None else {n: getattr(self, n).weight.data for n in self._TABLES}
 
     def fused_optimizer_state(self):
-        """Row-wise optimizer state of ``fused_train_step`` for a checkpoint: per table the moments and the update count, plus
-        the dense Adam state of the mapping function (recbole's checkpoint stores ``optimizer.state_dict()``; this is its
-        counterpart for ``optimizer_mode='rowwise'``)."""
-        cache = self.__dict__.get('_fused')
-        if not cache:
-            return {}
-        self.fused_sync()
-        out = {'tables': {k: {'step': st.step, 'exp_avg': st.exp_avg, 'exp_avg_sq': st.exp_avg_sq} for k, st in cache['states'].items()}}
-        for key, step in cache['steps'].items():
+        """The shared per-table state, plus the dense Adam state of the mapping function."""
+        out = super().fused_optimizer_state()
+        for key, step in self.__dict__.get('_fused', {}).get('steps', {}).items():
             if key[0] == 'map' and step.map_opt is not None:
                 out.setdefault('mapping', {})[key[1]] = step.map_opt.state_dict()
         return out
 
     def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
-        """Restore what ``fused_optimizer_state`` returned (before the next ``fused_train_step``).  ``adam``: the mode training
-        goes on with; in exact mode every row is current at its table's update count (the checkpoint was written flushed)."""
-        from ...fused import RowwiseState, OPT_ADAM, OPT_SGD
-        cache = self.__dict__.setdefault('_fused', {'states': {}, 'steps': {}})
-        code = OPT_ADAM if opt == 'adam' else OPT_SGD
-        for name, rec in state.get('tables', {}).items():
-            st = cache['states'].get(name)
-            if st is None:
-                st = cache['states'][name] = RowwiseState(getattr(self, name).weight.data, code, exact=adam == 'exact')
-            st.step = int(rec['step'])
-            if rec['exp_avg'] is not None:
-                st.exp_avg.copy_(rec['exp_avg']); st.exp_avg_sq.copy_(rec['exp_avg_sq'])
-            st.restored()
+        """The shared per-table restore; the mapping's Adam state is handed to the OVERLAP step when it is built."""
+        super().load_fused_optimizer_state(state, opt=opt, adam=adam)
         self._pending_map_state = state.get('mapping', {})
 
     # ---- scoring ------------------------------------------------------------------------------------------------

@@ -1,0 +1,83 @@
+"""Model-side bookkeeping of the O(batch) row-wise training path (``optimizer_mode='rowwise'``), shared by every model with a
+``fused_train_step``: the cache of per-table optimizer states and step objects, the checks of the (opt, adam) arguments, and the
+methods the trainer calls around the step (``fused_replayed``, ``fused_sync``, ``fused_optimizer_state``,
+``load_fused_optimizer_state``).  Which step class a batch gets stays with the model."""
+from ..fused import RowwiseState, OPT_ADAM, OPT_SGD, rowwise_bound_lag
+
+
+class RowwiseTraining:
+    """Mixin next to ``CrossDomainRecommender``.  State: ``self._fused = {'states': {table name: RowwiseState}, 'steps': {key: step
+    object}}``, created by the first accepted ``fused_train_step``.  The model supplies ``_fused_phase_step()``: the step object
+    the current phase's captured ``fused_train_step`` runs."""
+
+    @staticmethod
+    def _fused_args(opt, adam, lr, betas, eps, weight_decay):
+        """Checks ``fused_train_step``'s (opt, adam) -> (exact, optimizer code, the step classes' optimizer keywords).  Touches nothing:
+        the model's own rejections come between this and ``_fused_cache``, so that a rejected call leaves no state behind."""
+        if adam not in ('lazy', 'exact'):
+            raise ValueError(f"adam must be 'lazy' or 'exact', got {adam!r}")
+        exact = adam == 'exact'
+        if exact and opt != 'adam':
+            raise ValueError(f"adam='exact' is the reference's dense Adam: it needs opt='adam', got {opt!r}")
+        return exact, OPT_ADAM if opt == 'adam' else OPT_SGD, dict(opt=opt, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    def _fused_cache(self, exact=None):
+        """The cache, created on first use.  ``exact`` given: the mode of this ``fused_train_step`` -- one per model."""
+        cache = self.__dict__.setdefault('_fused', {'states': {}, 'steps': {}})
+        if exact is not None:
+            for name, st in cache['states'].items():
+                if st.exact != exact:
+                    raise ValueError(f"{name} was trained with adam={'exact' if st.exact else 'lazy'!r}; one row-wise Adam mode per model")
+        return cache
+
+    def _fused_state(self, name, code, exact):
+        """The ``RowwiseState`` of the embedding table ``self.<name>``, created on first use."""
+        states = self._fused['states']
+        if name not in states:
+            states[name] = RowwiseState(getattr(self, name).weight.data, code, exact=exact)
+        return states[name]
+
+    def _fused_step(self, key, fits, build):
+        """The step object cached under ``key`` if ``fits(step)`` still holds, else ``build()``'s, which replaces it."""
+        steps = self._fused['steps']
+        step = steps.get(key)
+        if step is None or not fits(step):
+            step = steps[key] = build()
+        return step
+
+    def fused_replayed(self, n=1):
+        """Host bookkeeping of ``n`` hipGraph replays of the current phase's ``fused_train_step`` (the update counts' host mirrors)."""
+        step = self._fused_phase_step()
+        step.replayed(n)
+        for st in step._states():
+            rowwise_bound_lag(st)                               # (exact mode without the moving window only)
+
+    def fused_sync(self):
+        """``fused_train_step(adam='exact')``: bring every row of every table to its update count -- the tables and moments then equal
+        the reference's dense Adam (before evaluation, checkpoints, the end of training).  Lazy mode: nothing to do."""
+        cache = self.__dict__.get('_fused')
+        if cache:
+            for st in cache['states'].values():
+                if st.exact:
+                    st.flush()
+
+    def fused_optimizer_state(self):
+        """Row-wise optimizer state of ``fused_train_step`` for a checkpoint: per table the moments and the update count (recbole's
+        checkpoint stores ``optimizer.state_dict()``; this is its counterpart for ``optimizer_mode='rowwise'``)."""
+        cache = self.__dict__.get('_fused')
+        if not cache:
+            return {}
+        self.fused_sync()
+        return {'tables': {k: {'step': st.step, 'exp_avg': st.exp_avg, 'exp_avg_sq': st.exp_avg_sq} for k, st in cache['states'].items()}}
+
+    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
+        """Restore what ``fused_optimizer_state`` returned (before the next ``fused_train_step``).  ``adam``: the mode training goes on
+        with; in exact mode every row is current at its table's update count (the checkpoint was written flushed)."""
+        self._fused_cache()
+        code = OPT_ADAM if opt == 'adam' else OPT_SGD
+        for name, rec in state.get('tables', {}).items():
+            st = self._fused_state(name, code, adam == 'exact')
+            st.step = int(rec['step'])
+            if rec['exp_avg'] is not None:
+                st.exp_avg.copy_(rec['exp_avg']); st.exp_avg_sq.copy_(rec['exp_avg_sq'])
+            st.restored()
