@@ -203,17 +203,6 @@ __global__ __launch_bounds__(kBlock) void segsum_long_finish_kernel(int D, const
     }
 }
 
-#define DISPATCH_LPR(lpr, ...)                                  \
-    switch (lpr) {                                              \
-        case 1: { constexpr int L = 1; __VA_ARGS__; } break;    \
-        case 2: { constexpr int L = 2; __VA_ARGS__; } break;    \
-        case 4: { constexpr int L = 4; __VA_ARGS__; } break;    \
-        case 8: { constexpr int L = 8; __VA_ARGS__; } break;    \
-        case 16: { constexpr int L = 16; __VA_ARGS__; } break;  \
-        case 32: { constexpr int L = 32; __VA_ARGS__; } break;  \
-        default: { constexpr int L = 64; __VA_ARGS__; } break;  \
-    }
-
 }  // namespace
 
 extern "C" int cdr_dedup_workspace_bytes(int64_t n, size_t* bytes) {

@@ -25,16 +25,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kUnroll = 4;
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-inline int grid_for(int64_t units, int per_block) {
-    int64_t g = (units + per_block - 1) / per_block;
-    const int64_t cap = CDR_NUM_CU * 8;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void bpr_partial_diff_kernel(const float* __restrict__ U, const float* __restrict__ I, int D,
                                                                   const int64_t* __restrict__ uid, const int64_t* __restrict__ pid,
@@ -313,17 +303,6 @@ __global__ __launch_bounds__(kBlock) void ids_unpack32_kernel(const int32_t* __r
 }
 
 }  // namespace
-
-#define DISPATCH_LPR(lpr, ...)                                  \
-    switch (lpr) {                                              \
-        case 1: { constexpr int L = 1; __VA_ARGS__; } break;    \
-        case 2: { constexpr int L = 2; __VA_ARGS__; } break;    \
-        case 4: { constexpr int L = 4; __VA_ARGS__; } break;    \
-        case 8: { constexpr int L = 8; __VA_ARGS__; } break;    \
-        case 16: { constexpr int L = 16; __VA_ARGS__; } break;  \
-        case 32: { constexpr int L = 32; __VA_ARGS__; } break;  \
-        default: { constexpr int L = 64; __VA_ARGS__; } break;  \
-    }
 
 extern "C" int cdr_bpr_partial_diff(cdr_ctx* ctx, void* stream, const float* user_cols, const float* item_cols, int Ds,
                                     const int64_t* uid, const int64_t* pid, const int64_t* nid, int64_t B, float* diff) {

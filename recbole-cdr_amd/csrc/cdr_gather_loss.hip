@@ -14,8 +14,6 @@ constexpr int kBlock = 256;
 constexpr int kUnroll = 4;
 constexpr int kUnrollPoint = 8;      // pointwise rows carry 2 row loads each (BPR triples 3): keep as many bytes in flight
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // ------------------------------------------------------------------------------------------------ BPR forward
 // out4 = {total, main, ||U_b||_F, ||I_b||_F}
 template <bool SYS = false>
@@ -508,26 +506,7 @@ inline int64_t units_for(int64_t B, int unroll, int per_block) {
     return (B + u - 1) / u;
 }
 
-inline int grid_for(int64_t units, int per_block) {
-    int64_t g = (units + per_block - 1) / per_block;
-    const int64_t cap = CDR_NUM_CU * 8;       // 2048 blocks = 8 per CU, grid-stride beyond (guide G11)
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
-
-#define DISPATCH_LPR(lpr, ...)                                  \
-    switch (lpr) {                                              \
-        case 1: { constexpr int L = 1; __VA_ARGS__; } break;    \
-        case 2: { constexpr int L = 2; __VA_ARGS__; } break;    \
-        case 4: { constexpr int L = 4; __VA_ARGS__; } break;    \
-        case 8: { constexpr int L = 8; __VA_ARGS__; } break;    \
-        case 16: { constexpr int L = 16; __VA_ARGS__; } break;  \
-        case 32: { constexpr int L = 32; __VA_ARGS__; } break;  \
-        default: { constexpr int L = 64; __VA_ARGS__; } break;  \
-    }
 
 extern "C" int cdr_bpr_fwd(cdr_ctx* ctx, void* stream, const float* user_tab, const float* item_tab, int D,
                            const int64_t* uid, const int64_t* pid, const int64_t* nid, int64_t B, float gamma,

@@ -819,17 +819,6 @@ inline row_flag_views flag_views(const uint8_t* work, int64_t rows) {
 
 #define GR_GRID(total) dim3(grid_cap(((total) + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream
 
-#define DISPATCH_LPR(lpr, ...)                                  \
-    switch (lpr) {                                              \
-        case 1: { constexpr int L = 1; __VA_ARGS__; } break;    \
-        case 2: { constexpr int L = 2; __VA_ARGS__; } break;    \
-        case 4: { constexpr int L = 4; __VA_ARGS__; } break;    \
-        case 8: { constexpr int L = 8; __VA_ARGS__; } break;    \
-        case 16: { constexpr int L = 16; __VA_ARGS__; } break;  \
-        case 32: { constexpr int L = 32; __VA_ARGS__; } break;  \
-        default: { constexpr int L = 64; __VA_ARGS__; } break;  \
-    }
-
 extern "C" int cdr_spmm_csr_f32(void* stream, const int64_t* indptr, const int64_t* indices, const float* values,
                                 int64_t n_rows, const float* E, int D, float* out) {
     CDR_CHECK_ARG(indptr && indices && values && E && out && n_rows > 0 && D > 0 && (D & 3) == 0);

@@ -27,16 +27,6 @@ constexpr int kBlock = 256;
 
 struct item_rec { int32_t urow; float coef; };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-inline int grid_for(int64_t units, int per_block) {
-    int64_t g = (units + per_block - 1) / per_block;
-    const int64_t cap = CDR_NUM_CU * 8;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 // ------------------------------------------------------------------------------------------------ forward + compact grads
 // KC negatives per positive are in flight together (k is walked in chunks of KC), UNR positives per lane group.
 template <int LPR, int KC, int UNR>
@@ -380,17 +370,6 @@ __global__ __launch_bounds__(kBlock) void long_finish2_kernel(float* __restrict_
         }
     }
 }
-
-#define DISPATCH_LPR(lpr, ...)                                  \
-    switch (lpr) {                                              \
-        case 1: { constexpr int L = 1; __VA_ARGS__; } break;    \
-        case 2: { constexpr int L = 2; __VA_ARGS__; } break;    \
-        case 4: { constexpr int L = 4; __VA_ARGS__; } break;    \
-        case 8: { constexpr int L = 8; __VA_ARGS__; } break;    \
-        case 16: { constexpr int L = 16; __VA_ARGS__; } break;  \
-        case 32: { constexpr int L = 32; __VA_ARGS__; } break;  \
-        default: { constexpr int L = 64; __VA_ARGS__; } break;  \
-    }
 
 template <int SRC>
 int apply2(cdr_ctx* ctx, hipStream_t s, int opt, float* table, float* exp_avg, float* exp_avg_sq, int D, const uint32_t* keys,

@@ -37,13 +37,6 @@ struct lz_table {
 };
 struct lz_args { lz_table t[kMaxTab]; int count, D; float lr, b1, b2, eps, wd; int64_t hp_mask; };   // hp is a ring of hp_mask + 1 entries
 
-inline int grid_for(int64_t units, int per_block) {
-    int64_t g = (units + per_block - 1) / per_block;
-    const int64_t cap = CDR_NUM_CU * 8;
-    if (g > cap) g = cap;
-    return (int)(g < 1 ? 1 : g);
-}
-
 // replay updates (from, to] of one row chunk without gradient
 __device__ __forceinline__ void replay(float4& w, float4& m, float4& v, int64_t from, int64_t to, const float2* __restrict__ hp,
                                        const lz_args& a) {
@@ -469,17 +462,6 @@ __global__ __launch_bounds__(kBlock) void lz_flush_kernel(lz_args a, int64_t row
         if (sub == 0) tb.last[row] = (int32_t)t;
     }
 }
-
-#define DISPATCH_LPR(lpr, ...)                                  \
-    switch (lpr) {                                              \
-        case 1: { constexpr int L = 1; __VA_ARGS__; } break;    \
-        case 2: { constexpr int L = 2; __VA_ARGS__; } break;    \
-        case 4: { constexpr int L = 4; __VA_ARGS__; } break;    \
-        case 8: { constexpr int L = 8; __VA_ARGS__; } break;    \
-        case 16: { constexpr int L = 16; __VA_ARGS__; } break;  \
-        case 32: { constexpr int L = 32; __VA_ARGS__; } break;  \
-        default: { constexpr int L = 64; __VA_ARGS__; } break;  \
-    }
 
 int fill(lz_args& a, int count, int D, float* const* W, float* const* M, float* const* V, int32_t* const* last,
          const uint32_t* const* keys, const uint32_t* const* perm, const int64_t* n, const float* const* G, const int64_t* ldg,

@@ -1,13 +1,19 @@
-// Fused row-wise training step for tables too large for dense gradients / dense Adam (BASELINE config C5):
+// Fused row-wise training step for tables too large for dense gradients / dense Adam (BASELINE config C5).
 //
-//   cdr_bpr_fwd_grad   one pass over the batch: gather 3 rows per triple, loss partials, and the two compact gradient
-//                      rows every other row gradient is made of:  GU[b] = g_b (p - n),  GP[b] = g_b u
-//                      (dI[pid_b] += GP[b], dI[nid_b] -= GP[b]).  Nothing table-sized is ever written.
-//   cdr_sort_ids       stable LSD radix sort (rocPRIM) of the touched row ids with their occurrence index, over only the
-//                      significant key bits -> every table row's occurrences become one contiguous segment.
-//   cdr_rowwise_apply  one lane-group per segment head: sums the segment's gradient rows in occurrence order (fixed
-//                      order => deterministic, no float atomics), adds the EmbLoss term count * c * W[r], and applies
-//                      the optimizer (SGD, or Adam with per-row moments) in place: one read-modify-write per touched row.
+// Every fused entry point is one call of five stages on one stream (host helpers: "what the host entry points share" and
+// "the fused step's skeleton" below):
+//   1 EmbLoss head       embloss_head: norms of the batch's rows -> coefficients (+ head counters cleared, device update counts)
+//   2 sort and flags     sort_ids_with (stable rocPRIM radix sort of both tables' ids, one key space) + occ_flags: every row's
+//                        occurrences become one segment; flags = "only occurrence", heads of the duplicate segments (heads_view)
+//   3 forward set-up     make_tables: table pointers + optimizer scalars of both sides
+//   4 forward-and-apply  the variant's own kernel: rows occurring once updated in place, duplicates leave gradient rows
+//   5 tail               finish_and_apply_dups: dups_plan_make -> the variant's one-block finishing kernel -> apply_dups_pair
+//                        (segment sums in occurrence order: deterministic, no float atomics; EmbLoss term count * c * W[r])
+// What varies: cdr_bpr_step_fused[_dev] stage 1-2 (count path: ids without a sort) and 4; cdr_point_step_fused 4;
+// cdr_*_step_fused_kmajor 1 (point), 4 and the item side's limits; cdr_*_step_presort + cdr_bpr_step_from_diff /
+// cdr_point_step_from_dot split 2 from 1, 4, 5 around an all-reduce; cdr_bpr_shard_local_step sorts users only;
+// cdr_bpr_shard_plan + cdr_bpr_shard_step own key-making kernel in 2, the shard kernels in 5; cdr_point_step_fused_pair_dev own
+// kernels in 1, 2 (key making), 4 and the finish.  cdr_bpr_fwd_grad / cdr_sort_ids / cdr_rowwise_apply are the unfused calls.
 //
 // Semantics: exactly "sum of the batch's gradients evaluated at the pre-step weights", as autograd + a dense optimizer
 // would compute for the touched rows.  Rows not in the batch are not touched (for Adam this is the usual lazy/sparse
@@ -27,16 +33,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kUnroll = 4;
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-inline int grid_for(int64_t units, int per_block) {
-    int64_t g = (units + per_block - 1) / per_block;
-    const int64_t cap = CDR_NUM_CU * 8;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
 
 // ------------------------------------------------------------------------------------------------ forward + compact grads
 // SCATTER (row-sharded step): the item operand is the buffer of received rows, one entry per occurrence, and the item
@@ -1952,17 +1948,6 @@ __global__ __launch_bounds__(1024) void count_sort_kernel(const int64_t* __restr
 
 }  // namespace
 
-#define DISPATCH_LPR(lpr, ...)                                  \
-    switch (lpr) {                                              \
-        case 1: { constexpr int L = 1; __VA_ARGS__; } break;    \
-        case 2: { constexpr int L = 2; __VA_ARGS__; } break;    \
-        case 4: { constexpr int L = 4; __VA_ARGS__; } break;    \
-        case 8: { constexpr int L = 8; __VA_ARGS__; } break;    \
-        case 16: { constexpr int L = 16; __VA_ARGS__; } break;  \
-        case 32: { constexpr int L = 32; __VA_ARGS__; } break;  \
-        default: { constexpr int L = 64; __VA_ARGS__; } break;  \
-    }
-
 extern "C" int cdr_bpr_fwd_grad(cdr_ctx* ctx, void* stream, const float* user_tab, const float* item_tab, int D,
                                 const int64_t* uid, const int64_t* pid, const int64_t* nid, int64_t B, int64_t B_mean,
                                 float gamma, float reg_weight, float* out6, float* GU, float* GP, int scatter) {
@@ -2037,13 +2022,88 @@ static inline unsigned bits_for(int64_t num_rows) {
     return b;
 }
 
+// ------------------------------------------------------------------------------------------------ what the host entry points share
+namespace {
+
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// A step's index buffer `heads` = {cnt[4] | headsA[n_a / 2 + 1] | headsB[n_b / 2 + 1]}: the two duplicate-segment head lists of
+// occ_flags_kernel (a list of n occurrences has at most n / 2 segments of two and more) behind their lengths cnt[0], cnt[1].
+struct heads_view {
+    unsigned* cnt; uint32_t* headsA; uint32_t* headsB;
+    heads_view(uint32_t* heads, int64_t n_a) : cnt((unsigned*)heads), headsA(heads + 4), headsB(headsA + (n_a / 2 + 1)) {}
+    static int64_t words(int64_t n_a, int64_t n_b) { return 4 + (n_a / 2 + 1) + (n_b / 2 + 1); }
+};
+
+// The count path's duplicate list (cdr_ctx_set_id_counters): kListHdr header words + the 3 B occurrences rounded up to a power of two.
+inline size_t count_list_bytes(int64_t B) {
+    int64_t P = 1024;
+    while (P < 3 * B) P <<= 1;
+    return (size_t)(P + kListHdr) * sizeof(uint64_t);
+}
+
+// Keys of a two-table sort: table A's rows as they are, table B's rows with bit hb set (key_base = 1 << hb; hb + 1 key bits in all).
+inline unsigned two_table_bits(int64_t rows_a, int64_t rows_b) {
+    const unsigned a = bits_for(rows_a), b = bits_for(rows_b);
+    return a > b ? a : b;
+}
+
+apply_hp make_hp(int opt, float lr, float beta1, float beta2, float eps, float wd, int64_t step) {
+    float step_size = lr, bc2_sqrt = 1.f;
+    if (opt == 1) {
+        cdr_adam_hp((double)step, lr, beta1, beta2, step_size, bc2_sqrt);       // (bc2_sqrt carries cdr_adam_hp's bc2: cdr_adam_math.h)
+    }
+    return apply_hp{lr, beta1, beta2, eps, wd, step_size, bc2_sqrt};
+}
+
+// Long-segment scratch of one segmented apply over n occurrences (empty when no segment can be longer than kLongSeg):
+//   counters[4] (256 bytes) | seg_long[long_cap] | seg_piece[piece_cap] | int pcnt[piece_cap] | float partial[piece_cap][D]
+struct long_scratch {
+    int64_t long_cap = 0, piece_cap = 0;
+    size_t o_long = 0, o_piece = 0, o_cnt = 0, o_part = 0, bytes = 0;          // bytes: up to the end of partial, not rounded up
+    long_scratch() = default;
+    long_scratch(int64_t n, int D) {
+        if (n <= kLongSeg) return;
+        long_cap = n / (kLongSeg + 1) + 1;
+        piece_cap = n / kPiece + long_cap + 1;
+        o_long = 256; o_piece = o_long + up256(sizeof(seg_long) * long_cap); o_cnt = o_piece + up256(sizeof(seg_piece) * piece_cap);
+        o_part = o_cnt + up256(sizeof(int) * piece_cap); bytes = o_part + sizeof(float) * (size_t)piece_cap * D;
+    }
+    void bind(char* base, dup_side& t) const {
+        t.counters = (unsigned*)base; t.longs = (seg_long*)(base + o_long); t.pieces = (seg_piece*)(base + o_piece);
+        t.pcnt = (int*)(base + o_cnt); t.partial = (float*)(base + o_part);
+    }
+};
+
+}  // namespace
+
 extern "C" int cdr_sort_workspace_bytes(int64_t n, int64_t num_rows, size_t* bytes) {
     CDR_CHECK_ARG(bytes && n > 0 && num_rows > 0 && num_rows <= (int64_t)0xFFFFFFFFu && n <= (int64_t)0x7FFFFFFF);
     size_t tmp = 0;
     hipError_t e = sort_pairs(nullptr, tmp, nullptr, nullptr, nullptr, nullptr, (size_t)n, bits_for(num_rows), (hipStream_t)0);
     if (e != hipSuccess) { cdr_set_error("cdr_sort_workspace_bytes: %s", hipGetErrorString(e)); return (int)e; }
-    tmp = (tmp + 255) & ~(size_t)255;
-    *bytes = tmp + 2 * (((size_t)n * sizeof(uint32_t) + 255) & ~(size_t)255);
+    *bytes = up256(tmp) + 2 * up256((size_t)n * sizeof(uint32_t));
+    return CDR_OK;
+}
+
+// What every id sort shares: the workspace {keys_in[n] | vals_in[n] | rocPRIM's temporary} (cdr_sort_workspace_bytes), the caller's
+// key-making launch -- make_keys(keys_in, vals_in) -- and the radix sort over the bits of `key_space`, in one CDR_TAG_SORT bracket.
+template <class MakeKeys>
+static int sort_ids_with(cdr_ctx* ctx, hipStream_t s, int64_t n, int64_t key_space, uint32_t* keys_sorted, uint32_t* perm, void* ws,
+                         size_t ws_bytes, MakeKeys&& make_keys) {
+    size_t need = 0;
+    int rc = cdr_sort_workspace_bytes(n, key_space, &need);
+    if (rc) return rc;
+    CDR_CHECK_ARG(ws_bytes >= need);
+    const size_t arr = up256((size_t)n * sizeof(uint32_t));
+    uint32_t* keys_in = (uint32_t*)ws;
+    uint32_t* vals_in = (uint32_t*)((char*)ws + arr);
+    void* tmp = (char*)ws + 2 * arr;
+    size_t tmp_bytes = ws_bytes - 2 * arr;
+    cdr_time_scope ts(ctx, CDR_TAG_SORT, s);
+    make_keys(keys_in, vals_in);
+    CDR_LAUNCH_CHECK();
+    CDR_HIP(sort_pairs(tmp, tmp_bytes, keys_in, keys_sorted, vals_in, perm, (size_t)n, bits_for(key_space), s));
     return CDR_OK;
 }
 
@@ -2052,21 +2112,10 @@ extern "C" int cdr_sort_ids(cdr_ctx* ctx, void* stream, const int64_t* ids0, int
                             size_t workspace_bytes) {
     const int64_t n = n0 + n1;
     CDR_CHECK_ARG(ids0 && n0 > 0 && (n1 == 0 || ids1) && keys_sorted && perm && workspace);
-    size_t need = 0;
-    int rc = cdr_sort_workspace_bytes(n, num_rows, &need);
-    if (rc) return rc;
-    CDR_CHECK_ARG(workspace_bytes >= need);
     hipStream_t s = (hipStream_t)stream;
-    const size_t arr = ((size_t)n * sizeof(uint32_t) + 255) & ~(size_t)255;
-    uint32_t* keys_in = (uint32_t*)workspace;
-    uint32_t* vals_in = (uint32_t*)((char*)workspace + arr);
-    void* tmp = (char*)workspace + 2 * arr;
-    size_t tmp_bytes = workspace_bytes - 2 * arr;
-    cdr_time_scope ts(ctx, CDR_TAG_SORT, s);
-    make_keys_kernel<<<dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s>>>(ids0, n0, ids1, n1, keys_in, vals_in);
-    CDR_LAUNCH_CHECK();
-    CDR_HIP(sort_pairs(tmp, tmp_bytes, keys_in, keys_sorted, vals_in, perm, (size_t)n, bits_for(num_rows), s));
-    return CDR_OK;
+    return sort_ids_with(ctx, s, n, num_rows, keys_sorted, perm, workspace, workspace_bytes, [&](uint32_t* keys_in, uint32_t* vals_in) {
+        make_keys_kernel<<<dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s>>>(ids0, n0, ids1, n1, keys_in, vals_in);
+    });
 }
 
 extern "C" int cdr_sort_ids_two_tables(cdr_ctx* ctx, void* stream, const int64_t* ids_a, int64_t n_a, int64_t rows_a,
@@ -2076,23 +2125,14 @@ extern "C" int cdr_sort_ids_two_tables(cdr_ctx* ctx, void* stream, const int64_t
     const int64_t n = n_a + n_b0 + n_b1;
     CDR_CHECK_ARG(ids_a && n_a > 0 && ids_b0 && n_b0 > 0 && (n_b1 == 0 || ids_b1) && keys_sorted && perm && key_base_out && workspace);
     CDR_CHECK_ARG(rows_a > 0 && rows_b > 0);
-    const unsigned hb = bits_for(rows_a) > bits_for(rows_b) ? bits_for(rows_a) : bits_for(rows_b);
+    const unsigned hb = two_table_bits(rows_a, rows_b);
     CDR_CHECK_ARG(hb < 31);
     const uint32_t key_base = 1u << hb;
-    size_t need = 0;
-    int rc = cdr_sort_workspace_bytes(n, (int64_t)key_base * 2, &need);
-    if (rc) return rc;
-    CDR_CHECK_ARG(workspace_bytes >= need);
     hipStream_t s = (hipStream_t)stream;
-    const size_t arr = ((size_t)n * sizeof(uint32_t) + 255) & ~(size_t)255;
-    uint32_t* keys_in = (uint32_t*)workspace;
-    uint32_t* vals_in = (uint32_t*)((char*)workspace + arr);
-    void* tmp = (char*)workspace + 2 * arr;
-    size_t tmp_bytes = workspace_bytes - 2 * arr;
-    cdr_time_scope ts(ctx, CDR_TAG_SORT, s);
-    make_keys2_kernel<<<dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s>>>(ids_a, n_a, ids_b0, n_b0, ids_b1, n_b1, key_base, keys_in, vals_in);
-    CDR_LAUNCH_CHECK();
-    CDR_HIP(sort_pairs(tmp, tmp_bytes, keys_in, keys_sorted, vals_in, perm, (size_t)n, hb + 1, s));
+    int rc = sort_ids_with(ctx, s, n, (int64_t)key_base * 2, keys_sorted, perm, workspace, workspace_bytes, [&](uint32_t* keys_in, uint32_t* vals_in) {
+        make_keys2_kernel<<<dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s>>>(ids_a, n_a, ids_b0, n_b0, ids_b1, n_b1, key_base, keys_in, vals_in);
+    });
+    if (rc) return rc;
     *key_base_out = key_base;
     return CDR_OK;
 }
@@ -2112,78 +2152,105 @@ extern "C" int cdr_rowwise_apply(cdr_ctx* ctx, void* stream, int opt, float* tab
         if (exp_avg) exp_avg -= (int64_t)key_base * D;
         if (exp_avg_sq) exp_avg_sq -= (int64_t)key_base * D;
     }
-    float step_size = lr, bc2_sqrt = 1.f;
-    if (opt == 1) {
-        cdr_adam_hp((double)step, lr, beta1, beta2, step_size, bc2_sqrt);       // (bc2_sqrt carries cdr_adam_hp's bc2: cdr_adam_math.h)
-    }
     const int lpr = cdr_lpr_for(D);
     const int grid = grid_for(n, kBlock / lpr);
     const bool is_signed = neg_start < n;
-    const apply_hp hp{lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt};
-    // long-segment scratch: counters | seg_long[long_cap] | seg_piece[piece_cap] | int pcnt[piece_cap] | float partial[piece_cap][D]
-    const bool may_have_long = n > kLongSeg;
-    unsigned* counters = nullptr; seg_long* longs = nullptr; seg_piece* pieces = nullptr; int* pcnt = nullptr; float* partial = nullptr;
-    int64_t long_cap = 0, piece_cap = 0;
-    if (may_have_long) {
+    const apply_hp hp = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step);
+    const long_scratch ls(n, D);
+    dup_side sc{};                                          // (only its five scratch members are used here)
+    if (ls.bytes) {
         CDR_CHECK_ARG(ctx != nullptr);
-        long_cap = n / (kLongSeg + 1) + 1;
-        piece_cap = n / kPiece + long_cap + 1;
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_long = 256, o_piece = o_long + up(sizeof(seg_long) * long_cap), o_cnt = o_piece + up(sizeof(seg_piece) * piece_cap),
-                     o_part = o_cnt + up(sizeof(int) * piece_cap), total = o_part + sizeof(float) * (size_t)piece_cap * D;
         void* base = nullptr;
-        int rc = cdr_ctx_scratch(ctx, total, &base);
+        int rc = cdr_ctx_scratch(ctx, ls.bytes, &base);
         if (rc != CDR_OK) return rc;
-        counters = (unsigned*)base; longs = (seg_long*)((char*)base + o_long); pieces = (seg_piece*)((char*)base + o_piece);
-        pcnt = (int*)((char*)base + o_cnt); partial = (float*)((char*)base + o_part);
-        CDR_HIP(cdr_zero_u32(counters, 4, s));
+        ls.bind((char*)base, sc);
+        CDR_HIP(cdr_zero_u32(sc.counters, 4, s));
     }
     cdr_time_scope ts(ctx, is_signed ? CDR_TAG_APPLY_SIGNED : CDR_TAG_APPLY_UNSIGNED, s);
-#define APPLY_ARGS table, exp_avg, exp_avg_sq, D, keys_sorted, perm, n, G, neg_start, reg_limit, reg_coef, hp, occ_ids, counters, longs, pieces
+#define APPLY_ARGS table, exp_avg, exp_avg_sq, D, keys_sorted, perm, n, G, neg_start, reg_limit, reg_coef, hp, occ_ids, sc.counters, sc.longs, sc.pieces
     if (opt == 0 && !is_signed) { DISPATCH_LPR(lpr, rowwise_apply_kernel<L, 0, false><<<dim3(grid), dim3(kBlock), 0, s>>>(APPLY_ARGS)); }
     else if (opt == 0) { DISPATCH_LPR(lpr, rowwise_apply_kernel<L, 0, true><<<dim3(grid), dim3(kBlock), 0, s>>>(APPLY_ARGS)); }
     else if (!is_signed) { DISPATCH_LPR(lpr, rowwise_apply_kernel<L, 1, false><<<dim3(grid), dim3(kBlock), 0, s>>>(APPLY_ARGS)); }
     else { DISPATCH_LPR(lpr, rowwise_apply_kernel<L, 1, true><<<dim3(grid), dim3(kBlock), 0, s>>>(APPLY_ARGS)); }
 #undef APPLY_ARGS
     CDR_LAUNCH_CHECK();
-    if (may_have_long) {
+    if (ls.bytes) {
         // sized for the worst case, but a launch whose counters read 0 retires in a few microseconds
-        const int gp = (int)(piece_cap < 2048 ? piece_cap : 2048);          // one workgroup per piece (looping past 2,048)
-        if (is_signed) { DISPATCH_LPR(lpr, seg_piece_sum_kernel<L, true><<<dim3(gp), dim3(kBlock), 0, s>>>(D, perm, G, neg_start, reg_limit, occ_ids, counters, pieces, partial, pcnt)); }
-        else { DISPATCH_LPR(lpr, seg_piece_sum_kernel<L, false><<<dim3(gp), dim3(kBlock), 0, s>>>(D, perm, G, neg_start, reg_limit, occ_ids, counters, pieces, partial, pcnt)); }
+        const int gp = (int)(ls.piece_cap < 2048 ? ls.piece_cap : 2048);          // one workgroup per piece (looping past 2,048)
+        if (is_signed) { DISPATCH_LPR(lpr, seg_piece_sum_kernel<L, true><<<dim3(gp), dim3(kBlock), 0, s>>>(D, perm, G, neg_start, reg_limit, occ_ids, sc.counters, sc.pieces, sc.partial, sc.pcnt)); }
+        else { DISPATCH_LPR(lpr, seg_piece_sum_kernel<L, false><<<dim3(gp), dim3(kBlock), 0, s>>>(D, perm, G, neg_start, reg_limit, occ_ids, sc.counters, sc.pieces, sc.partial, sc.pcnt)); }
         CDR_LAUNCH_CHECK();
-        const int gl = grid_for(long_cap < 4096 ? long_cap : 4096, kBlock / lpr);
-        if (opt == 0) { DISPATCH_LPR(lpr, seg_long_finish_kernel<L, 0><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, reg_coef, hp, counters, longs, partial, pcnt)); }
-        else { DISPATCH_LPR(lpr, seg_long_finish_kernel<L, 1><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, reg_coef, hp, counters, longs, partial, pcnt)); }
+        const int gl = grid_for(ls.long_cap < 4096 ? ls.long_cap : 4096, kBlock / lpr);
+        if (opt == 0) { DISPATCH_LPR(lpr, seg_long_finish_kernel<L, 0><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, reg_coef, hp, sc.counters, sc.longs, sc.partial, sc.pcnt)); }
+        else { DISPATCH_LPR(lpr, seg_long_finish_kernel<L, 1><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, reg_coef, hp, sc.counters, sc.longs, sc.partial, sc.pcnt)); }
         CDR_LAUNCH_CHECK();
     }
     return CDR_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ the fused step (round 3)
+// ------------------------------------------------------------------------------------------------ the fused step's skeleton
 namespace {
 
-// Both tables' duplicate-row applies of a fused step: one scratch request carved for the two sides, three launches with blockIdx.y =
-// side instead of six (+ two counter clears, which the caller folds into step_finish_keep_kernel: dups_plan first, then that launch).
-struct dup_host { float* table; float* m; float* v; const uint32_t* keys; const uint32_t* perm; int64_t n; const uint32_t* heads; const unsigned* nheads;
+// The two tables of a step with the optimizer scalars of their updates (a table that is only read: opt_item = 0, no moments).
+struct step_tables { tab_ptrs TU, TI; apply_hp hu, hi; };
+step_tables make_tables(int opt_user, float* user_tab, float* user_m, float* user_v, int64_t step_user, int opt_item, float* item_tab,
+                        float* item_m, float* item_v, int64_t step_item, float lr, float beta1, float beta2, float eps, float wd) {
+    return {{user_tab, user_m, user_v}, {item_tab, item_m, item_v}, make_hp(opt_user, lr, beta1, beta2, eps, wd, step_user),
+            make_hp(opt_item, lr, beta1, beta2, eps, wd, step_item)};
+}
+
+// Stage 1, EmbLoss head: the squared norms of the n_rows gathered (user, item) rows -> coefficients in out9[4], out9[5].  Without
+// regularisation the norms launch is skipped (ngrid = 0 says so to coef_finish_kernel).  The finishing block also clears the head
+// lists' counters `cnt` and, when given, advances the device-resident update counts (their Adam scalars -> hp_dev).
+int embloss_head(cdr_ctx* ctx, hipStream_t s, const float* user_tab, const float* item_tab, int D, const int64_t* uid, const int64_t* pid,
+                 int64_t n_rows, int64_t B, int kmul, float reg_weight, float* out9, unsigned* cnt, int64_t* step_user_dev = nullptr,
+                 int64_t* step_item_dev = nullptr, float* hp_dev = nullptr, float lr = 0.f, float beta1 = 0.f, float beta2 = 0.f) {
+    int ngrid = 0;
+    if (reg_weight != 0.f) {
+        const int lpr = cdr_lpr_for(D);
+        ngrid = grid_for((n_rows + 7) / 8, kBlock / lpr);
+        cdr_time_scope ts(ctx, CDR_TAG_BATCH_NORMS, s);
+        DISPATCH_LPR(lpr, batch_norms_kernel<L><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, n_rows, ctx->partials));
+        CDR_LAUNCH_CHECK();
+    }
+    coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B, ngrid ? reg_weight : 0.f, out9, kmul, step_user_dev, step_item_dev, hp_dev,
+                                                        lr, beta1, beta2, cnt);
+    CDR_LAUNCH_CHECK();
+    return CDR_OK;
+}
+
+// Stage 2 behind the sort: per-occurrence "only occurrence of its row" flags and the duplicate segments' heads of the sorted list
+// [n_a keys of table A | n - n_a keys of table B].
+int occ_flags(cdr_ctx* ctx, hipStream_t s, const uint32_t* keys, const uint32_t* perm, int64_t n_a, int64_t n, int fstride, uint8_t* flags,
+              const heads_view& hv, bool stat = false) {
+    cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
+    occ_flags_kernel<<<dim3(grid_for(n, kBlock * kFlagIT)), dim3(kBlock), 0, s>>>(keys, perm, n_a, n, fstride, flags, hv.headsA, hv.headsB, hv.cnt, stat);
+    CDR_LAUNCH_CHECK();
+    return CDR_OK;
+}
+
+// Stage 5, both tables' duplicate-row applies: one scratch request carved for the two sides, three launches with blockIdx.y = side
+// instead of six (+ two counter clears, which the step's one-block finishing kernel does: finish_and_apply_dups).
+struct dup_host { tab_ptrs T; const uint32_t* keys; const uint32_t* perm; int64_t n; const uint32_t* heads; const unsigned* nheads;
                   const float* G; int64_t neg_start, reg_limit; const float* reg_coef; apply_hp hp; uint32_t key_base;
                   float* out = nullptr; const uint32_t* uidx = nullptr; };
-struct dups_plan { dup_side side[2]; int64_t long_cap[2], piece_cap[2]; };
+struct dups_plan { dup_side side[2]; long_scratch ls[2]; };
 
-static int dups_plan_make(cdr_ctx* ctx, int D, const dup_host (&h)[2], dups_plan& pl) {
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off[2][5], total = 0;
+// The sides of a step on the sorted list [n_user user keys | n_item item keys]: users over GU with every occurrence positive and
+// regularised, items over GI with occurrences from neg_start_item on subtracted and those below reg_limit_item regularised.
+void make_sides(dup_host (&sides)[2], const step_tables& T, const uint32_t* keys, const uint32_t* perm, const heads_view& hv, const float* GU,
+                const float* GI, int64_t n_user, int64_t n_item, int64_t neg_start_item, int64_t reg_limit_item, const float* coef_user,
+                const float* coef_item, uint32_t key_base) {
+    sides[0] = {T.TU, keys, perm, n_user, hv.headsA, hv.cnt, GU, n_user, n_user, coef_user, T.hu, 0};
+    sides[1] = {T.TI, keys + n_user, perm + n_user, n_item, hv.headsB, hv.cnt + 1, GI, neg_start_item, reg_limit_item, coef_item, T.hi, key_base};
+}
+
+int dups_plan_make(cdr_ctx* ctx, int D, const dup_host (&h)[2], dups_plan& pl) {
+    size_t off[2], total = 0;
     for (int i = 0; i < 2; ++i) {
-        pl.long_cap[i] = pl.piece_cap[i] = 0;
-        if (h[i].n > kLongSeg) {
-            pl.long_cap[i] = h[i].n / (kLongSeg + 1) + 1;
-            pl.piece_cap[i] = h[i].n / kPiece + pl.long_cap[i] + 1;
-            off[i][0] = total; total += 256;
-            off[i][1] = total; total += up(sizeof(seg_long) * pl.long_cap[i]);
-            off[i][2] = total; total += up(sizeof(seg_piece) * pl.piece_cap[i]);
-            off[i][3] = total; total += up(sizeof(int) * pl.piece_cap[i]);
-            off[i][4] = total; total += up(sizeof(float) * (size_t)pl.piece_cap[i] * D);
-        }
+        pl.ls[i] = long_scratch(h[i].n, D);
+        off[i] = total;
+        total += up256(pl.ls[i].bytes);
     }
     char* base = nullptr;
     if (total) {
@@ -2195,56 +2262,69 @@ static int dups_plan_make(cdr_ctx* ctx, int D, const dup_host (&h)[2], dups_plan
     for (int i = 0; i < 2; ++i) {
         dup_side& t = pl.side[i];
         const int64_t kb = (int64_t)h[i].key_base * D;
-        t.W = h[i].table - kb; t.M = h[i].m ? h[i].m - kb : nullptr; t.V = h[i].v ? h[i].v - kb : nullptr;
+        t.W = h[i].T.W - kb; t.M = h[i].T.M ? h[i].T.M - kb : nullptr; t.V = h[i].T.V ? h[i].T.V - kb : nullptr;
         t.keys = h[i].keys; t.perm = h[i].perm; t.n = h[i].n; t.heads = h[i].heads; t.nheads = h[i].nheads; t.G = h[i].G;
         t.neg_start = h[i].neg_start; t.reg_limit = h[i].reg_limit; t.reg_coef = h[i].reg_coef; t.hp = h[i].hp;
         t.counters = nullptr; t.longs = nullptr; t.pieces = nullptr; t.pcnt = nullptr; t.partial = nullptr;
         t.out = h[i].out; t.uidx = h[i].uidx;
-        if (pl.long_cap[i]) {
-            t.counters = (unsigned*)(base + off[i][0]); t.longs = (seg_long*)(base + off[i][1]); t.pieces = (seg_piece*)(base + off[i][2]);
-            t.pcnt = (int*)(base + off[i][3]); t.partial = (float*)(base + off[i][4]);
-        }
+        if (pl.ls[i].bytes) pl.ls[i].bind(base + off[i], t);
     }
     return CDR_OK;
 }
 
-static int apply_dups_pair(cdr_ctx* ctx, hipStream_t s, int opt, int D, const dups_plan& pl) {
+// The two kernel pairs of apply_dups_pair: both sides update their table (every one-GPU step), or side 1 sums its segments into the
+// send buffer dup_side::out (the row-sharded step).
+struct table_dups {
+    template <int L, int OPT> static constexpr auto dups = rowwise_apply_dups2_kernel<L, OPT>;
+    template <int L, int OPT> static constexpr auto long_finish = seg_long_finish2_kernel<L, OPT>;
+};
+struct shard_dups {
+    template <int L, int OPT> static constexpr auto dups = shard_dups_kernel<L, OPT>;
+    template <int L, int OPT> static constexpr auto long_finish = shard_long_finish_kernel<L, OPT>;
+};
+
+template <class K>
+int apply_dups_pair(cdr_ctx* ctx, hipStream_t s, int opt, int D, const dups_plan& pl) {
     const int lpr = cdr_lpr_for(D);
-    const int64_t nmax = pl.side[0].n > pl.side[1].n ? pl.side[0].n : pl.side[1].n;
+    const int64_t nmax = pl.side[0].n > pl.side[1].n ? pl.side[0].n : pl.side[1].n;     // (row shard: the item side's 2 Bl)
     const int grid = grid_for(nmax / 16 + 1, kBlock / lpr);          // four segments per lane group and round (apply_dups)
     {
         cdr_time_scope ts(ctx, CDR_TAG_APPLY_SIGNED, s);
-        if (opt == 0) { DISPATCH_LPR(lpr, rowwise_apply_dups2_kernel<L, 0><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
-        else { DISPATCH_LPR(lpr, rowwise_apply_dups2_kernel<L, 1><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
+        if (opt == 0) { DISPATCH_LPR(lpr, K::template dups<L, 0><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
+        else { DISPATCH_LPR(lpr, K::template dups<L, 1><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
     }
     CDR_LAUNCH_CHECK();
-    if (pl.long_cap[0] || pl.long_cap[1]) {
-        const int64_t pc = pl.piece_cap[0] > pl.piece_cap[1] ? pl.piece_cap[0] : pl.piece_cap[1];
-        const int64_t lc = pl.long_cap[0] > pl.long_cap[1] ? pl.long_cap[0] : pl.long_cap[1];
+    if (pl.ls[0].long_cap || pl.ls[1].long_cap) {
+        const int64_t pc = pl.ls[0].piece_cap > pl.ls[1].piece_cap ? pl.ls[0].piece_cap : pl.ls[1].piece_cap;
+        const int64_t lc = pl.ls[0].long_cap > pl.ls[1].long_cap ? pl.ls[0].long_cap : pl.ls[1].long_cap;
         const int gp = (int)(pc < 2048 ? pc : 2048);                        // one workgroup per piece (looping past 2,048)
         DISPATCH_LPR(lpr, seg_piece_sum2_kernel<L><<<dim3(gp, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
         CDR_LAUNCH_CHECK();
         const int gl = grid_for(lc < 4096 ? lc : 4096, kBlock / lpr);
-        if (opt == 0) { DISPATCH_LPR(lpr, seg_long_finish2_kernel<L, 0><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
-        else { DISPATCH_LPR(lpr, seg_long_finish2_kernel<L, 1><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
+        if (opt == 0) { DISPATCH_LPR(lpr, K::template long_finish<L, 0><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
+        else { DISPATCH_LPR(lpr, K::template long_finish<L, 1><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
         CDR_LAUNCH_CHECK();
     }
     return CDR_OK;
 }
 
-static apply_hp make_hp(int opt, float lr, float beta1, float beta2, float eps, float wd, int64_t step) {
-    float step_size = lr, bc2_sqrt = 1.f;
-    if (opt == 1) {
-        cdr_adam_hp((double)step, lr, beta1, beta2, step_size, bc2_sqrt);       // (bc2_sqrt carries cdr_adam_hp's bc2: cdr_adam_math.h)
-    }
-    return apply_hp{lr, beta1, beta2, eps, wd, step_size, bc2_sqrt};
+// The tail of every step: plan the two sides' scratch, let the step's one-block finishing kernel run -- finish(counters of side 0,
+// counters of side 1) launches it; it writes the loss vector and clears the long-segment counters given -- then the applies.
+template <class K = table_dups, class Finish>
+int finish_and_apply_dups(cdr_ctx* ctx, hipStream_t s, int opt, int D, const dup_host (&sides)[2], Finish&& finish) {
+    dups_plan pl;
+    int rc = dups_plan_make(ctx, D, sides, pl);
+    if (rc) return rc;
+    finish(pl.side[0].counters, pl.side[1].counters);
+    CDR_LAUNCH_CHECK();
+    return apply_dups_pair<K>(ctx, s, opt, D, pl);
 }
 
 }  // namespace
 
 extern "C" int cdr_bpr_step_fused_heads_words(int64_t B, int64_t* words) {
     CDR_CHECK_ARG(words && B > 0);
-    *words = 4 + (B / 2 + 1) + (B + 1);          // {counters[4] | heads of the user list | heads of the item list}
+    *words = heads_view::words(B, 2 * B);          // heads of the user list | heads of the item list [pid | nid]
     return CDR_OK;
 }
 
@@ -2257,18 +2337,14 @@ static int bpr_step_fused_impl(cdr_ctx* ctx, void* stream, int opt, float* user_
                                void* sort_ws, size_t sort_ws_bytes) {
     hipStream_t s = (hipStream_t)stream;
     const int lpr = cdr_lpr_for(D);
-    unsigned* cnt = (unsigned*)heads;
-    uint32_t* headsA = heads + 4;
-    uint32_t* headsB = headsA + (B / 2 + 1);           // (cnt[0..3] are cleared by coef_finish_kernel)
+    const heads_view hv(heads, B);                     // (cnt[0..3] are cleared by coef_finish_kernel)
     uint32_t key_base = 0;
     int rc;
     // ---- ids without a sort (medium batches, counters handed over by cdr_ctx_set_id_counters): see "round 6: ids without a sort"
-    int64_t P = 1024;
-    while (P < 3 * B) P <<= 1;
     const bool count_path = ctx->idc_user && ctx->idc_item && ctx->idc_user_rows == user_rows && ctx->idc_item_rows == item_rows &&
-                            B >= kCountMinB && B <= kCountMaxB && ctx->idc_list_bytes >= (size_t)(P + kListHdr) * sizeof(uint64_t);
+                            B >= kCountMinB && B <= kCountMaxB && ctx->idc_list_bytes >= count_list_bytes(B);
     if (count_path) {
-        const unsigned hb = bits_for(user_rows) > bits_for(item_rows) ? bits_for(user_rows) : bits_for(item_rows);
+        const unsigned hb = two_table_bits(user_rows, item_rows);
         CDR_CHECK_ARG(hb < 31);
         key_base = 1u << hb;
         const int ngrid = grid_for((B + 7) / 8, kBlock / lpr);
@@ -2284,72 +2360,49 @@ static int bpr_step_fused_impl(cdr_ctx* ctx, void* stream, int opt, float* user_
         }
         CDR_LAUNCH_CHECK();
         coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, reg_weight != 0.f ? ngrid : 0, B, reg_weight, out9, 1, step_user_dev, step_item_dev, hp_dev,
-                                                            lr, beta1, beta2, cnt);
+                                                            lr, beta1, beta2, hv.cnt);
         CDR_LAUNCH_CHECK();
         {
             cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
             count_flags_kernel<<<dim3(grid_for(B, kBlock)), dim3(kBlock), 0, s>>>(uid, pid, nid, B, ctx->idc_user, ctx->idc_item, key_base, (uint32_t*)flags,
-                                                                                 (uint64_t*)ctx->idc_list, cnt);
+                                                                                 (uint64_t*)ctx->idc_list, hv.cnt);
             CDR_LAUNCH_CHECK();
             count_sort_kernel<<<dim3(kRankBlocks + 128), dim3(1024), 0, s>>>(uid, pid, nid, B, ctx->idc_user, ctx->idc_item, key_base,
-                                                                                            (uint64_t*)ctx->idc_list, keys, perm, headsA, headsB, cnt);
+                                                                                            (uint64_t*)ctx->idc_list, keys, perm, hv.headsA, hv.headsB, hv.cnt);
         }
         CDR_LAUNCH_CHECK();
     } else {
-    // ---- EmbLoss coefficients first (they do not need the sort): out9[4], out9[5]  (+ the device-resident update counts, when given)
-    if (reg_weight != 0.f) {
-        const int ngrid = grid_for((B + 7) / 8, kBlock / lpr);
-        {
-            cdr_time_scope ts(ctx, CDR_TAG_BATCH_NORMS, s);
-            DISPATCH_LPR(lpr, batch_norms_kernel<L><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, B, ctx->partials));
-        }
-        CDR_LAUNCH_CHECK();
-        coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B, reg_weight, out9, 1, step_user_dev, step_item_dev, hp_dev, lr, beta1, beta2,
-                                                            (unsigned*)heads);
-    } else {
-        coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, 0, B, 0.f, out9, 1, step_user_dev, step_item_dev, hp_dev, lr, beta1, beta2,
-                                                            (unsigned*)heads);
+        // ---- EmbLoss coefficients first (they do not need the sort): out9[4], out9[5]  (+ the device-resident update counts, when given)
+        rc = embloss_head(ctx, s, user_tab, item_tab, D, uid, pid, B, B, 1, reg_weight, out9, hv.cnt, step_user_dev, step_item_dev, hp_dev, lr, beta1, beta2);
+        if (rc) return rc;
+        rc = cdr_sort_ids_two_tables(ctx, stream, uid, B, user_rows, pid, B, nid, B, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes);
+        if (rc) return rc;
+        rc = occ_flags(ctx, s, keys, perm, B, 3 * B, 4, flags, hv, B <= kCountMaxB);
+        if (rc) return rc;
     }
-    CDR_LAUNCH_CHECK();
-    rc = cdr_sort_ids_two_tables(ctx, stream, uid, B, user_rows, pid, B, nid, B, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes);
-    if (rc) return rc;
-    const int fgrid = grid_for(3 * B, kBlock * kFlagIT);
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
-        occ_flags_kernel<<<dim3(fgrid), dim3(kBlock), 0, s>>>(keys, perm, B, 3 * B, 4, flags, headsA, headsB, cnt, B <= kCountMaxB);
-    }
-    CDR_LAUNCH_CHECK();
-    }
-    apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_user);
-    apply_hp hi = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_item);
-    if (hp_dev && opt == 1) { hu.dev = hp_dev; hi.dev = hp_dev + 2; }          // the scalars coef_finish_kernel left on the device
-    const tab_ptrs TU{user_tab, user_m, user_v}, TI{item_tab, item_m, item_v};
+    step_tables T = make_tables(opt, user_tab, user_m, user_v, step_user, opt, item_tab, item_m, item_v, step_item, lr, beta1, beta2, eps, weight_decay);
+    if (hp_dev && opt == 1) { T.hu.dev = hp_dev; T.hi.dev = hp_dev + 2; }          // the scalars coef_finish_kernel left on the device
     static const int un = [] { const char* e = getenv("CDR_FWD_APPLY_UN"); return (e && e[0] == '2') ? 2 : 1; }();   // A/B switch (tools/)
     const int grid = grid_for((B + un - 1) / un, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FA_ARGS TU, TI, D, uid, pid, nid, (const uint32_t*)flags, B, gamma, 1.0f / (float)B, out9 + 4, hu, hi, GU, GP, ctx->partials
+#define FA_ARGS T.TU, T.TI, D, uid, pid, nid, (const uint32_t*)flags, B, gamma, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials
         if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
         else if (un == 1) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
         else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 2><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
 #undef FA_ARGS
     }
     CDR_LAUNCH_CHECK();
-    const dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, B, headsA, cnt, GU, B, B, out9 + 4, hu, 0},
-                               {item_tab, item_m, item_v, keys + B, perm + B, 2 * B, headsB, cnt + 1, GP, B, B, out9 + 5, hi, key_base}};
-    dups_plan pl;
-    rc = dups_plan_make(ctx, D, sides, pl);
-    if (rc) return rc;
-    step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, pl.side[0].counters, pl.side[1].counters);
-    CDR_LAUNCH_CHECK();
-    return apply_dups_pair(ctx, s, opt, D, pl);
+    dup_host sides[2];
+    make_sides(sides, T, keys, perm, hv, GU, GP, B, 2 * B, B, B, out9 + 4, out9 + 5, key_base);
+    return finish_and_apply_dups(ctx, s, opt, D, sides, [&](unsigned* za, unsigned* zb) {
+        step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, za, zb);
+    });
 }
 
 extern "C" int cdr_id_count_workspace_bytes(int64_t B, size_t* bytes) {
     CDR_CHECK_ARG(bytes && B > 0 && 3 * B <= (int64_t)0x7FFFFFFF);
-    int64_t P = 1024;
-    while (P < 3 * B) P <<= 1;
-    *bytes = (size_t)(P + 8) * sizeof(uint64_t);             // 8: the list's header words (kListHdr)
+    *bytes = count_list_bytes(B);
     return CDR_OK;
 }
 
@@ -2404,49 +2457,29 @@ extern "C" int cdr_point_step_fused(cdr_ctx* ctx, void* stream, int loss_kind, i
     CDR_CHECK_ARG(((uintptr_t)flags & 3) == 0);
     hipStream_t s = (hipStream_t)stream;
     const int lpr = cdr_lpr_for(D);
-    if (reg_weight != 0.f) {
-        const int ngrid = grid_for((B + 7) / 8, kBlock / lpr);
-        {
-            cdr_time_scope ts(ctx, CDR_TAG_BATCH_NORMS, s);
-            DISPATCH_LPR(lpr, batch_norms_kernel<L><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, iid, B, ctx->partials));
-        }
-        CDR_LAUNCH_CHECK();
-        coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B, reg_weight, out9, 1, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, (unsigned*)heads);
-    } else {
-        coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, 0, B, 0.f, out9, 1, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, (unsigned*)heads);
-    }
-    CDR_LAUNCH_CHECK();
-    uint32_t key_base = 0;
-    int rc = cdr_sort_ids_two_tables(ctx, stream, uid, B, user_rows, iid, B, nullptr, 0, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes);
+    const heads_view hv(heads, B);
+    int rc = embloss_head(ctx, s, user_tab, item_tab, D, uid, iid, B, B, 1, reg_weight, out9, hv.cnt);
     if (rc) return rc;
-    unsigned* cnt = (unsigned*)heads;
-    uint32_t* headsA = heads + 4;
-    uint32_t* headsB = headsA + (B / 2 + 1);
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
-        occ_flags_kernel<<<dim3(grid_for(2 * B, kBlock * kFlagIT)), dim3(kBlock), 0, s>>>(keys, perm, B, 2 * B, 4, flags, headsA, headsB, cnt);
-    }
-    CDR_LAUNCH_CHECK();
-    const apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_user);
-    const apply_hp hi = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_item);
-    const tab_ptrs TU{user_tab, user_m, user_v}, TI{item_tab, item_m, item_v};
+    uint32_t key_base = 0;
+    rc = cdr_sort_ids_two_tables(ctx, stream, uid, B, user_rows, iid, B, nullptr, 0, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes);
+    if (rc) return rc;
+    rc = occ_flags(ctx, s, keys, perm, B, 2 * B, 4, flags, hv);
+    if (rc) return rc;
+    const step_tables T = make_tables(opt, user_tab, user_m, user_v, step_user, opt, item_tab, item_m, item_v, step_item, lr, beta1, beta2, eps, weight_decay);
     const int grid = grid_for(B, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-#define PA_ARGS loss_kind, TU, TI, D, uid, iid, label, (const uint32_t*)flags, B, 1.0f / (float)B, out9 + 4, hu, hi, GU, GI, ctx->partials
+#define PA_ARGS loss_kind, T.TU, T.TI, D, uid, iid, label, (const uint32_t*)flags, B, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials
         if (opt == 0) { DISPATCH_LPR(lpr, point_fwd_apply_kernel<L, 0><<<dim3(grid), dim3(kBlock), 0, s>>>(PA_ARGS)); }
         else { DISPATCH_LPR(lpr, point_fwd_apply_kernel<L, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(PA_ARGS)); }
 #undef PA_ARGS
     }
     CDR_LAUNCH_CHECK();
-    const dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, B, headsA, cnt, GU, B, B, out9 + 4, hu, 0},
-                               {item_tab, item_m, item_v, keys + B, perm + B, B, headsB, cnt + 1, GI, B, B, out9 + 5, hi, key_base}};
-    dups_plan pl;
-    rc = dups_plan_make(ctx, D, sides, pl);
-    if (rc) return rc;
-    step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, pl.side[0].counters, pl.side[1].counters);
-    CDR_LAUNCH_CHECK();
-    return apply_dups_pair(ctx, s, opt, D, pl);
+    dup_host sides[2];
+    make_sides(sides, T, keys, perm, hv, GU, GI, B, B, B, B, out9 + 4, out9 + 5, key_base);
+    return finish_and_apply_dups(ctx, s, opt, D, sides, [&](unsigned* za, unsigned* zb) {
+        step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, za, zb);
+    });
 }
 
 // The pointwise step per POSITIVE: uid [S] (the first S entries of recbole's tiled user column), iid [S + S k] = [positives | k-major
@@ -2465,32 +2498,25 @@ extern "C" int cdr_point_step_fused_kmajor(cdr_ctx* ctx, void* stream, int loss_
     hipStream_t s = (hipStream_t)stream;
     const int lpr = cdr_lpr_for(D);
     const int fstride = (2 + k + 3) & ~3;
+    const heads_view hv(heads, S);
     const int ngrid = reg_weight != 0.f ? grid_for(S, kBlock / lpr) : 0;
     if (reg_weight != 0.f) {
         cdr_time_scope ts(ctx, CDR_TAG_BATCH_NORMS, s);
         DISPATCH_LPR(lpr, point_norms_kmajor_kernel<L><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, iid, S, k, ctx->partials));
         CDR_LAUNCH_CHECK();
     }
-    point_coef_kmajor_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B, k, reg_weight, out12, (unsigned*)heads);
+    point_coef_kmajor_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B, k, reg_weight, out12, hv.cnt);
     CDR_LAUNCH_CHECK();
     uint32_t key_base = 0;
     int rc = cdr_sort_ids_two_tables(ctx, stream, uid, S, user_rows, iid, S, iid + S, S * (int64_t)k, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes);
     if (rc) return rc;
-    unsigned* cnt = (unsigned*)heads;
-    uint32_t* headsA = heads + 4;
-    uint32_t* headsB = headsA + (S / 2 + 1);
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
-        occ_flags_kernel<<<dim3(grid_for(S + nI, kBlock * kFlagIT)), dim3(kBlock), 0, s>>>(keys, perm, S, S + nI, fstride, flags, headsA, headsB, cnt);
-    }
-    CDR_LAUNCH_CHECK();
-    const apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_user);
-    const apply_hp hi = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_item);
-    const tab_ptrs TU{user_tab, user_m, user_v}, TI{item_tab, item_m, item_v};
+    rc = occ_flags(ctx, s, keys, perm, S, S + nI, fstride, flags, hv);
+    if (rc) return rc;
+    const step_tables T = make_tables(opt, user_tab, user_m, user_v, step_user, opt, item_tab, item_m, item_v, step_item, lr, beta1, beta2, eps, weight_decay);
     const int grid = grid_for(S, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-#define PK_ARGS loss_kind, TU, TI, D, uid, iid, label, flags, fstride, S, k, 1.0f / (float)B, out12 + 4, hu, hi, GU, GI, ctx->partials
+#define PK_ARGS loss_kind, T.TU, T.TI, D, uid, iid, label, flags, fstride, S, k, 1.0f / (float)B, out12 + 4, T.hu, T.hi, GU, GI, ctx->partials
         if (opt == 0) { DISPATCH_LPR(lpr, point_fwd_apply_kmajor_kernel<L, 0, 2><<<dim3(grid), dim3(kBlock), 0, s>>>(PK_ARGS)); }
         else if (k <= 1) { DISPATCH_LPR(lpr, point_fwd_apply_kmajor_kernel<L, 1, 2><<<dim3(grid), dim3(kBlock), 0, s>>>(PK_ARGS)); }
         else { DISPATCH_LPR(lpr, point_fwd_apply_kmajor_kernel<L, 1, 3><<<dim3(grid), dim3(kBlock), 0, s>>>(PK_ARGS)); }
@@ -2499,14 +2525,11 @@ extern "C" int cdr_point_step_fused_kmajor(cdr_ctx* ctx, void* stream, int loss_
     CDR_LAUNCH_CHECK();
     // duplicate rows: users over GU [S, D] with (1 + k) c_u per list occurrence (out12[9]); items over GI [S + S k, D], every occurrence
     // with c_i (reg_limit = the whole list)
-    const dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, S, headsA, cnt, GU, S, S, out12 + 9, hu, 0},
-                               {item_tab, item_m, item_v, keys + S, perm + S, nI, headsB, cnt + 1, GI, nI, nI, out12 + 5, hi, key_base}};
-    dups_plan pl;
-    rc = dups_plan_make(ctx, D, sides, pl);
-    if (rc) return rc;
-    step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out12, pl.side[0].counters, pl.side[1].counters);
-    CDR_LAUNCH_CHECK();
-    return apply_dups_pair(ctx, s, opt, D, pl);
+    dup_host sides[2];
+    make_sides(sides, T, keys, perm, hv, GU, GI, S, nI, nI, nI, out12 + 9, out12 + 5, key_base);
+    return finish_and_apply_dups(ctx, s, opt, D, sides, [&](unsigned* za, unsigned* zb) {
+        step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out12, za, zb);
+    });
 }
 
 // ---- round 5: the fused single-occurrence update inside the two multi-GPU layouts -----------------------------------
@@ -2524,13 +2547,7 @@ extern "C" int cdr_bpr_step_presort(cdr_ctx* ctx, void* stream, const int64_t* u
     int rc = cdr_sort_ids_two_tables(ctx, stream, uid, B, user_rows, pid, B, nid, B, item_rows, keys, perm, key_base_out, sort_ws, sort_ws_bytes);
     if (rc) return rc;
     CDR_HIP(cdr_zero_u32(heads, 4, s));                     // the two head lists' counters
-    const int fgrid = grid_for(3 * B, kBlock * kFlagIT);
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
-        occ_flags_kernel<<<dim3(fgrid), dim3(kBlock), 0, s>>>(keys, perm, B, 3 * B, 4, flags, heads + 4, heads + 4 + (B / 2 + 1), (unsigned*)heads);
-    }
-    CDR_LAUNCH_CHECK();
-    return CDR_OK;
+    return occ_flags(ctx, s, keys, perm, B, 3 * B, 4, flags, heads_view(heads, B));
 }
 
 extern "C" int cdr_bpr_step_from_diff(cdr_ctx* ctx, void* stream, int opt, float* user_tab, float* user_m, float* user_v, float* item_tab,
@@ -2546,27 +2563,21 @@ extern "C" int cdr_bpr_step_from_diff(cdr_ctx* ctx, void* stream, int opt, float
     const int lpr = cdr_lpr_for(Ds);
     coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, 0, B, reg_weight, out9, 1, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, diff + B);
     CDR_LAUNCH_CHECK();
-    const apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_user);
-    const apply_hp hi = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_item);
-    const tab_ptrs TU{user_tab, user_m, user_v}, TI{item_tab, item_m, item_v};
+    const step_tables T = make_tables(opt, user_tab, user_m, user_v, step_user, opt, item_tab, item_m, item_v, step_item, lr, beta1, beta2, eps, weight_decay);
     const int grid = grid_for(B, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FA_ARGS TU, TI, Ds, uid, pid, nid, (const uint32_t*)flags, B, gamma, 1.0f / (float)B, out9 + 4, hu, hi, GU, GP, ctx->partials, diff
+#define FA_ARGS T.TU, T.TI, Ds, uid, pid, nid, (const uint32_t*)flags, B, gamma, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials, diff
         if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
         else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
 #undef FA_ARGS
     }
     CDR_LAUNCH_CHECK();
-    unsigned* cnt = (unsigned*)heads;
-    const dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, B, heads + 4, cnt, GU, B, B, out9 + 4, hu, 0},
-                               {item_tab, item_m, item_v, keys + B, perm + B, 2 * B, heads + 4 + (B / 2 + 1), cnt + 1, GP, B, B, out9 + 5, hi, key_base}};
-    dups_plan pl;
-    int rc = dups_plan_make(ctx, Ds, sides, pl);
-    if (rc) return rc;
-    step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, pl.side[0].counters, pl.side[1].counters, diff + B);
-    CDR_LAUNCH_CHECK();
-    return apply_dups_pair(ctx, s, opt, Ds, pl);
+    dup_host sides[2];
+    make_sides(sides, T, keys, perm, heads_view(heads, B), GU, GP, B, 2 * B, B, B, out9 + 4, out9 + 5, key_base);
+    return finish_and_apply_dups(ctx, s, opt, Ds, sides, [&](unsigned* za, unsigned* zb) {
+        step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, za, zb, diff + B);
+    });
 }
 
 // The pointwise rows of the dimension layout (cdr_point_partial_dot -> all-reduce -> here), same cut as the BPR pair above:
@@ -2581,12 +2592,7 @@ extern "C" int cdr_point_step_presort(cdr_ctx* ctx, void* stream, const int64_t*
     int rc = cdr_sort_ids_two_tables(ctx, stream, uid, B, user_rows, iid, B, nullptr, 0, item_rows, keys, perm, key_base_out, sort_ws, sort_ws_bytes);
     if (rc) return rc;
     CDR_HIP(cdr_zero_u32(heads, 4, s));
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
-        occ_flags_kernel<<<dim3(grid_for(2 * B, kBlock * kFlagIT)), dim3(kBlock), 0, s>>>(keys, perm, B, 2 * B, 4, flags, heads + 4, heads + 4 + (B / 2 + 1), (unsigned*)heads);
-    }
-    CDR_LAUNCH_CHECK();
-    return CDR_OK;
+    return occ_flags(ctx, s, keys, perm, B, 2 * B, 4, flags, heads_view(heads, B));
 }
 
 extern "C" int cdr_point_step_from_dot(cdr_ctx* ctx, void* stream, int loss_kind, int opt, float* user_tab, float* user_m, float* user_v,
@@ -2602,27 +2608,21 @@ extern "C" int cdr_point_step_from_dot(cdr_ctx* ctx, void* stream, int loss_kind
     const int lpr = cdr_lpr_for(Ds);
     coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, 0, B, reg_weight, out9, 1, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, dot + B);
     CDR_LAUNCH_CHECK();
-    const apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_user);
-    const apply_hp hi = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_item);
-    const tab_ptrs TU{user_tab, user_m, user_v}, TI{item_tab, item_m, item_v};
+    const step_tables T = make_tables(opt, user_tab, user_m, user_v, step_user, opt, item_tab, item_m, item_v, step_item, lr, beta1, beta2, eps, weight_decay);
     const int grid = grid_for(B, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-#define PA_ARGS loss_kind, TU, TI, Ds, uid, iid, label, (const uint32_t*)flags, B, 1.0f / (float)B, out9 + 4, hu, hi, GU, GI, ctx->partials, dot
+#define PA_ARGS loss_kind, T.TU, T.TI, Ds, uid, iid, label, (const uint32_t*)flags, B, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials, dot
         if (opt == 0) { DISPATCH_LPR(lpr, point_fwd_apply_kernel<L, 0, true><<<dim3(grid), dim3(kBlock), 0, s>>>(PA_ARGS)); }
         else { DISPATCH_LPR(lpr, point_fwd_apply_kernel<L, 1, true><<<dim3(grid), dim3(kBlock), 0, s>>>(PA_ARGS)); }
 #undef PA_ARGS
     }
     CDR_LAUNCH_CHECK();
-    unsigned* cnt = (unsigned*)heads;
-    const dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, B, heads + 4, cnt, GU, B, B, out9 + 4, hu, 0},
-                               {item_tab, item_m, item_v, keys + B, perm + B, B, heads + 4 + (B / 2 + 1), cnt + 1, GI, B, B, out9 + 5, hi, key_base}};
-    dups_plan pl;
-    int rc = dups_plan_make(ctx, Ds, sides, pl);
-    if (rc) return rc;
-    step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, pl.side[0].counters, pl.side[1].counters, dot + B);
-    CDR_LAUNCH_CHECK();
-    return apply_dups_pair(ctx, s, opt, Ds, pl);
+    dup_host sides[2];
+    make_sides(sides, T, keys, perm, heads_view(heads, B), GU, GI, B, B, B, B, out9 + 4, out9 + 5, key_base);
+    return finish_and_apply_dups(ctx, s, opt, Ds, sides, [&](unsigned* za, unsigned* zb) {
+        step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, za, zb, dot + B);
+    });
 }
 
 // ROW shard (shard.ShardedBPRStep): after user-aligned routing the user rows of a rank's triples are its own, the item rows arrive in a
@@ -2663,34 +2663,26 @@ extern "C" int cdr_bpr_shard_local_step(cdr_ctx* ctx, void* stream, int opt, flo
     int rc = cdr_sort_ids(ctx, stream, u_loc, Bl, nullptr, 0, user_rows, keys, perm, sort_ws, sort_ws_bytes);
     if (rc) return rc;
     CDR_HIP(cdr_zero_u32(heads, 4, s));
-    unsigned* cnt = (unsigned*)heads;
-    uint32_t* headsA = heads + 4;
-    uint32_t* headsB = headsA + (Bl / 2 + 1);                       // stays empty: no item row is ever updated here
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
-        occ_flags_kernel<<<dim3(grid_for(Bl, kBlock * kFlagIT)), dim3(kBlock), 0, s>>>(keys, perm, Bl, Bl, 4, flags, headsA, headsB, cnt);
-    }
-    CDR_LAUNCH_CHECK();
-    const apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_user);
-    const apply_hp hi = make_hp(0, lr, beta1, beta2, eps, weight_decay, 1);                // (never used: the p / n flag bytes stay 0)
-    const tab_ptrs TU{user_tab, user_m, user_v}, TI{const_cast<float*>(irows), nullptr, nullptr};
+    const heads_view hv(heads, Bl);                                 // (headsB stays empty: no item row is ever updated here)
+    rc = occ_flags(ctx, s, keys, perm, Bl, Bl, 4, flags, hv);
+    if (rc) return rc;
+    // (the item side's scalars are never used: the p / n flag bytes stay 0)
+    const step_tables T = make_tables(opt, user_tab, user_m, user_v, step_user, 0, const_cast<float*>(irows), nullptr, nullptr, 1, lr, beta1, beta2, eps, weight_decay);
     const int grid = grid_for(Bl, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FA_ARGS TU, TI, D, u_loc, ip, in, (const uint32_t*)flags, Bl, gamma, 1.0f / (float)B_global, out9 + 4, hu, hi, GU, GP, ctx->partials
+#define FA_ARGS T.TU, T.TI, D, u_loc, ip, in, (const uint32_t*)flags, Bl, gamma, 1.0f / (float)B_global, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials
         if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
         else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
 #undef FA_ARGS
     }
     CDR_LAUNCH_CHECK();
-    const dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, Bl, headsA, cnt, GU, Bl, Bl, out9 + 4, hu, 0},
-                               {const_cast<float*>(irows), nullptr, nullptr, keys, perm, 0, headsB, cnt + 1, GP, 0, 0, out9 + 5, hi, 0}};
-    dups_plan pl;
-    rc = dups_plan_make(ctx, D, sides, pl);
-    if (rc) return rc;
-    shard_sums_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, out9, pl.side[0].counters);
-    CDR_LAUNCH_CHECK();
-    return apply_dups_pair(ctx, s, opt, D, pl);
+    dup_host sides[2];
+    make_sides(sides, T, keys, perm, hv, GU, GP, Bl, 0, 0, 0, out9 + 4, out9 + 5, 0);
+    sides[1].keys = keys; sides[1].perm = perm;                     // an empty item side: it names the start of the (user-only) list
+    return finish_and_apply_dups(ctx, s, opt, D, sides, [&](unsigned* za, unsigned*) {
+        shard_sums_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, out9, za);
+    });
 }
 
 // ---- round 6: the row-sharded step on its own passes --------------------------------------------------------------
@@ -2715,20 +2707,27 @@ static int shard_key_bits(int64_t user_rows, int64_t item_local_rows, int world,
 }
 }  // namespace
 
+// the request list's scan reuses the sort's workspace: {excl[2 Bl] | rocPRIM's temporary}
+static int shard_scan_bytes(int64_t Bl, size_t* bytes) {
+    size_t tmp = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, tmp, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), head_flag_op{nullptr}),
+                                           (uint32_t*)nullptr, 0u, (size_t)(2 * Bl), rocprim::plus<uint32_t>());
+    if (e != hipSuccess) { cdr_set_error("cdr_bpr_shard_plan_sizes: %s", hipGetErrorString(e)); return (int)e; }
+    *bytes = up256((size_t)(2 * Bl) * sizeof(uint32_t)) + up256(tmp);
+    return CDR_OK;
+}
+
 extern "C" int cdr_bpr_shard_plan_sizes(int64_t Bl, int64_t user_rows, int64_t item_local_rows, int world, int64_t* heads_words,
                                         size_t* ws_bytes) {
     CDR_CHECK_ARG(heads_words && ws_bytes && Bl > 0 && 3 * Bl <= (int64_t)0x7FFFFFFF);
     shard_bits kb;
     CDR_CHECK_ARG(shard_key_bits(user_rows, item_local_rows, world, kb) == CDR_OK);
-    *heads_words = 4 + (Bl / 2 + 1) + (Bl + 1);
-    size_t sort_need = 0;
+    *heads_words = heads_view::words(Bl, 2 * Bl);
+    size_t sort_need = 0, scan_need = 0;
     int rc = cdr_sort_workspace_bytes(3 * Bl, (int64_t)kb.key_base * 2, &sort_need);
     if (rc) return rc;
-    size_t tmp = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tmp, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), head_flag_op{nullptr}),
-                                           (uint32_t*)nullptr, 0u, (size_t)(2 * Bl), rocprim::plus<uint32_t>());
-    if (e != hipSuccess) { cdr_set_error("cdr_bpr_shard_plan_sizes: %s", hipGetErrorString(e)); return (int)e; }
-    const size_t scan_need = (((size_t)(2 * Bl) * sizeof(uint32_t) + 255) & ~(size_t)255) + ((tmp + 255) & ~(size_t)255);
+    rc = shard_scan_bytes(Bl, &scan_need);
+    if (rc) return rc;
     *ws_bytes = sort_need > scan_need ? sort_need : scan_need;
     return CDR_OK;
 }
@@ -2741,33 +2740,23 @@ extern "C" int cdr_bpr_shard_plan(cdr_ctx* ctx, void* stream, const int64_t* rec
     CDR_CHECK_ARG(Bl > 0 && 3 * Bl <= (int64_t)0x7FFFFFFF && ((uintptr_t)flags & 3) == 0);
     shard_bits kb;
     CDR_CHECK_ARG(shard_key_bits(user_rows, item_local_rows, world, kb) == CDR_OK);
-    int64_t hw = 0; size_t need = 0;
-    int rc = cdr_bpr_shard_plan_sizes(Bl, user_rows, item_local_rows, world, &hw, &need);
+    size_t scan_need = 0;
+    int rc = shard_scan_bytes(Bl, &scan_need);
     if (rc) return rc;
-    CDR_CHECK_ARG(ws_bytes >= need);
+    CDR_CHECK_ARG(ws_bytes >= scan_need);                   // (sort_ids_with checks the sort's own need)
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = 3 * Bl;
-    const size_t arr = ((size_t)n * sizeof(uint32_t) + 255) & ~(size_t)255;
-    uint32_t* keys_in = (uint32_t*)ws;
-    uint32_t* vals_in = (uint32_t*)((char*)ws + arr);
-    void* tmp = (char*)ws + 2 * arr;
-    size_t tmp_bytes = ws_bytes - 2 * arr;
-    unsigned* cnt = (unsigned*)heads;
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_SORT, s);
-        shard_keys_kernel<<<dim3(grid_for(Bl, kBlock)), dim3(kBlock), 0, s>>>(recv3, Bl, (uint32_t)world, kb.lb, kb.key_base, u_loc, keys_in, vals_in, cnt);
-        CDR_LAUNCH_CHECK();
-        CDR_HIP(sort_pairs(tmp, tmp_bytes, keys_in, keys, vals_in, perm, (size_t)n, kb.hb + 1, s));
-    }
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
-        occ_flags_kernel<<<dim3(grid_for(n, kBlock * kFlagIT)), dim3(kBlock), 0, s>>>(keys, perm, Bl, n, 4, flags, heads + 4, heads + 4 + (Bl / 2 + 1), cnt);
-    }
-    CDR_LAUNCH_CHECK();
+    const heads_view hv(heads, Bl);
+    rc = sort_ids_with(ctx, s, n, (int64_t)kb.key_base * 2, keys, perm, ws, ws_bytes, [&](uint32_t* keys_in, uint32_t* vals_in) {
+        shard_keys_kernel<<<dim3(grid_for(Bl, kBlock)), dim3(kBlock), 0, s>>>(recv3, Bl, (uint32_t)world, kb.lb, kb.key_base, u_loc, keys_in, vals_in, hv.cnt);
+    });
+    if (rc) return rc;
+    rc = occ_flags(ctx, s, keys, perm, Bl, n, 4, flags, hv);
+    if (rc) return rc;
     // the request list from section B (the sort's inputs are dead: the scan reuses the workspace)
     const int64_t nB = 2 * Bl;
     const uint32_t* keysB = keys + Bl;
-    const size_t arrB = ((size_t)nB * sizeof(uint32_t) + 255) & ~(size_t)255;
+    const size_t arrB = up256((size_t)nB * sizeof(uint32_t));
     uint32_t* excl = (uint32_t*)ws;
     void* stmp = (char*)ws + arrB;
     size_t stmp_bytes = ws_bytes - arrB;
@@ -2808,47 +2797,23 @@ extern "C" int cdr_bpr_shard_step(cdr_ctx* ctx, void* stream, int opt, float* us
     CDR_CHECK_ARG(((uintptr_t)flags & 3) == 0);
     hipStream_t s = (hipStream_t)stream;
     const int lpr = cdr_lpr_for(D);
-    const apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_user);
-    const apply_hp hi = make_hp(0, lr, beta1, beta2, eps, weight_decay, 1);                // (no item row is updated on this side)
-    const tab_ptrs TU{user_tab, user_m, user_v}, TI{const_cast<float*>(irows), nullptr, nullptr};
+    // (no item row is updated on this side)
+    const step_tables T = make_tables(opt, user_tab, user_m, user_v, step_user, 0, const_cast<float*>(irows), nullptr, nullptr, 1, lr, beta1, beta2, eps, weight_decay);
     const int grid = grid_for(Bl, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FA_ARGS TU, TI, D, u_loc, umap, umap + Bl, (const uint32_t*)flags, Bl, gamma, 1.0f / (float)B_global, out9 + 4, hu, hi, GU, GP, ctx->partials, nullptr, GS
+#define FA_ARGS T.TU, T.TI, D, u_loc, umap, umap + Bl, (const uint32_t*)flags, Bl, gamma, 1.0f / (float)B_global, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials, nullptr, GS
         if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
         else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
 #undef FA_ARGS
     }
     CDR_LAUNCH_CHECK();
-    unsigned* cnt = (unsigned*)heads;
-    dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, Bl, heads + 4, cnt, GU, Bl, Bl, out9 + 4, hu, 0},
-                         {const_cast<float*>(irows), nullptr, nullptr, keys + Bl, perm + Bl, 2 * Bl, heads + 4 + (Bl / 2 + 1), cnt + 1, GP, Bl, Bl,
-                          out9 + 5, hi, 0}};
+    dup_host sides[2];
+    make_sides(sides, T, keys, perm, heads_view(heads, Bl), GU, GP, Bl, 2 * Bl, Bl, Bl, out9 + 4, out9 + 5, 0);
     sides[1].out = GS; sides[1].uidx = uidx;
-    dups_plan pl;
-    int rc = dups_plan_make(ctx, D, sides, pl);
-    if (rc) return rc;
-    shard_sums2_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, out9, pl.side[0].counters, pl.side[1].counters);
-    CDR_LAUNCH_CHECK();
-    const int dgrid = grid_for((2 * Bl) / 16 + 1, kBlock / lpr);
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_APPLY_SIGNED, s);
-        if (opt == 0) { DISPATCH_LPR(lpr, shard_dups_kernel<L, 0><<<dim3(dgrid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
-        else { DISPATCH_LPR(lpr, shard_dups_kernel<L, 1><<<dim3(dgrid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
-    }
-    CDR_LAUNCH_CHECK();
-    if (pl.long_cap[0] || pl.long_cap[1]) {
-        const int64_t pc = pl.piece_cap[0] > pl.piece_cap[1] ? pl.piece_cap[0] : pl.piece_cap[1];
-        const int64_t lc = pl.long_cap[0] > pl.long_cap[1] ? pl.long_cap[0] : pl.long_cap[1];
-        const int gp = (int)(pc < 2048 ? pc : 2048);                        // one workgroup per piece (looping past 2,048)
-        DISPATCH_LPR(lpr, seg_piece_sum2_kernel<L><<<dim3(gp, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
-        CDR_LAUNCH_CHECK();
-        const int gl = grid_for(lc < 4096 ? lc : 4096, kBlock / lpr);
-        if (opt == 0) { DISPATCH_LPR(lpr, shard_long_finish_kernel<L, 0><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
-        else { DISPATCH_LPR(lpr, shard_long_finish_kernel<L, 1><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
-        CDR_LAUNCH_CHECK();
-    }
-    return CDR_OK;
+    return finish_and_apply_dups<shard_dups>(ctx, s, opt, D, sides, [&](unsigned* za, unsigned* zb) {
+        shard_sums2_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, out9, za, zb);
+    });
 }
 
 // The owner's side: ids = `runs` ascending duplicate-free runs of local rows (one per requesting rank, in rank order), grads one summed
@@ -2885,7 +2850,7 @@ extern "C" int cdr_bpr_step_fused_kmajor_sizes(int64_t S, int k, int64_t* flag_b
     CDR_CHECK_ARG(flag_bytes && heads_words && S > 0 && k >= 1 && k <= 64);
     const int fstride = (2 + k + 3) & ~3;
     *flag_bytes = S * (int64_t)fstride;
-    *heads_words = 4 + (S / 2 + 1) + ((S + S * (int64_t)k) / 2 + 1);
+    *heads_words = heads_view::words(S, S + S * (int64_t)k);
     return CDR_OK;
 }
 
@@ -2903,37 +2868,19 @@ extern "C" int cdr_bpr_step_fused_kmajor(cdr_ctx* ctx, void* stream, int opt, fl
     hipStream_t s = (hipStream_t)stream;
     const int lpr = cdr_lpr_for(D);
     const int fstride = (2 + k + 3) & ~3;
-    if (reg_weight != 0.f) {
-        const int ngrid = grid_for((S + 7) / 8, kBlock / lpr);
-        {
-            cdr_time_scope ts(ctx, CDR_TAG_BATCH_NORMS, s);
-            DISPATCH_LPR(lpr, batch_norms_kernel<L><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, S, ctx->partials));
-        }
-        CDR_LAUNCH_CHECK();
-        coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B, reg_weight, out9, k, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, (unsigned*)heads);
-    } else {
-        coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, 0, B, 0.f, out9, k, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, (unsigned*)heads);
-    }
-    CDR_LAUNCH_CHECK();
-    uint32_t key_base = 0;
-    int rc = cdr_sort_ids_two_tables(ctx, stream, uid, S, user_rows, pid, S, nid, B, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes);
+    const heads_view hv(heads, S);                     // (cnt[0..3] are cleared by coef_finish_kernel)
+    int rc = embloss_head(ctx, s, user_tab, item_tab, D, uid, pid, S, B, k, reg_weight, out9, hv.cnt);
     if (rc) return rc;
-    unsigned* cnt = (unsigned*)heads;
-    uint32_t* headsA = heads + 4;
-    uint32_t* headsB = headsA + (S / 2 + 1);           // (cnt[0..3] were cleared by coef_finish_kernel)
-    const int fgrid = grid_for(S + nI, kBlock * kFlagIT);
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
-        occ_flags_kernel<<<dim3(fgrid), dim3(kBlock), 0, s>>>(keys, perm, S, S + nI, fstride, flags, headsA, headsB, cnt);
-    }
-    CDR_LAUNCH_CHECK();
-    const apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_user);
-    const apply_hp hi = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step_item);
-    const tab_ptrs TU{user_tab, user_m, user_v}, TI{item_tab, item_m, item_v};
+    uint32_t key_base = 0;
+    rc = cdr_sort_ids_two_tables(ctx, stream, uid, S, user_rows, pid, S, nid, B, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes);
+    if (rc) return rc;
+    rc = occ_flags(ctx, s, keys, perm, S, S + nI, fstride, flags, hv);
+    if (rc) return rc;
+    const step_tables T = make_tables(opt, user_tab, user_m, user_v, step_user, opt, item_tab, item_m, item_v, step_item, lr, beta1, beta2, eps, weight_decay);
     const int grid = grid_for(S, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FK_ARGS TU, TI, D, uid, pid, nid, flags, fstride, S, k, gamma, 1.0f / (float)B, out9 + 4, hu, hi, GU, GI, ctx->partials
+#define FK_ARGS T.TU, T.TI, D, uid, pid, nid, flags, fstride, S, k, gamma, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials
         if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kmajor_kernel<L, 0, 4><<<dim3(grid), dim3(kBlock), 0, s>>>(FK_ARGS)); }
         else if (k <= 2) { DISPATCH_LPR(lpr, bpr_fwd_apply_kmajor_kernel<L, 1, 2><<<dim3(grid), dim3(kBlock), 0, s>>>(FK_ARGS)); }
         else { DISPATCH_LPR(lpr, bpr_fwd_apply_kmajor_kernel<L, 1, 4><<<dim3(grid), dim3(kBlock), 0, s>>>(FK_ARGS)); }
@@ -2941,16 +2888,12 @@ extern "C" int cdr_bpr_step_fused_kmajor(cdr_ctx* ctx, void* stream, int opt, fl
     }
     CDR_LAUNCH_CHECK();
     // duplicate rows: users over GU [S, D]; items over GI [S + B, D] (one row per occurrence of [pid | nid], signs folded in)
-    const dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, S, headsA, cnt, GU, S, S, out9 + 4, hu, 0},
-                               {item_tab, item_m, item_v, keys + S, perm + S, nI, headsB, cnt + 1, GI, nI, S, out9 + 5, hi, key_base}};
-    dups_plan pl;
-    rc = dups_plan_make(ctx, D, sides, pl);
-    if (rc) return rc;
-    step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, pl.side[0].counters, pl.side[1].counters);
-    CDR_LAUNCH_CHECK();
-    return apply_dups_pair(ctx, s, opt, D, pl);
+    dup_host sides[2];
+    make_sides(sides, T, keys, perm, hv, GU, GI, S, nI, nI, S, out9 + 4, out9 + 5, key_base);
+    return finish_and_apply_dups(ctx, s, opt, D, sides, [&](unsigned* za, unsigned* zb) {
+        step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, za, zb);
+    });
 }
-
 
 // ================================================================================================ CMF's two-domain step on shared tables
 // cmf.py:75-99: both domains' batches train ONE user and ONE item table, and the reference takes one torch.optim.Adam step on the summed
@@ -3197,9 +3140,7 @@ extern "C" int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int los
     const int64_t N = B_s + B_t;
     const int lpr = cdr_lpr_for(D);
     const float wreg_s = alpha * reg_s, wreg_t = (1.0f - alpha) * reg_t;
-    unsigned* cnt = (unsigned*)heads;
-    uint32_t* headsA = heads + 4;
-    uint32_t* headsB = headsA + (N / 2 + 1);           // (cnt[0..3] are cleared by pair_coef_kernel)
+    const heads_view hv(heads, N);                     // (cnt[0..3] are cleared by pair_coef_kernel)
     // ---- EmbLoss coefficients first (they do not need the sort) + the device-resident update counts
     int ngrid = 0;
     if (wreg_s != 0.f || wreg_t != 0.f) {
@@ -3209,54 +3150,35 @@ extern "C" int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int los
         CDR_LAUNCH_CHECK();
     }
     pair_coef_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B_s, B_t, wreg_s, wreg_t, out16, step_user_dev, step_item_dev,
-                                                      opt == 1 ? hp_dev : nullptr, lr, beta1, beta2, cnt);
+                                                      opt == 1 ? hp_dev : nullptr, lr, beta1, beta2, hv.cnt);
     CDR_LAUNCH_CHECK();
     // ---- one sort of both tables' keys: [su | tu] and key_base + [si | ti]
-    const unsigned hb = bits_for(user_rows) > bits_for(item_rows) ? bits_for(user_rows) : bits_for(item_rows);
+    const unsigned hb = two_table_bits(user_rows, item_rows);
     CDR_CHECK_ARG(hb < 31);
     const uint32_t key_base = 1u << hb;
-    {
-        size_t need = 0;
-        int rc = cdr_sort_workspace_bytes(2 * N, (int64_t)key_base * 2, &need);
-        if (rc) return rc;
-        CDR_CHECK_ARG(sort_ws_bytes >= need);
-        const size_t arr = ((size_t)(2 * N) * sizeof(uint32_t) + 255) & ~(size_t)255;
-        uint32_t* keys_in = (uint32_t*)sort_ws;
-        uint32_t* vals_in = (uint32_t*)((char*)sort_ws + arr);
-        void* tmp = (char*)sort_ws + 2 * arr;
-        size_t tmp_bytes = sort_ws_bytes - 2 * arr;
-        cdr_time_scope ts(ctx, CDR_TAG_SORT, s);
+    int rc = sort_ids_with(ctx, s, 2 * N, (int64_t)key_base * 2, keys, perm, sort_ws, sort_ws_bytes, [&](uint32_t* keys_in, uint32_t* vals_in) {
         make_keys_pair_kernel<<<dim3(grid_for(2 * N, kBlock)), dim3(kBlock), 0, s>>>(su, B_s, tu, B_t, si, B_s, ti, B_t, key_base, keys_in, vals_in);
-        CDR_LAUNCH_CHECK();
-        CDR_HIP(sort_pairs(tmp, tmp_bytes, keys_in, keys, vals_in, perm, (size_t)(2 * N), hb + 1, s));
-    }
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_OCC_FLAGS, s);
-        occ_flags_kernel<<<dim3(grid_for(2 * N, kBlock * kFlagIT)), dim3(kBlock), 0, s>>>(keys, perm, N, 2 * N, 4, flags, headsA, headsB, cnt);
-    }
-    CDR_LAUNCH_CHECK();
+    });
+    if (rc) return rc;
+    rc = occ_flags(ctx, s, keys, perm, N, 2 * N, 4, flags, hv);
+    if (rc) return rc;
     // ---- forward + single rows in place; the Adam scalars of the new counts come from hp_dev (apply_hp::dev)
-    apply_hp hu = make_hp(opt, lr, beta1, beta2, eps, weight_decay, 1), hi = hu;
-    if (opt == 1) { hu.dev = hp_dev; hi.dev = hp_dev + 2; }
-    const tab_ptrs TU{user_tab, user_m, user_v}, TI{item_tab, item_m, item_v};
+    step_tables T = make_tables(opt, user_tab, user_m, user_v, 1, opt, item_tab, item_m, item_v, 1, lr, beta1, beta2, eps, weight_decay);
+    if (opt == 1) { T.hu.dev = hp_dev; T.hi.dev = hp_dev + 2; }
     const int grid = grid_for(N, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-#define PP_ARGS loss_kind, TU, TI, D, su, si, ys, B_s, tu, ti, yt, B_t, (const uint32_t*)flags, alpha / (float)B_s, (1.0f - alpha) / (float)B_t, \
-                out16 + 9, hu, hi, GU, GI, ctx->partials
+#define PP_ARGS loss_kind, T.TU, T.TI, D, su, si, ys, B_s, tu, ti, yt, B_t, (const uint32_t*)flags, alpha / (float)B_s, (1.0f - alpha) / (float)B_t, \
+                out16 + 9, T.hu, T.hi, GU, GI, ctx->partials
         if (opt == 0) { DISPATCH_LPR(lpr, point_pair_fwd_apply_kernel<L, 0><<<dim3(grid), dim3(kBlock), 0, s>>>(PP_ARGS)); }
         else { DISPATCH_LPR(lpr, point_pair_fwd_apply_kernel<L, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(PP_ARGS)); }
 #undef PP_ARGS
     }
     CDR_LAUNCH_CHECK();
     // ---- every row with more than one occurrence: one update from the sum of its (complete) gradient rows
-    const dup_host sides[2] = {{user_tab, user_m, user_v, keys, perm, N, headsA, cnt, GU, N, N, nullptr, hu, 0},
-                               {item_tab, item_m, item_v, keys + N, perm + N, N, headsB, cnt + 1, GI, N, N, nullptr, hi, key_base}};
-    dups_plan pl;
-    int rc = dups_plan_make(ctx, D, sides, pl);
-    if (rc) return rc;
-    pair_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B_s, B_t, alpha, reg_s, reg_t, out16, pl.side[0].counters,
-                                                        pl.side[1].counters);
-    CDR_LAUNCH_CHECK();
-    return apply_dups_pair(ctx, s, opt, D, pl);
+    dup_host sides[2];
+    make_sides(sides, T, keys, perm, hv, GU, GI, N, N, N, N, nullptr, nullptr, key_base);
+    return finish_and_apply_dups(ctx, s, opt, D, sides, [&](unsigned* za, unsigned* zb) {
+        pair_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B_s, B_t, alpha, reg_s, reg_t, out16, za, zb);
+    });
 }
