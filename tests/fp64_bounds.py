@@ -1,4 +1,5 @@
-"""First-order fp32 error bounds shared by the fp64 reference tests (test_gpu_step_fp64.py, test_gpu_bitgcf_fp64.py).
+"""First-order fp32 error bounds and float64 references shared by the fp64 reference tests (test_gpu_step_fp64.py,
+test_gpu_cmf_rowwise.py, test_gpu_dense_loss_fp64.py, test_gpu_bitgcf_fp64.py, ...).
 
 u = 2^-24 is the unit roundoff of fp32 and gamma_k = k u / (1 - k u) the bound of a k-term fp32 sum or product chain (Higham).
 apply_fp64 is one optimizer update in float64 from the device state before it, with the per-element bound described in
@@ -8,6 +9,10 @@ import torch
 U32 = 2.0 ** -24            # unit roundoff of fp32
 K_SUM = 8                   # the "small constant" of k = D + occurrences + K_SUM (product, subtraction p - n, reg / wd terms)
 K_ADAM = 12                 # ulps of the Adam update term (see test_gpu_step_fp64.py's docstring)
+K_COEF = 8                  # ulps of the per-occurrence loss coefficient beyond its score error
+K_REG = 4                   # ulps of the EmbLoss coefficient reg / (B ||X||) beyond its D-term row sums (fp64 sum, sqrt, two fp32 ops)
+LOSS_RTOL = 1e-5
+GAMMA = 1e-10               # BPRLoss gamma (recbole): -log(gamma + sigmoid(pos - neg))
 
 
 def gam(k):
@@ -97,3 +102,209 @@ def adam_replay_fp64(state, err, t_from, n, lr, wd=0.0, b1=0.9, b2=0.999, eps=1e
     for t in range(t_from + 1, t_from + n + 1):
         state, err = adam_idle_fp64(state, err, t, lr, wd, b1, b2, eps)
     return state, err
+
+
+# ---------------------------------------------------------------------------------------------------------------------- fp64 losses
+# Loss and summed per-row gradients of the three batch losses in float64 (test_gpu_step_fp64.py's docstring derives the bounds).
+# A part = (rows, G, A, E, occ): unique row ids, summed gradient, sum|term|, summed coefficient-error terms, occurrences.
+#
+# What the dense drop-in path (functional.BPRGatherLoss / PointGatherLoss / TwoDomainPointLoss) adds to the row-wise steps:
+#   * ``go``: the upstream gradient (a float as the backward kernel reads it).  It multiplies every gradient term and no loss value.  The
+#     kernels form go * gcoef[t] (pair: (go * w_d) * gcoef[t]) and go * reg / (B ||X||): one (pair: two) more fp32 roundings on the
+#     coefficient and one more on the reg coefficient.  The coefficient's own roundings are 1/B, the products and the division of
+#     csrc/cdr_gather_loss.hip's g = ... lines -- at most 6 (BPR), 5 (BCE: pq cancels exactly, both factors are the same fp32 value),
+#     3 (MSE) -- so K_COEF = 8 holds them with the upstream factor; the reg coefficient's count K_REG grows by one per extra product.
+#   * separate EmbLoss tables (PointGatherLoss reg_user_w / reg_item_w): the norms and the reg terms come from the reg tables' rows
+#     and land in the reg tables' gradients (two more parts).
+#   * ``detail``: a dict that receives main loss, the two norms, the per-occurrence coefficients g (WITHOUT go) and their bound.
+
+def _occ_sums(n_rows, inv, terms, absum, cerr):
+    G = torch.zeros(n_rows, terms.shape[1], device=terms.device, dtype=torch.float64)
+    A, E = torch.zeros_like(G), torch.zeros_like(G)
+    G.index_add_(0, inv, terms); A.index_add_(0, inv, absum); E.index_add_(0, inv, cerr)
+    return G, A, E, torch.bincount(inv, minlength=n_rows)
+
+
+def bpr_grads_fp64(U, I, uid, pid, nid, reg, go=None, detail=None):
+    """Loss and summed row gradients of  BPRLoss(u.p, u.n) + reg * EmbLoss(u, p)  (recbole; emcdr.py domain_loss) in float64.
+    Returns (loss, user part, item part)."""
+    B, D = uid.numel(), U.shape[1]
+    ru, inv_u = torch.unique(uid, return_inverse=True)
+    ri, inv_i = torch.unique(torch.cat([pid, nid]), return_inverse=True)
+    Ur, Ir = U[ru].double(), I[ri].double()
+    u, p, n = Ur[inv_u], Ir[inv_i[:B]], Ir[inv_i[B:]]
+    ua, pa, na = u.abs(), p.abs(), n.abs()
+    x = (u * p).sum(1) - (u * n).sum(1)
+    ex = gam(D + 2) * ((ua * pa).sum(1) + (ua * na).sum(1)) + U32 * x.abs()
+    s, q = torch.sigmoid(x), torch.sigmoid(-x)
+    h = GAMMA + s
+    g = -(s * q) / h / B
+    dgdx = -(s * q * (q - s) * h - (s * q) ** 2) / (h * h) / B
+    dgds = -((1 - 2 * s) * h - s * q) / (h * h) / B
+    delta = dgdx.abs() * ex + K_COEF * U32 * (dgds.abs() * s + g.abs())
+    nu, ni = u.norm(), p.norm()
+    main = -torch.log(GAMMA + s).mean()
+    loss = main + reg * (nu + ni) / B
+    if detail is not None:
+        detail.update(main=float(main), nu=float(nu), ni=float(ni), g=g, delta=delta)
+    k_reg = K_REG
+    if go is not None:
+        g, delta, k_reg = go * g, abs(go) * delta, K_REG + 1
+    cu = (1.0 if go is None else go) * reg / (B * nu) if reg else 0.0
+    ci = (1.0 if go is None else go) * reg / (B * ni) if reg else 0.0
+    gc = gam(D + k_reg)
+    g1, delta = g.unsqueeze(1), delta.unsqueeze(1)
+    ut = (g1 * (p - n) + cu * u, g1.abs() * (pa + na) + abs(cu) * ua, delta * (p - n).abs() + gc * abs(cu) * ua)
+    del x, s, q, h, dgdx, dgds
+    it = (torch.cat([g1 * u + ci * p, -g1 * u]), torch.cat([g1.abs() * ua + abs(ci) * pa, g1.abs() * ua]),
+          torch.cat([delta * ua + gc * abs(ci) * pa, delta * ua]))
+    del u, p, n, ua, pa, na
+    return float(loss), (ru, *_occ_sums(ru.numel(), inv_u, *ut)), (ri, *_occ_sums(ri.numel(), inv_i, *it))
+
+
+def point_grads_fp64(U, I, uid, iid, label, reg, kind, go=None, RU=None, RI=None, detail=None):
+    """Loss and summed row gradients of  MSE(u.i, y)  or  BCE(sigmoid(u.i), y)  + reg * EmbLoss(u, i)  in float64.  With ``RU`` / ``RI``
+    the EmbLoss rows come from those tables (same ids) and two more parts, the reg tables' gradients, are returned."""
+    B, D = uid.numel(), U.shape[1]
+    ru, inv_u = torch.unique(uid, return_inverse=True)
+    ri, inv_i = torch.unique(iid, return_inverse=True)
+    u, i = U[ru].double()[inv_u], I[ri].double()[inv_i]
+    ua, ia = u.abs(), i.abs()
+    y = label.double()
+    x = (u * i).sum(1)
+    ex = gam(D + 2) * (ua * ia).sum(1) + U32 * x.abs()
+    if kind == 'mse':
+        d = x - y
+        main = (d * d).mean()
+        g = 2 * d / B
+        delta = 2 * (ex + U32 * d.abs()) / B + K_COEF * U32 * g.abs()
+    else:
+        s, q = torch.sigmoid(x), torch.sigmoid(-x)
+        main = -(y * torch.log(s).clamp(min=-100) + (1 - y) * torch.log(q).clamp(min=-100)).mean()
+        g = (s - y) / B
+        delta = s * q * ex / B + K_COEF * U32 * (g.abs() + s / B)
+    sep = RU is not None
+    ur, ir = (RU[ru].double()[inv_u], RI[ri].double()[inv_i]) if sep else (u, i)
+    nu, ni = ur.norm(), ir.norm()
+    loss = main + reg * (nu + ni) / B
+    if detail is not None:
+        detail.update(main=float(main), nu=float(nu), ni=float(ni), g=g, delta=delta)
+    k_reg = K_REG
+    if go is not None:
+        g, delta, k_reg = go * g, abs(go) * delta, K_REG + 1
+    cu = (1.0 if go is None else go) * reg / (B * nu) if reg else 0.0
+    ci = (1.0 if go is None else go) * reg / (B * ni) if reg else 0.0
+    gc = gam(D + k_reg)
+    g1, d1 = g.unsqueeze(1), delta.unsqueeze(1)
+    if sep:
+        ut, it = (g1 * i, g1.abs() * ia, d1 * ia), (g1 * u, g1.abs() * ua, d1 * ua)
+        rut, rit = (cu * ur, abs(cu) * ur.abs(), gc * abs(cu) * ur.abs()), (ci * ir, abs(ci) * ir.abs(), gc * abs(ci) * ir.abs())
+        return (float(loss), (ru, *_occ_sums(ru.numel(), inv_u, *ut)), (ri, *_occ_sums(ri.numel(), inv_i, *it)),
+                (ru, *_occ_sums(ru.numel(), inv_u, *rut)), (ri, *_occ_sums(ri.numel(), inv_i, *rit)))
+    ut = (g1 * i + cu * u, g1.abs() * ia + abs(cu) * ua, d1 * ia + gc * abs(cu) * ua)
+    it = (g1 * u + ci * i, g1.abs() * ua + abs(ci) * ia, d1 * ua + gc * abs(ci) * ia)
+    return float(loss), (ru, *_occ_sums(ru.numel(), inv_u, *ut)), (ri, *_occ_sums(ri.numel(), inv_i, *it))
+
+
+def pair_grads_fp64(U, I, doms, go=None, detail=None):
+    """The summed loss  sum_d w_d (BCE(sigmoid(u.i), y) + reg_d EmbLoss(u, i))  over the domains ``doms`` = [(uid, iid, y, reg, w)] and its
+    per-row gradients in float64 (one part per table: rows, summed gradient, sum|term|, summed coefficient errors, occurrences).  The BCE
+    derivative keeps torch's fp32 clamp: (p - y) pq / max(pq, 1e-12) with pq from the fp32 sigmoid (0 where it saturates).  ``detail``: a
+    list that receives one dict per domain (main, nu, ni, the coefficients g without w and go, their bound)."""
+    D = U.shape[1]
+    ru, inv_u = torch.unique(torch.cat([d[0] for d in doms]), return_inverse=True)
+    ri, inv_i = torch.unique(torch.cat([d[1] for d in doms]), return_inverse=True)
+    Ur, Ir = U[ru].double(), I[ri].double()
+    ut, it, parts, loss, off = [[], [], []], [[], [], []], [], 0.0, 0
+    f = 1.0 if go is None else go
+    k_reg = K_REG if go is None else K_REG + 2
+    for uid, iid, label, reg, w in doms:
+        B = uid.numel()
+        u, i = Ur[inv_u[off:off + B]], Ir[inv_i[off:off + B]]
+        off += B
+        ua, ia = u.abs(), i.abs()
+        y = label.double()
+        x = (u * i).sum(1)
+        ex = gam(D + 2) * (ua * ia).sum(1) + U32 * x.abs()
+        s, q = torch.sigmoid(x), torch.sigmoid(-x)
+        p32 = torch.sigmoid(x.float())
+        pq = ((1 - p32) * p32).double()
+        clamp = torch.where(pq < 1e-12, pq / 1e-12, torch.ones_like(pq))
+        main = -(y * torch.log(s).clamp(min=-100) + (1 - y) * torch.log(q).clamp(min=-100)).mean()
+        if detail is not None:
+            detail.append(dict(g=(s - y) * clamp / B, delta=s * q * ex / B + K_COEF * U32 * ((s - y).abs() / B + s / B)))
+        g = f * w * (s - y) * clamp / B
+        delta = abs(f) * w * (s * q * ex / B + K_COEF * U32 * ((s - y).abs() / B + s / B))
+        nu, ni = u.norm(), i.norm()
+        emb = (nu + ni) / B
+        loss += w * (float(main) + reg * float(emb))
+        parts.append((float(main), float(emb)))
+        if detail is not None:
+            detail[-1].update(main=float(main), nu=float(nu), ni=float(ni))
+        cu = f * w * reg / (B * nu) if reg else 0.0
+        ci = f * w * reg / (B * ni) if reg else 0.0
+        gc = gam(D + k_reg)
+        g1, d1 = g.unsqueeze(1), delta.unsqueeze(1)
+        for acc, t in ((ut, (g1 * i + cu * u, g1.abs() * ia + abs(cu) * ua, d1 * ia + gc * abs(cu) * ua)),
+                       (it, (g1 * u + ci * i, g1.abs() * ua + abs(ci) * ia, d1 * ua + gc * abs(ci) * ia))):
+            for j in range(3):
+                acc[j].append(t[j])
+    upart = (ru, *_occ_sums(ru.numel(), inv_u, *[torch.cat(a) for a in ut]))
+    ipart = (ri, *_occ_sums(ri.numel(), inv_i, *[torch.cat(a) for a in it]))
+    return loss, parts, upart, ipart
+
+
+# ---------------------------------------------------------------------------------------------------------------------- dense checker
+# What test_gpu_dense_loss_fp64.py holds the drop-in losses to, and what test_fp64_bounds.py feeds an fp32 autograd result (and three
+# mutations of it) through without a GPU.  No sampling: every scalar, every coefficient, every element of every row of every gradient.
+
+def check_scalar(tag, got, want):
+    assert abs(got - want) <= LOSS_RTOL * abs(want), f'{tag}: {got!r} vs fp64 {want!r} (rel {abs(got - want) / max(abs(want), 1e-300):.3g})'
+    return abs(got - want) / (LOSS_RTOL * abs(want)) if want else 0.0
+
+
+def check_dense_grad(tag, grad, part, D):
+    """A dense [rows, D] gradient against a part: the batch's rows within _grad_bound element by element, EVERY other row +0.0 bit for
+    bit.  Returns the worst error / bound."""
+    rows, G, A, E, occ = part
+    assert grad.dim() == 2 and grad.shape[1] == D == G.shape[1] and grad.dtype == torch.float32, (tag, tuple(grad.shape), grad.dtype)
+    n = grad.shape[0]
+    touched = torch.zeros(n, dtype=torch.bool, device=grad.device)
+    touched[rows] = True
+    assert int(touched.sum()) == rows.numel() and bool((occ > 0).all()), f'{tag}: the reference rows are not the distinct batch rows'
+    dirty = (grad.contiguous().view(torch.int32) != 0).any(1) & ~touched
+    assert not bool(dirty.any()), (f'{tag}: {int(dirty.sum())} of {n - rows.numel()} rows outside the batch are not +0.0, '
+                                   f'e.g. row {int(torch.nonzero(dirty)[0])}: {grad[int(torch.nonzero(dirty)[0])][:4].tolist()}')
+    got = grad[rows].double()
+    assert bool(torch.isfinite(got).all()), f'{tag}: non-finite values'
+    bound = _grad_bound(D, G, A, E, occ)
+    err = (got - G).abs()
+    r = torch.where(err > 0, err / bound.clamp(min=1e-300), torch.zeros_like(err))
+    worst = float(r.max())
+    if worst > 1.0:
+        j = int(r.argmax())
+        row, col = j // D, j % D
+        raise AssertionError(f'{tag}: error / bound = {worst:.3g} at table row {int(rows[row])} col {col} ({int(occ[row])} occurrences): '
+                             f'got {float(got[row, col])!r} want {float(G[row, col])!r} bound {float(bound[row, col]):.3g}')
+    return worst
+
+
+def check_dense_result(tag, got, ref, D):
+    """got: {'scalars': {name: float}, 'coefs': [tensor or None], 'grads': [dense gradient]}; ref: {'scalars': {name: float64 value},
+    'coefs': [(g, delta)], 'parts': [part]} -- the same names, the same order.  Returns {quantity: worst error / bound}."""
+    assert set(got['scalars']) == set(ref['scalars']) and len(got['grads']) == len(ref['parts']) and len(got['coefs']) == len(ref['coefs'])
+    worst = {}
+    for k, v in ref['scalars'].items():
+        worst[k] = check_scalar(f'{tag}: {k}', got['scalars'][k], v)
+    for j, (c, (g, delta)) in enumerate(zip(got['coefs'], ref['coefs'])):
+        if c is None:
+            continue
+        assert c.shape == g.shape, (tag, c.shape, g.shape)
+        err = (c.double() - g).abs()
+        r = torch.where(err > 0, err / delta.clamp(min=1e-300), torch.zeros_like(err))
+        worst[f'coef{j}'] = float(r.max())
+        assert worst[f'coef{j}'] <= 1.0, (f'{tag}: coefficient of occurrence {int(r.argmax())} of batch {j}: got {float(c[int(r.argmax())])!r} '
+                                          f'want {float(g[int(r.argmax())])!r}, error / bound = {worst[f"coef{j}"]:.3g}')
+    for j, (gr, part) in enumerate(zip(got['grads'], ref['parts'])):
+        worst[f'grad{j}'] = check_dense_grad(f'{tag}: gradient {j}', gr, part, D)
+    return worst

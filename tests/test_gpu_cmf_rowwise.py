@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from fp64_bounds import U32, apply_fp64, gam, ulp32
+from fp64_bounds import U32, apply_fp64, gam, pair_grads_fp64, ulp32
 from golden_util import Golden, cases
 from helpers import DEV, FakeDataset, base_config, load_params, to_dev, assert_close
 from test_gpu_step_fp64 import K_COEF, LOSS_RTOL, _check_table, _fmt, _live, _occ_sums, _snapshot, _zipf
@@ -55,47 +55,6 @@ def test_one_sgd_step_moves_every_row_by_the_reference_gradient(name):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 2. fp64 bounds
-
-def pair_grads_fp64(U, I, doms):
-    """The summed loss  sum_d w_d (BCE(sigmoid(u.i), y) + reg_d EmbLoss(u, i))  over the domains ``doms`` = [(uid, iid, y, reg, w)] and its
-    per-row gradients in float64 (one part per table: rows, summed gradient, sum|term|, summed coefficient errors, occurrences).  The BCE
-    derivative keeps torch's fp32 clamp: (p - y) pq / max(pq, 1e-12) with pq from the fp32 sigmoid (0 where it saturates)."""
-    D = U.shape[1]
-    ru, inv_u = torch.unique(torch.cat([d[0] for d in doms]), return_inverse=True)
-    ri, inv_i = torch.unique(torch.cat([d[1] for d in doms]), return_inverse=True)
-    Ur, Ir = U[ru].double(), I[ri].double()
-    ut, it, parts, loss, off = [[], [], []], [[], [], []], [], 0.0, 0
-    for uid, iid, label, reg, w in doms:
-        B = uid.numel()
-        u, i = Ur[inv_u[off:off + B]], Ir[inv_i[off:off + B]]
-        off += B
-        ua, ia = u.abs(), i.abs()
-        y = label.double()
-        x = (u * i).sum(1)
-        ex = gam(D + 2) * (ua * ia).sum(1) + U32 * x.abs()
-        s, q = torch.sigmoid(x), torch.sigmoid(-x)
-        p32 = torch.sigmoid(x.float())
-        pq = ((1 - p32) * p32).double()
-        clamp = torch.where(pq < 1e-12, pq / 1e-12, torch.ones_like(pq))
-        main = -(y * torch.log(s).clamp(min=-100) + (1 - y) * torch.log(q).clamp(min=-100)).mean()
-        g = w * (s - y) * clamp / B
-        delta = w * (s * q * ex / B + K_COEF * U32 * ((s - y).abs() / B + s / B))
-        nu, ni = u.norm(), i.norm()
-        emb = (nu + ni) / B
-        loss += w * (float(main) + reg * float(emb))
-        parts.append((float(main), float(emb)))
-        cu = w * reg / (B * nu) if reg else 0.0
-        ci = w * reg / (B * ni) if reg else 0.0
-        gc = gam(D + 4)
-        g1, d1 = g.unsqueeze(1), delta.unsqueeze(1)
-        for acc, t in ((ut, (g1 * i + cu * u, g1.abs() * ia + cu * ua, d1 * ia + gc * cu * ua)),
-                       (it, (g1 * u + ci * i, g1.abs() * ua + ci * ia, d1 * ua + gc * ci * ia))):
-            for j in range(3):
-                acc[j].append(t[j])
-    upart = (ru, *_occ_sums(ru.numel(), inv_u, *[torch.cat(a) for a in ut]))
-    ipart = (ri, *_occ_sums(ri.numel(), inv_i, *[torch.cat(a) for a in it]))
-    return loss, parts, upart, ipart
-
 
 def _pair_ids(shape, Bs, Bt, nu, ni, gen):
     """(su, si, tu, ti) of one step; ``shape``: 'zipf' (Zipf items plus one item hot in both domains), 'overlap' (every target user also

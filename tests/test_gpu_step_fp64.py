@@ -18,86 +18,10 @@ touched row -- and their moments are compared bit for bit."""
 import pytest
 import torch
 
-from fp64_bounds import U32, apply_fp64, gam
+from fp64_bounds import GAMMA, K_COEF, LOSS_RTOL, U32, _occ_sums, apply_fp64, bpr_grads_fp64, gam, point_grads_fp64   # noqa: F401 (re-exported)
 from helpers import DEV
 
 pytestmark = pytest.mark.gpu
-
-K_COEF = 8                  # ulps of the per-occurrence loss coefficient beyond its score error
-LOSS_RTOL = 1e-5
-GAMMA = 1e-10               # BPRLoss gamma (recbole): -log(gamma + sigmoid(pos - neg))
-
-
-def _occ_sums(n_rows, inv, terms, absum, cerr):
-    G = torch.zeros(n_rows, terms.shape[1], device=terms.device, dtype=torch.float64)
-    A, E = torch.zeros_like(G), torch.zeros_like(G)
-    G.index_add_(0, inv, terms); A.index_add_(0, inv, absum); E.index_add_(0, inv, cerr)
-    return G, A, E, torch.bincount(inv, minlength=n_rows)
-
-
-# ---------------------------------------------------------------------------------------------------------------------- fp64 reference
-
-def bpr_grads_fp64(U, I, uid, pid, nid, reg):
-    """Loss and summed row gradients of  BPRLoss(u.p, u.n) + reg * EmbLoss(u, p)  (recbole; emcdr.py domain_loss) in float64.
-    Returns (loss, user part, item part); a part = (rows, G, A, E, occ): unique row ids, summed gradient, sum|term|, summed
-    coefficient-error terms, occurrences."""
-    B, D = uid.numel(), U.shape[1]
-    ru, inv_u = torch.unique(uid, return_inverse=True)
-    ri, inv_i = torch.unique(torch.cat([pid, nid]), return_inverse=True)
-    Ur, Ir = U[ru].double(), I[ri].double()
-    u, p, n = Ur[inv_u], Ir[inv_i[:B]], Ir[inv_i[B:]]
-    ua, pa, na = u.abs(), p.abs(), n.abs()
-    x = (u * p).sum(1) - (u * n).sum(1)
-    ex = gam(D + 2) * ((ua * pa).sum(1) + (ua * na).sum(1)) + U32 * x.abs()
-    s, q = torch.sigmoid(x), torch.sigmoid(-x)
-    h = GAMMA + s
-    g = -(s * q) / h / B
-    dgdx = -(s * q * (q - s) * h - (s * q) ** 2) / (h * h) / B
-    dgds = -((1 - 2 * s) * h - s * q) / (h * h) / B
-    delta = (dgdx.abs() * ex + K_COEF * U32 * (dgds.abs() * s + g.abs())).unsqueeze(1)
-    nu, ni = u.norm(), p.norm()
-    loss = -torch.log(GAMMA + s).mean() + reg * (nu + ni) / B
-    cu = reg / (B * nu) if reg else 0.0
-    ci = reg / (B * ni) if reg else 0.0
-    gc = gam(D + 4)
-    g1 = g.unsqueeze(1)
-    ut = (g1 * (p - n) + cu * u, g1.abs() * (pa + na) + cu * ua, delta * (p - n).abs() + gc * cu * ua)
-    del x, s, q, h, dgdx, dgds
-    it = (torch.cat([g1 * u + ci * p, -g1 * u]), torch.cat([g1.abs() * ua + ci * pa, g1.abs() * ua]),
-          torch.cat([delta * ua + gc * ci * pa, delta * ua]))
-    del u, p, n, ua, pa, na
-    return float(loss), (ru, *_occ_sums(ru.numel(), inv_u, *ut)), (ri, *_occ_sums(ri.numel(), inv_i, *it))
-
-
-def point_grads_fp64(U, I, uid, iid, label, reg, kind):
-    """Loss and summed row gradients of  MSE(u.i, y)  or  BCE(sigmoid(u.i), y)  + reg * EmbLoss(u, i)  in float64."""
-    B, D = uid.numel(), U.shape[1]
-    ru, inv_u = torch.unique(uid, return_inverse=True)
-    ri, inv_i = torch.unique(iid, return_inverse=True)
-    u, i = U[ru].double()[inv_u], I[ri].double()[inv_i]
-    ua, ia = u.abs(), i.abs()
-    y = label.double()
-    x = (u * i).sum(1)
-    ex = gam(D + 2) * (ua * ia).sum(1) + U32 * x.abs()
-    if kind == 'mse':
-        d = x - y
-        main = (d * d).mean()
-        g = 2 * d / B
-        delta = 2 * (ex + U32 * d.abs()) / B + K_COEF * U32 * g.abs()
-    else:
-        s, q = torch.sigmoid(x), torch.sigmoid(-x)
-        main = -(y * torch.log(s).clamp(min=-100) + (1 - y) * torch.log(q).clamp(min=-100)).mean()
-        g = (s - y) / B
-        delta = s * q * ex / B + K_COEF * U32 * (g.abs() + s / B)
-    nu, ni = u.norm(), i.norm()
-    loss = main + reg * (nu + ni) / B
-    cu = reg / (B * nu) if reg else 0.0
-    ci = reg / (B * ni) if reg else 0.0
-    gc = gam(D + 4)
-    g1, d1 = g.unsqueeze(1), delta.unsqueeze(1)
-    ut = (g1 * i + cu * u, g1.abs() * ia + cu * ua, d1 * ia + gc * cu * ua)
-    it = (g1 * u + ci * i, g1.abs() * ua + ci * ia, d1 * ua + gc * ci * ia)
-    return float(loss), (ru, *_occ_sums(ru.numel(), inv_u, *ut)), (ri, *_occ_sums(ri.numel(), inv_i, *it))
 
 
 # ---------------------------------------------------------------------------------------------------------------------- checks
