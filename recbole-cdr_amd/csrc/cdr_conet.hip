@@ -27,11 +27,11 @@
 #include <string.h>
 #include <type_traits>
 #include "cdr_common.h"
+#include "cdr_mfma.h"
 #include <vector>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kMaxL = CDR_CONET_MAX_LAYERS;
 constexpr int kRows = 32;                       // rows per workgroup pass = one MFMA M tile
 constexpr int kJobFloats = 6 * 1024 + 128;      // a wgrad job's partial: six 32x32 tiles + four bias rows
@@ -56,15 +56,6 @@ struct conet_grads {
 };
 struct conet_tiles { int ntiles; int off[kMaxL + 1]; };
 
-__device__ __forceinline__ float4 ldw4(const float* p, bool vec) {
-    return vec ? ld4(p) : make_float4(p[0], p[1], p[2], p[3]);
-}
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.f;
-    return z;
-}
 #ifdef CDR_CONET_PROF
 __device__ long long* g_conet_prof = nullptr;
 #define STAMP(i) do { if (g_conet_prof && blockIdx.x == 0 && threadIdx.x == 0) g_conet_prof[i] = wall_clock64(); } while (0)
@@ -74,20 +65,6 @@ __device__ long long* g_conet_prof = nullptr;
 #define STAMP(i) do { } while (0)
 #define STAMPB(i) do { } while (0)
 #endif
-#define MFMA4(acc, a, b)                                                          \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32((a).x, (b).x, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32((a).y, (b).y, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32((a).z, (b).z, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32((a).w, (b).w, acc, 0, 0, 0)
-#define MF1(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0)
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e. waits for every global STORE of
-// the phase (the saved activations / gz / gx0 rows, which nothing in the kernel reads back): ~1.5 us per layer, more than
-// the small layers' MFMA time.  Register results of global LOADS are still waited for by their consumers.
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // The {Ws, Wt, H} of every layer >= 1 into LDS, rows padded to din + 4 floats (conflict-free 16-B fragment reads).
 __device__ __forceinline__ void stage_weights(const conet_net& net, float* wl) {
     const bool vec = net.vec != 0;

@@ -21,10 +21,10 @@
 // (Tried: two users per pass, i.e. two independent accumulator chains per wave: 260 VGPRs -> one wave per SIMD instead of two, 0.57 ->
 //  0.47 of the fp32 MFMA peak at 64 users x 1 M items.  Two resident waves hide more than two chains in one.)
 #include "cdr_common.h"
+#include "cdr_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kFsBlock = 256;                    // 4 waves: 4 item tiles per workgroup pass, one user chunk
 constexpr int kFsUsers = 32;                     // users per LDS chunk (32 x 64 floats = 8 KB)
 

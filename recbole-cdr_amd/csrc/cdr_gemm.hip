@@ -14,10 +14,10 @@
 // accumulator column is an N index and every store instruction writes 32 consecutive floats per half-wave.
 #include <stdlib.h>
 #include "cdr_common.h"
+#include "cdr_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;
 constexpr int LDS_STRIDE = BK + 4;   // 36 dwords

@@ -7,10 +7,10 @@
 // (v_mfma_f32_32x32x2_f32: both operands are read down a column, 128 contiguous bytes per half-wave and row), partial tiles added
 // through LDS in wave order (no float atomics: run-to-run identical), the bias gradient as the running sum of the A operand.
 #include "cdr_common.h"
+#include "cdr_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kBlock = 256;
 constexpr int kWgPart = 32 * 32 + 32;                          // floats of one partial: a dW tile + its bias row
 constexpr int kWgWaves = 8, kWgBlock = 64 * kWgWaves;     // linear_wgrad_small_kernel: waves (= batch-row slices) per 32 x 32 tile

@@ -9,8 +9,8 @@
 //                       CU: four MFMA waves do forward / loss / weight-gradient tiles / dL/dS on 32 ids at a time out of LDS, four
 //                       row waves keep the next block's six rows per id in flight with LDS DMA and apply SGD / Adam to the
 //                       two table rows in place -- see the comment above the kernel.  3.3 TB/s at OB = 65,536.
-//   map_pipe2_kernel    the same two wave groups for the reference's default mapping, Linear + Tanh + Linear with D and H in {64, 128}
-//                       (gz and dL/dS share an LDS buffer; seven barriers per block): 1.6-1.8 TB/s.
+//   map_pipe3_kernel    the same two wave groups for the reference's default mapping, Linear + Tanh + Linear with D and H in {64, 128}
+//                       (gz and dL/dS share an LDS buffer; seven barriers per block; the row waves also accumulate the weight gradients).
 //   map_step_kernel     (every other mapping shape: deeper MLPs, odd widths, Ds != Dt) a workgroup owns 32 ids at a time: gathers S[id]
 //                       and T[id] into LDS, runs the mapping function
 //                       (Linear, or Linear+Tanh ... Linear) on v_mfma_f32_32x32x2_f32 with the activations in LDS,
@@ -29,6 +29,7 @@
 #include <type_traits>
 #include <cstdlib>
 #include "cdr_common.h"
+#include "cdr_mfma.h"
 #include "cdr_adam_math.h"
 
 // The rows of the two user tables are touched once per step: their LDS-DMA loads and their write-backs are issued non-temporal (rows of
@@ -43,7 +44,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kMapMaxL = CDR_MAP_MAX_LAYERS;
 constexpr int kRows = 32;
 constexpr int kSlots = 8;                      // weight-gradient tiles a wave may own (128 accumulator registers)
@@ -62,24 +62,6 @@ struct map_opt { float lr, b1, b2, eps, wd; int opt; };
 struct map_params { float* W[kMapMaxL]; float* b[kMapMaxL]; float* mW[kMapMaxL]; float* vW[kMapMaxL]; float* mb[kMapMaxL]; float* vb[kMapMaxL];
                     int64_t* sW[kMapMaxL]; int64_t* sb[kMapMaxL]; };
 
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.f;
-    return z;
-}
-__device__ __forceinline__ float4 ldw4(const float* p, bool vec) {
-    return vec ? ld4(p) : make_float4(p[0], p[1], p[2], p[3]);
-}
-#define MFMA4(acc, a, b)                                                          \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32((a).x, (b).x, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32((a).y, (b).y, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32((a).z, (b).z, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32((a).w, (b).w, acc, 0, 0, 0)
-#define MF1(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0)
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 __device__ __forceinline__ void adam_hp(const map_opt& o, const int64_t* step_dev, int64_t plus, float& step_size, float& bc2_sqrt) {
     step_size = o.lr; bc2_sqrt = 1.f;
     if (o.opt == 1) {
@@ -94,12 +76,6 @@ __device__ __forceinline__ float upd1(float w, float g, float& m, float& v, cons
     m += (g - m) * (1.0f - o.b1);
     v = o.b2 * v + (1.0f - o.b2) * g * g;
     return w - cdr_adam_term(m, v, step_size, bc2_sqrt, o.eps);
-}
-
-// (round 4 had a second form of this update on v_rcp_f32 / v_sqrt_f32 for map_pipe_kernel alone; since round 5 EVERY Adam kernel of the
-// library takes its update term from cdr_adam_term, so the pipe kernels call the same function as everything else)
-__device__ __forceinline__ float updq(float w, float g, float& m, float& v, const map_opt& o, float step_size, float bc2) {
-    return upd1(w, g, m, v, o, step_size, bc2);
 }
 
 // SLOTS: weight-gradient tiles per wave (4 -> 64 accumulator registers, 8 -> 128)
@@ -361,61 +337,56 @@ __device__ __forceinline__ void glds16(const float* g, float* lds_wave_base) {
                  : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
 }
 
-template <int NI>
-__global__ __launch_bounds__(512, 1) void map_pipe_kernel(map_net net, map_opt opt, float* __restrict__ S, float* __restrict__ mS,
-                                                         float* __restrict__ vS, float* __restrict__ T, float* __restrict__ mT,
-                                                         float* __restrict__ vT, const int64_t* __restrict__ idx, int64_t n,
-                                                         const int64_t* __restrict__ step_s, const int64_t* __restrict__ step_t,
-                                                         float* __restrict__ wpart, double* __restrict__ lpart, map_params bump) {
-    constexpr int D = 32 * NI;                 // Ds == Dt
-    constexpr int LR = D / 4;                  // 16-byte chunks (= DMA lanes) per row
-    constexpr int RPI = 64 / LR;               // rows per DMA instruction (1 KiB of LDS)
-    constexpr int GS = D + 4;                  // padded row stride of the two MFMA-written buffers
-    constexpr int SLOTS = NI * NI / 4 > 0 ? NI * NI / 4 : 1;       // weight-gradient tiles per MFMA wave
-    constexpr int NJ = (NI + 3) / 4;           // 32-column jobs per MFMA wave
-    constexpr int NQ = NI;                     // DMA instructions per row wave and array (4 row waves)
-    // target rows updated before barrier M (the rest after it).  Stamps of one block (tools/prof_mapstep.py): whatever update arithmetic
-    // a row wave has left after M runs against the dL/dS contraction of its SIMD (resident weights: back-to-back MFMAs) and takes 2.5-3 us
-    // per quarter of the rows where a quarter takes 0.9 us before M, and barrier E then waits for it.  Halves: 0.1251 ms per launch at
-    // OB = 65,536; three quarters before M: 0.1238; everything: 0.1223 (alternating processes on one box, profiles/r03_ab_map_qt.txt).
-    constexpr int QT = NQ;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float rok[3][kRows];
-    __shared__ int64_t rid[3][kRows];
-    __shared__ double red[4];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li0 = lane & 31, lh0 = lane >> 5;
-    const bool rowwave = wave >= 4;
-    float* GZ = smem;                          // [32][GS]  mapped -> gz = dL/d mapped
-    float* GX = GZ + kRows * GS;               // [32][GS]  dL/dS
-    float* SS = GX + kRows * GS;               // [2][32][D] source rows (swizzled)
-    float* ST = SS + 2 * kRows * D;            // [32][D] each, swizzled alike
-    float* SMT = ST + kRows * D;
-    float* SVT = SMT + kRows * D;
-    float* SMS = SVT + kRows * D;
-    float* SVS = SMS + kRows * D;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool adam = opt.opt != 0;
-    float ss_s, bc_s, ss_t, bc_t;
-    adam_hp(opt, step_s, 1, ss_s, bc_s);
-    adam_hp(opt, step_t, 1, ss_t, bc_t);
-    const float gscale = 2.0f / ((float)n * (float)D);
-    const float* __restrict__ W = net.W[0];
-    if (blockIdx.x == 0 && t == 0 && bump.sW[0]) bump.sW[0][0] += 1;
-    const int64_t nrb = (n + kRows - 1) / kRows;
-    f32x16 wacc[SLOTS];
-#pragma unroll
-    for (int q = 0; q < SLOTS; ++q) wacc[q] = zero16();
-    double lsum = 0.0;
+// ---- what the two-wave-group kernels (map_pipe_kernel, map_pipe3_kernel) share: the LDS carve, the row waves' staging and update,
+// the first block's prologue.  The per-block schedules -- which barrier, which wave group -- and the epilogues are the kernels'.
+using std::integral_constant;
+#define IC(v) integral_constant<int, (v)>{}
 
-    // (address arithmetic below is re-derived per phase from a laundered lane id: left alone, LICM hoists ~200 loop-invariant LDS /
-    //  global offsets out of the block loop and spills them -- and a spill reload inside a row wave is a vector memory load whose
-    //  wait drains the DMA queue)
-    auto fresh = [](int v) { asm volatile("" : "+v"(v)); return v; };
-    // ---- row waves: lane <-> (row, physical chunk) of DMA instruction i = pw + 4 q, q < NQ
-    const int pw = wave - 4;
+// The dynamic LDS of one workgroup, float offsets; NI = D / 32, and NHI = H / 32 for the MLP kernel (0: the linear kernel).
+// The kernels carve with it and the host sizes the launch with it.
+template <int NI, int NHI = 0>
+struct pipe_lds {
+    static constexpr int D = 32 * NI, GS = D + 4, HS = 32 * NHI + 4;         // GS, HS: padded row strides of the MFMA-written buffers
+    static constexpr int GZ = 0;                                            // [32][GS]  mapped -> gz = dL/d mapped
+    static constexpr int GX = NHI ? GZ : GZ + kRows * GS;                   // [32][GS]  dL/dS (MLP: in gz's buffer, see map_pipe3_kernel)
+    static constexpr int HB = GZ + kRows * GS;                              // [32][HS]  MLP only: hidden activations -> dL/d(hidden pre-activation)
+    static constexpr int SS = NHI ? HB + kRows * HS : GX + kRows * GS;      // [2][32][D] source rows (swizzled)
+    static constexpr int ST = SS + 2 * kRows * D;                           // [32][D] each, swizzled alike
+    static constexpr int SMT = ST + kRows * D, SVT = SMT + kRows * D, SMS = SVT + kRows * D, SVS = SMS + kRows * D;
+    static constexpr size_t bytes = (size_t)(SVS + kRows * D) * sizeof(float);
+};
+
+// (address arithmetic in these kernels is re-derived per phase from a laundered lane id: left alone, LICM hoists ~200 loop-invariant LDS /
+//  global offsets out of the block loop and spills them -- and a spill reload inside a row wave is a vector memory load whose
+//  wait drains the DMA queue)
+__device__ __forceinline__ int fresh(int v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ unsigned lds_off(const float* p) {
+    return (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p);
+}
+
+// ---- row waves: lane <-> (row, physical chunk) of DMA instruction i = pw + 4 q, q < NQ
+template <int NI>
+struct row_wave {
+    static constexpr int D = 32 * NI;          // Ds == Dt
+    static constexpr int LR = D / 4;           // 16-byte chunks (= DMA lanes) per row
+    static constexpr int RPI = 64 / LR;        // rows per DMA instruction (1 KiB of LDS)
+    static constexpr int GS = D + 4;           // padded row stride of the two MFMA-written buffers
+    static constexpr int NQ = NI;              // DMA instructions per row wave and array (4 row waves)
+    const int lane, pw;                        // pw: which of the four row waves (negative in an MFMA wave)
+    const bool adam;
+    const map_opt& opt;
+    const unsigned bSS, bST, bSMT, bSVT, bSMS, bSVS;       // LDS byte addresses of the staged arrays (pipe_lds's tail): the DMA's destinations
+
+    // (the methods are `inline`, not __forceinline__, on purpose: inlined with the kernel's own code by the same pass, as the lambdas
+    //  they were, they compile to the instruction streams the profiles were taken on; forced inlining runs earlier and moved both
+    //  kernels off them -- map_pipe_kernel<4> sits at 256 VGPRs)
+    __device__ inline row_wave(const float* ss, int lane_, int pw_, const map_opt& o)
+        : lane(lane_), pw(pw_), adam(o.opt != 0), opt(o), bSS(lds_off(ss)), bST(lds_off(ss + 2 * kRows * D)), bSMT(lds_off(ss + 3 * kRows * D)),
+          bSVT(lds_off(ss + 4 * kRows * D)), bSMS(lds_off(ss + 5 * kRows * D)), bSVS(lds_off(ss + 6 * kRows * D)) {}
+
     // byte offsets of this lane's NQ chunks inside a table, for the rows of one block: all ids are read from LDS first (one wait),
     // and the result serves every table staged for that block
-    auto row_offsets = [&](const int64_t* ids, int64_t (&off)[NQ]) {
+    __device__ inline void row_offsets(const int64_t* ids, int64_t (&off)[NQ]) const {
         const int ln = fresh(lane);
         int64_t idv[NQ];
 #pragma unroll
@@ -425,9 +396,9 @@ __global__ __launch_bounds__(512, 1) void map_pipe_kernel(map_net net, map_opt o
             const int row = (pw + 4 * q) * RPI + ln / LR, p = ln % LR;
             off[q] = (idv[q] * D + 4 * (p ^ (row & (LR - 1)))) * (int64_t)sizeof(float);
         }
-    };
+    }
     // NQ DMA instructions of one table in ONE asm statement: M0 saved once, set per instruction, restored once
-    auto stage = [&](const float* __restrict__ tab, unsigned dst_bytes, const int64_t (&off)[NQ]) {
+    __device__ inline void stage(const float* __restrict__ tab, unsigned dst_bytes, const int64_t (&off)[NQ]) const {
         const char* base = reinterpret_cast<const char*>(tab);
         const unsigned d0 = __builtin_amdgcn_readfirstlane(dst_bytes + (unsigned)pw * 1024u);   // instruction i = pw + 4 q writes 1 KiB at i * 1 KiB
         unsigned keep;
@@ -444,19 +415,17 @@ __global__ __launch_bounds__(512, 1) void map_pipe_kernel(map_net net, map_opt o
             asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" MAP_NT "\n\t"
                          "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off" MAP_NT "\n\ts_mov_b32 m0, %0"
                          : "=&s"(keep) : "v"(base + off[0]), "v"(base + off[1]), "s"(d0), "s"(d0 + 4096u) : "memory");
-    };
-    auto lds_off = [](const float* p) {
-        return (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p);
-    };
-    const unsigned bSS = lds_off(SS), bST = lds_off(ST), bSMT = lds_off(SMT), bSVT = lds_off(SVT), bSMS = lds_off(SMS), bSVS = lds_off(SVS);
-    int64_t roff[NQ];
+    }
     // Adam / SGD on this lane's chunks of DMA instructions [Q0, Q1): g = sign * G[row][logical chunk].  Every operand of the
-    // whole range is requested before the arithmetic starts (one wave per role and SIMD: nothing else hides the LDS latency)
-    auto apply = [&](auto Q0c, auto Q1c, float* __restrict__ tab, float* __restrict__ mtab, float* __restrict__ vtab, const float* stW,
-                     const float* stM, const float* stV, const float* G, float sign, const int64_t* ids, const float* ok,
-                     float ssz, float bcs) {
-        constexpr int Q0 = decltype(Q0c)::value, Q1 = decltype(Q1c)::value, NQQ = Q1 - Q0 > 0 ? Q1 - Q0 : 1;
+    // whole range is requested before the arithmetic starts (one wave per role and SIMD: nothing else hides the LDS latency).
+    // Each lane updates exactly the 16-byte chunks it staged itself: same lane -> (row, chunk) map as row_offsets.
+    template <class Q0c, class Q1c>
+    __device__ inline void apply(Q0c, Q1c, float* __restrict__ tab, float* __restrict__ mtab, float* __restrict__ vtab,
+                                          const float* stW, const float* stM, const float* stV, const float* G, float sign,
+                                          const int64_t* ids, const float* ok, float ssz, float bcs) const {
+        constexpr int Q0 = Q0c::value, Q1 = Q1c::value, NQQ = Q1 - Q0 > 0 ? Q1 - Q0 : 1;
         if (Q1 <= Q0) return;
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
         const int ln = fresh(lane);
         const float rbc = bcs;                       // cdr_adam_hp's bc2 as it is
         const int r0 = ln / LR, p = ln % LR;
@@ -475,30 +444,82 @@ __global__ __launch_bounds__(512, 1) void map_pipe_kernel(map_net net, map_opt o
 #pragma unroll
         for (int q = 0; q < Q1 - Q0; ++q) {
             float4 wn;
-            wn.x = updq(w[q].x, sign * g[q].x, m[q].x, v[q].x, opt, ssz, rbc); wn.y = updq(w[q].y, sign * g[q].y, m[q].y, v[q].y, opt, ssz, rbc);
-            wn.z = updq(w[q].z, sign * g[q].z, m[q].z, v[q].z, opt, ssz, rbc); wn.w = updq(w[q].w, sign * g[q].w, m[q].w, v[q].w, opt, ssz, rbc);
+            wn.x = upd1(w[q].x, sign * g[q].x, m[q].x, v[q].x, opt, ssz, rbc); wn.y = upd1(w[q].y, sign * g[q].y, m[q].y, v[q].y, opt, ssz, rbc);
+            wn.z = upd1(w[q].z, sign * g[q].z, m[q].z, v[q].z, opt, ssz, rbc); wn.w = upd1(w[q].w, sign * g[q].w, m[q].w, v[q].w, opt, ssz, rbc);
             if (okf[q] != 0.f) {
                 MAP_ST4(tab + o[q], wn);
                 if (adam) { MAP_ST4(mtab + o[q], m[q]); MAP_ST4(vtab + o[q], v[q]); }
             }
         }
-    };
-    using std::integral_constant;
-#define IC(v) integral_constant<int, (v)>{}
-    if (t < kRows) {                                                     // ids of this workgroup's first block
-        const int64_t g = (int64_t)blockIdx.x * kRows + t;
-        rid[0][t] = idx[g < n ? g : n - 1];
-        rok[0][t] = g < n ? 1.f : 0.f;
     }
-    __syncthreads();
-    if (rowwave) {
-        __builtin_amdgcn_s_setprio(3);
-        row_offsets(rid[0], roff);
-        stage(S, bSS, roff);
-        stage(T, bST, roff);
-        if (adam) { stage(mT, bSMT, roff); stage(vT, bSVT, roff); }
-        vm_wait<0>();
+    // The workgroup's first block: its ids into rid / rok (every wave), then the row waves raise their priority and stage its
+    // S, T, mT, vT rows, and wait for them.  The caller's lds_barrier() publishes them.
+    __device__ inline void first_block(int64_t* rid, float* rok, const int64_t* __restrict__ idx, int64_t n, const float* S,
+                                                const float* T, const float* mT, const float* vT) const {
+        const int t = threadIdx.x;
+        if (t < kRows) {
+            const int64_t g = (int64_t)blockIdx.x * kRows + t;
+            rid[t] = idx[g < n ? g : n - 1];
+            rok[t] = g < n ? 1.f : 0.f;
+        }
+        __syncthreads();
+        if (pw >= 0) {
+            int64_t roff[NQ];
+            __builtin_amdgcn_s_setprio(3);
+            row_offsets(rid, roff);
+            stage(S, bSS, roff);
+            stage(T, bST, roff);
+            if (adam) { stage(mT, bSMT, roff); stage(vT, bSVT, roff); }
+            vm_wait<0>();
+        }
     }
+};
+
+template <int NI>
+__global__ __launch_bounds__(512, 1) void map_pipe_kernel(map_net net, map_opt opt, float* __restrict__ S, float* __restrict__ mS,
+                                                         float* __restrict__ vS, float* __restrict__ T, float* __restrict__ mT,
+                                                         float* __restrict__ vT, const int64_t* __restrict__ idx, int64_t n,
+                                                         const int64_t* __restrict__ step_s, const int64_t* __restrict__ step_t,
+                                                         float* __restrict__ wpart, double* __restrict__ lpart, map_params bump) {
+    using LDS = pipe_lds<NI>;
+    using RW = row_wave<NI>;
+    constexpr int D = RW::D, LR = RW::LR, GS = RW::GS, NQ = RW::NQ;
+    constexpr int SLOTS = NI * NI / 4 > 0 ? NI * NI / 4 : 1;       // weight-gradient tiles per MFMA wave
+    constexpr int NJ = (NI + 3) / 4;           // 32-column jobs per MFMA wave
+    // target rows updated before barrier M (the rest after it).  Stamps of one block (tools/prof_mapstep.py): whatever update arithmetic
+    // a row wave has left after M runs against the dL/dS contraction of its SIMD (resident weights: back-to-back MFMAs) and takes 2.5-3 us
+    // per quarter of the rows where a quarter takes 0.9 us before M, and barrier E then waits for it.  Halves: 0.1251 ms per launch at
+    // OB = 65,536; three quarters before M: 0.1238; everything: 0.1223 (alternating processes on one box, profiles/r03_ab_map_qt.txt).
+    constexpr int QT = NQ;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ float rok[3][kRows];
+    __shared__ int64_t rid[3][kRows];
+    __shared__ double red[4];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li0 = lane & 31, lh0 = lane >> 5;
+    const bool rowwave = wave >= 4;
+    float* GZ = smem + LDS::GZ;
+    float* GX = smem + LDS::GX;
+    float* SS = smem + LDS::SS;
+    float* ST = smem + LDS::ST;
+    float* SMT = smem + LDS::SMT;
+    float* SVT = smem + LDS::SVT;
+    float* SMS = smem + LDS::SMS;
+    float* SVS = smem + LDS::SVS;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float ss_s, bc_s, ss_t, bc_t;
+    adam_hp(opt, step_s, 1, ss_s, bc_s);
+    adam_hp(opt, step_t, 1, ss_t, bc_t);
+    const float gscale = 2.0f / ((float)n * (float)D);
+    const float* __restrict__ W = net.W[0];
+    if (blockIdx.x == 0 && t == 0 && bump.sW[0]) bump.sW[0][0] += 1;
+    const int64_t nrb = (n + kRows - 1) / kRows;
+    f32x16 wacc[SLOTS];
+#pragma unroll
+    for (int q = 0; q < SLOTS; ++q) wacc[q] = zero16();
+    double lsum = 0.0;
+    const RW rw(SS, lane, wave - 4, opt);
+    int64_t roff[NQ];
+    rw.first_block(rid[0], rok[0], idx, n, S, T, mT, vT);
     lds_barrier();
     // weights that stay in registers across blocks: ALL of the dL/dS contraction's (it reads W down a column -- 4-byte strided
     // loads whose L2 latency under the step's HBM load no one-group look-ahead covers) and the first K group of the forward's
@@ -654,25 +675,25 @@ __global__ __launch_bounds__(512, 1) void map_pipe_kernel(map_net net, map_opt o
         } else {
             vm_wait<0>();                                                // T, mT, vT of this block and mS, vS of the previous one
             MP_STAMP(1);
-            if (k > 0) apply(IC(0), IC(NQ / 2), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
+            if (k > 0) rw.apply(IC(0), IC(NQ / 2), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
             MP_STAMP(2);
             lds_barrier();                                               // ---- X
-            if (k > 0) apply(IC(NQ / 2), IC(NQ), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
+            if (k > 0) rw.apply(IC(NQ / 2), IC(NQ), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
             MP_STAMP(9);
-            if (has_next) { row_offsets(rid[r3n], roff); stage(S, bSS + (unsigned)((par ^ 1) * kRows * D * 4), roff); }
-            if (adam) { row_offsets(rid[r3], roff); stage(mS, bSMS, roff); stage(vS, bSVS, roff); }
+            if (has_next) { rw.row_offsets(rid[r3n], roff); rw.stage(S, rw.bSS + (unsigned)((par ^ 1) * kRows * D * 4), roff); }
+            if (rw.adam) { rw.row_offsets(rid[r3], roff); rw.stage(mS, rw.bSMS, roff); rw.stage(vS, rw.bSVS, roff); }
             MP_STAMP(3);
             lds_barrier();                                               // ---- F
             MP_STAMP(4);
-            apply(IC(0), IC(QT), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);   // dL/dT[id] = -dL/d mapped
+            rw.apply(IC(0), IC(QT), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);   // dL/dT[id] = -dL/d mapped
             MP_STAMP(5);
             lds_barrier();                                               // ---- M
-            apply(IC(QT), IC(NQ), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);
+            rw.apply(IC(QT), IC(NQ), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);
             MP_STAMP(10);
             if (has_next) {
-                row_offsets(rid[r3n], roff);
-                stage(T, bST, roff);
-                if (adam) { stage(mT, bSMT, roff); stage(vT, bSVT, roff); vm_wait<5 * NQ>(); } else vm_wait<NQ>();
+                rw.row_offsets(rid[r3n], roff);
+                rw.stage(T, rw.bST, roff);
+                if (rw.adam) { rw.stage(mT, rw.bSMT, roff); rw.stage(vT, rw.bSVT, roff); vm_wait<5 * NQ>(); } else vm_wait<NQ>();
             }                                                            // (the next block's source rows have landed)
             MP_STAMP(7);
             lds_barrier();                                               // ---- E
@@ -682,7 +703,7 @@ __global__ __launch_bounds__(512, 1) void map_pipe_kernel(map_net net, map_opt o
     if (rowwave) {                                                       // the last block's source rows
         const int par = (k - 1) & 1, r3 = (k - 1) % 3;
         vm_wait<0>();
-        apply(IC(0), IC(NQ), S, mS, vS, SS + par * kRows * D, SMS, SVS, GX, 1.f, rid[r3], rok[r3], ss_s, bc_s);
+        rw.apply(IC(0), IC(NQ), S, mS, vS, SS + par * kRows * D, SMS, SVS, GX, 1.f, rid[r3], rok[r3], ss_s, bc_s);
     } else {
         float* o = wpart + (size_t)blockIdx.x * ((size_t)net.ntiles * 1024 + net.nbias);
 #pragma unroll
@@ -705,424 +726,38 @@ __global__ __launch_bounds__(512, 1) void map_pipe_kernel(map_net net, map_opt o
 // Twice the MFMA phases per block (two forwards, two weight-gradient phases, two data-gradient phases: seven barriers) around the same
 // row-wave schedule.  LDS: one more operand buffer (the hidden activations) does not fit beside everything else, so gz = dL/d mapped and
 // dL/dS SHARE a buffer -- gz is dead once the target rows are updated and the first layer's backward has run, dL/dS is dead once the
-// source rows are updated, which the row waves finish before the next block's forward reaches its epilogue.  Weights come from L2
-// (32 weight-gradient tiles take half of the register file).
-template <int NI, int NHI>
-__global__ __launch_bounds__(512, 1) void map_pipe2_kernel(map_net net, map_opt opt, float* __restrict__ S, float* __restrict__ mS,
-                                                         float* __restrict__ vS, float* __restrict__ T, float* __restrict__ mT,
-                                                         float* __restrict__ vT, const int64_t* __restrict__ idx, int64_t n,
-                                                         const int64_t* __restrict__ step_s, const int64_t* __restrict__ step_t,
-                                                         float* __restrict__ wpart, double* __restrict__ lpart, map_params bump) {
-    constexpr int D = 32 * NI;                 // Ds == Dt
-    constexpr int H = 32 * NHI;                // hidden width
-    constexpr int HS = H + 4;
-    constexpr int LR = D / 4;                  // 16-byte chunks (= DMA lanes) per row
-    constexpr int RPI = 64 / LR;               // rows per DMA instruction (1 KiB of LDS)
-    constexpr int GS = D + 4;                  // padded row stride of the two MFMA-written buffers
-    constexpr int TL = NI * NHI;               // weight-gradient tiles per layer (layer 0: [H][D], layer 1: [D][H])
-    constexpr int SL = TL / 4;                 // ... per MFMA wave and layer (TL is a multiple of 4)
-    constexpr int NJD = (NI + 3) / 4, NJH = (NHI + 3) / 4;      // 32-column jobs per MFMA wave over D / over H
-    constexpr int NQ = NI;                     // DMA instructions per row wave and array (4 row waves)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float rok[3][kRows];
-    __shared__ int64_t rid[3][kRows];
-    __shared__ double red[4];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li0 = lane & 31, lh0 = lane >> 5;
-    const bool rowwave = wave >= 4;
-    float* GZ = smem;                          // [32][GS]  mapped -> gz = dL/d mapped, later dL/dS (shared: see above)
-    float* GX = GZ;
-    float* HB = GZ + kRows * GS;               // [32][HS]  hidden activations -> dL/d(hidden pre-activation)
-    float* SS = HB + kRows * HS;               // [2][32][D] source rows (swizzled)
-    float* ST = SS + 2 * kRows * D;            // [32][D] each, swizzled alike
-    float* SMT = ST + kRows * D;
-    float* SVT = SMT + kRows * D;
-    float* SMS = SVT + kRows * D;
-    float* SVS = SMS + kRows * D;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool adam = opt.opt != 0;
-    float ss_s, bc_s, ss_t, bc_t;
-    adam_hp(opt, step_s, 1, ss_s, bc_s);
-    adam_hp(opt, step_t, 1, ss_t, bc_t);
-    const float gscale = 2.0f / ((float)n * (float)D);
-    const float* __restrict__ W1 = net.W[0];   // [H][D]
-    const float* __restrict__ W2 = net.W[1];   // [D][H]
-    const float* __restrict__ B1 = net.b[0];
-    const float* __restrict__ B2 = net.b[1];
-    if (blockIdx.x == 0 && t == 0) {
-        for (int l = 0; l < 2; ++l) { if (bump.sW[l]) bump.sW[l][0] += 1; if (bump.sb[l]) bump.sb[l][0] += 1; }
-    }
-    const int64_t nrb = (n + kRows - 1) / kRows;
-    f32x16 wacc[2 * SL];                       // [0, SL): layer 0's tiles wave + 4 q ; [SL, 2 SL): layer 1's
-#pragma unroll
-    for (int q = 0; q < 2 * SL; ++q) wacc[q] = zero16();
-    float bacc = 0.f;                          // MFMA-wave thread t owns flat bias element t (b1 then b2)
-    double lsum = 0.0;
-
-    // (address arithmetic below is re-derived per phase from a laundered lane id: left alone, LICM hoists ~200 loop-invariant LDS /
-    //  global offsets out of the block loop and spills them -- and a spill reload inside a row wave is a vector memory load whose
-    //  wait drains the DMA queue)
-    auto fresh = [](int v) { asm volatile("" : "+v"(v)); return v; };
-    // ---- row waves: lane <-> (row, physical chunk) of DMA instruction i = pw + 4 q, q < NQ
-    const int pw = wave - 4;
-    // byte offsets of this lane's NQ chunks inside a table, for the rows of one block: all ids are read from LDS first (one wait),
-    // and the result serves every table staged for that block
-    auto row_offsets = [&](const int64_t* ids, int64_t (&off)[NQ]) {
-        const int ln = fresh(lane);
-        int64_t idv[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) idv[q] = ids[(pw + 4 * q) * RPI + ln / LR];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int row = (pw + 4 * q) * RPI + ln / LR, p = ln % LR;
-            off[q] = (idv[q] * D + 4 * (p ^ (row & (LR - 1)))) * (int64_t)sizeof(float);
-        }
-    };
-    // NQ DMA instructions of one table in ONE asm statement: M0 saved once, set per instruction, restored once
-    auto stage = [&](const float* __restrict__ tab, unsigned dst_bytes, const int64_t (&off)[NQ]) {
-        const char* base = reinterpret_cast<const char*>(tab);
-        const unsigned d0 = __builtin_amdgcn_readfirstlane(dst_bytes + (unsigned)pw * 1024u);   // instruction i = pw + 4 q writes 1 KiB at i * 1 KiB
-        unsigned keep;
-        if constexpr (NQ == 4)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" MAP_NT "\n\t"
-                         "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off" MAP_NT "\n\t"
-                         "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off" MAP_NT "\n\t"
-                         "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, off" MAP_NT "\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(base + off[0]), "v"(base + off[1]), "v"(base + off[2]), "v"(base + off[3]),
-                           "s"(d0), "s"(d0 + 4096u), "s"(d0 + 8192u), "s"(d0 + 12288u)
-                         : "memory");
-        else
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" MAP_NT "\n\t"
-                         "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off" MAP_NT "\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(base + off[0]), "v"(base + off[1]), "s"(d0), "s"(d0 + 4096u) : "memory");
-    };
-    auto lds_off = [](const float* p) {
-        return (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p);
-    };
-    const unsigned bSS = lds_off(SS), bST = lds_off(ST), bSMT = lds_off(SMT), bSVT = lds_off(SVT), bSMS = lds_off(SMS), bSVS = lds_off(SVS);
-    int64_t roff[NQ];
-    // Adam / SGD on this lane's chunks of DMA instructions [Q0, Q1): g = sign * G[row][logical chunk].  Every operand of the
-    // whole range is requested before the arithmetic starts (one wave per role and SIMD: nothing else hides the LDS latency)
-    auto apply = [&](auto Q0c, auto Q1c, float* __restrict__ tab, float* __restrict__ mtab, float* __restrict__ vtab, const float* stW,
-                     const float* stM, const float* stV, const float* G, float sign, const int64_t* ids, const float* ok,
-                     float ssz, float bcs) {
-        constexpr int Q0 = decltype(Q0c)::value, Q1 = decltype(Q1c)::value, NQQ = Q1 - Q0 > 0 ? Q1 - Q0 : 1;
-        if (Q1 <= Q0) return;
-        const int ln = fresh(lane);
-        const float rbc = bcs;                       // cdr_adam_hp's bc2 as it is
-        const int r0 = ln / LR, p = ln % LR;
-        float4 w[NQQ], g[NQQ], m[NQQ], v[NQQ];
-        int64_t o[NQQ];
-        float okf[NQQ];
-#pragma unroll
-        for (int q = 0; q < Q1 - Q0; ++q) {
-            const int row = (pw + 4 * (Q0 + q)) * RPI + r0, c = p ^ (row & (LR - 1)), so = (row * LR + p) * 4;
-            w[q] = ld4(stW + so); g[q] = ld4(G + row * GS + 4 * c);
-            m[q] = z4; v[q] = z4;
-            if (adam) { m[q] = ld4(stM + so); v[q] = ld4(stV + so); }
-            o[q] = ids[row] * D + 4 * c;
-            okf[q] = ok[row];
-        }
-#pragma unroll
-        for (int q = 0; q < Q1 - Q0; ++q) {
-            float4 wn;
-            wn.x = updq(w[q].x, sign * g[q].x, m[q].x, v[q].x, opt, ssz, rbc); wn.y = updq(w[q].y, sign * g[q].y, m[q].y, v[q].y, opt, ssz, rbc);
-            wn.z = updq(w[q].z, sign * g[q].z, m[q].z, v[q].z, opt, ssz, rbc); wn.w = updq(w[q].w, sign * g[q].w, m[q].w, v[q].w, opt, ssz, rbc);
-            if (okf[q] != 0.f) {
-                MAP_ST4(tab + o[q], wn);
-                if (adam) { MAP_ST4(mtab + o[q], m[q]); MAP_ST4(vtab + o[q], v[q]); }
-            }
-        }
-    };
-    using std::integral_constant;
-#define IC(v) integral_constant<int, (v)>{}
-    if (t < kRows) {                                                     // ids of this workgroup's first block
-        const int64_t g = (int64_t)blockIdx.x * kRows + t;
-        rid[0][t] = idx[g < n ? g : n - 1];
-        rok[0][t] = g < n ? 1.f : 0.f;
-    }
-    __syncthreads();
-    if (rowwave) {
-        __builtin_amdgcn_s_setprio(3);
-        row_offsets(rid[0], roff);
-        stage(S, bSS, roff);
-        stage(T, bST, roff);
-        if (adam) { stage(mT, bSMT, roff); stage(vT, bSVT, roff); }
-        vm_wait<0>();
-    }
-    lds_barrier();
-    int k = 0;
-    for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x, ++k) {
-        const int par = k & 1, r3 = k % 3, r3n = (k + 1) % 3, r3p = (k + 2) % 3;
-        const bool has_next = rb + gridDim.x < nrb;
-        float* Xs = SS + par * kRows * D;                               // this block's source rows
-        MP_STAMP(0);
-        if (!rowwave) {
-            int64_t idn = 0; float okn = 0.f;
-            if (t < kRows && has_next) { const int64_t g = (rb + gridDim.x) * kRows + t; idn = idx[g < n ? g : n - 1]; okn = g < n ? 1.f : 0.f; }
-            int li = fresh(li0), lh = fresh(lh0);
-            // C[32 x 32-col tile] = A (LDS, one row per lane) x Wg[ncol][0..K) -- weight ROWS, K in groups of four steps, the next
-            // group's weights (L2) and operand chunks (LDS) requested before the current group's sixteen MFMAs
-            auto contract_rows = [&](auto Kc, const float* __restrict__ Wg, int ncol, auto a_chunk) {
-                constexpr int K = decltype(Kc)::value;
-                f32x16 acc = zero16();
-                const float* wm = Wg + (int64_t)ncol * K + 4 * lh;
-                float4 nm[4], an[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { nm[j] = ld4(wm + 8 * j); an[j] = a_chunk(2 * j + lh); }
-#pragma unroll
-                for (int g = 0; g < K / 32; ++g) {
-                    float4 cm[4], ca[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { cm[j] = nm[j]; ca[j] = an[j]; }
-                    if (g + 1 < K / 32) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) { nm[j] = ld4(wm + 8 * (4 * (g + 1) + j)); an[j] = a_chunk(2 * (4 * (g + 1) + j) + lh); }
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { MFMA4(acc, ca[j], cm[j]); }
-                }
-                return acc;
-            };
-            // C = A (LDS) x Wg[0..K)[ncol] -- weight COLUMNS (the data-gradient products): four strided words per K step
-            auto contract_cols = [&](auto Kc, auto LDc, const float* __restrict__ Wg, int ncol, const float* ao) {
-                constexpr int K = decltype(Kc)::value, LDW = decltype(LDc)::value;
-                f32x16 acc = zero16();
-                const float* w0 = Wg + (int64_t)(4 * lh) * LDW + ncol;
-                float4 nb[4], an[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { const float* p = w0 + (int64_t)(8 * j) * LDW; nb[j] = make_float4(p[0], p[LDW], p[2 * LDW], p[3 * LDW]); an[j] = ld4(ao + 8 * j); }
-#pragma unroll
-                for (int g = 0; g < K / 32; ++g) {
-                    float4 cb[4], ca[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { cb[j] = nb[j]; ca[j] = an[j]; }
-                    if (g + 1 < K / 32) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int kk = 8 * (4 * (g + 1) + j);
-                            const float* p = w0 + (int64_t)kk * LDW;
-                            nb[j] = make_float4(p[0], p[LDW], p[2 * LDW], p[3 * LDW]); an[j] = ld4(ao + kk);
-                        }
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { MFMA4(acc, ca[j], cb[j]); }
-                }
-                return acc;
-            };
-            // ---- forward 0: HB = tanh(X W1^T + b1)
-#pragma unroll
-            for (int jj = 0; jj < NJH; ++jj) {
-                const int job = wave + 4 * jj;
-                if (job < NHI) {
-                    const int ncol = job * 32 + li;
-                    const float* xr = Xs + li * D;
-                    const int sw = li & (LR - 1);
-                    const f32x16 acc = contract_rows(IC(D), W1, ncol, [&](int ch) { return ld4(xr + ((ch ^ sw) << 2)); });
-                    MP_STAMP(1);
-                    const float bv = B1 ? B1[ncol] : 0.f;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) HB[((r & 3) + 8 * (r >> 2) + 4 * lh) * HS + ncol] = tanhf(acc[r] + bv);
-                }
-            }
-            if (t < kRows && has_next) { rid[r3n][t] = idn; rok[r3n][t] = okn; }
-            MP_STAMP(2);
-            lds_barrier();                                               // ---- 1: hidden activations complete
-            // ---- forward 1: mapped = HB W2^T + b2 (kept in registers across the barrier)
-            li = fresh(li0); lh = fresh(lh0);
-            f32x16 am[NJD];
-#pragma unroll
-            for (int jj = 0; jj < NJD; ++jj) {
-                const int job = wave + 4 * jj;
-                am[jj] = zero16();
-                if (job < NI) {
-                    const float* hr = HB + li * HS;
-                    am[jj] = contract_rows(IC(H), W2, job * 32 + li, [&](int ch) { return ld4(hr + 4 * ch); });
-                }
-            }
-            MP_STAMP(3);
-            lds_barrier();                                               // ---- X: target rows landed; the previous dL/dS is consumed
-            li = fresh(li0); lh = fresh(lh0);
-#pragma unroll
-            for (int jj = 0; jj < NJD; ++jj) {
-                const int job = wave + 4 * jj;
-                if (job < NI) {
-                    const int ncol = job * 32 + li;
-                    const float bv = B2 ? B2[ncol] : 0.f;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        const float tv = ST[(row * LR + ((ncol >> 2) ^ (row & (LR - 1)))) * 4 + (ncol & 3)];
-                        const float d = rok[r3][row] != 0.f ? (am[jj][r] + bv) - tv : 0.f;       // nn.MSELoss (emcdr.py:81,162)
-                        lsum += (double)d * (double)d;
-                        GZ[row * GS + ncol] = gscale * d;
-                    }
-                }
-            }
-            MP_STAMP(4);
-            lds_barrier();                                               // ---- F: gz complete
-            // weight-gradient tiles of one layer: dW[m][nn] += sum_rows gz[row][m] in[row][nn]; the 32 operand words of a tile are
-            // requested before its 16 MFMAs, the next tile's before them
-            auto dw_layer = [&](auto QBc, auto NTWc, const float* gzb, int gzs, auto in_word) {
-                constexpr int QB = decltype(QBc)::value, NTW = decltype(NTWc)::value;
-                float av[2][16], bv[2][16];
-                auto fetch = [&](int q, float* a_, float* b_) {
-                    const int loc = wave + 4 * q, mt = loc / NTW, nt = loc - mt * NTW;
-                    const int l_i = fresh(li0), l_h = fresh(lh0);
-                    const float* ga = gzb + (4 * l_h) * gzs + mt * 32 + l_i;
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int rc = 8 * (e >> 2) + (e & 3);
-                        a_[e] = ga[rc * gzs];
-                        b_[e] = in_word(rc, l_h, nt * 32 + l_i);
-                    }
-                };
-                fetch(0, av[0], bv[0]);
-#pragma unroll
-                for (int q = 0; q < SL; ++q) {
-                    if (q + 1 < SL) fetch(q + 1, av[(q + 1) & 1], bv[(q + 1) & 1]);
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) MF1(wacc[QB + q], av[q & 1][e], bv[q & 1][e]);
-                }
-            };
-            // ---- layer 1: dW2 += gz^T HB ; db2 += column sums of gz
-            dw_layer(IC(SL), IC(NHI), GZ, GS, [&](int rc, int l_h, int nn) { return HB[(rc + 4 * l_h) * HS + nn]; });
-            if (B2 && t >= H && t < H + D) {
-                float sum = 0.f;
-                for (int row = 0; row < kRows; ++row) sum += GZ[row * GS + (t - H)];
-                bacc += sum;
-            }
-            MP_STAMP(5);
-            lds_barrier();                                               // ---- 4: HB may be overwritten
-            // ---- dL/d hidden = gz W2, folded with tanh' = 1 - a^2, in place over HB
-            li = fresh(li0); lh = fresh(lh0);
-#pragma unroll
-            for (int jj = 0; jj < NJH; ++jj) {
-                const int job = wave + 4 * jj;
-                if (job < NHI) {
-                    const int ncol = job * 32 + li;
-                    const f32x16 acc = contract_cols(IC(D), IC(H), W2, ncol, GZ + li * GS + 4 * lh);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int o = ((r & 3) + 8 * (r >> 2) + 4 * lh) * HS + ncol;
-                        const float a_ = HB[o];
-                        HB[o] = acc[r] * (1.0f - a_ * a_);
-                    }
-                }
-            }
-            MP_STAMP(6);
-            lds_barrier();                                               // ---- 5: gz0 complete
-            // ---- layer 0: dW1 += gz0^T X ; db1 += column sums of gz0
-            dw_layer(IC(0), IC(NI), HB, HS, [&](int rc, int l_h, int nn) {
-                return Xs[(rc + 4 * l_h) * D + ((((nn >> 2) ^ (l_h << 2)) ^ (rc & (LR - 1))) << 2) + (nn & 3)];
-            });
-            if (B1 && t < H) {
-                float sum = 0.f;
-                for (int row = 0; row < kRows; ++row) sum += HB[row * HS + t];
-                bacc += sum;
-            }
-            MP_STAMP(7);
-            lds_barrier();                                               // ---- M: the target update has read gz for the last time
-            // ---- dL/dS = gz0 W1 into the shared buffer
-            li = fresh(li0); lh = fresh(lh0);
-#pragma unroll
-            for (int jj = 0; jj < NJD; ++jj) {
-                const int job = wave + 4 * jj;
-                if (job < NI) {
-                    const int ncol = job * 32 + li;
-                    const f32x16 acc = contract_cols(IC(H), IC(D), W1, ncol, HB + li * HS + 4 * lh);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) GX[((r & 3) + 8 * (r >> 2) + 4 * lh) * GS + ncol] = acc[r];
-                }
-            }
-            MP_STAMP(8);
-            lds_barrier();                                               // ---- E
-            MP_STAMP(9);
-        } else {
-            vm_wait<0>();                                                // T, mT, vT of this block and mS, vS of the previous one
-            MP_STAMP(1);
-            if (k > 0) apply(IC(0), IC(NQ / 2), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
-            lds_barrier();                                               // ---- 1
-            if (k > 0) apply(IC(NQ / 2), IC(NQ), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
-            if (has_next) { row_offsets(rid[r3n], roff); stage(S, bSS + (unsigned)((par ^ 1) * kRows * D * 4), roff); }
-            if (adam) { row_offsets(rid[r3], roff); stage(mS, bSMS, roff); stage(vS, bSVS, roff); }
-            MP_STAMP(2);
-            lds_barrier();                                               // ---- X: dL/dS of the previous block is consumed
-            MP_STAMP(3);
-            lds_barrier();                                               // ---- F
-            MP_STAMP(4);
-            apply(IC(0), IC(NQ / 2), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);   // dL/dT[id] = -dL/d mapped
-            lds_barrier();                                               // ---- 4
-            apply(IC(NQ / 2), IC(NQ), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);
-            if (has_next) {
-                row_offsets(rid[r3n], roff);
-                stage(T, bST, roff);
-                if (adam) { stage(mT, bSMT, roff); stage(vT, bSVT, roff); }
-            }
-            lds_barrier();                                               // ---- 5
-            MP_STAMP(5);
-            lds_barrier();                                               // ---- M: gz has been read for the last time
-            if (has_next) { if (adam) vm_wait<5 * NQ>(); else vm_wait<NQ>(); }   // the next block's source rows have landed
-            MP_STAMP(7);
-            lds_barrier();                                               // ---- E
-            MP_STAMP(8);
-        }
-    }
-    if (rowwave) {                                                       // the last block's source rows
-        const int par = (k - 1) & 1, r3 = (k - 1) % 3;
-        vm_wait<0>();
-        apply(IC(0), IC(NQ), S, mS, vS, SS + par * kRows * D, SMS, SVS, GX, 1.f, rid[r3], rok[r3], ss_s, bc_s);
-    } else {
-        float* o = wpart + (size_t)blockIdx.x * ((size_t)net.ntiles * 1024 + net.nbias);
-#pragma unroll
-        for (int q = 0; q < 2 * SL; ++q) {
-            const int tile = (q < SL ? 0 : TL) + wave + 4 * (q < SL ? q : q - SL);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[(size_t)tile * 1024 + r * 64 + lane] = wacc[q][r];
-        }
-        if (t < net.nbias) o[(size_t)net.ntiles * 1024 + t] = bacc;
-        lsum = wave_sum_d(lsum);
-        if (lane == 0) red[wave] = lsum;
-    }
-    __syncthreads();
-    if (t == 0) lpart[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// ---- map_pipe2_kernel with (i) the weight-gradient accumulation in the ROW waves and (ii) every contraction's weight tile resident
-// in registers one contraction ahead (round 3; the comment inside says what the stamps showed) -----------------------------------
+// source rows are updated, which the row waves finish before the next block's forward reaches its epilogue.
+// The weight-gradient accumulation (32 tiles: 128 registers per wave) runs in the ROW waves, and the MFMA waves hold every contraction's
+// weight tile in registers one contraction ahead; the comment inside says why, docs/HISTORY.md describes the form this replaced
+// (round 3: map_pipe2_kernel, weight gradients in the MFMA waves and weights streamed from L2).
 template <int NI, int NHI>
 __global__ __launch_bounds__(512, 1) void map_pipe3_kernel(map_net net, map_opt opt, float* __restrict__ S, float* __restrict__ mS,
                                                          float* __restrict__ vS, float* __restrict__ T, float* __restrict__ mT,
                                                          float* __restrict__ vT, const int64_t* __restrict__ idx, int64_t n,
                                                          const int64_t* __restrict__ step_s, const int64_t* __restrict__ step_t,
                                                          float* __restrict__ wpart, double* __restrict__ lpart, map_params bump) {
-    constexpr int D = 32 * NI;                 // Ds == Dt
+    using LDS = pipe_lds<NI, NHI>;
+    using RW = row_wave<NI>;
+    constexpr int D = RW::D, LR = RW::LR, GS = RW::GS, NQ = RW::NQ;
     constexpr int H = 32 * NHI;                // hidden width
-    constexpr int HS = H + 4;
-    constexpr int LR = D / 4;                  // 16-byte chunks (= DMA lanes) per row
-    constexpr int RPI = 64 / LR;               // rows per DMA instruction (1 KiB of LDS)
-    constexpr int GS = D + 4;                  // padded row stride of the two MFMA-written buffers
+    constexpr int HS = LDS::HS;
     constexpr int TL = NI * NHI;               // weight-gradient tiles per layer (layer 0: [H][D], layer 1: [D][H])
-    constexpr int SL = TL / 4;                 // ... per MFMA wave and layer (TL is a multiple of 4)
-    constexpr int NJD = (NI + 3) / 4, NJH = (NHI + 3) / 4;      // 32-column jobs per MFMA wave over D / over H
-    constexpr int NQ = NI;                     // DMA instructions per row wave and array (4 row waves)
+    constexpr int SL = TL / 4;                 // ... per row wave and layer (TL is a multiple of 4)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ float rok[3][kRows];
     __shared__ int64_t rid[3][kRows];
     __shared__ double red[4];
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li0 = lane & 31, lh0 = lane >> 5;
     const bool rowwave = wave >= 4;
-    float* GZ = smem;                          // [32][GS]  mapped -> gz = dL/d mapped, later dL/dS (shared: see above)
-    float* GX = GZ;
-    float* HB = GZ + kRows * GS;               // [32][HS]  hidden activations -> dL/d(hidden pre-activation)
-    float* SS = HB + kRows * HS;               // [2][32][D] source rows (swizzled)
-    float* ST = SS + 2 * kRows * D;            // [32][D] each, swizzled alike
-    float* SMT = ST + kRows * D;
-    float* SVT = SMT + kRows * D;
-    float* SMS = SVT + kRows * D;
-    float* SVS = SMS + kRows * D;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool adam = opt.opt != 0;
+    float* GZ = smem + LDS::GZ;                // later dL/dS (shared: see above)
+    float* GX = smem + LDS::GX;
+    float* HB = smem + LDS::HB;
+    float* SS = smem + LDS::SS;
+    float* ST = smem + LDS::ST;
+    float* SMT = smem + LDS::SMT;
+    float* SVT = smem + LDS::SVT;
+    float* SMS = smem + LDS::SMS;
+    float* SVS = smem + LDS::SVS;
     float ss_s, bc_s, ss_t, bc_t;
     adam_hp(opt, step_s, 1, ss_s, bc_s);
     adam_hp(opt, step_t, 1, ss_t, bc_t);
@@ -1137,104 +772,15 @@ __global__ __launch_bounds__(512, 1) void map_pipe3_kernel(map_net net, map_opt 
     const int64_t nrb = (n + kRows - 1) / kRows;
     float bacc = 0.f;                          // MFMA-wave thread t owns flat bias element t (b1 then b2)
     double lsum = 0.0;
-
-    // (address arithmetic below is re-derived per phase from a laundered lane id: left alone, LICM hoists ~200 loop-invariant LDS /
-    //  global offsets out of the block loop and spills them -- and a spill reload inside a row wave is a vector memory load whose
-    //  wait drains the DMA queue)
-    auto fresh = [](int v) { asm volatile("" : "+v"(v)); return v; };
-    // ---- row waves: lane <-> (row, physical chunk) of DMA instruction i = pw + 4 q, q < NQ
     const int pw = wave - 4;
-    // byte offsets of this lane's NQ chunks inside a table, for the rows of one block: all ids are read from LDS first (one wait),
-    // and the result serves every table staged for that block
-    auto row_offsets = [&](const int64_t* ids, int64_t (&off)[NQ]) {
-        const int ln = fresh(lane);
-        int64_t idv[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) idv[q] = ids[(pw + 4 * q) * RPI + ln / LR];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int row = (pw + 4 * q) * RPI + ln / LR, p = ln % LR;
-            off[q] = (idv[q] * D + 4 * (p ^ (row & (LR - 1)))) * (int64_t)sizeof(float);
-        }
-    };
-    // NQ DMA instructions of one table in ONE asm statement: M0 saved once, set per instruction, restored once
-    auto stage = [&](const float* __restrict__ tab, unsigned dst_bytes, const int64_t (&off)[NQ]) {
-        const char* base = reinterpret_cast<const char*>(tab);
-        const unsigned d0 = __builtin_amdgcn_readfirstlane(dst_bytes + (unsigned)pw * 1024u);   // instruction i = pw + 4 q writes 1 KiB at i * 1 KiB
-        unsigned keep;
-        if constexpr (NQ == 4)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" MAP_NT "\n\t"
-                         "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off" MAP_NT "\n\t"
-                         "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off" MAP_NT "\n\t"
-                         "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, off" MAP_NT "\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(base + off[0]), "v"(base + off[1]), "v"(base + off[2]), "v"(base + off[3]),
-                           "s"(d0), "s"(d0 + 4096u), "s"(d0 + 8192u), "s"(d0 + 12288u)
-                         : "memory");
-        else
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" MAP_NT "\n\t"
-                         "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off" MAP_NT "\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(base + off[0]), "v"(base + off[1]), "s"(d0), "s"(d0 + 4096u) : "memory");
-    };
-    auto lds_off = [](const float* p) {
-        return (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p);
-    };
-    const unsigned bSS = lds_off(SS), bST = lds_off(ST), bSMT = lds_off(SMT), bSVT = lds_off(SVT), bSMS = lds_off(SMS), bSVS = lds_off(SVS);
+    const RW rw(SS, lane, pw, opt);
     int64_t roff[NQ];
-    // Adam / SGD on this lane's chunks of DMA instructions [Q0, Q1): g = sign * G[row][logical chunk].  Every operand of the
-    // whole range is requested before the arithmetic starts (one wave per role and SIMD: nothing else hides the LDS latency)
-    auto apply = [&](auto Q0c, auto Q1c, float* __restrict__ tab, float* __restrict__ mtab, float* __restrict__ vtab, const float* stW,
-                     const float* stM, const float* stV, const float* G, float sign, const int64_t* ids, const float* ok,
-                     float ssz, float bcs) {
-        constexpr int Q0 = decltype(Q0c)::value, Q1 = decltype(Q1c)::value, NQQ = Q1 - Q0 > 0 ? Q1 - Q0 : 1;
-        if (Q1 <= Q0) return;
-        const int ln = fresh(lane);
-        const float rbc = bcs;                       // cdr_adam_hp's bc2 as it is
-        const int r0 = ln / LR, p = ln % LR;
-        float4 w[NQQ], g[NQQ], m[NQQ], v[NQQ];
-        int64_t o[NQQ];
-        float okf[NQQ];
-#pragma unroll
-        for (int q = 0; q < Q1 - Q0; ++q) {
-            const int row = (pw + 4 * (Q0 + q)) * RPI + r0, c = p ^ (row & (LR - 1)), so = (row * LR + p) * 4;
-            w[q] = ld4(stW + so); g[q] = ld4(G + row * GS + 4 * c);
-            m[q] = z4; v[q] = z4;
-            if (adam) { m[q] = ld4(stM + so); v[q] = ld4(stV + so); }
-            o[q] = ids[row] * D + 4 * c;
-            okf[q] = ok[row];
-        }
-#pragma unroll
-        for (int q = 0; q < Q1 - Q0; ++q) {
-            float4 wn;
-            wn.x = updq(w[q].x, sign * g[q].x, m[q].x, v[q].x, opt, ssz, rbc); wn.y = updq(w[q].y, sign * g[q].y, m[q].y, v[q].y, opt, ssz, rbc);
-            wn.z = updq(w[q].z, sign * g[q].z, m[q].z, v[q].z, opt, ssz, rbc); wn.w = updq(w[q].w, sign * g[q].w, m[q].w, v[q].w, opt, ssz, rbc);
-            if (okf[q] != 0.f) {
-                MAP_ST4(tab + o[q], wn);
-                if (adam) { MAP_ST4(mtab + o[q], m[q]); MAP_ST4(vtab + o[q], v[q]); }
-            }
-        }
-    };
-    using std::integral_constant;
-#define IC(v) integral_constant<int, (v)>{}
-    if (t < kRows) {                                                     // ids of this workgroup's first block
-        const int64_t g = (int64_t)blockIdx.x * kRows + t;
-        rid[0][t] = idx[g < n ? g : n - 1];
-        rok[0][t] = g < n ? 1.f : 0.f;
-    }
-    __syncthreads();
-    if (rowwave) {
-        __builtin_amdgcn_s_setprio(3);
-        row_offsets(rid[0], roff);
-        stage(S, bSS, roff);
-        stage(T, bST, roff);
-        if (adam) { stage(mT, bSMT, roff); stage(vT, bSVT, roff); }
-        vm_wait<0>();
-    }
+    rw.first_block(rid[0], rok[0], idx, n, S, T, mT, vT);
     lds_barrier();
-    // ---- MFMA waves: weight tiles of their 32-column job, one contraction AHEAD.  In map_pipe2_kernel the weights stream from L2
-    // one K group (0.45 us of MFMAs) ahead of their use, behind the row waves' DMA traffic in the CU's vector-memory path: stamps of
-    // one block show the four 64-MFMA contractions at 4.5 / 6.2 / 6.5 / 12 us where the matrix pipe needs 1.8-2 us each.  With the
-    // weight-gradient accumulators (128 registers) moved to the row waves, two 64-register tile buffers fit: the tile of the NEXT
+    // ---- MFMA waves: weight tiles of their 32-column job, one contraction AHEAD.  Streamed from L2 one K group (0.45 us of MFMAs)
+    // ahead of their use, the weights arrive behind the row waves' DMA traffic in the CU's vector-memory path: stamps of one block of
+    // that form showed the four 64-MFMA contractions at 4.5 / 6.2 / 6.5 / 12 us where the matrix pipe needs 1.8-2 us each.  With the
+    // weight-gradient accumulators (128 registers) in the row waves, two 64-register tile buffers fit here: the tile of the NEXT
     // contraction is requested before the current one starts and has a whole phase (and a barrier) to arrive.
     const int job = wave;                                                 // one 32-column tile per MFMA wave and contraction
     auto load_rows = [&](auto Kc, const float* __restrict__ Wg, int ncol, float4 (&T)[16]) {      // T[i] = Wg[ncol][8 i + 4 lh ..]
@@ -1421,25 +967,25 @@ __global__ __launch_bounds__(512, 1) void map_pipe3_kernel(map_net net, map_opt 
             MP_STAMP(0);
             vm_wait<0>();                                                // T, mT, vT of this block and mS, vS of the previous one
             MP_STAMP(1);
-            if (k > 0) apply(IC(0), IC(NQ / 2), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
+            if (k > 0) rw.apply(IC(0), IC(NQ / 2), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
             lds_barrier();                                               // ---- 1
-            if (k > 0) apply(IC(NQ / 2), IC(NQ), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
-            if (has_next) { row_offsets(rid[r3n], roff); stage(S, bSS + (unsigned)((par ^ 1) * kRows * D * 4), roff); }
-            if (adam) { row_offsets(rid[r3], roff); stage(mS, bSMS, roff); stage(vS, bSVS, roff); }
+            if (k > 0) rw.apply(IC(NQ / 2), IC(NQ), S, mS, vS, SS + (par ^ 1) * kRows * D, SMS, SVS, GX, 1.f, rid[r3p], rok[r3p], ss_s, bc_s);
+            if (has_next) { rw.row_offsets(rid[r3n], roff); rw.stage(S, rw.bSS + (unsigned)((par ^ 1) * kRows * D * 4), roff); }
+            if (rw.adam) { rw.row_offsets(rid[r3], roff); rw.stage(mS, rw.bSMS, roff); rw.stage(vS, rw.bSVS, roff); }
             MP_STAMP(2);
             lds_barrier();                                               // ---- X: dL/dS of the previous block is consumed
             MP_STAMP(3);
             lds_barrier();                                               // ---- F
             MP_STAMP(4);
-            apply(IC(0), IC(NQ / 2), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);   // dL/dT[id] = -dL/d mapped
+            rw.apply(IC(0), IC(NQ / 2), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);   // dL/dT[id] = -dL/d mapped
             // ---- layer 1: dW2 += gz^T HB (HB is overwritten after barrier 4)
             dw_layer(wacc, IC(SL), IC(NHI), GZ, GS, [&](int rc, int l_h, int nn) { return HB[(rc + 4 * l_h) * HS + nn]; });
             lds_barrier();                                               // ---- 4
-            apply(IC(NQ / 2), IC(NQ), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);
+            rw.apply(IC(NQ / 2), IC(NQ), T, mT, vT, ST, SMT, SVT, GZ, -1.f, rid[r3], rok[r3], ss_t, bc_t);
             if (has_next) {
-                row_offsets(rid[r3n], roff);
-                stage(T, bST, roff);
-                if (adam) { stage(mT, bSMT, roff); stage(vT, bSVT, roff); }
+                rw.row_offsets(rid[r3n], roff);
+                rw.stage(T, rw.bST, roff);
+                if (rw.adam) { rw.stage(mT, rw.bSMT, roff); rw.stage(vT, rw.bSVT, roff); }
             }
             lds_barrier();                                               // ---- 5
             MP_STAMP(5);
@@ -1448,7 +994,7 @@ __global__ __launch_bounds__(512, 1) void map_pipe3_kernel(map_net net, map_opt 
                 return Xs[(rc + 4 * l_h) * D + ((((nn >> 2) ^ (l_h << 2)) ^ (rc & (LR - 1))) << 2) + (nn & 3)];
             });
             lds_barrier();                                               // ---- M: gz has been read for the last time
-            if (has_next) { if (adam) vm_wait<5 * NQ>(); else vm_wait<NQ>(); }   // the next block's source rows have landed
+            if (has_next) { if (rw.adam) vm_wait<5 * NQ>(); else vm_wait<NQ>(); }   // the next block's source rows have landed
             MP_STAMP(7);
             lds_barrier();                                               // ---- E
             MP_STAMP(8);
@@ -1456,7 +1002,7 @@ __global__ __launch_bounds__(512, 1) void map_pipe3_kernel(map_net net, map_opt 
         {                                                                // the last block's source rows, then this wave's weight-gradient tiles
             const int par = (k - 1) & 1, r3 = (k - 1) % 3;
             vm_wait<0>();
-            apply(IC(0), IC(NQ), S, mS, vS, SS + par * kRows * D, SMS, SVS, GX, 1.f, rid[r3], rok[r3], ss_s, bc_s);
+            rw.apply(IC(0), IC(NQ), S, mS, vS, SS + par * kRows * D, SMS, SVS, GX, 1.f, rid[r3], rok[r3], ss_s, bc_s);
 #pragma unroll
             for (int q = 0; q < 2 * SL; ++q) {
                 const int tile = (q < SL ? 0 : TL) + pw + 4 * (q < SL ? q : q - SL);
@@ -1620,56 +1166,39 @@ extern "C" int cdr_map_step_unique(cdr_ctx* ctx, void* stream, int opt, float* s
     const bool pipe = L == 1 && !net.b[0] && net.vec && dims[1] == Dp && (Dp == 64 || Dp == 128);
     // ... and its two-layer form for the default tanh MLP: D -> H -> D, D and H in {64, 128}, biases on both layers or on neither
     const int Hp = L == 2 ? dims[1] : 0;
-    const bool pipe2 = L == 2 && net.vec && net.act[0] == CDR_ACT_TANH && dims[2] == Dp && (Dp == 64 || Dp == 128) &&
-                       (Hp == 64 || Hp == 128) && ((net.b[0] != nullptr) == (net.b[1] != nullptr));
-    const int nwg = (pipe || pipe2) ? wg_count(n, 1) : wg_count(n, 2);        // (three resident workgroups per CU measured no faster)
+    const bool mlp = L == 2 && net.vec && net.act[0] == CDR_ACT_TANH && dims[2] == Dp && (Dp == 64 || Dp == 128) &&
+                     (Hp == 64 || Hp == 128) && ((net.b[0] != nullptr) == (net.b[1] != nullptr));
+    const int nwg = (pipe || mlp) ? wg_count(n, 1) : wg_count(n, 2);          // (three resident workgroups per CU measured no faster)
     const size_t wbytes = (size_t)nwg * ((size_t)net.ntiles * 1024 + net.nbias) * sizeof(float);
     const size_t woff = (wbytes + 255) & ~(size_t)255;
     CDR_CHECK_ARG(workspace_bytes >= woff + (size_t)nwg * sizeof(double));
     float* wpart = (float*)workspace;
     double* lpart = (double*)((char*)workspace + woff);
-    const bool few = net.ntiles <= 16;
-    const void* fn = few ? (const void*)map_step_kernel<4> : (const void*)map_step_kernel<8>;
+    // the kernel, chosen once: the pipe kernels share a signature, map_step_kernel takes two LDS offsets more
+    using pipe_fn = void (*)(map_net, map_opt, float*, float*, float*, float*, float*, float*, const int64_t*, int64_t, const int64_t*,
+                             const int64_t*, float*, double*, map_params);
+    using step_fn = void (*)(map_net, map_opt, float*, float*, float*, float*, float*, float*, const int64_t*, int64_t, const int64_t*,
+                             const int64_t*, int, int, float*, double*, map_params);
+    pipe_fn pf = nullptr;
+    const step_fn sf = net.ntiles <= 16 ? map_step_kernel<4> : map_step_kernel<8>;
     if (pipe) {
-        lds = ((size_t)2 * kRows * (Dp + 4) + 7 * (size_t)kRows * Dp) * sizeof(float);
-        fn = Dp == 128 ? (const void*)map_pipe_kernel<4> : (const void*)map_pipe_kernel<2>;
-    }
-    if (pipe2) {
-        lds = ((size_t)kRows * (Dp + 4) + (size_t)kRows * (Hp + 4) + 7 * (size_t)kRows * Dp) * sizeof(float);
-        fn = Dp == 128 ? (Hp == 128 ? (const void*)map_pipe2_kernel<4, 4> : (const void*)map_pipe2_kernel<4, 2>)
-                       : (Hp == 128 ? (const void*)map_pipe2_kernel<2, 4> : (const void*)map_pipe2_kernel<2, 2>);
-        const void* fn3 = Dp == 128 ? (Hp == 128 ? (const void*)map_pipe3_kernel<4, 4> : (const void*)map_pipe3_kernel<4, 2>)
-                                    : (Hp == 128 ? (const void*)map_pipe3_kernel<2, 4> : (const void*)map_pipe3_kernel<2, 2>);
-        if (lds > 64 * 1024) {
-            hipError_t e3 = hipFuncSetAttribute(fn3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e3 != hipSuccess) { cdr_set_error("cdr_map_step_unique: %zu B of LDS refused: %s", lds, hipGetErrorString(e3)); return (int)e3; }
-        }
+        if (Dp == 128) { pf = map_pipe_kernel<4>; lds = pipe_lds<4>::bytes; } else { pf = map_pipe_kernel<2>; lds = pipe_lds<2>::bytes; }
+    } else if (mlp) {
+        if (Dp == 128 && Hp == 128) { pf = map_pipe3_kernel<4, 4>; lds = pipe_lds<4, 4>::bytes; }
+        else if (Dp == 128) { pf = map_pipe3_kernel<4, 2>; lds = pipe_lds<4, 2>::bytes; }
+        else if (Hp == 128) { pf = map_pipe3_kernel<2, 4>; lds = pipe_lds<2, 4>::bytes; }
+        else { pf = map_pipe3_kernel<2, 2>; lds = pipe_lds<2, 2>::bytes; }
     }
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(pf ? (const void*)pf : (const void*)sf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) { cdr_set_error("cdr_map_step_unique: %zu B of LDS refused: %s", lds, hipGetErrorString(e)); return (int)e; }
     }
     const map_opt mo{lr, beta1, beta2, eps, weight_decay, opt};
     hipStream_t s = (hipStream_t)stream;
     {
         cdr_time_scope ts(ctx, CDR_TAG_MAP_STEP, s);
-#define MS_ARGS net, mo, src_tab, src_m, src_v, tgt_tab, tgt_m, tgt_v, idx, n, step_src_dev, step_tgt_dev, gx, to, wpart, lpart, P
-#define MP_ARGS net, mo, src_tab, src_m, src_v, tgt_tab, tgt_m, tgt_v, idx, n, step_src_dev, step_tgt_dev, wpart, lpart, P
-        static const bool old_pipe2 = [] { const char* e = getenv("CDR_MAP_PIPE2"); return e && e[0] == '1'; }();     // A/B switch (tools/)
-        if (pipe2 && !old_pipe2 && Dp == 128 && Hp == 128) map_pipe3_kernel<4, 4><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (pipe2 && !old_pipe2 && Dp == 128) map_pipe3_kernel<4, 2><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (pipe2 && !old_pipe2 && Hp == 128) map_pipe3_kernel<2, 4><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (pipe2 && !old_pipe2) map_pipe3_kernel<2, 2><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (pipe2 && Dp == 128 && Hp == 128) map_pipe2_kernel<4, 4><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (pipe2 && Dp == 128) map_pipe2_kernel<4, 2><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (pipe2 && Hp == 128) map_pipe2_kernel<2, 4><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (pipe2) map_pipe2_kernel<2, 2><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (pipe && Dp == 128) map_pipe_kernel<4><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (pipe) map_pipe_kernel<2><<<dim3(nwg), dim3(512), lds, s>>>(MP_ARGS);
-        else if (few) map_step_kernel<4><<<dim3(nwg), dim3(256), lds, s>>>(MS_ARGS);
-        else map_step_kernel<8><<<dim3(nwg), dim3(256), lds, s>>>(MS_ARGS);
-#undef MP_ARGS
-#undef MS_ARGS
+        if (pf) pf<<<dim3(nwg), dim3(512), lds, s>>>(net, mo, src_tab, src_m, src_v, tgt_tab, tgt_m, tgt_v, idx, n, step_src_dev, step_tgt_dev, wpart, lpart, P);
+        else sf<<<dim3(nwg), dim3(256), lds, s>>>(net, mo, src_tab, src_m, src_v, tgt_tab, tgt_m, tgt_v, idx, n, step_src_dev, step_tgt_dev, gx, to, wpart, lpart, P);
     }
     CDR_LAUNCH_CHECK();
     int64_t elems = 0;

@@ -26,9 +26,6 @@ The losses are held to LOSS_RTOL relative of the fp64 value.  Every row outside 
 touched id in particular -- stays bit-identical in both tables, weights and moments alike; the device counters advance by exactly
 one and the host mirrors agree.  Each case prints its worst error / bound per quantity."""
 import gc
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -61,7 +58,7 @@ def _cdiv(a, b):
 
 def _unique_depth(n, per_cu, bias):
     """Reduction depth of a mapping gradient on the distinct-id path (csrc/cdr_mapstep.hip).  wg_count(n, per_cu) workgroups
-    (per_cu = 1 for map_pipe_kernel / map_pipe2_kernel / map_pipe3_kernel, 2 for map_step_kernel) walk the 32-id blocks
+    (per_cu = 1 for map_pipe_kernel / map_pipe3_kernel, 2 for map_step_kernel) walk the 32-id blocks
     rb = blockIdx.x, + gridDim.x, ...  A weight element is one MFMA accumulator chain across all of a workgroup's blocks (16
     v_mfma_f32_32x32x2f32 per block: 32 ids, `MF1(wacc[q], ...)`), +1 for the product; a bias element is a 32-row sequential sum per
     block added into `bacc` once per block.  map_finish_kernel then adds workgroups sub, sub + 16, ... in sixteen strided sums
@@ -376,7 +373,7 @@ def _build(dims, bias, n, rows, optname, seed, misalign=False):
 
 def _per_cu(dims, bias, misalign):
     """cdr_map_step_unique's workgroups per CU: 1 for the two-wave-group kernels (`pipe`: linear without bias, Ds == Dt in {64, 128};
-    `pipe2`: tanh D-H-D, D and H in {64, 128}, biases on both layers or on neither; 16-byte aligned weights), else 2."""
+    `mlp`: tanh D-H-D, D and H in {64, 128}, biases on both layers or on neither; 16-byte aligned weights), else 2."""
     if misalign or dims[0] != dims[-1] or dims[0] not in (64, 128):
         return 2
     if len(dims) == 2:
@@ -516,26 +513,6 @@ def test_emcdr_fused_overlap_step_vs_fp64():
     batches = [1 + _distinct_ids(n, ids.OU - 1, gen) for _ in range(3)]                    # ids 1 and OU - 1 in every batch
     _run(fm, batches, ('adam', lr, (0.9, 0.999), 1e-8, wd), f'EMCDR.fused_train_step OVERLAP non_linear D={D} n={n} wd={wd}', True,
          lambda m, is_b: _unique_depth(m, 1, is_b), run=lambda idx: model.fused_train_step({'overlap': idx}, **kw))
-
-
-# ---------------------------------------------------------------------------------------------------------------------- CDR_MAP_PIPE2=1
-
-def _pipe2_child():
-    """Run in a fresh process with CDR_MAP_PIPE2=1 (read once per process): map_pipe2_kernel in place of map_pipe3_kernel."""
-    _unique_case((128, 128, 128), True, 65536, 'adam_hp')
-    _unique_case((64, 128, 64), True, 8193, 'adam')
-
-
-def test_map_pipe2_kernel_vs_fp64():
-    """map_pipe2_kernel (reachable through CDR_MAP_PIPE2=1 only) held to the same bounds: tanh 128-128-128 and 64-128-64, in a
-    child process under a time limit."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = (f'import sys; sys.path[:0] = [{here!r}, {os.path.dirname(here)!r}]\n'
-            'import test_gpu_map_step_fp64 as m\nm._pipe2_child()\n')
-    cmd = [sys.executable] + (['-s'] if sys.flags.no_user_site else []) + ['-c', code]
-    r = subprocess.run(cmd, env=dict(os.environ, CDR_MAP_PIPE2='1'), capture_output=True, text=True, timeout=300)
-    print(r.stdout.replace('\nunique', '\nCDR_MAP_PIPE2=1 unique'))
-    assert r.returncode == 0, f'child exited with {r.returncode}:\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}'
 
 
 @pytest.fixture(scope='module', autouse=True)
