@@ -266,5 +266,3 @@ static inline int grid_for(int64_t units, int per_block) {
     if (g < 1) g = 1;
     return (int)g;
 }
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }

@@ -11,7 +11,7 @@
 //
 //   cdr_bpr_partial_diff     diff[t] = <u,p> - <u,n> over this rank's columns; diff[B], diff[B+1] = its share of
 //                            sum |u|^2, sum |p|^2 (the EmbLoss norms, emb_loss of recbole: App. A) -> all-reduce(sum)
-//   cdr_bpr_grad_from_diff   s = sigmoid(x), g = -(1/B) s (1-s) / (gamma + s)   (identical on every rank), the compact
+//   cdr_bpr_grad_from_diff   g = bpr_term's derivative at x (cdr_loss_math.h; identical on every rank), the compact
 //                            gradient rows GU[t] = g (p - n), GP[t] = g u on this rank's columns, the loss, and the
 //                            EmbLoss coefficients from the all-reduced norms; cdr_sort_ids_two_tables +
 //                            cdr_rowwise_apply then run unchanged on [rows, Ds] tables.
@@ -19,6 +19,7 @@
 // All sizes are static (no bucket counts, no host sync); the rows are re-gathered after the all-reduce (2 x 3 Ds floats
 // per triple instead of 3), which is the price for not keeping 3 B Ds floats alive across the collective.
 #include "cdr_common.h"
+#include "cdr_loss_math.h"
 
 namespace {
 
@@ -71,10 +72,7 @@ __global__ __launch_bounds__(kBlock) void bpr_partial_diff_kernel(const float* _
         }
     }
     block_sum_d<2>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 __global__ __launch_bounds__(kBlock) void partial_norms_kernel(const double* __restrict__ partials, int nblocks,
@@ -127,19 +125,18 @@ __global__ __launch_bounds__(kBlock) void bpr_grad_from_diff_kernel(const float*
         for (int r = 0; r < kUnroll; ++r) {
             const int64_t t = base + (int64_t)r * TG;
             if (t < B) {
-                const float s = sigmoidf_(x[r]);
-                const float g = -invB * (s * (1.0f - s)) / (gamma + s);
+                float l, g;
+                bpr_term(x[r], gamma, invB, l, g);
                 if (live) {
-                    st4(GU + t * D + 4 * sub, make_float4(g * (p[r].x - n[r].x), g * (p[r].y - n[r].y),
-                                                          g * (p[r].z - n[r].z), g * (p[r].w - n[r].w)));
-                    st4(GP + t * D + 4 * sub, make_float4(g * u[r].x, g * u[r].y, g * u[r].z, g * u[r].w));
+                    st4(GU + t * D + 4 * sub, scale_diff4(g, p[r], n[r]));
+                    st4(GP + t * D + 4 * sub, scale4(g, u[r]));
                 }
-                if (sub == 0) acc[0] += (double)(-logf(gamma + s));
+                if (sub == 0) acc[0] += (double)l;
             }
         }
     }
     block_sum_d<1>(acc, smem);
-    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * CDR_PARTIAL_STRIDE] = acc[0];
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // out9 as cdr_bpr_fwd_grad's: {total, main, ||U_b||, ||I_b||, c_u, c_i, sum loss, sum u^2, sum p^2}; the two norms come
@@ -156,8 +153,8 @@ __global__ __launch_bounds__(kBlock) void dimshard_finish_kernel(const double* _
         const float nu = sqrtf(norms2[0]), ni = sqrtf(norms2[1]);
         out9[1] = main_loss; out9[2] = nu; out9[3] = ni;
         out9[0] = main_loss + reg_weight * ((nu + ni) / (float)B);
-        out9[4] = (reg_weight != 0.f && nu > 0.f) ? reg_weight / ((float)B * nu) : 0.f;
-        out9[5] = (reg_weight != 0.f && ni > 0.f) ? reg_weight / ((float)B * ni) : 0.f;
+        out9[4] = embloss_coef(reg_weight, B, nu);
+        out9[5] = embloss_coef(reg_weight, B, ni);
         out9[6] = (float)acc[0]; out9[7] = norms2[0]; out9[8] = norms2[1];
     }
 }
@@ -208,10 +205,7 @@ __global__ __launch_bounds__(kBlock) void point_partial_dot_kernel(const float* 
         }
     }
     block_sum_d<2>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 template <int LPR>
@@ -252,25 +246,17 @@ __global__ __launch_bounds__(kBlock) void point_grad_from_dot_kernel(int loss_ki
             if (t < B) {
                 const float y = yl[r];
                 float l, g;
-                if (loss_kind == CDR_LOSS_MSE) {
-                    const float d = x[r] - y;
-                    l = d * d; g = 2.0f * d * invB;
-                } else {                                       // torch BCELoss on sigmoid(dot): -100 log clamp, 1e-12 backward clamp
-                    const float p = sigmoidf_(x[r]);
-                    l = (y - 1.0f) * fmaxf(logf(1.0f - p), -100.0f) - y * fmaxf(logf(p), -100.0f);
-                    const float pq = (1.0f - p) * p;
-                    g = (p - y) / fmaxf(pq, 1e-12f) * invB * pq;
-                }
+                point_term(loss_kind, x[r], y, invB, l, g);
                 if (live) {
-                    st4(GU + t * D + 4 * sub, make_float4(g * v[r].x, g * v[r].y, g * v[r].z, g * v[r].w));
-                    st4(GI + t * D + 4 * sub, make_float4(g * u[r].x, g * u[r].y, g * u[r].z, g * u[r].w));
+                    st4(GU + t * D + 4 * sub, scale4(g, v[r]));
+                    st4(GI + t * D + 4 * sub, scale4(g, u[r]));
                 }
                 if (sub == 0) acc[0] += (double)l;
             }
         }
     }
     block_sum_d<1>(acc, smem);
-    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * CDR_PARTIAL_STRIDE] = acc[0];
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // ids travel as int32 (table rows < 2^31 everywhere in this library: the sort keys are 32-bit): 12 B per triple on the links.

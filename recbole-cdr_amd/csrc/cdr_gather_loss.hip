@@ -7,6 +7,7 @@
 // Dots are reduced inside the group with xor-shuffles; per-interaction losses and the two EmbLoss square sums are
 // accumulated in fp64 per lane, reduced per block, and finished by one block in a fixed order (no float atomics).
 #include "cdr_common.h"
+#include "cdr_loss_math.h"
 
 namespace {
 
@@ -84,10 +85,10 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_kernel(const float* __restrict
                 float sp = group_sum<LPR>(dot4(p[r], p[r]));
                 if (t < B && sub == 0) {
                     const float s = sigmoidf_(dp - dn);
-                    acc[0] += (double)(-logf(gamma + s));
+                    acc[0] += (double)bpr_loss(s, gamma);
                     acc[1] += (double)su;
                     acc[2] += (double)sp;
-                    if (gcoef) gcoef[t] = -invB * (s * (1.0f - s)) / (gamma + s);
+                    if (gcoef) gcoef[t] = bpr_grad(s, gamma, invB);
                 }
             }
         } else {
@@ -105,19 +106,16 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_kernel(const float* __restrict
                 dp = group_sum<LPR>(dp); dn = group_sum<LPR>(dn); su = group_sum<LPR>(su); sp = group_sum<LPR>(sp);
                 if (sub == 0) {
                     const float s = sigmoidf_(dp - dn);
-                    acc[0] += (double)(-logf(gamma + s));
+                    acc[0] += (double)bpr_loss(s, gamma);
                     acc[1] += (double)su;
                     acc[2] += (double)sp;
-                    if (gcoef) gcoef[t] = -invB * (s * (1.0f - s)) / (gamma + s);
+                    if (gcoef) gcoef[t] = bpr_grad(s, gamma, invB);
                 }
             }
         }
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        cdr_store_sys(o, acc[0]); cdr_store_sys(o + 1, acc[1]); cdr_store_sys(o + 2, acc[2]);
-    }
+    if (threadIdx.x == 0) store_partials_sys(partials, acc);
     // small grids: the block that signs in last is the finishing pass (no second launch)
     if (ticket && cdr_sign_in_last_wide(ticket, gridDim.x)) loss_finish_body<true>(partials, gridDim.x, B, reg_weight, out4);
 }
@@ -141,12 +139,12 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_scalar_kernel(const float* __r
         dp = group_sum<64>(dp); dn = group_sum<64>(dn); su = group_sum<64>(su); sp = group_sum<64>(sp);
         if (lane == 0) {
             const float s = sigmoidf_(dp - dn);
-            acc[0] += (double)(-logf(gamma + s)); acc[1] += (double)su; acc[2] += (double)sp;
-            if (gcoef) gcoef[t] = -invB * (s * (1.0f - s)) / (gamma + s);
+            acc[0] += (double)bpr_loss(s, gamma); acc[1] += (double)su; acc[2] += (double)sp;
+            if (gcoef) gcoef[t] = bpr_grad(s, gamma, invB);
         }
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0) {                                   // store_partials (cdr_loss_math.h), in place: the helper changed this kernel's code
         double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
         o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
     }
@@ -175,6 +173,7 @@ __global__ __launch_bounds__(kBlock) void bpr_bwd_dense_kernel(const float* __re
     const int D4 = D >> 2;
     const float go = grad_out ? grad_out[0] : 1.0f;
     const float nu = out4[2], ni = out4[3];
+    // embloss_coef (cdr_loss_math.h), in place: through the helper the two coefficients' shared tests compile differently
     const float cu = (reg_weight != 0.f && nu > 0.f) ? go * reg_weight / ((float)B * nu) : 0.f;
     const float ci = (reg_weight != 0.f && ni > 0.f) ? go * reg_weight / ((float)B * ni) : 0.f;
     for (int64_t t = gg; t < B; t += TG) {
@@ -205,6 +204,7 @@ __global__ __launch_bounds__(kBlock) void bpr_bwd_dense_scalar_kernel(const floa
     const int64_t TW = (int64_t)gridDim.x * (kBlock / 64);
     const float go = grad_out ? grad_out[0] : 1.0f;
     const float nu = out4[2], ni = out4[3];
+    // embloss_coef (cdr_loss_math.h), in place: through the helper the two coefficients' shared tests compile differently
     const float cu = (reg_weight != 0.f && nu > 0.f) ? go * reg_weight / ((float)B * nu) : 0.f;
     const float ci = (reg_weight != 0.f && ni > 0.f) ? go * reg_weight / ((float)B * ni) : 0.f;
     for (int64_t t = gw; t < B; t += TW) {
@@ -294,17 +294,7 @@ __device__ __forceinline__ void point_fwd_body(int loss_kind, const float* __res
             if (t < B && sub == 0) {
                 const float y = yl[r];
                 float l, g, sc;
-                if (loss_kind == CDR_LOSS_MSE) {
-                    const float d = dx - y;
-                    l = d * d; g = 2.0f * d * invB; sc = dx;
-                } else {
-                    const float p = sigmoidf_(dx);
-                    // torch BCELoss: (y-1)*max(log(1-p),-100) - y*max(log(p),-100); backward (p-y)/max((1-p)p,1e-12)
-                    l = (y - 1.0f) * fmaxf(logf(1.0f - p), -100.0f) - y * fmaxf(logf(p), -100.0f);
-                    const float pq = (1.0f - p) * p;
-                    g = (p - y) / fmaxf(pq, 1e-12f) * invB * pq;
-                    sc = p;
-                }
+                point_term(loss_kind, dx, y, invB, l, g, sc);
                 acc[0] += (double)l; acc[1] += (double)su; acc[2] += (double)si;
                 if (gcoef) gcoef[t] = g;
                 if (scores) scores[t] = sc;
@@ -312,10 +302,7 @@ __device__ __forceinline__ void point_fwd_body(int loss_kind, const float* __res
         }
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        cdr_store_sys(o, acc[0]); cdr_store_sys(o + 1, acc[1]); cdr_store_sys(o + 2, acc[2]);       // (see cdr_sign_in_last)
-    }
+    if (threadIdx.x == 0) store_partials_sys(partials, acc);
 }
 
 template <int LPR, bool SAME>
@@ -415,23 +402,14 @@ __global__ __launch_bounds__(kBlock) void point_fwd_scalar_kernel(int loss_kind,
         if (lane == 0) {
             const float y = label[t];
             float l, g, sc;
-            if (loss_kind == CDR_LOSS_MSE) { const float d = dx - y; l = d * d; g = 2.0f * d * invB; sc = dx; }
-            else {
-                const float p = sigmoidf_(dx);
-                l = (y - 1.0f) * fmaxf(logf(1.0f - p), -100.0f) - y * fmaxf(logf(p), -100.0f);
-                const float pq = (1.0f - p) * p;
-                g = (p - y) / fmaxf(pq, 1e-12f) * invB * pq; sc = p;
-            }
+            point_term(loss_kind, dx, y, invB, l, g, sc);
             acc[0] += (double)l; acc[1] += (double)su; acc[2] += (double)si;
             if (gcoef) gcoef[t] = g;
             if (scores) scores[t] = sc;
         }
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // ------------------------------------------------------------------------------------------------ pointwise dense backward
@@ -449,6 +427,7 @@ __device__ __forceinline__ void point_bwd_dense_body(const float* __restrict__ U
     const int64_t TW = (int64_t)gridDim.x * (kBlock / 64);
     const float go = (grad_out ? grad_out[0] : 1.0f) * gscale;     // gscale: the batch's weight in the caller's total (1 = none)
     const float nu = out4[2], ni = out4[3];
+    // embloss_coef (cdr_loss_math.h), in place: through the helper the two coefficients' shared tests compile differently
     const float cu = (reg_weight != 0.f && nu > 0.f) ? go * reg_weight / ((float)B * nu) : 0.f;
     const float ci = (reg_weight != 0.f && ni > 0.f) ? go * reg_weight / ((float)B * ni) : 0.f;
     for (int64_t t = gw; t < B; t += TW) {

@@ -19,6 +19,7 @@
 // two extra launches) for batches whose worst-case segment a single lane group can walk.
 #include "cdr_common.h"
 #include "cdr_adam_math.h"
+#include "cdr_loss_math.h"
 #include "cdr_ranksort.h"
 
 namespace {
@@ -92,13 +93,13 @@ __device__ __forceinline__ void bpr_fwd_kmajor_body(const float* __restrict__ U,
                     const float dn = group_sum<LPR>(dot4(u[r], n[r][c]));
                     if (m0 + c < k && ok[r]) {
                         const float s = sigmoidf_(dp[r] - dn);
-                        const float g = -invB * (s * (1.0f - s)) / (gamma + s);
+                        const float g = bpr_grad(s, gamma, invB);
                         gu[r].x += g * (p[r].x - n[r][c].x); gu[r].y += g * (p[r].y - n[r][c].y);
                         gu[r].z += g * (p[r].z - n[r][c].z); gu[r].w += g * (p[r].w - n[r][c].w);
                         gs[r] += g;
                         if (sub == 0) {
                             rec[S + jc[r] + (int64_t)(m0 + c) * S] = item_rec{(int32_t)iu[r], -g};
-                            acc[0] += (double)(-logf(gamma + s));
+                            acc[0] += (double)bpr_loss(s, gamma);
                         }
                     }
                 }
@@ -111,8 +112,8 @@ __device__ __forceinline__ void bpr_fwd_kmajor_body(const float* __restrict__ U,
         }
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)bid * CDR_PARTIAL_STRIDE;
+    if (threadIdx.x == 0) {                                   // store_partials (cdr_loss_math.h) with the caller's block number, in place: the
+        double* o = partials + (size_t)bid * CDR_PARTIAL_STRIDE;     // helper moved the scalar register allocation of the LPR = 32 kernels
         o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
     }
 }
@@ -166,8 +167,8 @@ __device__ __forceinline__ void kstep_finish_body(const double* __restrict__ par
         const float nu = (float)sqrt(acc[1]), ni = (float)sqrt(acc[2]);
         out9[1] = main_loss; out9[2] = nu; out9[3] = ni;
         out9[0] = main_loss + reg_weight * ((nu + ni) / (float)B);
-        out9[4] = (reg_weight != 0.f && nu > 0.f) ? (float)k * (reg_weight / ((float)B * nu)) : 0.f;
-        out9[5] = (reg_weight != 0.f && ni > 0.f) ? (float)k * (reg_weight / ((float)B * ni)) : 0.f;
+        out9[4] = embloss_coef(reg_weight, B, nu, (float)k);
+        out9[5] = embloss_coef(reg_weight, B, ni, (float)k);
         out9[6] = (float)acc[0]; out9[7] = (float)acc[1]; out9[8] = (float)acc[2];
         if (bump_a) bump_a[0] += 1;
         if (bump_b) bump_b[0] += 1;

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void ordered_bwd_kernel(ord_args a, int D) 
         if ((int)threadIdx.x < L.nseg) {
             const cdr_ord_seg& S = L.seg[threadIdx.x];
             const float go = my_go * S.go_scale;
-            float c = 0.f;
+            float c = 0.f;                                       // embloss_coef (cdr_loss_math.h) times the incoming gradient, in place: the helper changed this kernel's code
             if (S.R && S.reg_weight != 0.f && my_nrm > 0.f) c = go * S.reg_weight / ((float)S.B * my_nrm);
             seg_go[threadIdx.x] = go; seg_c[threadIdx.x] = c;
         }

@@ -28,6 +28,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 #include "cdr_common.h"
 #include "cdr_adam_math.h"
+#include "cdr_loss_math.h"
 
 namespace {
 
@@ -83,19 +84,18 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_grad_kernel(const float* __res
             const float sp = group_sum<LPR>(dot4(p[r], p[r]));
             if (t < B) {
                 const float s = sigmoidf_(dp - dn);
-                const float g = -invB * (s * (1.0f - s)) / (gamma + s);
+                const float g = bpr_grad(s, gamma, invB);
                 if (live) {
-                    st4n<(LPR >= 32)>(GU + t * D + 4 * sub, make_float4(g * (p[r].x - n[r].x), g * (p[r].y - n[r].y),
-                                                          g * (p[r].z - n[r].z), g * (p[r].w - n[r].w)));
+                    st4n<(LPR >= 32)>(GU + t * D + 4 * sub, scale_diff4(g, p[r], n[r]));
                     if (SCATTER) {
-                        st4n<(LPR >= 32)>(GP + ip[r] * D + 4 * sub, make_float4(g * u[r].x, g * u[r].y, g * u[r].z, g * u[r].w));
-                        st4n<(LPR >= 32)>(GP + in[r] * D + 4 * sub, make_float4(-g * u[r].x, -g * u[r].y, -g * u[r].z, -g * u[r].w));
+                        st4n<(LPR >= 32)>(GP + ip[r] * D + 4 * sub, scale4(g, u[r]));
+                        st4n<(LPR >= 32)>(GP + in[r] * D + 4 * sub, scale4(-g, u[r]));
                     } else {
-                        st4n<(LPR >= 32)>(GP + t * D + 4 * sub, make_float4(g * u[r].x, g * u[r].y, g * u[r].z, g * u[r].w));
+                        st4n<(LPR >= 32)>(GP + t * D + 4 * sub, scale4(g, u[r]));
                     }
                 }
                 if (sub == 0) {
-                    acc[0] += (double)(-logf(gamma + s));
+                    acc[0] += (double)bpr_loss(s, gamma);
                     acc[1] += (double)su;
                     acc[2] += (double)sp;
                 }
@@ -103,10 +103,7 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_grad_kernel(const float* __res
         }
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // Pointwise counterpart (EMCDR's default MF latent factor model: emcdr.py:111-122, MSE on the raw dot; BCE on sigmoid(dot) as in
@@ -152,11 +149,11 @@ __global__ __launch_bounds__(kBlock) void point_fwd_grad_kernel(int loss_kind, c
             const float si = group_sum<LPR>(dot4(v[r], v[r]));
             if (t < B) {
                 const float y = yl[r];
-                float l, g;
+                float l, g;                                    // point_term (cdr_loss_math.h), in place: the helper changed this kernel's code
                 if (loss_kind == CDR_LOSS_MSE) {
                     const float d = dx - y;
                     l = d * d; g = 2.0f * d * invB;
-                } else {                                       // torch BCELoss on sigmoid(dot): -100 log clamp, 1e-12 backward clamp
+                } else {
                     const float p = sigmoidf_(dx);
                     l = (y - 1.0f) * fmaxf(logf(1.0f - p), -100.0f) - y * fmaxf(logf(p), -100.0f);
                     const float pq = (1.0f - p) * p;
@@ -171,10 +168,7 @@ __global__ __launch_bounds__(kBlock) void point_fwd_grad_kernel(int loss_kind, c
         }
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // out9 = {total, main, ||U_b||, ||I_b||, c_u, c_i, sum loss, sum u^2, sum p^2} with c = reg_weight / (B * norm)
@@ -194,8 +188,8 @@ __global__ __launch_bounds__(kBlock) void step_finish_kernel(const double* __res
         const float nu = (float)sqrt(acc[1]), ni = (float)sqrt(acc[2]);
         out6[1] = main_loss; out6[2] = nu; out6[3] = ni;
         out6[0] = main_loss + reg_weight * ((nu + ni) / (float)B);
-        out6[4] = (reg_weight != 0.f && nu > 0.f) ? reg_weight / ((float)B * nu) : 0.f;
-        out6[5] = (reg_weight != 0.f && ni > 0.f) ? reg_weight / ((float)B * ni) : 0.f;
+        out6[4] = embloss_coef(reg_weight, B, nu);
+        out6[5] = embloss_coef(reg_weight, B, ni);
         out6[6] = (float)acc[0]; out6[7] = (float)acc[1]; out6[8] = (float)acc[2];
     }
 }
@@ -206,8 +200,8 @@ __global__ void finish_sums_kernel(const float* __restrict__ sums3, int64_t B, f
         const float nu = sqrtf(sums3[1]), ni = sqrtf(sums3[2]);
         out6[1] = main_loss; out6[2] = nu; out6[3] = ni;
         out6[0] = main_loss + reg_weight * ((nu + ni) / (float)B);
-        out6[4] = (reg_weight != 0.f && nu > 0.f) ? reg_weight / ((float)B * nu) : 0.f;
-        out6[5] = (reg_weight != 0.f && ni > 0.f) ? reg_weight / ((float)B * ni) : 0.f;
+        out6[4] = embloss_coef(reg_weight, B, nu);
+        out6[5] = embloss_coef(reg_weight, B, ni);
     }
 }
 
@@ -554,10 +548,7 @@ __global__ __launch_bounds__(kBlock) void batch_norms_kernel(const float* __rest
         }
     }
     block_sum_d<2>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // keys / perm: the two-table sort's output (section A = positions [0, nA): user keys; section B = [nA, n): item keys + key_base).
@@ -671,6 +662,7 @@ __global__ __launch_bounds__(kBlock) void coef_finish_kernel(const double* __res
     if (threadIdx.x == 0) {
         if (norms2) { acc[0] = (double)norms2[0]; acc[1] = (double)norms2[1]; }
         const float nu = (float)sqrt((double)kmul * acc[0]), ni = (float)sqrt((double)kmul * acc[1]);
+        // embloss_coef (cdr_loss_math.h) with k = kmul, in place: the helper changed this kernel's code
         out9[4] = (reg_weight != 0.f && nu > 0.f) ? (float)kmul * (reg_weight / ((float)B * nu)) : 0.f;
         out9[5] = (reg_weight != 0.f && ni > 0.f) ? (float)kmul * (reg_weight / ((float)B * ni)) : 0.f;
     }
@@ -813,9 +805,7 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kernel(tab_ptrs TU, tab_
                 sps[r] = group_sum<LPR>(dot4(p[r], p[r]));
                 x = dp - dn;
             }
-            const float s = sigmoidf_(x);
-            gco[r] = -invB * (s * (1.0f - s)) / (gamma + s);
-            lss[r] = -logf(gamma + s);
+            bpr_term(x, gamma, invB, lss[r], gco[r]);
         }
         // every request of this iteration -- rows AND the next ids -- has returned here; nothing below waits on vmcnt again
 #pragma unroll
@@ -859,10 +849,7 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kernel(tab_ptrs TU, tab_
         for (int r = 0; r < UN; ++r) { iu[r] = ju[r]; ip[r] = jp[r]; in[r] = jn[r]; fl[r] = gl[r]; xd[r] = yd[r]; }
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // The pointwise rows (user, item, label) -- EMCDR's default MF latent factor model (emcdr.py:111-122: MSE on the raw dot) and CMF's BCE
@@ -915,15 +902,7 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kernel(int loss_kind, 
         const float su = XD ? 0.f : group_sum<LPR>(dot4(u, u));
         const float si = XD ? 0.f : group_sum<LPR>(dot4(v, v));
         float l, g;
-        if (loss_kind == CDR_LOSS_MSE) {
-            const float d = dx - yl;
-            l = d * d; g = 2.0f * d * invB;
-        } else {                                               // torch BCELoss on sigmoid(dot): -100 log clamp, 1e-12 backward clamp
-            const float p = sigmoidf_(dx);
-            l = (yl - 1.0f) * fmaxf(logf(1.0f - p), -100.0f) - yl * fmaxf(logf(p), -100.0f);
-            const float pq = (1.0f - p) * p;
-            g = (p - yl) / fmaxf(pq, 1e-12f) * invB * pq;
-        }
+        point_term(loss_kind, dx, yl, invB, l, g);
         asm volatile("" : "+v"(ju), "+v"(ji), "+v"(gl), "+v"(yn), "+v"(xn));        // every request of this iteration has returned: stores below wait on nothing older
         __builtin_amdgcn_sched_barrier(0);
         const float4 gu = make_float4(g * v.x, g * v.y, g * v.z, g * v.w);
@@ -940,10 +919,7 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kernel(int loss_kind, 
         iu = ju; ii = ji; fl = gl; yl = yn; xd = xn;
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // The same idea on recbole's pairwise batch layout (S positives tiled k times, negatives k-major: crossdomain_sampler.py:148-152;
@@ -1014,10 +990,10 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kmajor_kernel(tab_ptrs T
                 const float dn = group_sum<LPR>(dot4(u, n[c]));
                 if (m0 + c < k) {
                     const float sg = sigmoidf_(dp - dn);
-                    const float g = -invB * (sg * (1.0f - sg)) / (gamma + sg);
+                    const float g = bpr_grad(sg, gamma, invB);
                     gu.x += g * (p.x - n[c].x); gu.y += g * (p.y - n[c].y); gu.z += g * (p.z - n[c].z); gu.w += g * (p.w - n[c].w);
                     gs += g;
-                    if (sub == 0) acc[0] += (double)(-logf(gamma + sg));
+                    if (sub == 0) acc[0] += (double)bpr_loss(sg, gamma);
                     const float4 gn = make_float4(0.f - g * u.x, 0.f - g * u.y, 0.f - g * u.z, 0.f - g * u.w);
                     if (fn[c]) {
                         const float4 wn = upd_math<OPT>(n[c], nm[c], nv[c], gn, 0.f, hi);
@@ -1037,10 +1013,7 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kmajor_kernel(tab_ptrs T
         } else if (live) st4n<(LPR >= 32)>(GI + j * D + 4 * sub, gp);
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // ---- pointwise rows per POSITIVE (round 5) ---------------------------------------------------------------------------------------------
@@ -1074,10 +1047,7 @@ __global__ __launch_bounds__(kBlock) void point_norms_kmajor_kernel(const float*
         if (sub == 0) { acc[0] += (double)(1 + k) * (double)su; acc[1] += (double)st; }
     }
     block_sum_d<2>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // out9[4], out9[5] = reg_weight / (B ||rows||) as coef_finish_kernel; out9[9] = (1 + k) out9[4]: the user coefficient per LIST occurrence
@@ -1093,8 +1063,8 @@ __global__ __launch_bounds__(kBlock) void point_coef_kmajor_kernel(const double*
     block_sum_d<2>(acc, smem);
     if (threadIdx.x == 0) {
         const float nu = (float)sqrt(acc[0]), ni = (float)sqrt(acc[1]);
-        out9[4] = (reg_weight != 0.f && nu > 0.f) ? reg_weight / ((float)B * nu) : 0.f;
-        out9[5] = (reg_weight != 0.f && ni > 0.f) ? reg_weight / ((float)B * ni) : 0.f;
+        out9[4] = embloss_coef(reg_weight, B, nu);
+        out9[5] = embloss_coef(reg_weight, B, ni);
         out9[9] = (float)(1 + k) * out9[4];
     }
 }
@@ -1150,15 +1120,7 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kmajor_kernel(int loss
                 if (r0 + c <= k) {
                     const float y = yl[c];
                     float l, g;
-                    if (loss_kind == CDR_LOSS_MSE) {
-                        const float d = dx - y;
-                        l = d * d; g = 2.0f * d * invB;
-                    } else {
-                        const float p = sigmoidf_(dx);
-                        l = (y - 1.0f) * fmaxf(logf(1.0f - p), -100.0f) - y * fmaxf(logf(p), -100.0f);
-                        const float pq = (1.0f - p) * p;
-                        g = (p - y) / fmaxf(pq, 1e-12f) * invB * pq;
-                    }
+                    point_term(loss_kind, dx, y, invB, l, g);
                     gu.x += g * v[c].x; gu.y += g * v[c].y; gu.z += g * v[c].z; gu.w += g * v[c].w;
                     if (sub == 0) { acc[0] += (double)l; acc[2] += (double)si; }
                     const float4 gi = make_float4(g * u.x, g * u.y, g * u.z, g * u.w);
@@ -1176,10 +1138,7 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kmajor_kernel(int loss
         } else if (live) st4n<(LPR >= 32)>(GU + j * D + 4 * sub, gu);
     }
     block_sum_d<3>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // End of a MEDIUM segment (3 .. kLongSeg occurrences) headed at sorted position q: the first position past q + 2 whose key differs.
@@ -1496,10 +1455,7 @@ __global__ __launch_bounds__(kBlock) void shard_norms_kernel(const float* __rest
         }
     }
     block_sum_d<2>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // The duplicate ITEM segments of a rank's routed triples: out[uidx[head]] = signed sum of GP over the segment's occurrences, in
@@ -1779,10 +1735,7 @@ __global__ __launch_bounds__(kBlock) void batch_norms_count_kernel(const float* 
     }
     if (NORMS) {
         block_sum_d<2>(acc, smem);
-        if (threadIdx.x == 0) {
-            double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-            o[0] = acc[0]; o[1] = acc[1];
-        }
+        if (threadIdx.x == 0) store_partials(partials, acc);
     }
 }
 
@@ -2966,10 +2919,7 @@ __global__ __launch_bounds__(kBlock) void pair_norms_kernel(const float* __restr
         }
     }
     block_sum_d<4>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // out[9..12] = {c_u_s, c_i_s, c_u_t, c_i_t}: c = w_d reg_d / (B_d ||rows||) (0 without EmbLoss or for a zero norm), w_s = alpha, w_t = 1 - alpha.
@@ -2998,7 +2948,7 @@ __global__ __launch_bounds__(kBlock) void pair_coef_kernel(const double* __restr
         for (int j = 0; j < 4; ++j) {
             const float wr = j < 2 ? wreg_s : wreg_t;
             const float B = (float)(j < 2 ? Bs : Bt);
-            out[9 + j] = (wr != 0.f && n[j] > 0.f) ? wr / (B * n[j]) : 0.f;
+            out[9 + j] = (wr != 0.f && n[j] > 0.f) ? wr / (B * n[j]) : 0.f;      // embloss_coef (cdr_loss_math.h), in place: the helper changed this kernel's code
         }
     }
 }
@@ -3056,15 +3006,7 @@ __global__ __launch_bounds__(kBlock) void point_pair_fwd_apply_kernel(int loss_k
         const float s_i = group_sum<LPR>(dot4(v, v));
         const float invB = src ? invB_s : invB_t;
         float l, g;
-        if (loss_kind == CDR_LOSS_MSE) {
-            const float d = dx - yl;
-            l = d * d; g = 2.0f * d * invB;
-        } else {                                               // torch BCELoss on sigmoid(dot): -100 log clamp, 1e-12 backward clamp
-            const float p = sigmoidf_(dx);
-            l = (yl - 1.0f) * fmaxf(logf(1.0f - p), -100.0f) - yl * fmaxf(logf(p), -100.0f);
-            const float pq = (1.0f - p) * p;
-            g = (p - yl) / fmaxf(pq, 1e-12f) * invB * pq;
-        }
+        point_term(loss_kind, dx, yl, invB, l, g);
         asm volatile("" : "+v"(ju), "+v"(ji), "+v"(gl), "+v"(yn));        // every request of this iteration has returned
         __builtin_amdgcn_sched_barrier(0);
         const float cu = src ? cus : cut, ci = src ? cis : cit;
@@ -3089,10 +3031,7 @@ __global__ __launch_bounds__(kBlock) void point_pair_fwd_apply_kernel(int loss_k
         iu = ju; ii = ji; fl = gl; yl = yn;
     }
     block_sum_d<6>(acc, smem);
-    if (threadIdx.x == 0) {
-        double* o = partials + (size_t)blockIdx.x * CDR_PARTIAL_STRIDE;
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3]; o[4] = acc[4]; o[5] = acc[5];
-    }
+    if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
 // out[0..8] = {total, BCE_s, BCE_t, EmbLoss_s, EmbLoss_t, ||U_s||, ||I_s||, ||U_t||, ||I_t||} from the forward's partials (BCE: the mean over
