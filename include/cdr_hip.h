@@ -55,7 +55,18 @@ int cdr_ctx_scrub_next(cdr_ctx* ctx, void* ptr, size_t bytes);
 int cdr_ctx_set_id_counters(cdr_ctx* ctx, uint32_t* user_counts, int64_t user_rows, uint32_t* item_counts, int64_t item_rows,
                             void* list_ws, size_t list_ws_bytes);
 int cdr_id_count_workspace_bytes(int64_t B, size_t* bytes);
-#define CDR_ABI_VERSION 61
+/* EmbLoss norms from a per-row cache (emcdr.py:129-131: reg_loss(user_e, pos_e) needs ||U[uid]||^2, ||I[pid]||^2 of the batch before any row
+ * moves): one record of cdr_norm_rec_floats() floats per table row, aligned to the record size, slot 0 = ||W[r]||^2 (the other slots are
+ * padding: a record is written whole, as one full burst, never as a partial line).  cdr_row_norms_build fills a table's records in one
+ * streaming pass.  While a context holds the two tables' caches (cdr_ctx_set_norm_cache; row counts checked against the step's own), the
+ * SORTED path of cdr_bpr_step_fused / _dev reads slot 0 of two records per triple instead of gathering two rows, and its three writers
+ * (the forward kernel's single rows, the duplicate-segment apply, the long-segment finish) store the record of every row they update: the
+ * same floats in the same summation order, so the step's results are bit-equal to the gather's.  Every OTHER writer of the table leaves
+ * the cache stale: keeping track of that is the caller's business (fused.py).  NULL pointers take the cache away again. */
+int cdr_norm_rec_floats(void);
+int cdr_row_norms_build(void* stream, const float* table, int64_t rows, int D, float* n2);
+int cdr_ctx_set_norm_cache(cdr_ctx* ctx, float* user_n2, int64_t user_rows, float* item_n2, int64_t item_rows);
+#define CDR_ABI_VERSION 62
 int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the header the library was built from; bumped on any signature change */
 
 /* Optional measurement aid: HIP-event brackets around the hot kernels, recorded on the stream each kernel is launched

@@ -34,7 +34,7 @@ def capturing(graph, stream):
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('CDR_LIB_PATH') or os.path.join(_HERE, 'lib', 'libcdrhip.so')   # env: A/B builds only
-ABI_VERSION = 61
+ABI_VERSION = 62
 SIGNIN_WORDS = 288          # CDR_SIGNIN_WORDS: the sign-in words cdr_adam_multi_dev's ``ticket`` points at
 
 CDR_LOSS_MSE, CDR_LOSS_BCE = 0, 1
@@ -71,6 +71,9 @@ _SIGNATURES = {
     'cdr_ctx_scrub_next': [_c_ptr, _c_ptr, ctypes.c_size_t],
     'cdr_ctx_set_id_counters': [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, ctypes.c_size_t],
     'cdr_id_count_workspace_bytes': [_c_i64, ctypes.POINTER(ctypes.c_size_t)],
+    'cdr_norm_rec_floats': [],
+    'cdr_row_norms_build': [_c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr],
+    'cdr_ctx_set_norm_cache': [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64],
     'cdr_bpr_fwd': [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_f32, _c_ptr, _c_ptr],
     'cdr_bpr_bwd_dense': [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_f32,
                           _c_ptr, _c_ptr, _c_ptr],

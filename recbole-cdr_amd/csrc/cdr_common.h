@@ -24,6 +24,10 @@ struct cdr_ctx {
     uint32_t* idc_user; int64_t idc_user_rows;
     uint32_t* idc_item; int64_t idc_item_rows;
     void* idc_list; size_t idc_list_bytes;
+    // cdr_ctx_set_norm_cache: the per-row squared-norm records of the NEXT fused BPR steps' two tables (csrc/cdr_step.hip, "EmbLoss norms
+    // from a per-row cache")
+    float* n2_user; int64_t n2_user_rows;
+    float* n2_item; int64_t n2_item_rows;
     // cdr_conet_defer_finish: a training forward of the CoNet towers leaves the addition of its blocks' loss partials to the backward's
     // weight-gradient launch (one workgroup more there instead of a launch of its own); `pending` between the two calls
     // conet_fb_kernel's weight staging: per 16-byte chunk of the padded LDS weight area, the address it is copied from (built on the host,

@@ -36,6 +36,7 @@ extern "C" int cdr_ctx_create(int device, cdr_ctx** out) {
     c->scratch_bytes = 0;
     c->scrub_ptr = nullptr; c->scrub_bytes = 0;
     c->idc_user = c->idc_item = nullptr; c->idc_user_rows = c->idc_item_rows = 0; c->idc_list = nullptr; c->idc_list_bytes = 0;
+    c->n2_user = c->n2_item = nullptr; c->n2_user_rows = c->n2_item_rows = 0;
     c->partials = nullptr;
     c->tickets = nullptr;
     hipError_t e = hipMalloc(&c->partials, sizeof(double) * CDR_MAX_PARTIAL_BLOCKS * CDR_PARTIAL_STRIDE);
@@ -135,5 +136,20 @@ extern "C" int cdr_ctx_set_id_counters(cdr_ctx* ctx, uint32_t* user_counts, int6
     CDR_CHECK_ARG(user_rows > 0 && item_rows > 0 && list_ws_bytes > 0);
     ctx->idc_user = user_counts; ctx->idc_user_rows = user_rows; ctx->idc_item = item_counts; ctx->idc_item_rows = item_rows;
     ctx->idc_list = list_ws; ctx->idc_list_bytes = list_ws_bytes;
+    return CDR_OK;
+}
+
+// The per-row squared-norm records (cdr_row_norms_build) of the two tables the NEXT cdr_bpr_step_fused / _dev calls on this context train:
+// their sorted path then takes the EmbLoss norms from the records and keeps the records of the rows it updates current.  NULL pointers
+// switch back to the gather.  The step checks the row counts against its own.
+extern "C" int cdr_ctx_set_norm_cache(cdr_ctx* ctx, float* user_n2, int64_t user_rows, float* item_n2, int64_t item_rows) {
+    CDR_CHECK_ARG(ctx != nullptr);
+    if (!user_n2 || !item_n2) {
+        ctx->n2_user = ctx->n2_item = nullptr; ctx->n2_user_rows = ctx->n2_item_rows = 0;
+        return CDR_OK;
+    }
+    const uintptr_t rec = (uintptr_t)cdr_norm_rec_floats() * sizeof(float);
+    CDR_CHECK_ARG(user_rows > 0 && item_rows > 0 && (uintptr_t)user_n2 % rec == 0 && (uintptr_t)item_n2 % rec == 0);
+    ctx->n2_user = user_n2; ctx->n2_user_rows = user_rows; ctx->n2_item = item_n2; ctx->n2_item_rows = item_rows;
     return CDR_OK;
 }

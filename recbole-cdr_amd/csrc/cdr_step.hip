@@ -35,6 +35,41 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kUnroll = 4;
 
+// EmbLoss norms from a per-row cache ("EmbLoss norms from a per-row cache" below): floats per record.  Slot 0 = ||W[r]||^2, the rest is
+// padding, so that a record is one whole 64-byte burst at the memory (the first cache's 4-byte records were partial-line
+// read-modify-writes: 0.26-0.30 ms per forward launch).  -DCDR_NORM_REC_FLOATS=32 builds the 128-byte form for the A/B.
+#ifndef CDR_NORM_REC_FLOATS
+#define CDR_NORM_REC_FLOATS 16
+#endif
+constexpr int kNormRecFloats = CDR_NORM_REC_FLOATS;
+static_assert(kNormRecFloats == 16 || kNormRecFloats == 32, "a record is one 64-byte or one 128-byte burst");
+
+// A lane's share of a row's squared norm for the records, in the very operations batch_norms_kernel's dot4(w, w) compiles to -- the
+// writers must produce the float the gather would, and left to itself hipcc contracts their copy of dot4 differently (that was the first
+// cache's "1 ulp off").  Read off batch_norms_kernel's ISA: rows of 512 bytes and more (LPR >= 32, non-temporal loads) take one multiply
+// and three fused multiply-adds, y first; narrower rows take packed multiplies and three plain additions.  tests/test_gpu_norm_cache.py
+// holds every lane width to it (cache against gather, bit for bit).
+template <int LPR>
+__device__ __forceinline__ float sqnorm4(float4 a) {
+    if constexpr (LPR >= 32) {
+        return __builtin_fmaf(a.w, a.w, __builtin_fmaf(a.z, a.z, __builtin_fmaf(a.x, a.x, a.y * a.y)));
+    } else {
+#pragma clang fp contract(off)
+        const float xx = a.x * a.x, yy = a.y * a.y, zz = a.z * a.z, ww = a.w * a.w;
+        return ((xx + yy) + zz) + ww;
+    }
+}
+
+// The lane group of a row writes the row's record whole (lane `sub` its float4 chunks), past the caches: s = the row's squared norm, in
+// every lane of the group (group_sum).
+template <int LPR>
+__device__ __forceinline__ void norm_rec_store(float* __restrict__ rec, float s, int sub) {
+#pragma unroll
+    for (int c = 0; c < kNormRecFloats / 4; c += LPR) {
+        if (c + sub < kNormRecFloats / 4) st4n<true>(rec + 4 * (c + sub), make_float4(c + sub == 0 ? s : 0.f, 0.f, 0.f, 0.f));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ forward + compact grads
 // SCATTER (row-sharded step): the item operand is the buffer of received rows, one entry per occurrence, and the item
 // gradients are written straight into the send buffer at the same positions: GP[pid[t]] = g u, GP[nid[t]] = -g u.
@@ -237,8 +272,8 @@ struct apply_hp { float lr, b1, b2, eps, wd, step_size, bc2_sqrt; const float* d
 #define HP_FROM_DEV(h) do { if ((h).dev) { (h).step_size = (h).dev[0]; (h).bc2_sqrt = (h).dev[1]; } } while (0)
 
 template <int LPR, int OPT>
-__device__ __forceinline__ void apply_update(float* __restrict__ wp, float* __restrict__ mp, float* __restrict__ vp, float4 w,
-                                             float4 acc, float rc, const apply_hp& h) {
+__device__ __forceinline__ float4 apply_update(float* __restrict__ wp, float* __restrict__ mp, float* __restrict__ vp, float4 w,
+                                               float4 acc, float rc, const apply_hp& h) {
     float4 gr = make_float4(acc.x + rc * w.x, acc.y + rc * w.y, acc.z + rc * w.z, acc.w + rc * w.w);
     float4 wn;
     if (OPT == 0) {
@@ -256,6 +291,7 @@ __device__ __forceinline__ void apply_update(float* __restrict__ wp, float* __re
                          w.z - cdr_adam_term(m.z, v.z, h.step_size, h.bc2_sqrt, h.eps), w.w - cdr_adam_term(m.w, v.w, h.step_size, h.bc2_sqrt, h.eps));
     }
     st4n<(LPR >= 32)>(wp, wn);
+    return wn;
 }
 
 template <int LPR, int OPT, bool SIGNED>
@@ -408,13 +444,15 @@ __global__ __launch_bounds__(kBlock) void seg_piece_sum_kernel(int D, const uint
 }
 
 // One lane group per long segment: piece sums added in piece order, then the same update as the head-only path.
-template <int LPR, int OPT>
+// NC (whole rows per lane group only, D <= 4 LPR): the updated row's squared-norm record goes to n2 (the fused BPR step's norm cache).
+template <int LPR, int OPT, bool NC = false>
 __device__ __forceinline__ void seg_long_finish_body(float* __restrict__ W, float* __restrict__ Mo, float* __restrict__ Vo,
                                                      int D, const uint32_t* __restrict__ keys,
                                                      const float* __restrict__ reg_coef, apply_hp hp,
                                                      const unsigned* __restrict__ counters,
                                                      const seg_long* __restrict__ longs,
-                                                     const float* __restrict__ partial, const int* __restrict__ pcnt) {
+                                                     const float* __restrict__ partial, const int* __restrict__ pcnt,
+                                                     float* __restrict__ n2 = nullptr) {
     HP_FROM_DEV(hp);
     constexpr int GPB = kBlock / LPR;
     const int sub = threadIdx.x % LPR;
@@ -427,6 +465,7 @@ __device__ __forceinline__ void seg_long_finish_body(float* __restrict__ W, floa
         const seg_long sg = longs[li];
         const uint32_t row = keys[sg.head];
         const int64_t np = (sg.len + kPiece - 1) / kPiece;
+        float4 wnew = make_float4(0.f, 0.f, 0.f, 0.f);               // (NC: this lane's chunk of the updated row; a dead lane keeps 0)
         for (int ch = sub; ch < D4; ch += LPR) {
             float* wp = W + (int64_t)row * D + 4 * ch;
             const float4 w = ld4n<(LPR >= 32)>(wp);
@@ -445,9 +484,10 @@ __device__ __forceinline__ void seg_long_finish_body(float* __restrict__ W, floa
                     if (k0 + j < np) { acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; acc.w += g[j].w; cnt += c[j]; }
                 }
             }
-            apply_update<LPR, OPT>(wp, OPT ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
-                              w, acc, c * (float)cnt, hp);
+            wnew = apply_update<LPR, OPT>(wp, OPT ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
+                                          w, acc, c * (float)cnt, hp);
         }
+        if (NC) norm_rec_store<LPR>(n2 + (int64_t)row * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wnew)), sub);
     }
 }
 template <int LPR, int OPT>
@@ -491,7 +531,8 @@ __global__ __launch_bounds__(kBlock) void make_keys2_kernel(const int64_t* __res
 //                             optimizer needs BEFORE the first row is updated): a gather of 2 rows per triple.  (First version: a
 //                             per-row squared-norm cache kept current by every writer -- its 2.6 M scattered 4-byte stores per
 //                             step, partial-line read-modify-writes at the HBM, cost 0.35 ms per domain step against 0.18 ms for
-//                             this gather, measured A/B.)
+//                             this gather, measured A/B.  The cache came back with 64-byte records written whole: "EmbLoss norms
+//                             from a per-row cache" below; this gather remains the path of every step that cannot use it.)
 //   bpr_fwd_apply_kernel      gather 3 rows (+ 2 moments per single row) -> loss -> single rows: optimizer in place;
 //                             duplicate rows: GU[b] / GP[b] as before
 //   rowwise_apply_dups_kernel the segmented apply over the duplicate segments only (same sums, same order as rowwise_apply_kernel)
@@ -549,6 +590,74 @@ __global__ __launch_bounds__(kBlock) void batch_norms_kernel(const float* __rest
     }
     block_sum_d<2>(acc, smem);
     if (threadIdx.x == 0) store_partials(partials, acc);
+}
+
+// ------------------------------------------------------------------------------------------------ EmbLoss norms from a per-row cache
+// batch_norms_kernel re-gathers two whole rows per triple (1.09 GB per domain step at C5) for two scalars.  The cache keeps the scalar:
+// NU / NI [rows, kNormRecFloats], slot 0 = ||W[r]||^2 formed as batch_norms_kernel forms it -- group_sum<LPR>(dot4(w, w)) over the same
+// lanes -- by cdr_row_norms_build and, for every row the sorted path of cdr_bpr_step_fused updates, by the kernel that has the new row
+// in registers (bpr_fwd_apply_kernel<.., NC>, rowwise_apply_dups2_kernel<.., NC>, seg_long_finish2_kernel<.., NC>).
+//
+// The reader below keeps batch_norms_kernel's grid, unroll, triple -> lane group assignment and accumulation order: the same floats enter
+// the same fp64 sums in the same order, so the partials -- and the coefficient coef_finish_kernel makes of them -- are bit-equal to the
+// gather's.  (Which is why it is a launch of its own and not part of make_keys2_kernel: another summation order may move the last bit.)
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void batch_norms_cached_kernel(const float* __restrict__ NU, const float* __restrict__ NI,
+                                                                    const int64_t* __restrict__ uid, const int64_t* __restrict__ pid, int64_t B,
+                                                                    double* __restrict__ partials) {
+    constexpr int GPB = kBlock / LPR;
+    constexpr int UNR = 8;
+    __shared__ double smem[2 * (kBlock / 64)];
+    const int sub = threadIdx.x % LPR;
+    const int64_t gg = (int64_t)blockIdx.x * GPB + threadIdx.x / LPR;
+    const int64_t TG = (int64_t)gridDim.x * GPB;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t base = gg; base < B; base += TG * UNR) {
+        int64_t iu[UNR], ip[UNR];
+        float su[UNR], sp[UNR];
+#pragma unroll
+        for (int r = 0; r < UNR; ++r) {
+            const int64_t t = base + (int64_t)r * TG;
+            const int64_t tc = t < B ? t : B - 1;
+            iu[r] = uid[tc]; ip[r] = pid[tc];
+        }
+#pragma unroll
+        for (int r = 0; r < UNR; ++r) {
+            const int64_t t = base + (int64_t)r * TG;
+            su[r] = sp[r] = 0.f;
+            if (t < B && sub == 0) { su[r] = NU[iu[r] * kNormRecFloats]; sp[r] = NI[ip[r] * kNormRecFloats]; }
+        }
+#pragma unroll
+        for (int r = 0; r < UNR; ++r) {
+            if (sub == 0) { acc[0] += (double)su[r]; acc[1] += (double)sp[r]; }
+        }
+    }
+    block_sum_d<2>(acc, smem);
+    if (threadIdx.x == 0) store_partials(partials, acc);
+}
+
+// The records of a whole table in one streaming pass: one lane group per row, four rows in flight.
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void row_norms_build_kernel(const float* __restrict__ W, int64_t rows, int D, float* __restrict__ n2) {
+    constexpr int GPB = kBlock / LPR;
+    const int sub = threadIdx.x % LPR;
+    const int64_t gg = (int64_t)blockIdx.x * GPB + threadIdx.x / LPR;
+    const int64_t TG = (int64_t)gridDim.x * GPB;
+    const bool live = sub < (D >> 2);
+    for (int64_t base = gg; base < rows; base += TG * kUnroll) {
+        float4 w[kUnroll];
+#pragma unroll
+        for (int r = 0; r < kUnroll; ++r) {
+            const int64_t row = base + (int64_t)r * TG;
+            w[r] = (row < rows && live) ? ld4n<(LPR >= 32)>(W + row * D + 4 * sub) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int r = 0; r < kUnroll; ++r) {
+            const int64_t row = base + (int64_t)r * TG;
+            const float s = group_sum<LPR>(sqnorm4<LPR>(w[r]));
+            if (row < rows) norm_rec_store<LPR>(n2 + row * kNormRecFloats, s, sub);
+        }
+    }
 }
 
 // keys / perm: the two-table sort's output (section A = positions [0, nA): user keys; section B = [nA, n): item keys + key_base).
@@ -726,14 +835,17 @@ __global__ __launch_bounds__(kBlock) void shard_sums_kernel(const double* __rest
 // read-only) and an item occurrence flagged "only occurrence of its row" is not updated -- its finished gradient row (g u + c_i p for the
 // positive, -g u for the negative) is written straight into the send slot of its row, GS[ip] / GS[in]; GP[t] = g u only when one of the
 // triple's two item rows is a duplicate (the segmented sum over the duplicates reads it).
-template <int LPR, int OPT, int UN, bool XD = false, bool SH = false>
+// NC (the plain step with a norm cache): the squared norm of every row updated here goes to its record in NU / NI, written whole.
+template <int LPR, int OPT, int UN, bool XD = false, bool SH = false, bool NC = false>
 __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kernel(tab_ptrs TU, tab_ptrs TI, int D, const int64_t* __restrict__ uid,
                                                                const int64_t* __restrict__ pid, const int64_t* __restrict__ nid,
                                                                const uint32_t* __restrict__ flags4, int64_t B, float gamma, float invB,
                                                                const float* __restrict__ coef, apply_hp hu, apply_hp hi,
                                                                float* __restrict__ GU, float* __restrict__ GP,
                                                                double* __restrict__ partials, const float* __restrict__ xdiff = nullptr,
-                                                               float* __restrict__ GS = nullptr) {
+                                                               float* __restrict__ GS = nullptr, float* __restrict__ NU = nullptr,
+                                                               float* __restrict__ NI = nullptr) {
+    static_assert(!NC || (!XD && !SH), "the norm cache belongs to the plain step");
     HP_FROM_DEV(hu); HP_FROM_DEV(hi);
     constexpr int GPB = kBlock / LPR;
     __shared__ double smem[3 * (kBlock / 64)];
@@ -822,6 +934,7 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kernel(tab_ptrs TU, tab_
             if (fu[r]) {
                 const float4 wu = upd_math<OPT>(u[r], um[r], uv[r], gu, cu, hu);
                 if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TU.M + ou[r], um[r]); st4n<(LPR >= 32)>(TU.V + ou[r], uv[r]); } st4n<(LPR >= 32)>(TU.W + ou[r], wu); }
+                if (NC) norm_rec_store<LPR>(NU + (int64_t)iu[r] * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wu)), sub);
             } else if (ok) st4n<(LPR >= 32)>(GU + t * D + 4 * sub, gu);
             // ---- positive item row (EmbLoss occurrence), negative item row (gradient -g u, no EmbLoss)
             if (SH) {
@@ -832,10 +945,12 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kernel(tab_ptrs TU, tab_
             if (fp[r]) {
                 const float4 wp = upd_math<OPT>(p[r], pm[r], pv[r], gi, ci, hi);
                 if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + op[r], pm[r]); st4n<(LPR >= 32)>(TI.V + op[r], pv[r]); } st4n<(LPR >= 32)>(TI.W + op[r], wp); }
+                if (NC) norm_rec_store<LPR>(NI + (int64_t)ip[r] * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wp)), sub);
             }
             if (fn[r]) {
                 const float4 wn = upd_math<OPT>(n[r], nm[r], nv[r], make_float4(0.f - gi.x, 0.f - gi.y, 0.f - gi.z, 0.f - gi.w), 0.f, hi);
                 if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + on[r], nm[r]); st4n<(LPR >= 32)>(TI.V + on[r], nv[r]); } st4n<(LPR >= 32)>(TI.W + on[r], wn); }
+                if (NC) norm_rec_store<LPR>(NI + (int64_t)in[r] * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wn)), sub);
             }
             }
             if (ok && !(fp[r] && fn[r])) st4n<(LPR >= 32)>(GP + t * D + 4 * sub, gi);
@@ -1180,8 +1295,8 @@ __device__ __forceinline__ int64_t seg_occ_at(const uint32_t* __restrict__ perm,
 
 // The segmented apply over the DUPLICATE segments only: heads[0 .. *nheads) are the sorted positions of their first occurrences
 // (any order: every segment is summed by one lane group in occurrence order, whoever takes it).  Long segments as in
-// rowwise_apply_kernel.
-template <int LPR, int OPT, bool SIGNED>
+// rowwise_apply_kernel.  NC (whole rows per lane group only): the updated row's squared-norm record goes to n2.
+template <int LPR, int OPT, bool SIGNED, bool NC = false>
 __device__ __forceinline__ void rowwise_apply_dups_body(float* __restrict__ W, float* __restrict__ Mo, float* __restrict__ Vo,
                                                         int D, const uint32_t* __restrict__ keys,
                                                         const uint32_t* __restrict__ perm, int64_t n,
@@ -1189,7 +1304,7 @@ __device__ __forceinline__ void rowwise_apply_dups_body(float* __restrict__ W, f
                                                         const float* __restrict__ G, int64_t neg_start, int64_t reg_limit,
                                                         const float* __restrict__ reg_coef, apply_hp hp,
                                                         unsigned* __restrict__ counters, seg_long* __restrict__ longs,
-                                                        seg_piece* __restrict__ pieces) {
+                                                        seg_piece* __restrict__ pieces, float* __restrict__ n2 = nullptr) {
     HP_FROM_DEV(hp);
     constexpr int GPB = kBlock / LPR;
     constexpr int SU = 4;                                 // segments in flight per lane group
@@ -1279,6 +1394,7 @@ __device__ __forceinline__ void rowwise_apply_dups_body(float* __restrict__ W, f
                     if (OPT == 1) { st4n<(LPR >= 32)>(Mo + off[j], m[j]); st4n<(LPR >= 32)>(Vo + off[j], v[j]); }
                     st4n<(LPR >= 32)>(W + off[j], wn);
                 }
+                if (NC) norm_rec_store<LPR>(n2 + (int64_t)row[j] * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wn)), sub);
             }
         }
     } else {
@@ -1341,12 +1457,13 @@ struct dup_side {
     const float* G; int64_t neg_start, reg_limit; const float* reg_coef; apply_hp hp;
     unsigned* counters; seg_long* longs; seg_piece* pieces; int* pcnt; float* partial;
     float* out = nullptr; const uint32_t* uidx = nullptr;     // row shard, item side: W = the received rows (read-only), out[uidx[position]] = the segment's sum
+    float* n2 = nullptr;                                      // NC kernels: the table's squared-norm records (moved back by key_base rows like W)
 };
-template <int LPR, int OPT>
+template <int LPR, int OPT, bool NC = false>
 __global__ __launch_bounds__(kBlock) void rowwise_apply_dups2_kernel(int D, dup_side a, dup_side b) {
     const dup_side& t = blockIdx.y ? b : a;
-    rowwise_apply_dups_body<LPR, OPT, true>(t.W, t.M, t.V, D, t.keys, t.perm, t.n, t.heads, t.nheads, t.G, t.neg_start, t.reg_limit, t.reg_coef, t.hp,
-                                            t.counters, t.longs, t.pieces);
+    rowwise_apply_dups_body<LPR, OPT, true, NC>(t.W, t.M, t.V, D, t.keys, t.perm, t.n, t.heads, t.nheads, t.G, t.neg_start, t.reg_limit, t.reg_coef, t.hp,
+                                                t.counters, t.longs, t.pieces, t.n2);
 }
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void seg_piece_sum2_kernel(int D, dup_side a, dup_side b) {
@@ -1354,11 +1471,11 @@ __global__ __launch_bounds__(kBlock) void seg_piece_sum2_kernel(int D, dup_side 
     if (t.counters == nullptr) return;
     seg_piece_sum_body<LPR, true>(D, t.perm, t.G, t.neg_start, t.reg_limit, nullptr, t.counters, t.pieces, t.partial, t.pcnt);
 }
-template <int LPR, int OPT>
+template <int LPR, int OPT, bool NC = false>
 __global__ __launch_bounds__(kBlock) void seg_long_finish2_kernel(int D, dup_side a, dup_side b) {
     const dup_side& t = blockIdx.y ? b : a;
     if (t.counters == nullptr) return;
-    seg_long_finish_body<LPR, OPT>(t.W, t.M, t.V, D, t.keys, t.reg_coef, t.hp, t.counters, t.longs, t.partial, t.pcnt);
+    seg_long_finish_body<LPR, OPT, NC>(t.W, t.M, t.V, D, t.keys, t.reg_coef, t.hp, t.counters, t.longs, t.partial, t.pcnt, t.n2);
 }
 
 // ================================================================================================ round 6: the row-sharded step's own passes
@@ -2157,13 +2274,18 @@ step_tables make_tables(int opt_user, float* user_tab, float* user_m, float* use
 // lists' counters `cnt` and, when given, advances the device-resident update counts (their Adam scalars -> hp_dev).
 int embloss_head(cdr_ctx* ctx, hipStream_t s, const float* user_tab, const float* item_tab, int D, const int64_t* uid, const int64_t* pid,
                  int64_t n_rows, int64_t B, int kmul, float reg_weight, float* out9, unsigned* cnt, int64_t* step_user_dev = nullptr,
-                 int64_t* step_item_dev = nullptr, float* hp_dev = nullptr, float lr = 0.f, float beta1 = 0.f, float beta2 = 0.f) {
+                 int64_t* step_item_dev = nullptr, float* hp_dev = nullptr, float lr = 0.f, float beta1 = 0.f, float beta2 = 0.f,
+                 const float* user_n2 = nullptr, const float* item_n2 = nullptr) {
     int ngrid = 0;
     if (reg_weight != 0.f) {
         const int lpr = cdr_lpr_for(D);
         ngrid = grid_for((n_rows + 7) / 8, kBlock / lpr);
         cdr_time_scope ts(ctx, CDR_TAG_BATCH_NORMS, s);
-        DISPATCH_LPR(lpr, batch_norms_kernel<L><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, n_rows, ctx->partials));
+        if (user_n2 && item_n2) {                   // the tables' squared-norm records: one float per row instead of the row
+            DISPATCH_LPR(lpr, batch_norms_cached_kernel<L><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_n2, item_n2, uid, pid, n_rows, ctx->partials));
+        } else {
+            DISPATCH_LPR(lpr, batch_norms_kernel<L><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, n_rows, ctx->partials));
+        }
         CDR_LAUNCH_CHECK();
     }
     coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B, ngrid ? reg_weight : 0.f, out9, kmul, step_user_dev, step_item_dev, hp_dev,
@@ -2186,7 +2308,7 @@ int occ_flags(cdr_ctx* ctx, hipStream_t s, const uint32_t* keys, const uint32_t*
 // instead of six (+ two counter clears, which the step's one-block finishing kernel does: finish_and_apply_dups).
 struct dup_host { tab_ptrs T; const uint32_t* keys; const uint32_t* perm; int64_t n; const uint32_t* heads; const unsigned* nheads;
                   const float* G; int64_t neg_start, reg_limit; const float* reg_coef; apply_hp hp; uint32_t key_base;
-                  float* out = nullptr; const uint32_t* uidx = nullptr; };
+                  float* out = nullptr; const uint32_t* uidx = nullptr; float* n2 = nullptr; };
 struct dups_plan { dup_side side[2]; long_scratch ls[2]; };
 
 // The sides of a step on the sorted list [n_user user keys | n_item item keys]: users over GU with every occurrence positive and
@@ -2220,6 +2342,7 @@ int dups_plan_make(cdr_ctx* ctx, int D, const dup_host (&h)[2], dups_plan& pl) {
         t.neg_start = h[i].neg_start; t.reg_limit = h[i].reg_limit; t.reg_coef = h[i].reg_coef; t.hp = h[i].hp;
         t.counters = nullptr; t.longs = nullptr; t.pieces = nullptr; t.pcnt = nullptr; t.partial = nullptr;
         t.out = h[i].out; t.uidx = h[i].uidx;
+        t.n2 = h[i].n2 ? h[i].n2 - (int64_t)h[i].key_base * kNormRecFloats : nullptr;
         if (pl.ls[i].bytes) pl.ls[i].bind(base + off[i], t);
     }
     return CDR_OK;
@@ -2230,6 +2353,10 @@ int dups_plan_make(cdr_ctx* ctx, int D, const dup_host (&h)[2], dups_plan& pl) {
 struct table_dups {
     template <int L, int OPT> static constexpr auto dups = rowwise_apply_dups2_kernel<L, OPT>;
     template <int L, int OPT> static constexpr auto long_finish = seg_long_finish2_kernel<L, OPT>;
+};
+struct table_dups_nc {                          // ... and keep the tables' squared-norm records current (dup_side::n2)
+    template <int L, int OPT> static constexpr auto dups = rowwise_apply_dups2_kernel<L, OPT, true>;
+    template <int L, int OPT> static constexpr auto long_finish = seg_long_finish2_kernel<L, OPT, true>;
 };
 struct shard_dups {
     template <int L, int OPT> static constexpr auto dups = shard_dups_kernel<L, OPT>;
@@ -2296,6 +2423,10 @@ static int bpr_step_fused_impl(cdr_ctx* ctx, void* stream, int opt, float* user_
     // ---- ids without a sort (medium batches, counters handed over by cdr_ctx_set_id_counters): see "round 6: ids without a sort"
     const bool count_path = ctx->idc_user && ctx->idc_item && ctx->idc_user_rows == user_rows && ctx->idc_item_rows == item_rows &&
                             B >= kCountMinB && B <= kCountMaxB && ctx->idc_list_bytes >= count_list_bytes(B);
+    // ---- the tables' squared-norm records (cdr_ctx_set_norm_cache), sorted path only: read by the EmbLoss head, kept current by the writers
+    const bool cached = !count_path && ctx->n2_user && ctx->n2_item && ctx->n2_user_rows == user_rows && ctx->n2_item_rows == item_rows;
+    float* NU = cached ? ctx->n2_user : nullptr;
+    float* NI = cached ? ctx->n2_item : nullptr;
     if (count_path) {
         const unsigned hb = two_table_bits(user_rows, item_rows);
         CDR_CHECK_ARG(hb < 31);
@@ -2326,7 +2457,8 @@ static int bpr_step_fused_impl(cdr_ctx* ctx, void* stream, int opt, float* user_
         CDR_LAUNCH_CHECK();
     } else {
         // ---- EmbLoss coefficients first (they do not need the sort): out9[4], out9[5]  (+ the device-resident update counts, when given)
-        rc = embloss_head(ctx, s, user_tab, item_tab, D, uid, pid, B, B, 1, reg_weight, out9, hv.cnt, step_user_dev, step_item_dev, hp_dev, lr, beta1, beta2);
+        rc = embloss_head(ctx, s, user_tab, item_tab, D, uid, pid, B, B, 1, reg_weight, out9, hv.cnt, step_user_dev, step_item_dev, hp_dev, lr, beta1, beta2,
+                          NU, NI);
         if (rc) return rc;
         rc = cdr_sort_ids_two_tables(ctx, stream, uid, B, user_rows, pid, B, nid, B, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes);
         if (rc) return rc;
@@ -2340,17 +2472,41 @@ static int bpr_step_fused_impl(cdr_ctx* ctx, void* stream, int opt, float* user_
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
 #define FA_ARGS T.TU, T.TI, D, uid, pid, nid, (const uint32_t*)flags, B, gamma, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials
-        if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
+#define FA_NC_ARGS FA_ARGS, nullptr, nullptr, NU, NI
+        if (cached) {
+            if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1, false, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_NC_ARGS)); }
+            else if (un == 1) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1, false, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_NC_ARGS)); }
+            else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 2, false, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_NC_ARGS)); }
+        }
+        else if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
         else if (un == 1) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
         else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 2><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
+#undef FA_NC_ARGS
 #undef FA_ARGS
     }
     CDR_LAUNCH_CHECK();
     dup_host sides[2];
     make_sides(sides, T, keys, perm, hv, GU, GP, B, 2 * B, B, B, out9 + 4, out9 + 5, key_base);
-    return finish_and_apply_dups(ctx, s, opt, D, sides, [&](unsigned* za, unsigned* zb) {
+    sides[0].n2 = NU; sides[1].n2 = NI;
+    auto finish = [&](unsigned* za, unsigned* zb) {
         step_finish_keep_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9, za, zb);
-    });
+    };
+    return cached ? finish_and_apply_dups<table_dups_nc>(ctx, s, opt, D, sides, finish) : finish_and_apply_dups(ctx, s, opt, D, sides, finish);
+}
+
+extern "C" int cdr_norm_rec_floats(void) { return kNormRecFloats; }
+
+// One streaming pass over a table: n2[r * cdr_norm_rec_floats()] = ||table[r]||^2 (the rest of the record 0), formed exactly as the fused
+// BPR step's norm gather forms it.  n2: [rows, cdr_norm_rec_floats()] floats, aligned to the record size.
+extern "C" int cdr_row_norms_build(void* stream, const float* table, int64_t rows, int D, float* n2) {
+    CDR_CHECK_ARG(table && n2 && rows > 0 && D > 0 && (D & 3) == 0 && D <= 256);
+    CDR_CHECK_ARG((uintptr_t)n2 % (kNormRecFloats * sizeof(float)) == 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int lpr = cdr_lpr_for(D);
+    const int grid = grid_for((rows + kUnroll - 1) / kUnroll, kBlock / lpr);
+    DISPATCH_LPR(lpr, row_norms_build_kernel<L><<<dim3(grid), dim3(kBlock), 0, s>>>(table, rows, D, n2));
+    CDR_LAUNCH_CHECK();
+    return CDR_OK;
 }
 
 extern "C" int cdr_id_count_workspace_bytes(int64_t B, size_t* bytes) {

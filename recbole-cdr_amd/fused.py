@@ -24,10 +24,25 @@ class RowwiseState:
 
     ``exact=True``: the reference's dense Adam instead of the lazy one (``rowwise_catch_up`` in front of every step on the table).
     The state then also holds ``last`` (int32 [rows]: the update each row reflects) and its own ring of per-update scalars, so that
-    tables stepped on different streams (parallel domains) share nothing mutable; ``flush()`` brings every row to ``step``."""
+    tables stepped on different streams (parallel domains) share nothing mutable; ``flush()`` brings every row to ``step``.
+
+    ``n2`` / ``n2_valid``: the table's squared-norm records (float [rows, cdr_norm_rec_floats()], slot 0 = ||table[r]||^2; csrc/cdr_step.hip,
+    "EmbLoss norms from a per-row cache"), allocated on the first fused BPR step that can use them.  Only that step's sorted path keeps them
+    current (``advance(keeps_norms=True)``); every other writer of the table -- any other ``advance``, the ``step`` setter, ``restored()``, a
+    replayed graph, an in-place torch op (seen by ``table._version``) -- leaves them stale, and the BPR step goes back to gathering rows
+    until it rebuilds them (``norms_ready``)."""
     _step = 0                 # class-level defaults: objects built with __new__ (layout transposes in dimshard.py) start consistent
     _step_dev = None
     exact = False
+    n2 = None
+    _n2_ok = False            # the records followed every native update since they were built
+    _n2_version = -1          # table._version the records were built at (an in-place torch op on the table moves it; the native steps do not)
+    _n2_tried = False         # a build was attempted (the first eligible step builds at once, later ones wait: NORMS_REBUILD_AFTER)
+    _n2_run = 0               # consecutive eligible BPR steps on the gather path since the records went stale
+
+    NORMS_REBUILD_AFTER = 4   # stale records are rebuilt after this many consecutive eligible gather steps (a phase that alternates writers
+                              # would otherwise stream the whole table through the build every step)
+    NORMS_MARGIN_BYTES = 4 << 30
 
     HP_CAPACITY = 1 << 12     # ring entries: with the moving window (period <= capacity / 2) no row falls a ring behind
 
@@ -54,8 +69,18 @@ class RowwiseState:
     @step.setter
     def step(self, value):                       # (checkpoint restore, layout changes) keeps the device mirror in step
         self._step = int(value)
+        self.n2_valid, self._n2_run = False, 0
         if self._step_dev is not None:
             self._step_dev.fill_(self._step)
+
+    @property
+    def n2_valid(self):
+        """The squared-norm records describe the table as it stands."""
+        return self._n2_ok and self.n2 is not None and self.table._version == self._n2_version
+
+    @n2_valid.setter
+    def n2_valid(self, value):
+        self._n2_ok = bool(value)
 
     @property
     def step_dev(self):
@@ -64,9 +89,12 @@ class RowwiseState:
             self._step_dev = torch.full((1,), int(self._step), device=self.table.device, dtype=torch.int64)
         return self._step_dev
 
-    def advance(self, device_bumped=False):
-        """One more update of this table.  ``device_bumped``: a kernel already incremented the device counter."""
+    def advance(self, device_bumped=False, keeps_norms=False):
+        """One more update of this table.  ``device_bumped``: a kernel already incremented the device counter.  ``keeps_norms``: the
+        update also wrote the squared-norm record of every row it moved (the cached BPR step alone)."""
         self._step += 1
+        if not keeps_norms:
+            self.n2_valid, self._n2_run = False, 0
         if self._step_dev is not None and not device_bumped:
             B_.call('cdr_inc_i64', B_.stream(), B_.i64(self._step_dev))
 
@@ -81,8 +109,38 @@ class RowwiseState:
                 B_.raw(self.last), self.table.shape[0], lr, b1, b2, eps, wd, B_.raw(self.hp), self.HP_CAPACITY, B_.i64(self.step_dev))
         self._flushed_at = self._step
 
+    @torch.no_grad()
+    def norms_build(self, max_bytes=None):
+        """Fill the squared-norm records from the table as it stands (one streaming pass on the current stream).  The array is allocated
+        on first use, and only if it fits ``max_bytes`` (when given) and leaves NORMS_MARGIN_BYTES of device memory free; False if refused."""
+        rec = int(B_.load().cdr_norm_rec_floats())
+        rows, D = self.table.shape
+        if self.n2 is None:
+            need = rows * rec * 4
+            dev = self.table.device
+            free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            if (max_bytes is not None and need > max_bytes) or free < need + self.NORMS_MARGIN_BYTES:
+                self.n2_valid, self._n2_run = False, 0
+                return False
+            self.n2 = torch.empty(rows, rec, device=dev, dtype=torch.float32)
+        B_.call('cdr_row_norms_build', B_.stream(), B_.f32(self.table), rows, D, B_.f32(self.n2))
+        self._n2_ok, self._n2_version, self._n2_run = True, self.table._version, 0
+        return True
+
+    def norms_ready(self, max_bytes=None):
+        """Before an eligible BPR step: True if the records are current -- building them if this is the first such step on the table, or
+        the NORMS_REBUILD_AFTER-th in a row since they went stale."""
+        if self.n2_valid:
+            return True
+        self.n2_valid = False
+        if self._n2_tried and self._n2_run < self.NORMS_REBUILD_AFTER:
+            return False
+        self._n2_tried = True
+        return self.norms_build(max_bytes)
+
     def restored(self):
         """Exact mode, after the table, moments and ``step`` were loaded: every row is current at ``step``."""
+        self.n2_valid, self._n2_run = False, 0
         if self.exact:
             self.last.fill_(self._step)
             self._flushed_at = self._step
@@ -200,7 +258,7 @@ class FusedBPRStep(_TwoTableStep):
 
     def __init__(self, user_table, item_table, max_batch, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, gamma=1e-10, reg_weight=0.0, user_state=None, item_state=None, fuse_singles=True, device_counts=True,
-                 id_path='auto'):
+                 id_path='auto', norm_cache='auto', norm_cache_max_bytes=None):
         super().__init__(user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state)
         self.gamma, self.reg_weight = gamma, reg_weight
         dev = user_table.device
@@ -231,6 +289,15 @@ class FusedBPRStep(_TwoTableStep):
         self._count = None
         self._use_count = self.id_path != 'sort'
         self._stat = None
+        self._count_on = False
+        # EmbLoss norms from the tables' squared-norm records (RowwiseState.n2) instead of a gather of two rows per triple: sorted path,
+        # reg_weight != 0, lazy Adam / SGD, not while capturing.  'auto': batches above COUNT_MAX_B (a table-sized array per table pays for
+        # itself only where the gather is a visible share of the step); 'on': any batch; 'off': never.  ``norm_cache_max_bytes``: the most
+        # one table's records may take (None: whatever leaves RowwiseState.NORMS_MARGIN_BYTES free).
+        self.norm_cache = os.environ.get('CDR_NORM_CACHE', norm_cache)          # env: A/B runs
+        assert self.norm_cache in ('auto', 'on', 'off')
+        self.norm_cache_max_bytes = norm_cache_max_bytes
+        self._nc_runs = None
 
     COUNT_MIN_B, COUNT_MAX_B = 16448, 131072
 
@@ -259,12 +326,40 @@ class FusedBPRStep(_TwoTableStep):
                     self._use_count = True
                 self._stat = None
         on = in_range and self._use_count and not (capturing and self._count is None)     # (never allocate + zero-fill 4 B per table row inside a capture)
+        self._count_on = on
         if on:
             cu, ci, ws = self._count_buffers()
             B_.call('cdr_ctx_set_id_counters', ctxh, B_.raw(cu), cu.numel(), B_.raw(ci), ci.numel(), B_.raw(ws), ws.numel())
         else:
             B_.call('cdr_ctx_set_id_counters', ctxh, None, 0, None, 0, None, 0)
         return in_range and self.id_path == 'auto' and not capturing
+
+    def _select_norm_cache(self, B):
+        """Hands the two tables' squared-norm records to the native context of the current stream if this step can use them and they are
+        current (or due to be built: RowwiseState.norms_ready); True if the step runs cached."""
+        states = (self.ustate, self.istate)
+        self._nc_runs = None
+        if torch.cuda.is_current_stream_capturing():
+            for st in states:                                    # (the captured launches gather, and their replays move rows)
+                st.n2_valid, st._n2_run = False, 0
+            return False
+        eligible = (self.norm_cache != 'off' and self.fuse_singles and not self._count_on and self.reg_weight != 0
+                    and (self.norm_cache == 'on' or B > self.COUNT_MAX_B) and not any(st.exact for st in states))
+        if not eligible:
+            return False
+        ready = [st.norms_ready(self.norm_cache_max_bytes) for st in states]         # (both: two stale tables are rebuilt in the same step)
+        if all(ready):
+            us, its = states
+            B_.call('cdr_ctx_set_norm_cache', B_.ctx(self.U.device), B_.f32(us.n2), us.table.shape[0], B_.f32(its.n2), its.table.shape[0])
+            return True
+        self._nc_runs = [st._n2_run for st in states]
+        return False
+
+    def _advance(self, cached, device_bumped=False):
+        for i, st in enumerate((self.ustate, self.istate)):
+            st.advance(device_bumped=device_bumped, keeps_norms=cached)
+            if self._nc_runs is not None:                        # an eligible step that gathered: one more towards the rebuild
+                st._n2_run = self._nc_runs[i] + 1
 
     def _note_stats(self, B):
         if self._stat is None:
@@ -291,15 +386,17 @@ class FusedBPRStep(_TwoTableStep):
         us, its = self.ustate, self.istate
         watch = self._select_id_path(B)
         try:
-            return self._step_fused_call(uid, pid, nid, B, us, its)
+            cached = self._select_norm_cache(B)
+            return self._step_fused_call(uid, pid, nid, B, us, its, cached)
         finally:
             # (the context is shared by every step object of this stream: it must not keep pointers into this object's buffers)
             B_.call('cdr_ctx_set_id_counters', B_.ctx(self.U.device), None, 0, None, 0, None, 0)
+            B_.call('cdr_ctx_set_norm_cache', B_.ctx(self.U.device), None, 0, None, 0)
             self._steps_seen = self.__dict__.get('_steps_seen', 0) + 1
             if watch and (self._steps_seen & 15) == 1:          # every 16th step: one 16-byte copy, read when it has landed
                 self._note_stats(B)
 
-    def _step_fused_call(self, uid, pid, nid, B, us, its):
+    def _step_fused_call(self, uid, pid, nid, B, us, its, cached=False):
         if self.opt == OPT_ADAM and self.device_counts:
             # the capturable form: the update counts live on the device and the call advances them itself (the host mirrors follow)
             if self._hp_dev is None:
@@ -311,11 +408,9 @@ class FusedBPRStep(_TwoTableStep):
                     float(self.reg_weight), *self._hp(), B_.i64(su), B_.i64(si), B_.f32(self._hp_dev), B_.f32(self.out6), B_.f32(self.GU),
                     B_.f32(self.GP), B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws_bytes)
             if not torch.cuda.is_current_stream_capturing():
-                us.advance(device_bumped=True)
-                its.advance(device_bumped=True)
+                self._advance(cached, device_bumped=True)
             return self.out6
-        us.advance()
-        its.advance()
+        self._advance(cached)
         B_.call('cdr_bpr_step_fused', B_.ctx(self.U.device), B_.stream(), self.opt, B_.f32(us.table), B_.f32(us.exp_avg),
                 B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq),
                 its.table.shape[0], self.D, B_.i64(uid), B_.i64(pid), B_.i64(nid), B, float(self.gamma),
