@@ -10,6 +10,7 @@
 #define CDR_MAX_PARTIAL_BLOCKS 4096          // grid cap of every two-pass reduction
 #define CDR_PARTIAL_STRIDE 8                 // doubles per block
 #define CDR_TICKETS 1024
+constexpr int kBlock = 256;                  // threads per workgroup of every kernel that does not name a size of its own
 
 struct cdr_ctx {
     int device;
@@ -262,6 +263,14 @@ static inline int cdr_lpr_for(int D) {        // lanes per row when a lane moves
         case 32: { constexpr int L = 32; __VA_ARGS__; } break;  \
         default: { constexpr int L = 64; __VA_ARGS__; } break;  \
     }
+
+// The same with `constexpr int O` = the optimizer (0 SGD, 1 Adam) beside L: a launch of a kernel<L, O, ...> is written once.  A third
+// compile-time axis is chosen inside the statement: auto kern = flag ? kernel<L, O, a> : kernel<L, O, b>; kern<<<...>>>(...).
+#define DISPATCH_LPR_OPT(lpr, opt, ...)                                         \
+    do {                                                                        \
+        if ((opt) == 0) { constexpr int O = 0; DISPATCH_LPR(lpr, __VA_ARGS__) } \
+        else { constexpr int O = 1; DISPATCH_LPR(lpr, __VA_ARGS__) }            \
+    } while (0)
 
 static inline int grid_for(int64_t units, int per_block) {
     int64_t g = (units + per_block - 1) / per_block;

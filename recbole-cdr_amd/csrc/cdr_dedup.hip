@@ -17,7 +17,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kLongSeg = 32;
 constexpr int kPiece = 256;
 

@@ -23,7 +23,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kUnroll = 4;
 
 template <int LPR>
@@ -79,11 +78,7 @@ __global__ __launch_bounds__(kBlock) void partial_norms_kernel(const double* __r
                                                                float* __restrict__ norms2) {
     __shared__ double smem[2 * (kBlock / 64)];
     double acc[2] = {0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1];
-    }
-    block_sum_d<2>(acc, smem);
+    sum_partials<2, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) { norms2[0] = (float)acc[0]; norms2[1] = (float)acc[1]; }
 }
 
@@ -146,8 +141,7 @@ __global__ __launch_bounds__(kBlock) void dimshard_finish_kernel(const double* _
                                                                  float* __restrict__ out9) {
     __shared__ double smem[kBlock / 64];
     double acc[1] = {0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) acc[0] += partials[(size_t)b * CDR_PARTIAL_STRIDE];
-    block_sum_d<1>(acc, smem);
+    sum_partials<1, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) {
         const float main_loss = (float)(acc[0] / (double)B);
         const float nu = sqrtf(norms2[0]), ni = sqrtf(norms2[1]);

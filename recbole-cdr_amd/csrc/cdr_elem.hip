@@ -2,10 +2,10 @@
 // K11, K12 minus the SpMM).  All HBM-bound streaming kernels: float4 (16 B) per lane where rows are 16-B aligned,
 // one wave per row for row reductions, fixed-order two-pass reductions for scalars.
 #include "cdr_common.h"
+#include "cdr_loss_math.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 
 inline int grid_cap(int64_t blocks) {
     const int64_t cap = CDR_NUM_CU * 8;
@@ -82,8 +82,7 @@ __global__ __launch_bounds__(kBlock) void scalar_finish_kernel(const double* __r
                                                                int mode, float* __restrict__ out1) {
     __shared__ double smem[4];
     double acc[1] = {0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) acc[0] += partials[(size_t)b * CDR_PARTIAL_STRIDE];
-    block_sum_d<1>(acc, smem);
+    sum_partials<1, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) out1[0] = mode == 0 ? (float)(acc[0] / (double)n) : (float)sqrt(acc[0]);
 }
 
@@ -277,11 +276,7 @@ __global__ __launch_bounds__(kBlock) void sscdr_map_finish_kernel(const double* 
                                                                   float lambda, float* __restrict__ out3) {
     __shared__ double smem[8];
     double acc[2] = {0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        acc[0] += partials[(size_t)b * CDR_PARTIAL_STRIDE];
-        acc[1] += partials[(size_t)b * CDR_PARTIAL_STRIDE + 1];
-    }
-    block_sum_d<2>(acc, smem);
+    sum_partials<2, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) {
         const float ls = (float)(acc[0] / (double)(n * D)), lu = (float)(acc[1] / (double)n);
         out3[1] = ls; out3[2] = lu;
@@ -327,11 +322,7 @@ __global__ __launch_bounds__(kBlock) void embloss_finish_kernel(const double* __
                                                                 float* __restrict__ out3) {
     __shared__ double smem[8];
     double acc[2] = {0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        acc[0] += partials[(size_t)b * CDR_PARTIAL_STRIDE];
-        acc[1] += partials[(size_t)b * CDR_PARTIAL_STRIDE + 1];
-    }
-    block_sum_d<2>(acc, smem);
+    sum_partials<2, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) {
         const float nu = (float)sqrt(acc[0]), ni = (float)sqrt(acc[1]);
         out3[1] = nu; out3[2] = ni; out3[0] = (nu + ni) / (float)B;

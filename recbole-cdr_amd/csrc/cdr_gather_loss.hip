@@ -11,7 +11,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kUnroll = 4;
 constexpr int kUnrollPoint = 8;      // pointwise rows carry 2 row loads each (BPR triples 3): keep as many bytes in flight
 
@@ -22,12 +21,7 @@ __device__ __forceinline__ void loss_finish_body(const double* __restrict__ part
                                                  float reg_weight, float* __restrict__ out4) {
     __shared__ double smem[3 * (kBlock / 64)];
     double acc[3] = {0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        if (SYS) { acc[0] += cdr_load_sys(o); acc[1] += cdr_load_sys(o + 1); acc[2] += cdr_load_sys(o + 2); }      // (past the L2s: cdr_sign_in_last)
-        else { acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2]; }
-    }
-    block_sum_d<3>(acc, smem);
+    sum_partials<3, kBlock, SYS>(partials, nblocks, acc, smem);                 // (SYS: past the L2s, cdr_sign_in_last)
     if (threadIdx.x == 0) {
         const float main_loss = (float)(acc[0] / (double)B);
         const float nu = (float)sqrt(acc[1]), ni = (float)sqrt(acc[2]);
@@ -337,7 +331,7 @@ __device__ __forceinline__ void loss_finish_pair_body(const double* __restrict__
                                                       const float* __restrict__ w, float* __restrict__ total) {
     __shared__ double smem[6 * (kBlock / 64)];
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
+    for (int b = threadIdx.x; b < nblocks; b += kBlock) {                           // (sum_partials reads one slot array; this one reads two)
         const double* o0 = partials + (size_t)b * CDR_PARTIAL_STRIDE;
         const double* o1 = o0 + kPairPartials;
         if (SYS) {
@@ -566,15 +560,11 @@ extern "C" int cdr_point_fwd(cdr_ctx* ctx, void* stream, int loss_kind, const fl
         grid = grid_for(units_for(B, kUnrollPoint, kBlock / lpr), kBlock / lpr);
         fused_finish = grid <= kSignInMaxBlocks;
         unsigned* tk = fused_finish ? ctx->tickets : nullptr;
-        if (same) {
-            DISPATCH_LPR(lpr, point_fwd_kernel<L, true><<<dim3(grid), dim3(kBlock), 0, s>>>(loss_kind,
-                                                  user_tab, item_tab, reg_user_tab, reg_item_tab, D, uid, iid, label, B,
-                                                  gcoef, scores, ctx->partials, tk, reg_weight, out4, zs, zn));
-        } else {
-            DISPATCH_LPR(lpr, point_fwd_kernel<L, false><<<dim3(grid), dim3(kBlock), 0, s>>>(loss_kind,
-                                                  user_tab, item_tab, reg_user_tab, reg_item_tab, D, uid, iid, label, B,
-                                                  gcoef, scores, ctx->partials, tk, reg_weight, out4, zs, zn));
-        }
+        DISPATCH_LPR(lpr, {
+            auto kern = same ? point_fwd_kernel<L, true> : point_fwd_kernel<L, false>;
+            kern<<<dim3(grid), dim3(kBlock), 0, s>>>(loss_kind, user_tab, item_tab, reg_user_tab, reg_item_tab, D, uid, iid, label, B, gcoef, scores, ctx->partials, tk,
+                                                     reg_weight, out4, zs, zn);
+        });
     } else {
         grid = grid_for(B, kBlock / 64);
         hipLaunchKernelGGL(point_fwd_scalar_kernel, dim3(grid), dim3(kBlock), 0, s, loss_kind, user_tab, item_tab,
@@ -630,8 +620,10 @@ extern "C" int cdr_point_fwd_pair_ex(cdr_ctx* ctx, void* stream, int loss_kind, 
     unsigned* tk = fused_finish ? ctx->tickets : nullptr;
     uint4* zs; int64_t zn;
     cdr_take_scrub(ctx, &zs, &zn);
-    if (same) { DISPATCH_LPR(lpr, point_fwd_pair_kernel<L, true><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(loss_kind, a, D, ctx->partials, tk, w, total, zs, zn)); }
-    else { DISPATCH_LPR(lpr, point_fwd_pair_kernel<L, false><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(loss_kind, a, D, ctx->partials, tk, w, total, zs, zn)); }
+    DISPATCH_LPR(lpr, {
+        auto kern = same ? point_fwd_pair_kernel<L, true> : point_fwd_pair_kernel<L, false>;
+        kern<<<dim3(grid, 2), dim3(kBlock), 0, s>>>(loss_kind, a, D, ctx->partials, tk, w, total, zs, zn);
+    });
     CDR_LAUNCH_CHECK();
     if (!fused_finish) loss_finish_pair_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, a, w, total);
     CDR_LAUNCH_CHECK();

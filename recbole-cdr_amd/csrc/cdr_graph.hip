@@ -11,7 +11,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 
 inline int grid_cap(int64_t blocks) {
     const int64_t cap = CDR_NUM_CU * 8;

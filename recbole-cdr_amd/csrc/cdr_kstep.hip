@@ -24,7 +24,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 
 struct item_rec { int32_t urow; float coef; };
 
@@ -157,11 +156,7 @@ __device__ __forceinline__ void kstep_finish_body(const double* __restrict__ par
                                                   float reg_weight, float* __restrict__ out9, int64_t* bump_a, int64_t* bump_b,
                                                   double* smem) {
     double acc[3] = {0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2];
-    }
-    block_sum_d<3>(acc, smem);
+    sum_partials<3, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) {
         const float main_loss = (float)(acc[0] / (double)B);
         const float nu = (float)sqrt(acc[1]), ni = (float)sqrt(acc[2]);
@@ -402,18 +397,15 @@ int apply2(cdr_ctx* ctx, hipStream_t s, int opt, float* table, float* exp_avg, f
         CDR_HIP(cdr_zero_u32(counters, 4, s));
     }
     cdr_time_scope ts(ctx, tag, s);
-#define A2 table, exp_avg, exp_avg_sq, D, keys, perm, n, G, rec, Usrc, reg_limit, reg_coef, hp, sd, counters, longs, pieces
-    if (opt == 0) { DISPATCH_LPR(lpr, apply2_kernel<L, 0, SRC><<<dim3(grid), dim3(kBlock), 0, s>>>(A2)); }
-    else { DISPATCH_LPR(lpr, apply2_kernel<L, 1, SRC><<<dim3(grid), dim3(kBlock), 0, s>>>(A2)); }
-#undef A2
+    DISPATCH_LPR_OPT(lpr, opt, apply2_kernel<L, O, SRC><<<dim3(grid), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys, perm, n, G, rec, Usrc, reg_limit, reg_coef, hp, sd,
+                                                                                           counters, longs, pieces));
     CDR_LAUNCH_CHECK();
     if (may_have_long) {
         const int gp = grid_for(piece_cap < 16384 ? piece_cap : 16384, kBlock / lpr);
         DISPATCH_LPR(lpr, piece_sum2_kernel<L, SRC><<<dim3(gp), dim3(kBlock), 0, s>>>(D, perm, G, rec, Usrc, reg_limit, counters, pieces, partial, pcnt));
         CDR_LAUNCH_CHECK();
         const int gl = grid_for(long_cap < 4096 ? long_cap : 4096, kBlock / lpr);
-        if (opt == 0) { DISPATCH_LPR(lpr, long_finish2_kernel<L, 0><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys, reg_coef, hp, sd, counters, longs, partial, pcnt)); }
-        else { DISPATCH_LPR(lpr, long_finish2_kernel<L, 1><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys, reg_coef, hp, sd, counters, longs, partial, pcnt)); }
+        DISPATCH_LPR_OPT(lpr, opt, long_finish2_kernel<L, O><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys, reg_coef, hp, sd, counters, longs, partial, pcnt));
         CDR_LAUNCH_CHECK();
     }
     return CDR_OK;

@@ -27,7 +27,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kMaxTab = 4;
 
 struct lz_table {

@@ -11,7 +11,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kWgPart = 32 * 32 + 32;                          // floats of one partial: a dW tile + its bias row
 constexpr int kWgWaves = 8, kWgBlock = 64 * kWgWaves;     // linear_wgrad_small_kernel: waves (= batch-row slices) per 32 x 32 tile
 

@@ -55,6 +55,19 @@ __device__ __forceinline__ void store_partials_sys(double* partials, const doubl
     for (int i = 0; i < N; ++i) cdr_store_sys(o + i, acc[i]);
 }
 
+// A finishing block of BLOCK threads: the N sums over the nblocks slots that store_partials filled (thread t adds slots t, t + BLOCK, ...
+// in that order, then block_sum_d<N>), valid in thread 0.  BLOCK is the launch's block size as a constant -- read from blockDim.x the loop
+// compiles to other code.  SYS: the slots were written by store_partials_sys and are read past the L2s.
+template <int N, int BLOCK, bool SYS = false>
+__device__ __forceinline__ void sum_partials(const double* partials, int nblocks, double (&acc)[N], double* smem) {
+    for (int b = threadIdx.x; b < nblocks; b += BLOCK) {
+        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
+#pragma unroll
+        for (int i = 0; i < N; ++i) acc[i] += SYS ? cdr_load_sys(o + i) : o[i];
+    }
+    block_sum_d<N>(acc, smem);
+}
+
 __device__ __forceinline__ float4 scale4(float g, float4 a) { return make_float4(g * a.x, g * a.y, g * a.z, g * a.w); }
 __device__ __forceinline__ float4 neg4(float4 a) { return make_float4(0.f - a.x, 0.f - a.y, 0.f - a.z, 0.f - a.w); }
 __device__ __forceinline__ float4 neg_scale4(float g, float4 a) { return neg4(scale4(g, a)); }

@@ -20,8 +20,8 @@
 
 namespace {
 
-constexpr int kBlock = 512;        // 8 waves: one wave per list entry; 80 registers: three workgroups (six waves per SIMD) on a CU
-constexpr int kEPB = kBlock / 64;   // list entries per workgroup
+constexpr int kOrdBlock = 512;        // 8 waves: one wave per list entry; 80 registers: three workgroups (six waves per SIMD) on a CU
+constexpr int kEPB = kOrdBlock / 64;   // list entries per workgroup
 constexpr int kIT = 512;            // list positions a wave tests per trip
 constexpr int kSL = 2;              // occurrences per lane group and round (4: 115 registers, one workgroup per CU less -- slower, r05_ab_ordered_ksl.txt)
 constexpr int kQMax = 4 * kSL;      // later occurrences a wave adds per round, at most
@@ -45,7 +45,7 @@ __device__ __forceinline__ float4 term_of(const cdr_ord_seg& S, float go, float 
     return t;
 }
 
-__global__ __launch_bounds__(kBlock) void ordered_bwd_kernel(ord_args a, int D) {
+__global__ __launch_bounds__(kOrdBlock) void ordered_bwd_kernel(ord_args a, int D) {
     extern __shared__ uint32_t lo[];
     __shared__ int wide;                                          // some id of the list does not fit 32 bits: confirm hits on 64
     __shared__ cdr_ord_list L;                                    // the list's descriptor: indexed by lane-dependent segment numbers below
@@ -99,13 +99,13 @@ __global__ __launch_bounds__(kBlock) void ordered_bwd_kernel(ord_args a, int D) 
         for (int s = 0; s < L.nseg; ++s) {
             const int n = (int)L.seg[s].n;
             const int64_t* __restrict__ ids = L.seg[s].ids;
-            for (int jj0 = threadIdx.x; jj0 < n; jj0 += kBlock * SU) {      // SU loads on their way per thread, then the LDS stores
+            for (int jj0 = threadIdx.x; jj0 < n; jj0 += kOrdBlock * SU) {      // SU loads on their way per thread, then the LDS stores
                 int64_t v[SU];
 #pragma unroll
-                for (int q = 0; q < SU; ++q) { const int j = jj0 + q * kBlock; v[q] = j < n ? ids[j] : 0; }
+                for (int q = 0; q < SU; ++q) { const int j = jj0 + q * kOrdBlock; v[q] = j < n ? ids[j] : 0; }
 #pragma unroll
                 for (int q = 0; q < SU; ++q) {
-                    const int j = jj0 + q * kBlock;
+                    const int j = jj0 + q * kOrdBlock;
                     if (j < n) { lo[off + j] = (uint32_t)v[q]; w |= ((uint64_t)v[q] >> 32) != 0; }
                 }
             }
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void ordered_bwd_kernel(ord_args a, int D) 
             if (threadIdx.x == 0) seg_end[s] = off;
         }
         if (threadIdx.x == 0) for (int s = L.nseg; s < CDR_ORD_MAX_SEGS; ++s) seg_end[s] = 0x7fffffff;
-        for (int j = N + threadIdx.x; j < Npad; j += kBlock) lo[j] = 0xffffffffu;      // a padding hit fails the j < N test
+        for (int j = N + threadIdx.x; j < Npad; j += kOrdBlock) lo[j] = 0xffffffffu;      // a padding hit fails the j < N test
         if (w) wide = 1;
         if ((int)threadIdx.x < L.nseg) {
             const cdr_ord_seg& S = L.seg[threadIdx.x];
@@ -315,7 +315,7 @@ extern "C" int cdr_ordered_bwd(void* stream, int D, const cdr_ord_list* lists, i
         CDR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ordered_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(CDR_ORD_MAX_TOTAL * 4 + 1024)));
     }
-    ordered_bwd_kernel<<<dim3(grid, used), dim3(kBlock), lds, (hipStream_t)stream>>>(a, D);
+    ordered_bwd_kernel<<<dim3(grid, used), dim3(kOrdBlock), lds, (hipStream_t)stream>>>(a, D);
     CDR_LAUNCH_CHECK();
     return CDR_OK;
 }

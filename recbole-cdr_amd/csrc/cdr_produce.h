@@ -6,8 +6,6 @@
 
 namespace cdr_produce {
 
-constexpr int kBlock = 256;
-
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

@@ -24,7 +24,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 
 struct tok_src {
     const uint8_t* bytes[2];

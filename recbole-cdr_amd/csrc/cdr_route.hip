@@ -8,7 +8,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 
 inline int grid_for(int64_t n) {
     int64_t g = (n + kBlock - 1) / kBlock;

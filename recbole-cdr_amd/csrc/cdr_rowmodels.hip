@@ -9,7 +9,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / CDR_WAVE;
 constexpr int kMaxJ = CDR_ROWMODEL_MAX_DIM / CDR_WAVE;       // registers per lane along D
 

@@ -2,12 +2,12 @@
 // (K7), activation backward, column sums, MSE, exact dense Adam (K13).  All HBM-bound: 16 B per lane, whole rows per
 // wave-instruction, grid capped at 8 blocks per CU with a grid stride.
 #include "cdr_common.h"
+#include "cdr_loss_math.h"
 #include "cdr_adam_math.h"
 #include "cdr_produce.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 
 inline int grid_cap(int64_t blocks) {
     const int64_t cap = CDR_NUM_CU * 8;
@@ -215,8 +215,7 @@ __global__ __launch_bounds__(kBlock) void mse_finish_kernel(const double* __rest
                                                             float* __restrict__ out1) {
     __shared__ double smem[4];
     double acc[1] = {0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) acc[0] += partials[(size_t)b * CDR_PARTIAL_STRIDE];
-    block_sum_d<1>(acc, smem);
+    sum_partials<1, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) out1[0] = (float)(acc[0] / (double)n);
 }
 

@@ -11,7 +11,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 using cdr_produce::mix64;
 using cdr_produce::draw_uniform;
 using cdr_produce::draw_alias;

@@ -32,7 +32,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kUnroll = 4;
 
 // EmbLoss norms from a per-row cache ("EmbLoss norms from a per-row cache" below): floats per record.  Slot 0 = ||W[r]||^2, the rest is
@@ -213,11 +212,7 @@ __global__ __launch_bounds__(kBlock) void step_finish_kernel(const double* __res
                                                              float reg_weight, float* __restrict__ out6) {
     __shared__ double smem[3 * (kBlock / 64)];
     double acc[3] = {0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2];
-    }
-    block_sum_d<3>(acc, smem);
+    sum_partials<3, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) {
         const float main_loss = (float)(acc[0] / (double)B);
         const float nu = (float)sqrt(acc[1]), ni = (float)sqrt(acc[2]);
@@ -554,6 +549,21 @@ __device__ __forceinline__ float4 upd_math(float4 w, float4& m, float4& v, float
                        w.z - cdr_adam_term(m.z, v.z, h.step_size, h.bc2_sqrt, h.eps), w.w - cdr_adam_term(m.w, v.w, h.step_size, h.bc2_sqrt, h.eps));
 }
 
+// A lane's chunk, at float offset `off`, of a row of table T.  row_moments: the two Adam moments (SGD: nothing is read, m and v keep what
+// they hold); the caller's `if` says for which rows.  row_store: moments and weights back in place.  `if constexpr` and references to m
+// and v, so that an SGD kernel's code never names them: passed by value they cost the k-major SGD kernels registers and split their
+// 16-byte stores.  The step around them stays written out in the kernels -- `if (single) { upd_math; row_store } else spill the gradient
+// row`: as one function it changed the code of every kernel that used it (tools/kernel_diff.py).
+template <int LPR, int OPT>
+__device__ __forceinline__ void row_moments(const tab_ptrs& T, int64_t off, float4& m, float4& v) {
+    if constexpr (OPT == 1) { m = ld4n<(LPR >= 32)>(T.M + off); v = ld4n<(LPR >= 32)>(T.V + off); }
+}
+template <int LPR, int OPT>
+__device__ __forceinline__ void row_store(const tab_ptrs& T, int64_t off, float4 w, const float4& m, const float4& v) {
+    if constexpr (OPT == 1) { st4n<(LPR >= 32)>(T.M + off, m); st4n<(LPR >= 32)>(T.V + off, v); }
+    st4n<(LPR >= 32)>(T.W + off, w);
+}
+
 // partials[block] = {sum_b ||U[uid[b]]||^2, sum_b ||I[pid[b]]||^2}: the EmbLoss norms of the batch (emcdr.py:129-131: reg_loss(user_e, pos_e))
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void batch_norms_kernel(const float* __restrict__ U, const float* __restrict__ I, int D,
@@ -763,11 +773,7 @@ __global__ __launch_bounds__(kBlock) void coef_finish_kernel(const double* __res
         cdr_adam_hp((double)st, lr, b1, b2, hp_dev[2 * threadIdx.x], hp_dev[2 * threadIdx.x + 1]);
     }
     double acc[2] = {0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1];
-    }
-    block_sum_d<2>(acc, smem);
+    sum_partials<2, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) {
         if (norms2) { acc[0] = (double)norms2[0]; acc[1] = (double)norms2[1]; }
         const float nu = (float)sqrt((double)kmul * acc[0]), ni = (float)sqrt((double)kmul * acc[1]);
@@ -787,11 +793,7 @@ __global__ __launch_bounds__(kBlock) void step_finish_keep_kernel(const double* 
     if (zero_a && threadIdx.x >= 64 && threadIdx.x < 68) zero_a[threadIdx.x - 64] = 0u;
     if (zero_b && threadIdx.x >= 128 && threadIdx.x < 132) zero_b[threadIdx.x - 128] = 0u;
     double acc[3] = {0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2];
-    }
-    block_sum_d<3>(acc, smem);
+    sum_partials<3, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) {
         if (norms2) { acc[1] = (double)norms2[0]; acc[2] = (double)norms2[1]; }
         const float main_loss = (float)(acc[0] / (double)B);
@@ -806,11 +808,7 @@ __global__ __launch_bounds__(kBlock) void step_finish_keep_kernel(const double* 
 __global__ __launch_bounds__(kBlock) void norm_sums_kernel(const double* __restrict__ partials, int nblocks, float* __restrict__ sums3) {
     __shared__ double smem[2 * (kBlock / 64)];
     double acc[2] = {0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1];
-    }
-    block_sum_d<2>(acc, smem);
+    sum_partials<2, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) { sums3[0] = 0.f; sums3[1] = (float)acc[0]; sums3[2] = (float)acc[1]; }
 }
 
@@ -821,11 +819,7 @@ __global__ __launch_bounds__(kBlock) void shard_sums_kernel(const double* __rest
     __shared__ double smem[3 * (kBlock / 64)];
     if (zero_a && threadIdx.x >= 64 && threadIdx.x < 68) zero_a[threadIdx.x - 64] = 0u;
     double acc[3] = {0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2];
-    }
-    block_sum_d<3>(acc, smem);
+    sum_partials<3, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) { out9[6] = (float)acc[0]; out9[7] = (float)acc[1]; out9[8] = (float)acc[2]; }
 }
 
@@ -888,11 +882,9 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kernel(tab_ptrs TU, tab_
             p[r] = ok ? ld4n<(LPR >= 32)>(TI.W + op[r]) : z4;
             n[r] = ok ? ld4n<(LPR >= 32)>(TI.W + on[r]) : z4;
             um[r] = uv[r] = pm[r] = pv[r] = nm[r] = nv[r] = z4;
-            if (OPT == 1) {
-                if (ok && fu[r]) { um[r] = ld4n<(LPR >= 32)>(TU.M + ou[r]); uv[r] = ld4n<(LPR >= 32)>(TU.V + ou[r]); }
-                if (!SH && ok && fp[r]) { pm[r] = ld4n<(LPR >= 32)>(TI.M + op[r]); pv[r] = ld4n<(LPR >= 32)>(TI.V + op[r]); }
-                if (!SH && ok && fn[r]) { nm[r] = ld4n<(LPR >= 32)>(TI.M + on[r]); nv[r] = ld4n<(LPR >= 32)>(TI.V + on[r]); }
-            }
+            if (ok && fu[r]) row_moments<LPR, OPT>(TU, ou[r], um[r], uv[r]);
+            if (!SH && ok && fp[r]) row_moments<LPR, OPT>(TI, op[r], pm[r], pv[r]);
+            if (!SH && ok && fn[r]) row_moments<LPR, OPT>(TI, on[r], nm[r], nv[r]);
         }
         uint32_t ju[UN], jp[UN], jn[UN], gl[UN];
         float yd[UN];
@@ -933,6 +925,7 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kernel(tab_ptrs TU, tab_
             // ---- user row
             if (fu[r]) {
                 const float4 wu = upd_math<OPT>(u[r], um[r], uv[r], gu, cu, hu);
+                // row_store, in place: the helper changed the code of the SH kernel at 64 lanes per row (Adam)
                 if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TU.M + ou[r], um[r]); st4n<(LPR >= 32)>(TU.V + ou[r], uv[r]); } st4n<(LPR >= 32)>(TU.W + ou[r], wu); }
                 if (NC) norm_rec_store<LPR>(NU + (int64_t)iu[r] * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wu)), sub);
             } else if (ok) st4n<(LPR >= 32)>(GU + t * D + 4 * sub, gu);
@@ -944,12 +937,12 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kernel(tab_ptrs TU, tab_
             } else {
             if (fp[r]) {
                 const float4 wp = upd_math<OPT>(p[r], pm[r], pv[r], gi, ci, hi);
-                if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + op[r], pm[r]); st4n<(LPR >= 32)>(TI.V + op[r], pv[r]); } st4n<(LPR >= 32)>(TI.W + op[r], wp); }
+                if (live) row_store<LPR, OPT>(TI, op[r], wp, pm[r], pv[r]);
                 if (NC) norm_rec_store<LPR>(NI + (int64_t)ip[r] * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wp)), sub);
             }
             if (fn[r]) {
                 const float4 wn = upd_math<OPT>(n[r], nm[r], nv[r], make_float4(0.f - gi.x, 0.f - gi.y, 0.f - gi.z, 0.f - gi.w), 0.f, hi);
-                if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + on[r], nm[r]); st4n<(LPR >= 32)>(TI.V + on[r], nv[r]); } st4n<(LPR >= 32)>(TI.W + on[r], wn); }
+                if (live) row_store<LPR, OPT>(TI, on[r], wn, nm[r], nv[r]);
                 if (NC) norm_rec_store<LPR>(NI + (int64_t)in[r] * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wn)), sub);
             }
             }
@@ -1002,10 +995,8 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kernel(int loss_kind, 
         const int64_t ou = (int64_t)iu * D + 4 * sub, oi = (int64_t)ii * D + 4 * sub;
         float4 u = live ? ld4n<(LPR >= 32)>(TU.W + ou) : z4, v = live ? ld4n<(LPR >= 32)>(TI.W + oi) : z4;
         float4 um = z4, uv = z4, im = z4, iv = z4;
-        if (OPT == 1) {
-            if (live && fu) { um = ld4n<(LPR >= 32)>(TU.M + ou); uv = ld4n<(LPR >= 32)>(TU.V + ou); }
-            if (live && fi) { im = ld4n<(LPR >= 32)>(TI.M + oi); iv = ld4n<(LPR >= 32)>(TI.V + oi); }
-        }
+        if (live && fu) row_moments<LPR, OPT>(TU, ou, um, uv);
+        if (live && fi) row_moments<LPR, OPT>(TI, oi, im, iv);
         uint32_t ju, ji, gl; float yn, xn = 0.f;
         {
             const int64_t tn = t + TG, tc = tn < B ? tn : B - 1;
@@ -1024,11 +1015,11 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kernel(int loss_kind, 
         const float4 gi = make_float4(g * u.x, g * u.y, g * u.z, g * u.w);
         if (fu) {
             const float4 wu = upd_math<OPT>(u, um, uv, gu, cu, hu);
-            if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TU.M + ou, um); st4n<(LPR >= 32)>(TU.V + ou, uv); } st4n<(LPR >= 32)>(TU.W + ou, wu); }
+            if (live) row_store<LPR, OPT>(TU, ou, wu, um, uv);
         } else if (live) st4n<(LPR >= 32)>(GU + t * D + 4 * sub, gu);
         if (fi) {
             const float4 wi = upd_math<OPT>(v, im, iv, gi, ci, hi);
-            if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + oi, im); st4n<(LPR >= 32)>(TI.V + oi, iv); } st4n<(LPR >= 32)>(TI.W + oi, wi); }
+            if (live) row_store<LPR, OPT>(TI, oi, wi, im, iv);
         } else if (live) st4n<(LPR >= 32)>(GI + t * D + 4 * sub, gi);
         if (sub == 0) { acc[0] += (double)l; acc[1] += (double)su; acc[2] += (double)si; }
         iu = ju; ii = ji; fl = gl; yl = yn; xd = xn;
@@ -1072,10 +1063,8 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kmajor_kernel(tab_ptrs T
         float4 u = z4, p = z4, um = z4, uv = z4, pm = z4, pv = z4;
         if (live) {
             u = ld4n<(LPR >= 32)>(TU.W + ou); p = ld4n<(LPR >= 32)>(TI.W + op);
-            if (OPT == 1) {
-                if (fu) { um = ld4n<(LPR >= 32)>(TU.M + ou); uv = ld4n<(LPR >= 32)>(TU.V + ou); }
-                if (fp) { pm = ld4n<(LPR >= 32)>(TI.M + op); pv = ld4n<(LPR >= 32)>(TI.V + op); }
-            }
+            if (fu) row_moments<LPR, OPT>(TU, ou, um, uv);
+            if (fp) row_moments<LPR, OPT>(TI, op, pm, pv);
         }
         float4 gu = z4;
         float gs = 0.f, dp = 0.f;
@@ -1093,7 +1082,7 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kmajor_kernel(tab_ptrs T
             for (int c = 0; c < KC; ++c) {
                 n[c] = live ? ld4n<(LPR >= 32)>(TI.W + on[c]) : z4;
                 nm[c] = nv[c] = z4;
-                if (OPT == 1 && live && fn[c]) { nm[c] = ld4n<(LPR >= 32)>(TI.M + on[c]); nv[c] = ld4n<(LPR >= 32)>(TI.V + on[c]); }
+                if (live && fn[c]) row_moments<LPR, OPT>(TI, on[c], nm[c], nv[c]);
             }
             if (m0 == 0) {
                 dp = group_sum<LPR>(dot4(u, p));
@@ -1112,19 +1101,19 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kmajor_kernel(tab_ptrs T
                     const float4 gn = make_float4(0.f - g * u.x, 0.f - g * u.y, 0.f - g * u.z, 0.f - g * u.w);
                     if (fn[c]) {
                         const float4 wn = upd_math<OPT>(n[c], nm[c], nv[c], gn, 0.f, hi);
-                        if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + on[c], nm[c]); st4n<(LPR >= 32)>(TI.V + on[c], nv[c]); } st4n<(LPR >= 32)>(TI.W + on[c], wn); }
+                        if (live) row_store<LPR, OPT>(TI, on[c], wn, nm[c], nv[c]);
                     } else if (live) st4n<(LPR >= 32)>(GI + (S + j + (int64_t)(m0 + c) * S) * D + 4 * sub, gn);
                 }
             }
         }
         if (fu) {
             const float4 wu = upd_math<OPT>(u, um, uv, gu, cu, hu);
-            if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TU.M + ou, um); st4n<(LPR >= 32)>(TU.V + ou, uv); } st4n<(LPR >= 32)>(TU.W + ou, wu); }
+            if (live) row_store<LPR, OPT>(TU, ou, wu, um, uv);
         } else if (live) st4n<(LPR >= 32)>(GU + j * D + 4 * sub, gu);
         const float4 gp = make_float4(gs * u.x, gs * u.y, gs * u.z, gs * u.w);
         if (fp) {
             const float4 wp = upd_math<OPT>(p, pm, pv, gp, ci, hi);
-            if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + op, pm); st4n<(LPR >= 32)>(TI.V + op, pv); } st4n<(LPR >= 32)>(TI.W + op, wp); }
+            if (live) row_store<LPR, OPT>(TI, op, wp, pm, pv);
         } else if (live) st4n<(LPR >= 32)>(GI + j * D + 4 * sub, gp);
     }
     block_sum_d<3>(acc, smem);
@@ -1171,11 +1160,7 @@ __global__ __launch_bounds__(kBlock) void point_coef_kmajor_kernel(const double*
     __shared__ double smem[2 * (kBlock / 64)];
     if (zero4 && threadIdx.x >= 64 && threadIdx.x < 68) zero4[threadIdx.x - 64] = 0u;
     double acc[2] = {0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1];
-    }
-    block_sum_d<2>(acc, smem);
+    sum_partials<2, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) {
         const float nu = (float)sqrt(acc[0]), ni = (float)sqrt(acc[1]);
         out9[4] = embloss_coef(reg_weight, B, nu);
@@ -1207,7 +1192,7 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kmajor_kernel(int loss
         float4 u = z4, um = z4, uv = z4;
         if (live) {
             u = ld4n<(LPR >= 32)>(TU.W + ou);
-            if (OPT == 1 && fu) { um = ld4n<(LPR >= 32)>(TU.M + ou); uv = ld4n<(LPR >= 32)>(TU.V + ou); }
+            if (fu) row_moments<LPR, OPT>(TU, ou, um, uv);
         }
         float4 gu = z4;
         float su = 0.f;
@@ -1225,7 +1210,7 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kmajor_kernel(int loss
             for (int c = 0; c < KC; ++c) {
                 v[c] = live ? ld4n<(LPR >= 32)>(TI.W + oi[c]) : z4;
                 vm[c] = vv[c] = z4;
-                if (OPT == 1 && live && fi[c]) { vm[c] = ld4n<(LPR >= 32)>(TI.M + oi[c]); vv[c] = ld4n<(LPR >= 32)>(TI.V + oi[c]); }
+                if (live && fi[c]) row_moments<LPR, OPT>(TI, oi[c], vm[c], vv[c]);
             }
             if (r0 == 0) su = group_sum<LPR>(dot4(u, u));
 #pragma unroll
@@ -1241,7 +1226,7 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kmajor_kernel(int loss
                     const float4 gi = make_float4(g * u.x, g * u.y, g * u.z, g * u.w);
                     if (fi[c]) {
                         const float4 wi = upd_math<OPT>(v[c], vm[c], vv[c], gi, ci, hi);
-                        if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + oi[c], vm[c]); st4n<(LPR >= 32)>(TI.V + oi[c], vv[c]); } st4n<(LPR >= 32)>(TI.W + oi[c], wi); }
+                        if (live) row_store<LPR, OPT>(TI, oi[c], wi, vm[c], vv[c]);
                     } else if (live) st4n<(LPR >= 32)>(GI + (j + (int64_t)(r0 + c) * S) * D + 4 * sub, gi);
                 }
             }
@@ -1249,7 +1234,7 @@ __global__ __launch_bounds__(kBlock) void point_fwd_apply_kmajor_kernel(int loss
         if (sub == 0) acc[1] += (double)(1 + k) * (double)su;
         if (fu) {
             const float4 wu = upd_math<OPT>(u, um, uv, gu, cu, hu);
-            if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TU.M + ou, um); st4n<(LPR >= 32)>(TU.V + ou, uv); } st4n<(LPR >= 32)>(TU.W + ou, wu); }
+            if (live) row_store<LPR, OPT>(TU, ou, wu, um, uv);
         } else if (live) st4n<(LPR >= 32)>(GU + j * D + 4 * sub, gu);
     }
     block_sum_d<3>(acc, smem);
@@ -1306,6 +1291,7 @@ __device__ __forceinline__ void rowwise_apply_dups_body(float* __restrict__ W, f
                                                         unsigned* __restrict__ counters, seg_long* __restrict__ longs,
                                                         seg_piece* __restrict__ pieces, float* __restrict__ n2 = nullptr) {
     HP_FROM_DEV(hp);
+    const tab_ptrs T{W, Mo, Vo};
     constexpr int GPB = kBlock / LPR;
     constexpr int SU = 4;                                 // segments in flight per lane group
     const int sub = threadIdx.x % LPR;
@@ -1346,7 +1332,7 @@ __device__ __forceinline__ void rowwise_apply_dups_body(float* __restrict__ W, f
                 w[j] = m[j] = v[j] = g0[j] = g1[j] = z4;
                 if (ok[j] && live) {
                     w[j] = ld4n<(LPR >= 32)>(W + off[j]);
-                    if (OPT == 1) { m[j] = ld4n<(LPR >= 32)>(Mo + off[j]); v[j] = ld4n<(LPR >= 32)>(Vo + off[j]); }
+                    row_moments<LPR, OPT>(T, off[j], m[j], v[j]);
                     const bool n0 = SIGNED && (int64_t)o0[j] >= neg_start, n1 = SIGNED && (int64_t)o1[j] >= neg_start;
                     g0[j] = ld4n<(LPR >= 32)>(G + (n0 ? (int64_t)o0[j] - neg_start : (int64_t)o0[j]) * D + 4 * sub);
                     g1[j] = ld4n<(LPR >= 32)>(G + (n1 ? (int64_t)o1[j] - neg_start : (int64_t)o1[j]) * D + 4 * sub);
@@ -1390,10 +1376,7 @@ __device__ __forceinline__ void rowwise_apply_dups_body(float* __restrict__ W, f
                     }
                 }
                 const float4 wn = upd_math<OPT>(w[j], m[j], v[j], acc, c * (float)cnt, hp);
-                if (live) {
-                    if (OPT == 1) { st4n<(LPR >= 32)>(Mo + off[j], m[j]); st4n<(LPR >= 32)>(Vo + off[j], v[j]); }
-                    st4n<(LPR >= 32)>(W + off[j], wn);
-                }
+                if (live) row_store<LPR, OPT>(T, off[j], wn, m[j], v[j]);
                 if (NC) norm_rec_store<LPR>(n2 + (int64_t)row[j] * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wn)), sub);
             }
         }
@@ -1407,7 +1390,7 @@ __device__ __forceinline__ void rowwise_apply_dups_body(float* __restrict__ W, f
                 const int64_t off = (int64_t)row * D + 4 * ch;
                 const float4 w = ld4n<(LPR >= 32)>(W + off);
                 float4 m = make_float4(0.f, 0.f, 0.f, 0.f), v = m;
-                if (OPT == 1) { m = ld4n<(LPR >= 32)>(Mo + off); v = ld4n<(LPR >= 32)>(Vo + off); }
+                row_moments<LPR, OPT>(T, off, m, v);
                 float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
                 int cnt = 0;
                 for (int64_t e = q; e < n && keys[e] == row; ++e) {
@@ -1419,8 +1402,7 @@ __device__ __forceinline__ void rowwise_apply_dups_body(float* __restrict__ W, f
                     cnt += (o < reg_limit) ? 1 : 0;
                 }
                 const float4 wn = upd_math<OPT>(w, m, v, acc, c * (float)cnt, hp);
-                if (OPT == 1) { st4n<(LPR >= 32)>(Mo + off, m); st4n<(LPR >= 32)>(Vo + off, v); }
-                st4n<(LPR >= 32)>(W + off, wn);
+                row_store<LPR, OPT>(T, off, wn, m, v);
             }
         }
     }
@@ -1737,11 +1719,7 @@ __global__ __launch_bounds__(kBlock) void shard_sums2_kernel(const double* __res
     if (zero_a && threadIdx.x >= 64 && threadIdx.x < 68) zero_a[threadIdx.x - 64] = 0u;
     if (zero_b && threadIdx.x >= 128 && threadIdx.x < 132) zero_b[threadIdx.x - 128] = 0u;
     double acc[3] = {0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2];
-    }
-    block_sum_d<3>(acc, smem);
+    sum_partials<3, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) out9[6] = (float)acc[0];
 }
 // The owner's apply of ONE ascending duplicate-free run (what a single requester sends): position q updates row ids[q] with gradient row
@@ -1750,6 +1728,7 @@ template <int LPR, int OPT>
 __global__ __launch_bounds__(kBlock) void apply_run_kernel(float* __restrict__ W, float* __restrict__ Mo, float* __restrict__ Vo, int D,
                                                            const int64_t* __restrict__ ids, int64_t n, const float* __restrict__ G, apply_hp hp) {
     HP_FROM_DEV(hp);
+    const tab_ptrs T{W, Mo, Vo};
     constexpr int GPB = kBlock / LPR, UN = 2;
     const int sub = threadIdx.x % LPR;
     const int64_t gg = (int64_t)blockIdx.x * GPB + threadIdx.x / LPR;
@@ -1770,7 +1749,7 @@ __global__ __launch_bounds__(kBlock) void apply_run_kernel(float* __restrict__ W
             w[j] = m[j] = v[j] = g[j] = z4;
             if (ok[j]) {
                 w[j] = ld4n<(LPR >= 32)>(W + off[j]); g[j] = ld4n<(LPR >= 32)>(G + q * D + 4 * sub);
-                if (OPT == 1) { m[j] = ld4n<(LPR >= 32)>(Mo + off[j]); v[j] = ld4n<(LPR >= 32)>(Vo + off[j]); }
+                row_moments<LPR, OPT>(T, off[j], m[j], v[j]);
             }
         }
 #pragma unroll
@@ -1779,8 +1758,7 @@ __global__ __launch_bounds__(kBlock) void apply_run_kernel(float* __restrict__ W
             // (0 + g first: the segmented apply's accumulator starts at zero -- same bits, also for g = -0)
             const float4 acc = make_float4(0.f + g[j].x, 0.f + g[j].y, 0.f + g[j].z, 0.f + g[j].w);
             const float4 wn = upd_math<OPT>(w[j], m[j], v[j], acc, 0.f, hp);
-            if (OPT == 1) { st4n<(LPR >= 32)>(Mo + off[j], m[j]); st4n<(LPR >= 32)>(Vo + off[j], v[j]); }
-            st4n<(LPR >= 32)>(W + off[j], wn);
+            row_store<LPR, OPT>(T, off[j], wn, m[j], v[j]);
         }
     }
 }
@@ -2030,13 +2008,10 @@ extern "C" int cdr_bpr_fwd_grad(cdr_ctx* ctx, void* stream, const float* user_ta
     const int grid = grid_for((B + kUnroll - 1) / kUnroll, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_GRAD, s);
-        if (scatter) {
-            DISPATCH_LPR(lpr, bpr_fwd_grad_kernel<L, true><<<dim3(grid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, nid,
-                                                                                                 B, gamma, invB, GU, GP, ctx->partials));
-        } else {
-            DISPATCH_LPR(lpr, bpr_fwd_grad_kernel<L, false><<<dim3(grid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, nid,
-                                                                                                  B, gamma, invB, GU, GP, ctx->partials));
-        }
+        DISPATCH_LPR(lpr, {
+            auto kern = scatter ? bpr_fwd_grad_kernel<L, true> : bpr_fwd_grad_kernel<L, false>;
+            kern<<<dim3(grid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, nid, B, gamma, invB, GU, GP, ctx->partials);
+        });
     }
     CDR_LAUNCH_CHECK();
     step_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B_mean, reg_weight, out6);
@@ -2237,22 +2212,23 @@ extern "C" int cdr_rowwise_apply(cdr_ctx* ctx, void* stream, int opt, float* tab
         CDR_HIP(cdr_zero_u32(sc.counters, 4, s));
     }
     cdr_time_scope ts(ctx, is_signed ? CDR_TAG_APPLY_SIGNED : CDR_TAG_APPLY_UNSIGNED, s);
-#define APPLY_ARGS table, exp_avg, exp_avg_sq, D, keys_sorted, perm, n, G, neg_start, reg_limit, reg_coef, hp, occ_ids, sc.counters, sc.longs, sc.pieces
-    if (opt == 0 && !is_signed) { DISPATCH_LPR(lpr, rowwise_apply_kernel<L, 0, false><<<dim3(grid), dim3(kBlock), 0, s>>>(APPLY_ARGS)); }
-    else if (opt == 0) { DISPATCH_LPR(lpr, rowwise_apply_kernel<L, 0, true><<<dim3(grid), dim3(kBlock), 0, s>>>(APPLY_ARGS)); }
-    else if (!is_signed) { DISPATCH_LPR(lpr, rowwise_apply_kernel<L, 1, false><<<dim3(grid), dim3(kBlock), 0, s>>>(APPLY_ARGS)); }
-    else { DISPATCH_LPR(lpr, rowwise_apply_kernel<L, 1, true><<<dim3(grid), dim3(kBlock), 0, s>>>(APPLY_ARGS)); }
-#undef APPLY_ARGS
+    DISPATCH_LPR_OPT(lpr, opt, {
+        auto kern = is_signed ? rowwise_apply_kernel<L, O, true> : rowwise_apply_kernel<L, O, false>;
+        kern<<<dim3(grid), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, perm, n, G, neg_start, reg_limit, reg_coef, hp, occ_ids,
+                                                 sc.counters, sc.longs, sc.pieces);
+    });
     CDR_LAUNCH_CHECK();
     if (ls.bytes) {
         // sized for the worst case, but a launch whose counters read 0 retires in a few microseconds
         const int gp = (int)(ls.piece_cap < 2048 ? ls.piece_cap : 2048);          // one workgroup per piece (looping past 2,048)
-        if (is_signed) { DISPATCH_LPR(lpr, seg_piece_sum_kernel<L, true><<<dim3(gp), dim3(kBlock), 0, s>>>(D, perm, G, neg_start, reg_limit, occ_ids, sc.counters, sc.pieces, sc.partial, sc.pcnt)); }
-        else { DISPATCH_LPR(lpr, seg_piece_sum_kernel<L, false><<<dim3(gp), dim3(kBlock), 0, s>>>(D, perm, G, neg_start, reg_limit, occ_ids, sc.counters, sc.pieces, sc.partial, sc.pcnt)); }
+        DISPATCH_LPR(lpr, {
+            auto kern = is_signed ? seg_piece_sum_kernel<L, true> : seg_piece_sum_kernel<L, false>;
+            kern<<<dim3(gp), dim3(kBlock), 0, s>>>(D, perm, G, neg_start, reg_limit, occ_ids, sc.counters, sc.pieces, sc.partial, sc.pcnt);
+        });
         CDR_LAUNCH_CHECK();
         const int gl = grid_for(ls.long_cap < 4096 ? ls.long_cap : 4096, kBlock / lpr);
-        if (opt == 0) { DISPATCH_LPR(lpr, seg_long_finish_kernel<L, 0><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, reg_coef, hp, sc.counters, sc.longs, sc.partial, sc.pcnt)); }
-        else { DISPATCH_LPR(lpr, seg_long_finish_kernel<L, 1><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, reg_coef, hp, sc.counters, sc.longs, sc.partial, sc.pcnt)); }
+        DISPATCH_LPR_OPT(lpr, opt, seg_long_finish_kernel<L, O><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, reg_coef, hp, sc.counters,
+                                                                                                 sc.longs, sc.partial, sc.pcnt));
         CDR_LAUNCH_CHECK();
     }
     return CDR_OK;
@@ -2370,8 +2346,7 @@ int apply_dups_pair(cdr_ctx* ctx, hipStream_t s, int opt, int D, const dups_plan
     const int grid = grid_for(nmax / 16 + 1, kBlock / lpr);          // four segments per lane group and round (apply_dups)
     {
         cdr_time_scope ts(ctx, CDR_TAG_APPLY_SIGNED, s);
-        if (opt == 0) { DISPATCH_LPR(lpr, K::template dups<L, 0><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
-        else { DISPATCH_LPR(lpr, K::template dups<L, 1><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
+        DISPATCH_LPR_OPT(lpr, opt, K::template dups<L, O><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
     }
     CDR_LAUNCH_CHECK();
     if (pl.ls[0].long_cap || pl.ls[1].long_cap) {
@@ -2381,8 +2356,7 @@ int apply_dups_pair(cdr_ctx* ctx, hipStream_t s, int opt, int D, const dups_plan
         DISPATCH_LPR(lpr, seg_piece_sum2_kernel<L><<<dim3(gp, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
         CDR_LAUNCH_CHECK();
         const int gl = grid_for(lc < 4096 ? lc : 4096, kBlock / lpr);
-        if (opt == 0) { DISPATCH_LPR(lpr, K::template long_finish<L, 0><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
-        else { DISPATCH_LPR(lpr, K::template long_finish<L, 1><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1])); }
+        DISPATCH_LPR_OPT(lpr, opt, K::template long_finish<L, O><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
         CDR_LAUNCH_CHECK();
     }
     return CDR_OK;
@@ -2434,13 +2408,10 @@ static int bpr_step_fused_impl(cdr_ctx* ctx, void* stream, int opt, float* user_
         const int ngrid = grid_for((B + 7) / 8, kBlock / lpr);
         {
             cdr_time_scope ts(ctx, CDR_TAG_BATCH_NORMS, s);
-            if (reg_weight != 0.f) {
-                DISPATCH_LPR(lpr, batch_norms_count_kernel<L, true><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, nid, B, ctx->idc_user,
-                                                                                                      ctx->idc_item, keys, (uint64_t*)ctx->idc_list, ctx->partials));
-            } else {
-                DISPATCH_LPR(lpr, batch_norms_count_kernel<L, false><<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, nid, B, ctx->idc_user,
-                                                                                                       ctx->idc_item, keys, (uint64_t*)ctx->idc_list, ctx->partials));
-            }
+            DISPATCH_LPR(lpr, {
+                auto kern = reg_weight != 0.f ? batch_norms_count_kernel<L, true> : batch_norms_count_kernel<L, false>;
+                kern<<<dim3(ngrid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, nid, B, ctx->idc_user, ctx->idc_item, keys, (uint64_t*)ctx->idc_list, ctx->partials);
+            });
         }
         CDR_LAUNCH_CHECK();
         coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, reg_weight != 0.f ? ngrid : 0, B, reg_weight, out9, 1, step_user_dev, step_item_dev, hp_dev,
@@ -2471,18 +2442,13 @@ static int bpr_step_fused_impl(cdr_ctx* ctx, void* stream, int opt, float* user_
     const int grid = grid_for((B + un - 1) / un, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FA_ARGS T.TU, T.TI, D, uid, pid, nid, (const uint32_t*)flags, B, gamma, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials
-#define FA_NC_ARGS FA_ARGS, nullptr, nullptr, NU, NI
-        if (cached) {
-            if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1, false, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_NC_ARGS)); }
-            else if (un == 1) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1, false, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_NC_ARGS)); }
-            else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 2, false, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_NC_ARGS)); }
-        }
-        else if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
-        else if (un == 1) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
-        else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 2><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
-#undef FA_NC_ARGS
-#undef FA_ARGS
+        DISPATCH_LPR_OPT(lpr, opt, {
+            constexpr int U2 = O == 1 ? 2 : 1;              // (the two-triple form exists for Adam only)
+            auto kern = cached ? (un == 2 ? bpr_fwd_apply_kernel<L, O, U2, false, false, true> : bpr_fwd_apply_kernel<L, O, 1, false, false, true>)
+                               : (un == 2 ? bpr_fwd_apply_kernel<L, O, U2> : bpr_fwd_apply_kernel<L, O, 1>);
+            kern<<<dim3(grid), dim3(kBlock), 0, s>>>(T.TU, T.TI, D, uid, pid, nid, (const uint32_t*)flags, B, gamma, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GP,
+                                                     ctx->partials, nullptr, nullptr, NU, NI);
+        });
     }
     CDR_LAUNCH_CHECK();
     dup_host sides[2];
@@ -2578,10 +2544,8 @@ extern "C" int cdr_point_step_fused(cdr_ctx* ctx, void* stream, int loss_kind, i
     const int grid = grid_for(B, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-#define PA_ARGS loss_kind, T.TU, T.TI, D, uid, iid, label, (const uint32_t*)flags, B, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials
-        if (opt == 0) { DISPATCH_LPR(lpr, point_fwd_apply_kernel<L, 0><<<dim3(grid), dim3(kBlock), 0, s>>>(PA_ARGS)); }
-        else { DISPATCH_LPR(lpr, point_fwd_apply_kernel<L, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(PA_ARGS)); }
-#undef PA_ARGS
+        DISPATCH_LPR_OPT(lpr, opt, point_fwd_apply_kernel<L, O><<<dim3(grid), dim3(kBlock), 0, s>>>(loss_kind, T.TU, T.TI, D, uid, iid, label, (const uint32_t*)flags, B,
+                                                                                                   1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials));
     }
     CDR_LAUNCH_CHECK();
     dup_host sides[2];
@@ -2625,11 +2589,12 @@ extern "C" int cdr_point_step_fused_kmajor(cdr_ctx* ctx, void* stream, int loss_
     const int grid = grid_for(S, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-#define PK_ARGS loss_kind, T.TU, T.TI, D, uid, iid, label, flags, fstride, S, k, 1.0f / (float)B, out12 + 4, T.hu, T.hi, GU, GI, ctx->partials
-        if (opt == 0) { DISPATCH_LPR(lpr, point_fwd_apply_kmajor_kernel<L, 0, 2><<<dim3(grid), dim3(kBlock), 0, s>>>(PK_ARGS)); }
-        else if (k <= 1) { DISPATCH_LPR(lpr, point_fwd_apply_kmajor_kernel<L, 1, 2><<<dim3(grid), dim3(kBlock), 0, s>>>(PK_ARGS)); }
-        else { DISPATCH_LPR(lpr, point_fwd_apply_kmajor_kernel<L, 1, 3><<<dim3(grid), dim3(kBlock), 0, s>>>(PK_ARGS)); }
-#undef PK_ARGS
+        DISPATCH_LPR_OPT(lpr, opt, {
+            constexpr int KW = O == 1 ? 3 : 2;              // item rows per round: 2; 3 for Adam when there is more than one negative
+            auto kern = k <= 1 ? point_fwd_apply_kmajor_kernel<L, O, 2> : point_fwd_apply_kmajor_kernel<L, O, KW>;
+            kern<<<dim3(grid), dim3(kBlock), 0, s>>>(loss_kind, T.TU, T.TI, D, uid, iid, label, flags, fstride, S, k, 1.0f / (float)B, out12 + 4, T.hu, T.hi, GU, GI,
+                                                     ctx->partials);
+        });
     }
     CDR_LAUNCH_CHECK();
     // duplicate rows: users over GU [S, D] with (1 + k) c_u per list occurrence (out12[9]); items over GI [S + S k, D], every occurrence
@@ -2676,10 +2641,8 @@ extern "C" int cdr_bpr_step_from_diff(cdr_ctx* ctx, void* stream, int opt, float
     const int grid = grid_for(B, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FA_ARGS T.TU, T.TI, Ds, uid, pid, nid, (const uint32_t*)flags, B, gamma, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials, diff
-        if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
-        else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
-#undef FA_ARGS
+        DISPATCH_LPR_OPT(lpr, opt, bpr_fwd_apply_kernel<L, O, 1, true><<<dim3(grid), dim3(kBlock), 0, s>>>(T.TU, T.TI, Ds, uid, pid, nid, (const uint32_t*)flags, B, gamma,
+                                                                                                          1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials, diff));
     }
     CDR_LAUNCH_CHECK();
     dup_host sides[2];
@@ -2721,10 +2684,8 @@ extern "C" int cdr_point_step_from_dot(cdr_ctx* ctx, void* stream, int loss_kind
     const int grid = grid_for(B, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-#define PA_ARGS loss_kind, T.TU, T.TI, Ds, uid, iid, label, (const uint32_t*)flags, B, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials, dot
-        if (opt == 0) { DISPATCH_LPR(lpr, point_fwd_apply_kernel<L, 0, true><<<dim3(grid), dim3(kBlock), 0, s>>>(PA_ARGS)); }
-        else { DISPATCH_LPR(lpr, point_fwd_apply_kernel<L, 1, true><<<dim3(grid), dim3(kBlock), 0, s>>>(PA_ARGS)); }
-#undef PA_ARGS
+        DISPATCH_LPR_OPT(lpr, opt, point_fwd_apply_kernel<L, O, true><<<dim3(grid), dim3(kBlock), 0, s>>>(loss_kind, T.TU, T.TI, Ds, uid, iid, label, (const uint32_t*)flags, B,
+                                                                                                         1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials, dot));
     }
     CDR_LAUNCH_CHECK();
     dup_host sides[2];
@@ -2780,10 +2741,8 @@ extern "C" int cdr_bpr_shard_local_step(cdr_ctx* ctx, void* stream, int opt, flo
     const int grid = grid_for(Bl, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FA_ARGS T.TU, T.TI, D, u_loc, ip, in, (const uint32_t*)flags, Bl, gamma, 1.0f / (float)B_global, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials
-        if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
-        else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
-#undef FA_ARGS
+        DISPATCH_LPR_OPT(lpr, opt, bpr_fwd_apply_kernel<L, O, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(T.TU, T.TI, D, u_loc, ip, in, (const uint32_t*)flags, Bl, gamma,
+                                                                                                    1.0f / (float)B_global, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials));
     }
     CDR_LAUNCH_CHECK();
     dup_host sides[2];
@@ -2911,10 +2870,9 @@ extern "C" int cdr_bpr_shard_step(cdr_ctx* ctx, void* stream, int opt, float* us
     const int grid = grid_for(Bl, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FA_ARGS T.TU, T.TI, D, u_loc, umap, umap + Bl, (const uint32_t*)flags, Bl, gamma, 1.0f / (float)B_global, out9 + 4, T.hu, T.hi, GU, GP, ctx->partials, nullptr, GS
-        if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 0, 1, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
-        else { DISPATCH_LPR(lpr, bpr_fwd_apply_kernel<L, 1, 1, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(FA_ARGS)); }
-#undef FA_ARGS
+        DISPATCH_LPR_OPT(lpr, opt, bpr_fwd_apply_kernel<L, O, 1, false, true><<<dim3(grid), dim3(kBlock), 0, s>>>(
+                                       T.TU, T.TI, D, u_loc, umap, umap + Bl, (const uint32_t*)flags, Bl, gamma, 1.0f / (float)B_global, out9 + 4, T.hu, T.hi, GU, GP,
+                                       ctx->partials, nullptr, GS));
     }
     CDR_LAUNCH_CHECK();
     dup_host sides[2];
@@ -2938,8 +2896,7 @@ extern "C" int cdr_shard_owner_apply(cdr_ctx* ctx, void* stream, int opt, float*
         const apply_hp hp = make_hp(opt, lr, beta1, beta2, eps, weight_decay, step);
         const int lpr = cdr_lpr_for(D);
         cdr_time_scope ts(ctx, CDR_TAG_APPLY_UNSIGNED, s);
-        if (opt == 0) { DISPATCH_LPR(lpr, apply_run_kernel<L, 0><<<dim3(grid_for((n + 1) / 2, kBlock / lpr)), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, ids, n, grads, hp)); }
-        else { DISPATCH_LPR(lpr, apply_run_kernel<L, 1><<<dim3(grid_for((n + 1) / 2, kBlock / lpr)), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, ids, n, grads, hp)); }
+        DISPATCH_LPR_OPT(lpr, opt, apply_run_kernel<L, O><<<dim3(grid_for((n + 1) / 2, kBlock / lpr)), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, ids, n, grads, hp));
         CDR_LAUNCH_CHECK();
         return CDR_OK;
     }
@@ -2989,11 +2946,11 @@ extern "C" int cdr_bpr_step_fused_kmajor(cdr_ctx* ctx, void* stream, int opt, fl
     const int grid = grid_for(S, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-#define FK_ARGS T.TU, T.TI, D, uid, pid, nid, flags, fstride, S, k, gamma, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials
-        if (opt == 0) { DISPATCH_LPR(lpr, bpr_fwd_apply_kmajor_kernel<L, 0, 4><<<dim3(grid), dim3(kBlock), 0, s>>>(FK_ARGS)); }
-        else if (k <= 2) { DISPATCH_LPR(lpr, bpr_fwd_apply_kmajor_kernel<L, 1, 2><<<dim3(grid), dim3(kBlock), 0, s>>>(FK_ARGS)); }
-        else { DISPATCH_LPR(lpr, bpr_fwd_apply_kmajor_kernel<L, 1, 4><<<dim3(grid), dim3(kBlock), 0, s>>>(FK_ARGS)); }
-#undef FK_ARGS
+        DISPATCH_LPR_OPT(lpr, opt, {
+            constexpr int KS = O == 1 ? 2 : 4;              // negatives per round: 4; 2 for Adam at k <= 2
+            auto kern = k <= 2 ? bpr_fwd_apply_kmajor_kernel<L, O, KS> : bpr_fwd_apply_kmajor_kernel<L, O, 4>;
+            kern<<<dim3(grid), dim3(kBlock), 0, s>>>(T.TU, T.TI, D, uid, pid, nid, flags, fstride, S, k, gamma, 1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials);
+        });
     }
     CDR_LAUNCH_CHECK();
     // duplicate rows: users over GU [S, D]; items over GI [S + B, D] (one row per occurrence of [pid | nid], signs folded in)
@@ -3094,11 +3051,7 @@ __global__ __launch_bounds__(kBlock) void pair_coef_kernel(const double* __restr
         if (hp_dev) cdr_adam_hp((double)st, lr, b1, b2, hp_dev[2 * threadIdx.x], hp_dev[2 * threadIdx.x + 1]);
     }
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
-        acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2]; acc[3] += o[3];
-    }
-    block_sum_d<4>(acc, smem);
+    sum_partials<4, kBlock>(partials, nblocks, acc, smem);
     if (threadIdx.x == 0) {
         const float n[4] = {(float)sqrt(acc[0]), (float)sqrt(acc[1]), (float)sqrt(acc[2]), (float)sqrt(acc[3])};
         for (int j = 0; j < 4; ++j) {
@@ -3145,10 +3098,8 @@ __global__ __launch_bounds__(kBlock) void point_pair_fwd_apply_kernel(int loss_k
         const int64_t ou = (int64_t)iu * D + 4 * sub, oi = (int64_t)ii * D + 4 * sub;
         float4 u = live ? ld4n<(LPR >= 32)>(TU.W + ou) : z4, v = live ? ld4n<(LPR >= 32)>(TI.W + oi) : z4;
         float4 um = z4, uv = z4, im = z4, iv = z4;
-        if (OPT == 1) {
-            if (live && fu) { um = ld4n<(LPR >= 32)>(TU.M + ou); uv = ld4n<(LPR >= 32)>(TU.V + ou); }
-            if (live && fi) { im = ld4n<(LPR >= 32)>(TI.M + oi); iv = ld4n<(LPR >= 32)>(TI.V + oi); }
-        }
+        if (live && fu) row_moments<LPR, OPT>(TU, ou, um, uv);
+        if (live && fi) row_moments<LPR, OPT>(TI, oi, im, iv);
         uint32_t ju, ji, gl; float yn;
         {
             const int64_t tn = t + TG, tc = tn < N ? tn : N - 1;
@@ -3170,13 +3121,13 @@ __global__ __launch_bounds__(kBlock) void point_pair_fwd_apply_kernel(int loss_k
         const float4 gi = make_float4(g * u.x, g * u.y, g * u.z, g * u.w);
         if (fu) {
             const float4 wu = upd_math<OPT>(u, um, uv, gu, cu, hu);
-            if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TU.M + ou, um); st4n<(LPR >= 32)>(TU.V + ou, uv); } st4n<(LPR >= 32)>(TU.W + ou, wu); }
+            if (live) row_store<LPR, OPT>(TU, ou, wu, um, uv);
         } else if (live) {
             st4n<(LPR >= 32)>(GU + t * D + 4 * sub, make_float4(gu.x + cu * u.x, gu.y + cu * u.y, gu.z + cu * u.z, gu.w + cu * u.w));
         }
         if (fi) {
             const float4 wi = upd_math<OPT>(v, im, iv, gi, ci, hi);
-            if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TI.M + oi, im); st4n<(LPR >= 32)>(TI.V + oi, iv); } st4n<(LPR >= 32)>(TI.W + oi, wi); }
+            if (live) row_store<LPR, OPT>(TI, oi, wi, im, iv);
         } else if (live) {
             st4n<(LPR >= 32)>(GI + t * D + 4 * sub, make_float4(gi.x + ci * v.x, gi.y + ci * v.y, gi.z + ci * v.z, gi.w + ci * v.w));
         }
@@ -3200,7 +3151,7 @@ __global__ __launch_bounds__(kBlock) void pair_finish_kernel(const double* __res
     if (zero_a && threadIdx.x >= 64 && threadIdx.x < 68) zero_a[threadIdx.x - 64] = 0u;
     if (zero_b && threadIdx.x >= 128 && threadIdx.x < 132) zero_b[threadIdx.x - 128] = 0u;
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
+    for (int b = threadIdx.x; b < nblocks; b += kBlock) {           // sum_partials (cdr_loss_math.h), in place: the helper changed this kernel's code
         const double* o = partials + (size_t)b * CDR_PARTIAL_STRIDE;
 #pragma unroll
         for (int j = 0; j < 6; ++j) acc[j] += o[j];
@@ -3263,11 +3214,9 @@ extern "C" int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int los
     const int grid = grid_for(N, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-#define PP_ARGS loss_kind, T.TU, T.TI, D, su, si, ys, B_s, tu, ti, yt, B_t, (const uint32_t*)flags, alpha / (float)B_s, (1.0f - alpha) / (float)B_t, \
-                out16 + 9, T.hu, T.hi, GU, GI, ctx->partials
-        if (opt == 0) { DISPATCH_LPR(lpr, point_pair_fwd_apply_kernel<L, 0><<<dim3(grid), dim3(kBlock), 0, s>>>(PP_ARGS)); }
-        else { DISPATCH_LPR(lpr, point_pair_fwd_apply_kernel<L, 1><<<dim3(grid), dim3(kBlock), 0, s>>>(PP_ARGS)); }
-#undef PP_ARGS
+        DISPATCH_LPR_OPT(lpr, opt, point_pair_fwd_apply_kernel<L, O><<<dim3(grid), dim3(kBlock), 0, s>>>(
+                                       loss_kind, T.TU, T.TI, D, su, si, ys, B_s, tu, ti, yt, B_t, (const uint32_t*)flags, alpha / (float)B_s, (1.0f - alpha) / (float)B_t,
+                                       out16 + 9, T.hu, T.hi, GU, GI, ctx->partials));
     }
     CDR_LAUNCH_CHECK();
     // ---- every row with more than one occurrence: one update from the sum of its (complete) gradient rows
