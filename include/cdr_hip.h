@@ -66,7 +66,7 @@ int cdr_id_count_workspace_bytes(int64_t B, size_t* bytes);
 int cdr_norm_rec_floats(void);
 int cdr_row_norms_build(void* stream, const float* table, int64_t rows, int D, float* n2);
 int cdr_ctx_set_norm_cache(cdr_ctx* ctx, float* user_n2, int64_t user_rows, float* item_n2, int64_t item_rows);
-#define CDR_ABI_VERSION 62
+#define CDR_ABI_VERSION 63
 int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the header the library was built from; bumped on any signature change */
 
 /* Optional measurement aid: HIP-event brackets around the hot kernels, recorded on the stream each kernel is launched
@@ -93,6 +93,7 @@ int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the
 #define CDR_TAG_BPR_FWD_APPLY 18        /* bpr_fwd_apply_kernel: forward + optimizer on the single-occurrence rows */
 #define CDR_TAG_BATCH_NORMS 19          /* batch_norms_kernel: EmbLoss norms of the batch's user and positive rows */
 #define CDR_TAG_CONET_FB 20             /* conet_fb_kernel: conet_fwd_kernel's and conet_bwd_kernel's passes over a row block in one launch */
+#define CDR_TAG_TRIPLET_FWD_GRAD 21   /* triplet_fwd_grad_kernel: SSCDR's triplet loss + compact gradient rows */
 int cdr_timing_enable(cdr_ctx* ctx, int capacity);
 int cdr_timing_collect(cdr_ctx* ctx, int* tags, float* ms, int max_n, int* n_out);
 
@@ -663,6 +664,19 @@ int cdr_bpr_fwd_grad(cdr_ctx* ctx, void* stream,
                      float gamma, float reg_weight, float* out9, float* GU /* [B,D] */, float* GP /* [B,D] */,
                      int scatter /* != 0 (row-sharded step): GP[pid[b]] = g u, GP[nid[b]] = -g u instead of GP[b] = g u */);
 int cdr_loss_finish_sums(void* stream, const float* sums3, int64_t B_mean, float reg_weight, float* out6);
+/* SSCDR's domain step, forward half (sscdr.py:120-128, 133-159): per triple the rows x = user_tab[uid], item_tab[pid], item_tab[nid] are
+ * "normalised" as the reference does -- y = x / (L > 1 ? L : 1) with L = sum x^2, the SQUARED length -- and take
+ * nn.TripletMarginLoss(margin, p = 2, eps): d1 = ||y_u - y_p + eps||, d2 = ||y_u - y_n + eps||, term max(d1 - d2 + margin, 0), mean over B.
+ * The gradient of that mean with respect to the three GATHERED rows (through the normalisation) is left as one compact row per
+ * occurrence: GU[t] for the user, GI[t] for the positive, GI[B + t] for the negative of triple t -- a closed hinge (d1 - d2 + margin <= 0)
+ * or a zero distance leaves zeros, as cdr_triplet_bwd does.  Apply them with cdr_sort_ids_two_tables(uid | pid ++ nid) and
+ * cdr_rowwise_apply(n = B, G = GU, neg_start = B) / (n = 2 B, G = GI, neg_start = 2 B), reg_limit = 0: nothing is negated and there is no
+ * EmbLoss.  out3 = {mean hinge loss, number of triples with an open hinge, 0}.  Block partials in fp64, a fixed summation order and no
+ * float atomics: a rerun is bit-equal.  D % 4 == 0, D <= 256, B > 0 (CDR_EINVAL before any launch otherwise).                    */
+int cdr_triplet_fwd_grad(cdr_ctx* ctx, void* stream, const float* user_tab, const float* item_tab, int D,
+                         const int64_t* uid, const int64_t* pid, const int64_t* nid, int64_t B,
+                         float margin, float eps, float* out3 /* {mean hinge loss, active triples, 0} */,
+                         float* GU /* [B, D] */, float* GI /* [2B, D]: rows [0,B) positives, [B,2B) negatives */);
 /* The same step with the optimizer of every row that occurs ONCE in the batch applied by the forward kernel itself (round 3;
  * replaces cdr_bpr_fwd_grad + cdr_sort_ids_two_tables + 2 x cdr_rowwise_apply for emcdr.py:123-131,146-154 + Adam): the EmbLoss
  * norms of the batch are gathered first (the gradient coefficient reg_weight / (B ||rows||) is needed before the first row is

@@ -41,6 +41,22 @@ __device__ __forceinline__ float embloss_coef(float reg_weight, int64_t B, float
     return (reg_weight != 0.f && norm > 0.f) ? k * (reg_weight / ((float)B * norm)) : 0.f;
 }
 
+// SSCDR's metric loss, per element (sscdr.py:120-128, 142-144): the squared-norm "normalize" divides a row by L = sum x^2 where L > 1
+// (the SQUARED length: the reference's quirk, kept) -- sqnorm_scale is that divisor, the arithmetic of sqnorm_normalize_fwd_kernel --
+// and nn.TripletMarginLoss(p=2, eps) on the normalised rows.  unit_dir: one element of d(distance)/d(difference) of a triple whose
+// hinge is open (`on`), 0 for a closed hinge or a zero distance -- triplet_bwd_kernel's and sscdr_map_loss_kernel's conventions.
+// sqnorm_bwd_elem: one element of the gradient taken back through the normalisation, g the gradient at the normalised element and
+// dot = <x, g> over the row -- sq_norm_bwd of cdr_elem.hip (sqnorm_normalize_bwd_kernel).
+__device__ __forceinline__ float sqnorm_scale(float L) { return L > 1.0f ? L : 1.0f; }
+__device__ __forceinline__ float unit_dir(bool on, float diff, float dist) { return (on && dist > 0.f) ? diff / dist : 0.f; }
+__device__ __forceinline__ float sqnorm_bwd_elem(float x, float g, float L, float dot) { return L > 1.0f ? g / L - (2.0f * dot / (L * L)) * x : g; }
+// One term of the hinge's batch sum, and whether it is open
+__device__ __forceinline__ float triplet_hinge(float d1, float d2, float margin, bool& on) {
+    const float h = d1 - d2 + margin;
+    on = h > 0.0f;
+    return fmaxf(h, 0.0f);
+}
+
 // Thread 0, after block_sum_d<N>: the block's N sums into its slot of cdr_ctx::partials.  _sys: past the L2s, for cdr_sign_in_last
 template <int N>
 __device__ __forceinline__ void store_partials(double* partials, const double (&acc)[N]) {

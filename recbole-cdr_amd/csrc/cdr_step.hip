@@ -205,6 +205,104 @@ __global__ __launch_bounds__(kBlock) void point_fwd_grad_kernel(int loss_kind, c
     if (threadIdx.x == 0) store_partials(partials, acc);
 }
 
+// SSCDR's domain loss (sscdr.py:120-128, 133-159): TripletMarginLoss on the squared-norm "normalised" rows of a (user, positive,
+// negative) triple, and its gradient taken back through the normalisation to the three gathered rows -- one compact gradient row per
+// OCCURRENCE: GU[t] (user), GI[t] (positive), GI[B + t] (negative), so that the segmented applies add and never negate.  A lane keeps
+// its float4 of the three rows and makes the three gradient float4s from them; eight group reductions per triple (three squared
+// norms, two distances, three <row, gradient> dots).  Lanes past the row's width hold zeros and are kept out of the distances (their
+// difference would be eps, not 0).  partials: [0] sum of the hinge terms, [1] triples with an open hinge.
+template <int LPR>
+__device__ __forceinline__ float4 sqnorm_bwd4(float4 x, float4 g, float L) {
+    const float d = group_sum<LPR>(dot4(x, g));
+    return make_float4(sqnorm_bwd_elem(x.x, g.x, L, d), sqnorm_bwd_elem(x.y, g.y, L, d), sqnorm_bwd_elem(x.z, g.z, L, d),
+                       sqnorm_bwd_elem(x.w, g.w, L, d));
+}
+
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void triplet_fwd_grad_kernel(const float* __restrict__ U, const float* __restrict__ I, int D,
+                                                                  const int64_t* __restrict__ uid, const int64_t* __restrict__ pid,
+                                                                  const int64_t* __restrict__ nid, int64_t B, float margin, float eps,
+                                                                  float invB, float* __restrict__ GU, float* __restrict__ GI,
+                                                                  double* __restrict__ partials) {
+    constexpr int GPB = kBlock / LPR;
+    __shared__ double smem[2 * (kBlock / 64)];
+    const int sub = threadIdx.x % LPR;
+    const int64_t gg = (int64_t)blockIdx.x * GPB + threadIdx.x / LPR;
+    const int64_t TG = (int64_t)gridDim.x * GPB;
+    const int D4 = D >> 2;
+    double acc[2] = {0.0, 0.0};
+    const bool live = sub < D4;
+    const float e = live ? eps : 0.f;
+
+    for (int64_t base = gg; base < B; base += TG * kUnroll) {
+        float4 u[kUnroll], p[kUnroll], n[kUnroll];
+        int64_t iu[kUnroll], ip[kUnroll], in[kUnroll];
+#pragma unroll
+        for (int r = 0; r < kUnroll; ++r) {                  // ids of every triple first, then every row load (vmcnt is in-order)
+            const int64_t t = base + (int64_t)r * TG;
+            const int64_t tc = t < B ? t : B - 1;
+            iu[r] = uid[tc]; ip[r] = pid[tc]; in[r] = nid[tc];
+        }
+#pragma unroll
+        for (int r = 0; r < kUnroll; ++r) {
+            const int64_t t = base + (int64_t)r * TG;
+            u[r] = p[r] = n[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (t < B && live) {
+                u[r] = ld4n<(LPR >= 32)>(U + iu[r] * D + 4 * sub);
+                p[r] = ld4n<(LPR >= 32)>(I + ip[r] * D + 4 * sub);
+                n[r] = ld4n<(LPR >= 32)>(I + in[r] * D + 4 * sub);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kUnroll; ++r) {
+            const int64_t t = base + (int64_t)r * TG;
+            const float Lu = group_sum<LPR>(dot4(u[r], u[r]));
+            const float Lp = group_sum<LPR>(dot4(p[r], p[r]));
+            const float Ln = group_sum<LPR>(dot4(n[r], n[r]));
+            const float su = sqnorm_scale(Lu), sp = sqnorm_scale(Lp), sn = sqnorm_scale(Ln);
+            const float4 yu = make_float4(u[r].x / su, u[r].y / su, u[r].z / su, u[r].w / su);
+            const float4 dp = make_float4(yu.x - p[r].x / sp + e, yu.y - p[r].y / sp + e, yu.z - p[r].z / sp + e, yu.w - p[r].w / sp + e);
+            const float4 dn = make_float4(yu.x - n[r].x / sn + e, yu.y - n[r].y / sn + e, yu.z - n[r].z / sn + e, yu.w - n[r].w / sn + e);
+            const float d1 = sqrtf(group_sum<LPR>(dot4(dp, dp)));
+            const float d2 = sqrtf(group_sum<LPR>(dot4(dn, dn)));
+            bool on;
+            const float hinge = triplet_hinge(d1, d2, margin, on);
+            const float4 u1 = make_float4(unit_dir(on, dp.x, d1), unit_dir(on, dp.y, d1), unit_dir(on, dp.z, d1), unit_dir(on, dp.w, d1));
+            const float4 u2 = make_float4(unit_dir(on, dn.x, d2), unit_dir(on, dn.y, d2), unit_dir(on, dn.z, d2), unit_dir(on, dn.w, d2));
+            // (the three reductions run for every triple, open hinge or not: a lane group is a whole wave at LPR = 64)
+            const float4 gu = sqnorm_bwd4<LPR>(u[r], scale_diff4(invB, u1, u2), Lu);
+            const float4 gp = sqnorm_bwd4<LPR>(p[r], neg_scale4(invB, u1), Lp);
+            const float4 gn = sqnorm_bwd4<LPR>(n[r], scale4(invB, u2), Ln);
+            if (t < B) {
+                if (live) {
+                    st4n<(LPR >= 32)>(GU + t * D + 4 * sub, gu);
+                    st4n<(LPR >= 32)>(GI + t * D + 4 * sub, gp);
+                    st4n<(LPR >= 32)>(GI + (B + t) * D + 4 * sub, gn);
+                }
+                if (sub == 0) {
+                    acc[0] += (double)hinge;
+                    acc[1] += on ? 1.0 : 0.0;
+                }
+            }
+        }
+    }
+    block_sum_d<2>(acc, smem);
+    if (threadIdx.x == 0) store_partials(partials, acc);
+}
+
+// out3 = {mean hinge loss, triples with an open hinge, 0}
+__global__ __launch_bounds__(kBlock) void triplet_finish_kernel(const double* __restrict__ partials, int nblocks, int64_t B,
+                                                                float* __restrict__ out3) {
+    __shared__ double smem[2 * (kBlock / 64)];
+    double acc[2] = {0.0, 0.0};
+    sum_partials<2, kBlock>(partials, nblocks, acc, smem);
+    if (threadIdx.x == 0) {
+        out3[0] = (float)(acc[0] / (double)B);
+        out3[1] = (float)acc[1];
+        out3[2] = 0.f;
+    }
+}
+
 // out9 = {total, main, ||U_b||, ||I_b||, c_u, c_i, sum loss, sum u^2, sum p^2} with c = reg_weight / (B * norm)
 // (0 when the norm is 0).  B is the batch size the mean and the EmbLoss are taken over (the GLOBAL batch when the
 // step is sharded: then out9[0..5] are provisional and cdr_loss_finish_sums recomputes them from all-reduced sums).
@@ -2034,6 +2132,25 @@ extern "C" int cdr_point_fwd_grad(cdr_ctx* ctx, void* stream, int loss_kind, con
     }
     CDR_LAUNCH_CHECK();
     step_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, reg_weight, out9);
+    CDR_LAUNCH_CHECK();
+    return CDR_OK;
+}
+
+extern "C" int cdr_triplet_fwd_grad(cdr_ctx* ctx, void* stream, const float* user_tab, const float* item_tab, int D,
+                                    const int64_t* uid, const int64_t* pid, const int64_t* nid, int64_t B, float margin, float eps,
+                                    float* out3, float* GU, float* GI) {
+    CDR_CHECK_ARG(ctx && user_tab && item_tab && uid && pid && nid && out3 && GU && GI);
+    CDR_CHECK_ARG(D > 0 && (D & 3) == 0 && D <= 256 && B > 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int lpr = cdr_lpr_for(D);
+    const int grid = grid_for((B + kUnroll - 1) / kUnroll, kBlock / lpr);
+    {
+        cdr_time_scope ts(ctx, CDR_TAG_TRIPLET_FWD_GRAD, s);
+        DISPATCH_LPR(lpr, triplet_fwd_grad_kernel<L><<<dim3(grid), dim3(kBlock), 0, s>>>(user_tab, item_tab, D, uid, pid, nid, B, margin, eps,
+                                                                                          1.0f / (float)B, GU, GI, ctx->partials));
+    }
+    CDR_LAUNCH_CHECK();
+    triplet_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B, out3);
     CDR_LAUNCH_CHECK();
     return CDR_OK;
 }

@@ -1,6 +1,6 @@
 """Fused row-wise training steps: forward + backward + optimizer for one batch without table-sized gradients
 (FusedBPRStep: pairwise BPR; FusedPointStep: pointwise MSE / BCE; FusedPointPairStep: CMF's two domains on shared tables;
-FusedMapStep: EMCDR's OVERLAP-phase mapping loss).
+FusedTripletStep: SSCDR's triplet margin loss; FusedMapStep / SSCDRMapStep: EMCDR's / SSCDR's OVERLAP-phase mapping loss).
 
 This is the large-table counterpart of ``loss.backward(); optimizer.step()`` in the reference's loop
 (recbole_cdr/trainer/trainer.py:59-73 -> recbole ``Trainer._train_epoch``): dense ``[rows, D]`` gradients and a dense
@@ -661,6 +661,137 @@ class FusedPointStep(_TwoTableStep):
                     B_.raw(self.keys[lo:lo + B]), B_.raw(self.perm[lo:lo + B]), B, B_.f32(G), B, B, B_.f32(coef), *self._hp(), st.step, None,
                     int(base))
         return self.out6
+
+
+class FusedTripletStep(_TwoTableStep):
+    """SSCDR's domain step (sscdr.py:120-128, 133-159): TripletMarginLoss(margin) on the squared-norm "normalised" rows of (user,
+    positive, negative) triples, both tables updated row-wise on the batch's rows.  The loss has no EmbLoss.  Five calls: forward +
+    one compact gradient row per occurrence (cdr_triplet_fwd_grad), one sort for both tables, two segmented applies.  The update counts
+    are the host's: not capturable."""
+
+    def __init__(self, user_table, item_table, max_batch, margin=1.0, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=0.0, user_state=None, item_state=None):
+        if user_table.shape[1] % 4 != 0 or user_table.shape[1] > 256:            # (before the base allocates any optimizer state)
+            raise ValueError(f'FusedTripletStep: D must be a multiple of 4 and <= 256, got {user_table.shape[1]}')
+        super().__init__(user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state)
+        self.margin = float(margin)
+        self.loss_eps = 1e-6                                                     # nn.TripletMarginLoss's eps (sscdr.py:69)
+        dev = user_table.device
+        Bm = int(max_batch)
+        self.max_batch = Bm
+        self.GU = torch.empty(Bm, self.D, device=dev, dtype=torch.float32)
+        self.GI = torch.empty(2 * Bm, self.D, device=dev, dtype=torch.float32)
+        self.out3 = torch.zeros(3, device=dev, dtype=torch.float32)
+        self.keys = torch.empty(3 * Bm, device=dev, dtype=torch.int32)          # one sort for both tables (see FusedBPRStep)
+        self.perm = torch.empty(3 * Bm, device=dev, dtype=torch.int32)
+        # (the sort switches configuration at 2^18 keys: a short tail batch may need more scratch than a full one)
+        self.ws, _ = self._sort_workspace(3 * Bm, min(3 * Bm, (1 << 18) - 1))
+        self._key_base = ctypes.c_uint32(0)
+
+    def step(self, uid, pid, nid):
+        """uid / pid / nid: int64 device tensors [B].  Returns out3 (view): [0] the loss, [1] the triples with an open hinge."""
+        B = uid.numel()
+        if not 1 <= B <= self.max_batch or pid.numel() != B or nid.numel() != B:
+            raise ValueError(f'FusedTripletStep: {B} / {pid.numel()} / {nid.numel()} ids, sized for 1..{self.max_batch} triples')
+        ctxh, s = B_.ctx(self.U.device), B_.stream()
+        GI = self.GI[:2 * B]                                                     # negatives at row B of THIS batch
+        B_.call('cdr_triplet_fwd_grad', ctxh, s, B_.f32(self.U), B_.f32(self.I), self.D, B_.i64(uid), B_.i64(pid), B_.i64(nid), B,
+                self.margin, self.loss_eps, B_.f32(self.out3), B_.f32(self.GU), B_.f32(GI))
+        B_.call('cdr_sort_ids_two_tables', ctxh, s, B_.i64(uid), B, self.U.shape[0], B_.i64(pid), B, B_.i64(nid), B, self.I.shape[0],
+                B_.raw(self.keys), B_.raw(self.perm), ctypes.byref(self._key_base), B_.raw(self.ws), self.ws.numel())
+        self.ustate.advance(); self.istate.advance()
+        # every occurrence has its own gradient row: neg_start = n (nothing is negated), reg_limit = 0 (no EmbLoss)
+        for st, lo, n, G, base in ((self.ustate, 0, B, self.GU, 0), (self.istate, B, 2 * B, GI, self._key_base.value)):
+            B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
+                    B_.raw(self.keys[lo:lo + n]), B_.raw(self.perm[lo:lo + n]), n, B_.f32(G), n, 0, None, *self._hp(), st.step, None,
+                    int(base))
+        return self.out3
+
+
+class SSCDRMapStep(_Step):
+    """SSCDR's OVERLAP phase (sscdr.py:161-187: MSE(mapping(source_a[idx]), target_a[idx]) + lambda x triplet(normalize(target_a[idx]),
+    normalize(mapping(source_b[pos])), normalize(mapping(source_b[neg])))) as an O(batch) step: the three touched tables are updated
+    row-wise -- source_a and target_a on ``idx`` (one sort serves both), source_b on ``pos ++ neg`` -- and the mapping's own parameters
+    keep the exact dense Adam (plain SGD with opt='sgd'), as in FusedMapStep.  Repeated ids in any list are summed by the segmented
+    applies.  The reference's overlap batch is 100 ids: the step is launch-bound and stays composed on the host (gather, the mapping
+    and the loss node through autograd on the gathered rows, sort, applies)."""
+
+    def __init__(self, source_a, target_a, source_b, mapping_fn, mapping_params, margin, lamda, opt='adam', lr=1e-3, betas=(0.9, 0.999),
+                 eps=1e-8, weight_decay=0.0, source_a_state=None, target_a_state=None, source_b_state=None):
+        from .trainer.trainer import DenseAdam
+        assert source_a.is_cuda and target_a.is_cuda and source_b.is_cuda, 'SSCDRMapStep needs ROCm device tensors'
+        assert source_a.shape[1] == target_a.shape[1] == source_b.shape[1]
+        super().__init__(opt, lr, betas, eps, weight_decay)
+        self.SA, self.TA, self.SB = source_a, target_a, source_b
+        self.D = source_a.shape[1]
+        self.mapping_fn = mapping_fn
+        self.mapping_params = list(mapping_params)
+        self.margin, self.lamda = float(margin), float(lamda)
+        self.sa_state = source_a_state if source_a_state is not None else RowwiseState(source_a, self.opt)
+        self.ta_state = target_a_state if target_a_state is not None else RowwiseState(target_a, self.opt)
+        self.sb_state = source_b_state if source_b_state is not None else RowwiseState(source_b, self.opt)
+        self.map_opt = DenseAdam(self.mapping_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) \
+            if self.opt == OPT_ADAM else None
+        self.loss = torch.zeros((), device=source_a.device, dtype=torch.float32)
+        self._ws = None
+
+    def _states(self):
+        return self.sa_state, self.ta_state, self.sb_state
+
+    def step(self, idx, pos, neg, bump=None):
+        """idx / pos / neg: int64 device tensors of n ids each (any shape).  ``bump``: optional device int64 [1] advanced once (the
+        device sampler's call counter, which the dense path advances in its gather launch).  Returns the loss (device scalar)."""
+        from . import functional as F_
+        idx, pos, neg = (x.reshape(-1).contiguous() for x in (idx, pos, neg))
+        n, D = idx.numel(), self.D
+        if pos.numel() != n or neg.numel() != n:
+            raise ValueError(f'SSCDRMapStep: {n} / {pos.numel()} / {neg.numel()} ids')
+        dev = self.SA.device
+        if n == 0:                                     # an empty batch is a no-op: no state advances
+            self.loss = torch.zeros((), device=dev, dtype=torch.float32)
+            return self.loss
+        s = B_.stream()
+        for p in self.mapping_params:
+            p.grad = None
+        X3 = torch.empty(3 * n, D, device=dev, dtype=torch.float32)
+        Tt = torch.empty(n, D, device=dev, dtype=torch.float32)
+        P4, I4 = ctypes.c_void_p * 4, ctypes.c_int64 * 4
+        keep = [idx, pos, neg, X3, Tt]
+        B_.call('cdr_gather_rows_multi', s, 4, P4(self.SA.data_ptr(), self.SB.data_ptr(), self.SB.data_ptr(), self.TA.data_ptr()), D,
+                P4(idx.data_ptr(), pos.data_ptr(), neg.data_ptr(), idx.data_ptr()), I4(n, n, n, n),
+                P4(X3.data_ptr(), X3.data_ptr() + 4 * n * D, X3.data_ptr() + 8 * n * D, Tt.data_ptr()), None if bump is None else B_.i64(bump))
+        del keep
+        X3.requires_grad_(True); Tt.requires_grad_(True)
+        total, _ = F_.SSCDRMapLoss.apply(self.mapping_fn(X3), Tt, self.margin, self.lamda)
+        total.backward()
+        self.loss = total.detach()
+        for st in self._states():
+            st.advance()
+        ctxh = B_.ctx(dev)
+        rows = max(self.SA.shape[0], self.TA.shape[0], self.SB.shape[0])
+        need = max(_sort_workspace_bytes(n, rows), _sort_workspace_bytes(2 * n, rows))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        keys = torch.empty(3 * n, device=dev, dtype=torch.int32)
+        perm = torch.empty(3 * n, device=dev, dtype=torch.int32)
+        # the same ids index source_a and target_a: one sort serves both applies; source_b's list is pos ++ neg, the order of X3[n:]
+        B_.call('cdr_sort_ids', ctxh, s, B_.i64(idx), n, None, 0, self.SA.shape[0], B_.raw(keys[:n]), B_.raw(perm[:n]), B_.raw(self._ws),
+                self._ws.numel())
+        B_.call('cdr_sort_ids', ctxh, s, B_.i64(pos), n, B_.i64(neg), n, self.SB.shape[0], B_.raw(keys[n:]), B_.raw(perm[n:]),
+                B_.raw(self._ws), self._ws.numel())
+        gX, gT = X3.grad.contiguous(), Tt.grad.contiguous()
+        for st, k, pm, m, G in ((self.sa_state, keys[:n], perm[:n], n, gX[:n]), (self.ta_state, keys[:n], perm[:n], n, gT),
+                                (self.sb_state, keys[n:], perm[n:], 2 * n, gX[n:])):
+            B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), D, B_.raw(k),
+                    B_.raw(pm), m, B_.f32(G), m, 0, None, *self._hp(), st.step, None, 0)
+        if self.map_opt is not None:
+            self.map_opt.step()
+        else:
+            with torch.no_grad():
+                for p in self.mapping_params:
+                    if p.grad is not None:
+                        p.add_(p.grad + self.wd * p if self.wd else p.grad, alpha=-self.lr)
+        return self.loss
 
 
 class FusedPointPairStep(_TwoTableStep):

@@ -7,6 +7,10 @@ The semi-supervised (interacted, non-interacted) ids are drawn on the host from 
 reference does inside its loss (sscdr.py:89-118) so that a seeded run samples the same ids -- or, with
 ``config['sscdr_device_sampler'] = True``, by a kernel over the device-resident interaction lists (``sample_device``: same
 distribution and constraints, counter-based RNG, no host work inside the loss, so the OVERLAP step replays as a hipGraph).
+
+``fused_train_step`` (``optimizer_mode='rowwise'``): every phase without table-sized gradients -- fused.FusedTripletStep on a domain's
+pair of tables, fused.SSCDRMapStep on the three tables of the OVERLAP phase; ``adam='exact'`` puts the catch-up of the reference's dense
+Adam in front of each (fused.rowwise_catch_up).
 """
 import numpy as np
 import torch
@@ -16,6 +20,7 @@ from ... import binding as B_
 from ... import functional as F_
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
+from ..rowwise import RowwiseTraining
 
 
 class MLPLayers(nn.Module):
@@ -36,7 +41,7 @@ class MLPLayers(nn.Module):
         return x
 
 
-class SSCDR(CrossDomainRecommender):
+class SSCDR(RowwiseTraining, CrossDomainRecommender):
     input_type = InputType.PAIRWISE
 
     def __init__(self, config, dataset):
@@ -60,6 +65,7 @@ class SSCDR(CrossDomainRecommender):
         self.target_user_embedding = nn.Embedding(self.total_num_users, self.embedding_size)
         self.target_item_embedding = nn.Embedding(self.total_num_items, self.embedding_size)
         self.apply(xavier_normal_initialization)
+        self.__dict__['_dist_cfg'] = config['dist_group'] if 'dist_group' in config else None
 
     def build_interacted_items(self, dataset, mode='user'):
         ds = dataset.source_domain_dataset
@@ -202,6 +208,106 @@ class SSCDR(CrossDomainRecommender):
             return self.calculate_map_loss(interaction)
         else:
             return self.calculate_target_loss(interaction)
+
+    # ---- O(batch) training step (large tables) ------------------------------------------------------------------
+    def fused_train_step(self, interaction, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam='lazy'):
+        """``calculate_loss -> backward -> optimizer.step`` of the current phase without table-sized gradients or a dense optimizer
+        sweep: what ``CrossDomainTrainer`` runs when ``config['optimizer_mode'] == 'rowwise'``.  SOURCE / TARGET / BOTH (the target step,
+        as in ``calculate_loss``): fused.FusedTripletStep on the domain's user and item table.  OVERLAP: fused.SSCDRMapStep on
+        source_a, target_a (the overlapped ids) and source_b (the semi-supervised ids, drawn ONCE per step by the sampler
+        ``calculate_map_loss`` would use: the numpy stream / the device call counter advance as in dense mode); the mapping's own
+        parameters take the exact dense Adam.  Same loss and per-row gradients as ``calculate_loss``; one optimizer state per table,
+        shared by the phases.  Returns the loss (device tensor).
+
+        ``adam='lazy'`` (default): rows the batch does not touch do not move.  ``adam='exact'``: the reference's dense Adam -- one
+        catch-up launch in front of every step (fused.rowwise_catch_up) on the tables and ids that step touches; the tables hold what
+        ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run.  One mode per model."""
+        from ...fused import FusedTripletStep, SSCDRMapStep, rowwise_catch_up
+        exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            raise NotImplementedError("SSCDR.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
+        D = self.embedding_size
+        if D % 4 != 0 or D > 256:
+            raise ValueError(f'SSCDR.fused_train_step needs embedding_size % 4 == 0 and embedding_size <= 256 (one float4 per lane, '
+                             f'at most 64 lanes per row), got {D}; use optimizer_mode=dense')
+        self._fused_cache(exact)
+
+        def state(name):
+            return self._fused_state(name, code, exact)
+
+        def catch_up(*tables):
+            if exact:
+                rowwise_catch_up(tables, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+        if self.phase == 'OVERLAP':
+            a, b = ('user', 'item') if self.mode == 'overlap_users' else ('item', 'user')
+            idx = interaction[self.OVERLAP_ID].reshape(-1)
+            names = (f'source_{a}_embedding', f'target_{a}_embedding', f'source_{b}_embedding')
+
+            def build_map_step():
+                step = SSCDRMapStep(*(getattr(self, n).weight.data for n in names), self.mapping_layer, list(self.mapping_layer.parameters()),
+                                    self.margin, self.lamda, source_a_state=state(names[0]), target_a_state=state(names[1]),
+                                    source_b_state=state(names[2]), **hp)
+                pending = self.__dict__.get('_pending_map_state', {}).pop(a, None)
+                if pending is not None and step.map_opt is not None:
+                    step.map_opt.load_state_dict(pending)
+                return step
+
+            step = self._fused_step(('map', a), lambda s: True, build_map_step)
+            if idx.numel() == 0:                                 # (an empty batch is a no-op: nothing is drawn, no table advances)
+                return step.step(idx, idx, idx)
+            bump = None
+            if self.device_sampler:
+                # (as the fused dense path: the step's gather launch advances the sampler's call counter)
+                self.__dict__['_bump_in_gather'] = True
+                try:
+                    pos, neg = self.sample_device(idx, mode=a)
+                finally:
+                    self.__dict__['_bump_in_gather'] = False
+                bump = self._device_lists(a)[3]
+            else:
+                pos, neg = self.sample(idx, mode=a)
+            catch_up((step.sa_state, [idx]), (step.ta_state, [idx]), (step.sb_state, [pos, neg]))
+            return step.step(idx, pos, neg, bump=bump)
+        domain = 'source' if self.phase == 'SOURCE' else 'target'
+        pre = domain.upper()
+        user = interaction[getattr(self, f'{pre}_USER_ID')].reshape(-1)
+        item = interaction[getattr(self, f'{pre}_ITEM_ID')].reshape(-1)
+        neg = interaction[getattr(self, f'{pre}_NEG_ITEM_ID')].reshape(-1)
+        rows = user.numel()
+        step = self._fused_step(('triplet', domain), lambda s: s.max_batch >= rows, lambda: FusedTripletStep(
+            getattr(self, f'{domain}_user_embedding').weight.data, getattr(self, f'{domain}_item_embedding').weight.data, rows,
+            margin=self.margin, user_state=state(f'{domain}_user_embedding'), item_state=state(f'{domain}_item_embedding'), **hp))
+        catch_up((step.ustate, [user]), (step.istate, [item, neg]))
+        return step.step(user, item, neg)[0]
+
+    def fused_graph_key(self, interaction, adam='lazy'):
+        """None for every phase: the steps read the host's update counts (and the OVERLAP step runs autograd), so the trainer launches
+        them and never captures them in a hipGraph."""
+        return None
+
+    def _fused_phase_step(self):
+        if self.phase == 'OVERLAP':
+            return self._fused['steps'][('map', 'user' if self.mode == 'overlap_users' else 'item')]
+        return self._fused['steps'][('triplet', 'source' if self.phase == 'SOURCE' else 'target')]
+
+    def fused_optimizer_state(self):
+        """The shared per-table state, plus the dense Adam state of the mapping and the device sampler's call counters (a resumed run
+        draws the ids the uninterrupted one would)."""
+        out = super().fused_optimizer_state()
+        for key, step in self.__dict__.get('_fused', {}).get('steps', {}).items():
+            if key[0] == 'map' and step.map_opt is not None:
+                out.setdefault('mapping', {})[key[1]] = step.map_opt.state_dict()
+        for mode, lists in self.__dict__.get('_dev_lists', {}).items():
+            out.setdefault('sampler_calls', {})[mode] = int(lists[3])
+        return out
+
+    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
+        """The shared per-table restore; the mapping's Adam state is handed to the OVERLAP step when it is built."""
+        super().load_fused_optimizer_state(state, opt=opt, adam=adam)
+        self._pending_map_state = dict(state.get('mapping', {}))
+        for mode, calls in state.get('sampler_calls', {}).items():
+            self._device_lists(mode)[3].fill_(int(calls))
 
     # ---- scoring --------------------------------------------------------------------------------------------------
     def _mapped_rows(self, kind, ids, n_overlap):
