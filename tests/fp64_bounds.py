@@ -308,3 +308,155 @@ def check_dense_result(tag, got, ref, D):
     for j, (gr, part) in enumerate(zip(got['grads'], ref['parts'])):
         worst[f'grad{j}'] = check_dense_grad(f'{tag}: gradient {j}', gr, part, D)
     return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------- running bounds
+# test_gpu_gemm_fp64.py and test_gpu_rowmodels_fp64.py restate a kernel operation by operation on EV pairs: ``v`` is the float64 value
+# of the quantity, ``e`` a bound of |what the fp32 kernel holds - v| carried along by the standard model fl(a op b) = (a op b)(1 + d),
+# |d| <= u (Higham, Accuracy and Stability, ch. 3: the running error analysis), with the input errors propagated through each
+# operation's derivative.  Every rule charges its OWN rounding on top (an fma that saves one only makes the bound loose), a sum of n
+# terms in ANY order gamma_{n-1} of the sum of magnitudes (the caller passes the real depth of a reduction whose order is known), and
+# every rounding TINY = 2^-126 for a result that leaves the normal range (a flushed or denormal intermediate).
+TINY = 2.0 ** -126
+K_EXP = 2                   # ulps of expf (ocml documents 1)
+K_TANH_EV = 4               # ulps of tanhf, as test_gpu_map_step_fp64.K_TANH
+K_SIG_EV = 4                # expf, add and division of 1 / (1 + expf(-z)), as test_gpu_conet_fp64.K_SIG
+
+
+class EV:
+    __slots__ = ('v', 'e')
+
+    def __init__(self, v, e=None):
+        self.v = v
+        self.e = torch.zeros_like(v) if e is None else e
+
+    @staticmethod
+    def lift(x, like=None):
+        if isinstance(x, EV):
+            return x
+        if not isinstance(x, torch.Tensor):
+            x = torch.tensor(float(x), dtype=torch.float64, device=like.v.device if like is not None else None)
+        return EV(x.double())
+
+    @staticmethod
+    def _rnd(v, e, k=1):
+        """k roundings of a result whose exact-arithmetic value is v and whose propagated error is e."""
+        return EV(v, e + k * U32 * (v.abs() + e) + TINY)
+
+    @property
+    def mag(self):
+        return self.v.abs() + self.e
+
+    def __neg__(self):
+        return EV(-self.v, self.e)
+
+    def __add__(self, o):
+        o = EV.lift(o, self)
+        return EV._rnd(self.v + o.v, self.e + o.e)
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        o = EV.lift(o, self)
+        return EV._rnd(self.v - o.v, self.e + o.e)
+
+    def __rsub__(self, o):
+        return EV.lift(o, self) - self
+
+    def __mul__(self, o):
+        o = EV.lift(o, self)
+        return EV._rnd(self.v * o.v, self.v.abs() * o.e + o.v.abs() * self.e + self.e * o.e)
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        o = EV.lift(o, self)
+        q = self.v / o.v
+        lo = (o.v.abs() - o.e).clamp(min=1e-300)
+        return EV._rnd(q, (self.e + q.abs() * o.e) / lo)
+
+    def __getitem__(self, idx):
+        return EV(self.v[idx], self.e[idx])
+
+    def unsqueeze(self, d):
+        return EV(self.v.unsqueeze(d), self.e.unsqueeze(d))
+
+    def exact_scale(self, c):
+        """Multiplication by a power of two (or by an exact 0 / 1 mask): no rounding."""
+        return EV(self.v * c, self.e * abs(c) if not isinstance(c, torch.Tensor) else self.e * c.abs())
+
+    def sum(self, dim, depth=None, keepdim=False):
+        """A sum of n terms; ``depth`` = the longest chain of additions a term goes through (default n - 1: any order)."""
+        n = self.v.shape[dim]
+        k = max(n - 1, 0) if depth is None else depth
+        m = self.mag.sum(dim, keepdim=keepdim)
+        return EV(self.v.sum(dim, keepdim=keepdim), self.e.sum(dim, keepdim=keepdim) + gam(k) * m + TINY)
+
+    def amax(self, dim, keepdim=False):
+        """max of computed values (fmaxf is exact): |max x^ - max x| <= the largest e among the entries that CAN be the computed maximum
+        (v + e reaches the largest v - e)."""
+        cand = (self.v + self.e) >= (self.v - self.e).amax(dim, keepdim=True)
+        return EV(self.v.amax(dim, keepdim=keepdim), (self.e * cand).amax(dim, keepdim=keepdim))
+
+    def maximum(self, o):
+        o = EV.lift(o, self)
+        return EV(torch.maximum(self.v, o.v), torch.maximum(self.e, o.e))
+
+    def relu(self):
+        """1-Lipschitz: the error passes where the unit can be alive, none where it is dead beyond its bound."""
+        return EV(self.v.clamp(min=0), self.e * (self.v > -self.e))
+
+    def step(self):
+        """[x > 0] as the kernel evaluates it on ITS value: exact unless |x| <= e, where either branch may be taken (error 1)."""
+        return EV((self.v > 0).double(), (self.v.abs() <= self.e).double() * (self.e > 0))
+
+    def ambiguous(self):
+        return (self.v.abs() <= self.e) & (self.e > 0)
+
+    def exp(self):
+        v = torch.exp(self.v)
+        e = self.e.clamp(max=700.0)             # (a masked score of -1e31 carries a huge bound into an exponential that is 0 either way)
+        return EV(v, v * torch.expm1(e) + K_EXP * U32 * v * torch.exp(e) + TINY)
+
+    def tanh(self):
+        a = torch.tanh(self.v)
+        return EV(a, self.e.clamp(max=2.0) * (1 - a * a + 2 * self.e).clamp(max=1.0) + K_TANH_EV * ulp32(a) + TINY)
+
+    def sigmoid(self):
+        p = torch.sigmoid(self.v)
+        return EV(p, (p * (1 - p) + self.e).clamp(max=0.25) * self.e + K_SIG_EV * U32 * p + TINY)
+
+    def matmul(self, o, depth, extra=2):
+        """self [M, K] @ o [K, N] accumulated along a chain of ``depth`` additions; ``extra`` roundings for the products and the
+        epilogue's first operation."""
+        o = EV.lift(o, self)
+        v = self.v @ o.v
+        m = self.mag @ o.mag
+        e = self.e @ o.v.abs() + self.v.abs() @ o.e + self.e @ o.e
+        return EV(v, e + gam(depth + extra) * m + TINY)
+
+    def ratio(self, got):
+        """error / bound of an fp32 result, elementwise (0 where the result is exact)."""
+        err = (got.double() - self.v).abs()
+        return torch.where(err > 0, err / self.e.clamp(min=1e-300), torch.zeros_like(err))
+
+
+def ev_cat(parts, dim=0):
+    return EV(torch.cat([p.v for p in parts], dim), torch.cat([p.e for p in parts], dim))
+
+
+def ev_where(cond, a, b):
+    a, b = EV.lift(a), EV.lift(b)
+    return EV(torch.where(cond, a.v, b.v), torch.where(cond, a.e, b.e))
+
+
+def colsum_depth(rows):
+    """cdr_colsum (csrc/cdr_rows.hip:166-198, 618-632): slabs of 64 rows (at most 128 slabs, then longer ones); inside a slab a wave adds
+    every fourth row into four accumulators (rows / 16 additions), three more to join them, three for the four waves; one thread then adds
+    the slabs in order."""
+    per = 64
+    slabs = -(-rows // per)
+    if slabs > 128:
+        per = -(-rows // 128)
+        slabs = -(-rows // per)
+    return -(-per // 16) + 3 + 3 + slabs

@@ -180,3 +180,46 @@ def test_dense_case_table_covers_every_launch_regime_without_a_gpu():
     """The coverage assertion of test_gpu_dense_loss_fp64.py is pure arithmetic: it holds (and fails on a changed table) here too."""
     import test_gpu_dense_loss_fp64 as T
     T.test_case_table_covers_every_launch_regime()
+
+
+def test_gemm_case_table_covers_every_regime_without_a_gpu():
+    """test_gpu_gemm_fp64.py's regime and route coverage and its ambiguity cap are arithmetic on seeded inputs: checked here on the CPU."""
+    import test_gpu_gemm_fp64 as T
+    T.test_case_table_covers_every_regime()
+
+
+def test_rowmodels_case_table_covers_every_regime_without_a_gpu():
+    """test_gpu_rowmodels_fp64.py's case table: every NATR register count, the grid-stride sizes, and the ambiguity cap on the CPU."""
+    import test_gpu_rowmodels_fp64 as T
+    T.test_case_table_covers_every_regime()
+
+
+def test_running_bounds_hold_for_fp32_on_the_cpu_and_reject_small_mutations():
+    """fp64_bounds.EV without a GPU: torch's own fp32 results lie inside the bounds the two fp64 test files build (a product with a tanh
+    epilogue; the oracle's max-min normalisation with tied extremes through autograd), and results that are subtly wrong do not."""
+    import test_gpu_gemm_fp64 as G
+    import test_gpu_rowmodels_fp64 as R
+    from fp64_bounds import EV
+    from oracle.dcdcsr import maxmin_normalize
+    gen = torch.Generator().manual_seed(5)
+    A, Bm, bias = torch.randn(70, 131, generator=gen), torch.randn(131, 45, generator=gen) * 0.3, torch.randn(45, generator=gen)
+    ref = (EV(A.double()).matmul(EV(Bm.double()), 131, extra=G.K_MFMA) + EV(bias.double())).tanh()
+    got = torch.tanh(A @ Bm + bias)
+    assert float(ref.ratio(got).max()) <= 1.0
+    assert float(ref.ratio(torch.tanh(A @ Bm + bias).t().contiguous().t() * (1 + 2e-6)).max()) > 1.0          # 17 ulps off
+    A2 = A.clone(); A2[3, 130] = 0.0                                                                              # the last k of one row dropped
+    assert float(ref.ratio(torch.tanh(A2 @ Bm + bias)).max()) > 1.0
+    x, gy = R._maxmin_inputs(41, 65)
+    mm, nmax, nmin = R.maxmin_fp64(x, gy)
+    xg = x.clone().requires_grad_(True)
+    y, mean_, max_ = maxmin_normalize(xg)
+    y.backward(gy)
+    assert float(mm['y'].ratio(y.detach()).max()) <= 1.0 and float(mm['gx'].ratio(xg.grad).max()) <= 1.0
+    assert float(mm['stats'].ratio(torch.cat([mean_, max_], 1).detach()).max()) <= 1.0
+    tied = int(torch.nonzero(nmax > 1)[0])                              # all of a tie's share to its first column instead of an even split
+    bad = xg.grad.clone()
+    cols = torch.nonzero(x[tied] == x[tied].max()).reshape(-1)
+    share = gy[tied, cols[1]] / (x[tied].max() - (x[tied].max() + x[tied].min()) / 2) - bad[tied, cols[1]]
+    bad[tied, cols[0]] -= share
+    bad[tied, cols[1]] += share
+    assert float(mm['gx'].ratio(bad).max()) > 1.0
