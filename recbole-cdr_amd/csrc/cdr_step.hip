@@ -334,9 +334,18 @@ __global__ void finish_sums_kernel(const float* __restrict__ sums3, int64_t B, f
 }
 
 // ------------------------------------------------------------------------------------------------ keys for the sort
+// Every key-making kernel also clears, grid-stride, the `zwords` words at `zspan`: the zero-initialised state of the sort's own launch
+// list ("the id sort's own launch list" below), which no launch of its own clears.  zspan = nullptr: the kernel only makes keys.
+__device__ __forceinline__ void sort_state_clear(uint32_t* __restrict__ zspan, int64_t zwords) {
+    if (!zspan) return;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < zwords; i += (int64_t)gridDim.x * blockDim.x) zspan[i] = 0u;
+}
+
 __global__ __launch_bounds__(kBlock) void make_keys_kernel(const int64_t* __restrict__ ids0, int64_t n0,
                                                            const int64_t* __restrict__ ids1, int64_t n1,
-                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                           uint32_t* __restrict__ zspan, int64_t zwords) {
+    sort_state_clear(zspan, zwords);
     const int64_t n = n0 + n1, stride = (int64_t)gridDim.x * kBlock;
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride) {
         keys[e] = (uint32_t)(e < n0 ? ids0[e] : ids1[e - n0]);
@@ -598,7 +607,9 @@ __global__ __launch_bounds__(kBlock) void seg_long_finish_kernel(float* __restri
 // puts them behind every user key and is subtracted again by the apply kernel.
 __global__ __launch_bounds__(kBlock) void make_keys2_kernel(const int64_t* __restrict__ a, int64_t na, const int64_t* __restrict__ b0,
                                                             int64_t nb0, const int64_t* __restrict__ b1, int64_t nb1, uint32_t key_base,
-                                                            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+                                                            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                            uint32_t* __restrict__ zspan, int64_t zwords) {
+    sort_state_clear(zspan, zwords);
     const int64_t n = na + nb0 + nb1, stride = (int64_t)gridDim.x * kBlock;
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride) {
         if (e < na) { keys[e] = (uint32_t)a[e]; vals[e] = (uint32_t)e; }
@@ -607,6 +618,71 @@ __global__ __launch_bounds__(kBlock) void make_keys2_kernel(const int64_t* __res
             keys[e] = key_base + (uint32_t)(o < nb0 ? b0[o] : b1[o - nb0]);
             vals[e] = (uint32_t)o;                               // occurrence index inside table b's own list
         }
+    }
+}
+
+// The big sort's shape (big_sort_config below): 1,024-thread blocks of 8 items, 9-bit digits, so 512 bins per digit place.
+constexpr unsigned kSortBlock = 1024, kSortItems = 8, kSortRadixBits = 9, kSortRadix = 1u << kSortRadixBits;
+constexpr unsigned kSortMaxPlaces = (32 + kSortRadixBits - 1) / kSortRadixBits;
+using sort_offs_t = size_t;                     // rocPRIM's offset type for a size_t item count, the one the library call instantiates
+
+// make_keys2_kernel, the digit histogram and its scan in ONE launch (the fused BPR step's sorted path): every key's digits are counted
+// in LDS as the key is made ([place][digit][4 stripes], rocPRIM's layout against same-address conflicts), a block adds its non-zero
+// bins to counts[place][512] with global atomics -- integer counts, the order does not matter -- and the block that signs in last
+// (cdr_sign_in_last: the atomics are acknowledged by memory before the ticket is taken, the finisher reads past its L2) turns every
+// place's counts into exclusive offsets, what rocPRIM's histogram and scan launches leave for its Onesweep passes.
+// counts and ticket must be zero at the start (the caller's earlier launch: coef_finish_kernel); zspan is cleared as in every key kernel.
+__global__ __launch_bounds__(kSortBlock) void make_keys2_offsets_kernel(const int64_t* __restrict__ a, int64_t na, const int64_t* __restrict__ b0,
+                                                                        int64_t nb0, const int64_t* __restrict__ b1, int64_t nb1,
+                                                                        uint32_t key_base, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                                        uint32_t* __restrict__ zspan, int64_t zwords,
+                                                                        sort_offs_t* __restrict__ counts, unsigned* __restrict__ ticket, unsigned places) {
+    constexpr unsigned kStripes = 4;
+    __shared__ unsigned hist[kSortMaxPlaces * kSortRadix * kStripes];
+    sort_state_clear(zspan, zwords);
+    const unsigned tid = threadIdx.x, bins = places * kSortRadix;
+    for (unsigned i = tid; i < bins * kStripes; i += kSortBlock) hist[i] = 0u;
+    __syncthreads();
+    const unsigned stripe = tid % kStripes;
+    const int64_t n = na + nb0 + nb1, stride = (int64_t)gridDim.x * kSortBlock;
+    for (int64_t e = (int64_t)blockIdx.x * kSortBlock + tid; e < n; e += stride) {
+        uint32_t k, v;
+        if (e < na) { k = (uint32_t)a[e]; v = (uint32_t)e; }
+        else {
+            const int64_t o = e - na;
+            k = key_base + (uint32_t)(o < nb0 ? b0[o] : b1[o - nb0]);
+            v = (uint32_t)o;
+        }
+        keys[e] = k; vals[e] = v;
+        for (unsigned p = 0; p < places; ++p) {
+            const unsigned digit = (k >> (p * kSortRadixBits)) & (kSortRadix - 1u);
+            atomicAdd(&hist[(p * kSortRadix + digit) * kStripes + stripe], 1u);
+        }
+    }
+    __syncthreads();
+    for (unsigned i = tid; i < bins; i += kSortBlock) {
+        unsigned t = 0;
+#pragma unroll
+        for (unsigned j = 0; j < kStripes; ++j) t += hist[i * kStripes + j];
+        if (t) atomicAdd(reinterpret_cast<unsigned long long*>(counts + i), (unsigned long long)t);
+    }
+    if (!cdr_sign_in_last(ticket, gridDim.x)) return;
+    unsigned* sc = hist;                                         // (every thread is past its reads of hist: cdr_sign_in_last's barriers)
+    for (unsigned p = 0; p < places; ++p) {
+        unsigned c = 0;
+        if (tid < kSortRadix) {
+            c = (unsigned)__hip_atomic_load(reinterpret_cast<unsigned long long*>(counts + p * kSortRadix + tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            sc[tid] = c;
+        }
+        __syncthreads();
+        for (unsigned d = 1; d < kSortRadix; d <<= 1) {          // inclusive scan of the 512 counts
+            const unsigned t = (tid < kSortRadix && tid >= d) ? sc[tid - d] : 0u;
+            __syncthreads();
+            if (tid < kSortRadix) sc[tid] += t;
+            __syncthreads();
+        }
+        if (tid < kSortRadix) counts[p * kSortRadix + tid] = (sort_offs_t)(sc[tid] - c);
+        __syncthreads();
     }
 }
 
@@ -861,9 +937,13 @@ __global__ __launch_bounds__(kBlock) void coef_finish_kernel(const double* __res
                                                              float reg_weight, float* __restrict__ out9, int kmul = 1,
                                                              int64_t* __restrict__ step_u_dev = nullptr, int64_t* __restrict__ step_i_dev = nullptr,
                                                              float* __restrict__ hp_dev = nullptr, float lr = 0.f, float b1 = 0.f, float b2 = 0.f,
-                                                             unsigned* __restrict__ zero4 = nullptr, const float* __restrict__ norms2 = nullptr) {
+                                                             unsigned* __restrict__ zero4 = nullptr, const float* __restrict__ norms2 = nullptr,
+                                                             uint32_t* __restrict__ zspan = nullptr, int zwords = 0) {
     __shared__ double smem[2 * (kBlock / 64)];
     if (zero4 && threadIdx.x >= 64 && threadIdx.x < 68) zero4[threadIdx.x - 64] = 0u;       // the head lists' counters (occ_flags_kernel): no launch of their own
+    if (zspan) {                                 // the id sort's digit counts and ticket (make_keys2_offsets_kernel, the next launch)
+        for (int i = threadIdx.x; i < zwords; i += kBlock) zspan[i] = 0u;
+    }
     if (hp_dev && threadIdx.x < 2) {
         int64_t* c = threadIdx.x == 0 ? step_u_dev : step_i_dev;
         const int64_t st = c[0] + 1;
@@ -1565,7 +1645,9 @@ __global__ __launch_bounds__(kBlock) void seg_long_finish2_kernel(int D, dup_sid
 // Also unpacks the user column and clears the two head-list counters (cnt) of occ_flags_kernel.
 __global__ __launch_bounds__(kBlock) void shard_keys_kernel(const int64_t* __restrict__ recv3, int64_t Bl, uint32_t G, unsigned lb,
                                                             uint32_t key_base, int64_t* __restrict__ u_loc, uint32_t* __restrict__ keys,
-                                                            uint32_t* __restrict__ vals, unsigned* __restrict__ cnt) {
+                                                            uint32_t* __restrict__ vals, unsigned* __restrict__ cnt,
+                                                            uint32_t* __restrict__ zspan, int64_t zwords) {
+    sort_state_clear(zspan, zwords);
     if (blockIdx.x == 0 && threadIdx.x < 4) cnt[threadIdx.x] = 0u;
     for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < Bl; t += (int64_t)gridDim.x * kBlock) {
         const int64_t u = recv3[3 * t];
@@ -2167,7 +2249,7 @@ extern "C" int cdr_loss_finish_sums(void* stream, const float* sums3, int64_t B_
 // 117 us against 161 us for the library's gfx950 default.  Used from 2^18 pairs up; smaller sorts keep the default.
 using big_sort_config = rocprim::radix_sort_config<
     rocprim::default_config, rocprim::default_config,
-    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, 8>, rocprim::kernel_config<1024, 8>, 9,
+    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<kSortBlock, kSortItems>, rocprim::kernel_config<kSortBlock, kSortItems>, kSortRadixBits,
                                         rocprim::block_radix_rank_algorithm::match>,
     (size_t)1 << 17>;          // (the library merge-sorts up to 2^20 items: 0.167 ms for 1,048,576 pairs against 0.06 with Onesweep)
 constexpr int64_t kBigSort = 1 << 18;
@@ -2183,6 +2265,111 @@ static inline unsigned bits_for(int64_t num_rows) {
     while (b < 32 && ((int64_t)1 << b) < num_rows) ++b;
     return b;
 }
+
+// ------------------------------------------------------------------------------------------------ the id sort's own launch list
+// rocprim::radix_sort_pairs at this size is 14 dependent launches of which 4 move keys: the histogram, its scan, one Onesweep pass per
+// digit place -- and 7 memsets (1 for the digit counts, per pass 1 for the look-back states and 1 for the ordered block-id counter).
+// From kBigSort pairs up the same device code (rocprim::detail::onesweep_histograms / onesweep_scan_histograms / onesweep_iteration with
+// big_sort_config's constants, in thin kernels of ours) is launched by a host loop that is the library's radix_sort_onesweep_impl
+// without the memsets: every pass has its own look-back region and its own block-id word, and everything that must start at zero is ONE
+// span of the workspace that the caller's key-making kernel clears (sort_state_clear) -- stream-ordered before the first pass on every
+// path, which matters: a pass spins on look-back states, so a stale state could hang it.  The result is the library's, bit for bit (a
+// stable sort's output is a function of the keys alone).  This leans on rocprim::detail, so it is tied to the one rocPRIM version it was
+// written against; any other version, a smaller sort, and CDR_OWN_SORT=0 (the A/B switch: tools/ab_id_sort.sh) take the public call.
+#if ROCPRIM_VERSION == 400200
+#define CDR_HAVE_OWN_SORT 1
+namespace {
+
+namespace rpd = rocprim::detail;
+using sort_bid_t = rpd::block_id_wrapper<unsigned int, true>;    // ordered block ids (the library's choice on gfx950): what makes the look-back safe
+
+__global__ __launch_bounds__(kSortBlock) void sort_hist_kernel(const uint32_t* keys, sort_offs_t* counts, sort_offs_t size, sort_offs_t full_blocks,
+                                                               unsigned end_bit) {
+    rpd::onesweep_histograms<kSortBlock, kSortItems, kSortRadixBits, false>(keys, counts, size, full_blocks, rocprim::identity_decomposer{}, 0u, end_bit);
+}
+__global__ __launch_bounds__(kSortBlock) void sort_scan_kernel(sort_offs_t* counts) {
+    rpd::onesweep_scan_histograms<kSortBlock, kSortRadixBits>(counts);
+}
+__global__ __launch_bounds__(kSortBlock) void sort_pass_kernel(const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
+                                                               unsigned size, sort_offs_t* offs_in, sort_offs_t* offs_out,
+                                                               rpd::onesweep_lookback_state* lookback, unsigned bit, unsigned cur_bits,
+                                                               unsigned full_blocks, sort_bid_t bid) {
+    rpd::onesweep_iteration<kSortBlock, kSortItems, kSortRadixBits, false, rocprim::block_radix_rank_algorithm::match>(
+        keys_in, keys_out, vals_in, vals_out, size, offs_in, offs_out, lookback, rocprim::identity_decomposer{}, bit, cur_bits, full_blocks, bid);
+}
+
+// The own list's part of the sort workspace, behind {keys_in | vals_in}:
+//   zero span A   counts[places][512] (sort_offs_t) | ticket line (32 words; word 0 = make_keys2_offsets_kernel's sign-in ticket)
+//   zero span B   block-id words, one 128-byte line per pass | look-back states [places][blocks][512]
+//   offs_tmp[512] | keys_tmp[n] | vals_tmp[n]                        (written before they are read: not cleared)
+// A and B are contiguous.  `blocks` is the grid of every pass and sizes the look-back regions -- one place, this constructor.
+struct own_sort_plan {
+    unsigned blocks = 0, full_blocks = 0, places = 0;
+    int64_t wordsA = 0, wordsB = 0;
+    size_t o_ids = 0, o_lookback = 0, o_offs_tmp = 0, o_keys_tmp = 0, o_vals_tmp = 0, bytes = 0;
+    own_sort_plan(size_t n, unsigned bits) {
+        constexpr size_t per_block = (size_t)kSortBlock * kSortItems;
+        blocks = (unsigned)((n + per_block - 1) / per_block);
+        full_blocks = n % per_block == 0 ? blocks : blocks - 1;
+        places = (bits + kSortRadixBits - 1) / kSortRadixBits;
+        const size_t arr = ((n * sizeof(uint32_t)) + 255) & ~(size_t)255;
+        wordsA = (int64_t)(places * kSortRadix * (sizeof(sort_offs_t) / 4) + 32);
+        o_ids = (size_t)wordsA * 4;
+        o_lookback = o_ids + (size_t)kSortMaxPlaces * 128;
+        const size_t lb_bytes = (size_t)places * blocks * kSortRadix * sizeof(rpd::onesweep_lookback_state);
+        wordsB = (int64_t)((o_lookback + lb_bytes - o_ids) / 4);
+        o_offs_tmp = (o_lookback + lb_bytes + 255) & ~(size_t)255;
+        o_keys_tmp = o_offs_tmp + kSortRadix * sizeof(sort_offs_t);
+        o_vals_tmp = o_keys_tmp + arr;
+        bytes = o_vals_tmp + arr;
+    }
+    sort_offs_t* counts(char* tmp) const { return (sort_offs_t*)tmp; }
+    unsigned* ticket(char* tmp) const { return (unsigned*)(tmp + (size_t)wordsA * 4 - 128); }
+};
+static_assert(sizeof(rpd::onesweep_lookback_state) == 4 && sizeof(sort_offs_t) % 4 == 0, "the zero span is counted in 32-bit words");
+
+// one batch of the library's loop (it cuts a sort into batches of 2^30 items; larger sorts keep the library call)
+constexpr int64_t kOwnSortMax = (int64_t)1 << 30;
+
+inline bool own_sort_on(int64_t n) {
+    static const bool on = [] { const char* e = getenv("CDR_OWN_SORT"); return !(e && e[0] == '0'); }();       // A/B switch (tools/)
+    return on && n >= kBigSort && n <= kOwnSortMax;
+}
+
+// histogram + scan of keys_in -> exclusive digit offsets in counts (what make_keys2_offsets_kernel does inside the key-making launch)
+inline hipError_t own_sort_offsets(const own_sort_plan& P, char* tmp, const uint32_t* keys_in, size_t n, unsigned bits, hipStream_t s) {
+    sort_hist_kernel<<<dim3(P.blocks), dim3(kSortBlock), 0, s>>>(keys_in, P.counts(tmp), (sort_offs_t)n, (sort_offs_t)P.full_blocks, bits);
+    sort_scan_kernel<<<dim3(P.places), dim3(kSortBlock), 0, s>>>(P.counts(tmp));
+    return hipGetLastError();
+}
+
+// radix_sort_onesweep_impl's pass loop: the first pass reads the input, the passes alternate between the temporaries and the output
+// so that the last one lands in the output.  Needs the offsets in counts and zero span B cleared.
+inline hipError_t own_sort_passes(const own_sort_plan& P, char* tmp, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in,
+                                  uint32_t* vals_out, size_t n, unsigned bits, hipStream_t s) {
+    uint32_t* keys_tmp = (uint32_t*)(tmp + P.o_keys_tmp);
+    uint32_t* vals_tmp = (uint32_t*)(tmp + P.o_vals_tmp);
+    auto* lookback = (rpd::onesweep_lookback_state*)(tmp + P.o_lookback);
+    bool to_output = (P.places - 1) % 2 == 0, from_input = true;
+    unsigned place = 0;
+    for (unsigned bit = 0; bit < bits; bit += kSortRadixBits, ++place) {
+        const uint32_t* ki = from_input ? keys_in : (to_output ? keys_tmp : keys_out);
+        const uint32_t* vi = from_input ? vals_in : (to_output ? vals_tmp : vals_out);
+        const unsigned cur_bits = bits - bit < kSortRadixBits ? bits - bit : kSortRadixBits;
+        sort_pass_kernel<<<dim3(P.blocks), dim3(kSortBlock), 0, s>>>(
+            ki, to_output ? keys_out : keys_tmp, vi, to_output ? vals_out : vals_tmp, (unsigned)n, P.counts(tmp) + (size_t)place * kSortRadix,
+            (sort_offs_t*)(tmp + P.o_offs_tmp), lookback + (size_t)place * P.blocks * kSortRadix, bit, cur_bits, P.full_blocks,
+            sort_bid_t::create(tmp + P.o_ids + (size_t)place * 128));
+        from_input = false;
+        to_output = !to_output;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+#else
+#define CDR_HAVE_OWN_SORT 0
+#endif
 
 // ------------------------------------------------------------------------------------------------ what the host entry points share
 namespace {
@@ -2244,15 +2431,27 @@ extern "C" int cdr_sort_workspace_bytes(int64_t n, int64_t num_rows, size_t* byt
     size_t tmp = 0;
     hipError_t e = sort_pairs(nullptr, tmp, nullptr, nullptr, nullptr, nullptr, (size_t)n, bits_for(num_rows), (hipStream_t)0);
     if (e != hipSuccess) { cdr_set_error("cdr_sort_workspace_bytes: %s", hipGetErrorString(e)); return (int)e; }
+#if CDR_HAVE_OWN_SORT
+    if (n >= kBigSort && n <= kOwnSortMax) {             // either list works on the same region (whatever CDR_OWN_SORT says: one size per shape)
+        const size_t own = own_sort_plan((size_t)n, bits_for(num_rows)).bytes;
+        if (own > tmp) tmp = own;
+    }
+#endif
     *bytes = up256(tmp) + 2 * up256((size_t)n * sizeof(uint32_t));
     return CDR_OK;
 }
 
-// What every id sort shares: the workspace {keys_in[n] | vals_in[n] | rocPRIM's temporary} (cdr_sort_workspace_bytes), the caller's
-// key-making launch -- make_keys(keys_in, vals_in) -- and the radix sort over the bits of `key_space`, in one CDR_TAG_SORT bracket.
+// What a key-making launch clears beside making keys (sort_state_clear; p = nullptr: nothing).
+struct sort_clear { uint32_t* p; int64_t words; };
+
+// What every id sort shares: the workspace {keys_in[n] | vals_in[n] | the sort's temporary} (cdr_sort_workspace_bytes), the caller's
+// key-making launch -- make_keys(keys_in, vals_in, z), which also clears z -- and the radix sort over the bits of `key_space`, in one
+// CDR_TAG_SORT bracket: the own launch list from kBigSort pairs up, else the library call.
+// keys_make_offsets: the caller's key-making launch leaves the digit offsets too whenever it is handed a span to clear (z.p != nullptr:
+// zero span B; the caller has cleared span A on the stream before, see own_sort_span_a) -- no histogram and scan launches then.
 template <class MakeKeys>
 static int sort_ids_with(cdr_ctx* ctx, hipStream_t s, int64_t n, int64_t key_space, uint32_t* keys_sorted, uint32_t* perm, void* ws,
-                         size_t ws_bytes, MakeKeys&& make_keys) {
+                         size_t ws_bytes, MakeKeys&& make_keys, bool keys_make_offsets = false) {
     size_t need = 0;
     int rc = cdr_sort_workspace_bytes(n, key_space, &need);
     if (rc) return rc;
@@ -2260,14 +2459,43 @@ static int sort_ids_with(cdr_ctx* ctx, hipStream_t s, int64_t n, int64_t key_spa
     const size_t arr = up256((size_t)n * sizeof(uint32_t));
     uint32_t* keys_in = (uint32_t*)ws;
     uint32_t* vals_in = (uint32_t*)((char*)ws + arr);
-    void* tmp = (char*)ws + 2 * arr;
+    char* tmp = (char*)ws + 2 * arr;
     size_t tmp_bytes = ws_bytes - 2 * arr;
+    const unsigned bits = bits_for(key_space);
     cdr_time_scope ts(ctx, CDR_TAG_SORT, s);
-    make_keys(keys_in, vals_in);
+#if CDR_HAVE_OWN_SORT
+    if (own_sort_on(n)) {
+        CDR_CHECK_ARG(((uintptr_t)tmp & 127) == 0);
+        const own_sort_plan P((size_t)n, bits);
+        if (keys_make_offsets) {
+            make_keys(keys_in, vals_in, sort_clear{(uint32_t*)(tmp + P.o_ids), P.wordsB});
+            CDR_LAUNCH_CHECK();
+        } else {
+            make_keys(keys_in, vals_in, sort_clear{(uint32_t*)tmp, P.wordsA + P.wordsB});
+            CDR_LAUNCH_CHECK();
+            CDR_HIP(own_sort_offsets(P, tmp, keys_in, (size_t)n, bits, s));
+        }
+        CDR_HIP(own_sort_passes(P, tmp, keys_in, keys_sorted, vals_in, perm, (size_t)n, bits, s));
+        return CDR_OK;
+    }
+#endif
+    make_keys(keys_in, vals_in, sort_clear{nullptr, 0});
     CDR_LAUNCH_CHECK();
-    CDR_HIP(sort_pairs(tmp, tmp_bytes, keys_in, keys_sorted, vals_in, perm, (size_t)n, bits_for(key_space), s));
+    CDR_HIP(sort_pairs(tmp, tmp_bytes, keys_in, keys_sorted, vals_in, perm, (size_t)n, bits, s));
     return CDR_OK;
 }
+
+#if CDR_HAVE_OWN_SORT
+// Zero span A (digit counts + ticket) of the sort that sort_ids_with will run on this workspace with keys_make_offsets, for the caller's
+// earlier launch to clear; words = 0 when that sort takes the library call or the workspace is too small (sort_ids_with refuses it).
+static sort_clear own_sort_span_a(int64_t n, int64_t key_space, void* ws, size_t ws_bytes) {
+    size_t need = 0;
+    if (!own_sort_on(n) || cdr_sort_workspace_bytes(n, key_space, &need) != CDR_OK || ws_bytes < need) return {nullptr, 0};
+    return {(uint32_t*)((char*)ws + 2 * up256((size_t)n * sizeof(uint32_t))), own_sort_plan((size_t)n, bits_for(key_space)).wordsA};
+}
+#else
+static sort_clear own_sort_span_a(int64_t, int64_t, void*, size_t) { return {nullptr, 0}; }
+#endif
 
 extern "C" int cdr_sort_ids(cdr_ctx* ctx, void* stream, const int64_t* ids0, int64_t n0, const int64_t* ids1, int64_t n1,
                             int64_t num_rows, uint32_t* keys_sorted, uint32_t* perm, void* workspace,
@@ -2275,28 +2503,50 @@ extern "C" int cdr_sort_ids(cdr_ctx* ctx, void* stream, const int64_t* ids0, int
     const int64_t n = n0 + n1;
     CDR_CHECK_ARG(ids0 && n0 > 0 && (n1 == 0 || ids1) && keys_sorted && perm && workspace);
     hipStream_t s = (hipStream_t)stream;
-    return sort_ids_with(ctx, s, n, num_rows, keys_sorted, perm, workspace, workspace_bytes, [&](uint32_t* keys_in, uint32_t* vals_in) {
-        make_keys_kernel<<<dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s>>>(ids0, n0, ids1, n1, keys_in, vals_in);
+    return sort_ids_with(ctx, s, n, num_rows, keys_sorted, perm, workspace, workspace_bytes, [&](uint32_t* keys_in, uint32_t* vals_in, sort_clear z) {
+        make_keys_kernel<<<dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s>>>(ids0, n0, ids1, n1, keys_in, vals_in, z.p, z.words);
     });
+}
+
+// key_base of a two-table sort (two_table_bits); 0: the key space does not fit
+static inline uint32_t two_table_key_base(int64_t rows_a, int64_t rows_b) {
+    const unsigned hb = two_table_bits(rows_a, rows_b);
+    return hb < 31 ? 1u << hb : 0u;
+}
+
+// span_a: zero span A of this very sort (own_sort_span_a with the same n, key space and workspace), ALREADY CLEARED by an earlier launch
+// on the stream -- the key-making launch then leaves the digit offsets itself (make_keys2_offsets_kernel); {nullptr, 0}: it does not.
+static int sort_two_tables(cdr_ctx* ctx, void* stream, const int64_t* ids_a, int64_t n_a, int64_t rows_a, const int64_t* ids_b0,
+                           int64_t n_b0, const int64_t* ids_b1, int64_t n_b1, int64_t rows_b, uint32_t* keys_sorted, uint32_t* perm,
+                           uint32_t* key_base_out, void* workspace, size_t workspace_bytes, sort_clear span_a) {
+    const int64_t n = n_a + n_b0 + n_b1;
+    CDR_CHECK_ARG(ids_a && n_a > 0 && ids_b0 && n_b0 > 0 && (n_b1 == 0 || ids_b1) && keys_sorted && perm && key_base_out && workspace);
+    CDR_CHECK_ARG(rows_a > 0 && rows_b > 0);
+    const uint32_t key_base = two_table_key_base(rows_a, rows_b);
+    CDR_CHECK_ARG(key_base != 0u);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = sort_ids_with(ctx, s, n, (int64_t)key_base * 2, keys_sorted, perm, workspace, workspace_bytes, [&](uint32_t* keys_in, uint32_t* vals_in, sort_clear z) {
+        if (span_a.p && z.p) {
+            const unsigned places = (bits_for((int64_t)key_base * 2) + kSortRadixBits - 1) / kSortRadixBits;
+            // (8 keys per thread as rocPRIM's histogram launch: a few hundred blocks keep the global atomics of the flush few)
+            const unsigned kgrid = (unsigned)((n + (int64_t)kSortBlock * kSortItems - 1) / ((int64_t)kSortBlock * kSortItems));
+            make_keys2_offsets_kernel<<<dim3(kgrid), dim3(kSortBlock), 0, s>>>(ids_a, n_a, ids_b0, n_b0, ids_b1, n_b1, key_base, keys_in, vals_in, z.p, z.words,
+                                                                               (sort_offs_t*)span_a.p, (unsigned*)span_a.p + span_a.words - 32, places);
+        } else {
+            make_keys2_kernel<<<dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s>>>(ids_a, n_a, ids_b0, n_b0, ids_b1, n_b1, key_base, keys_in, vals_in, z.p, z.words);
+        }
+    }, span_a.p != nullptr);
+    if (rc) return rc;
+    *key_base_out = key_base;
+    return CDR_OK;
 }
 
 extern "C" int cdr_sort_ids_two_tables(cdr_ctx* ctx, void* stream, const int64_t* ids_a, int64_t n_a, int64_t rows_a,
                                        const int64_t* ids_b0, int64_t n_b0, const int64_t* ids_b1, int64_t n_b1, int64_t rows_b,
                                        uint32_t* keys_sorted, uint32_t* perm, uint32_t* key_base_out, void* workspace,
                                        size_t workspace_bytes) {
-    const int64_t n = n_a + n_b0 + n_b1;
-    CDR_CHECK_ARG(ids_a && n_a > 0 && ids_b0 && n_b0 > 0 && (n_b1 == 0 || ids_b1) && keys_sorted && perm && key_base_out && workspace);
-    CDR_CHECK_ARG(rows_a > 0 && rows_b > 0);
-    const unsigned hb = two_table_bits(rows_a, rows_b);
-    CDR_CHECK_ARG(hb < 31);
-    const uint32_t key_base = 1u << hb;
-    hipStream_t s = (hipStream_t)stream;
-    int rc = sort_ids_with(ctx, s, n, (int64_t)key_base * 2, keys_sorted, perm, workspace, workspace_bytes, [&](uint32_t* keys_in, uint32_t* vals_in) {
-        make_keys2_kernel<<<dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s>>>(ids_a, n_a, ids_b0, n_b0, ids_b1, n_b1, key_base, keys_in, vals_in);
-    });
-    if (rc) return rc;
-    *key_base_out = key_base;
-    return CDR_OK;
+    return sort_two_tables(ctx, stream, ids_a, n_a, rows_a, ids_b0, n_b0, ids_b1, n_b1, rows_b, keys_sorted, perm, key_base_out, workspace,
+                           workspace_bytes, sort_clear{nullptr, 0});
 }
 
 extern "C" int cdr_rowwise_apply(cdr_ctx* ctx, void* stream, int opt, float* table, float* exp_avg, float* exp_avg_sq, int D,
@@ -2364,11 +2614,12 @@ step_tables make_tables(int opt_user, float* user_tab, float* user_m, float* use
 
 // Stage 1, EmbLoss head: the squared norms of the n_rows gathered (user, item) rows -> coefficients in out9[4], out9[5].  Without
 // regularisation the norms launch is skipped (ngrid = 0 says so to coef_finish_kernel).  The finishing block also clears the head
-// lists' counters `cnt` and, when given, advances the device-resident update counts (their Adam scalars -> hp_dev).
+// lists' counters `cnt` and `zspan` (zero span A of the id sort behind it: own_sort_span_a) and, when given, advances the
+// device-resident update counts (their Adam scalars -> hp_dev).
 int embloss_head(cdr_ctx* ctx, hipStream_t s, const float* user_tab, const float* item_tab, int D, const int64_t* uid, const int64_t* pid,
                  int64_t n_rows, int64_t B, int kmul, float reg_weight, float* out9, unsigned* cnt, int64_t* step_user_dev = nullptr,
                  int64_t* step_item_dev = nullptr, float* hp_dev = nullptr, float lr = 0.f, float beta1 = 0.f, float beta2 = 0.f,
-                 const float* user_n2 = nullptr, const float* item_n2 = nullptr) {
+                 const float* user_n2 = nullptr, const float* item_n2 = nullptr, sort_clear zspan = {nullptr, 0}) {
     int ngrid = 0;
     if (reg_weight != 0.f) {
         const int lpr = cdr_lpr_for(D);
@@ -2382,7 +2633,7 @@ int embloss_head(cdr_ctx* ctx, hipStream_t s, const float* user_tab, const float
         CDR_LAUNCH_CHECK();
     }
     coef_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, ngrid, B, ngrid ? reg_weight : 0.f, out9, kmul, step_user_dev, step_item_dev, hp_dev,
-                                                        lr, beta1, beta2, cnt);
+                                                        lr, beta1, beta2, cnt, nullptr, zspan.p, (int)zspan.words);
     CDR_LAUNCH_CHECK();
     return CDR_OK;
 }
@@ -2545,10 +2796,15 @@ static int bpr_step_fused_impl(cdr_ctx* ctx, void* stream, int opt, float* user_
         CDR_LAUNCH_CHECK();
     } else {
         // ---- EmbLoss coefficients first (they do not need the sort): out9[4], out9[5]  (+ the device-resident update counts, when given)
+        // (its finishing block also clears the digit counts and the ticket of the sort behind it, whose key-making launch then leaves
+        // the digit offsets itself: one id sort = key making + one launch per digit place.  CDR_OWN_SORT=1: the A/B arm without this.)
+        static const bool keys_make_offsets = [] { const char* e = getenv("CDR_OWN_SORT"); return !(e && e[0] == '1'); }();
+        const uint32_t kb = two_table_key_base(user_rows, item_rows);
+        const sort_clear span_a = keys_make_offsets && kb ? own_sort_span_a(3 * B, (int64_t)kb * 2, sort_ws, sort_ws_bytes) : sort_clear{nullptr, 0};
         rc = embloss_head(ctx, s, user_tab, item_tab, D, uid, pid, B, B, 1, reg_weight, out9, hv.cnt, step_user_dev, step_item_dev, hp_dev, lr, beta1, beta2,
-                          NU, NI);
+                          NU, NI, span_a);
         if (rc) return rc;
-        rc = cdr_sort_ids_two_tables(ctx, stream, uid, B, user_rows, pid, B, nid, B, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes);
+        rc = sort_two_tables(ctx, stream, uid, B, user_rows, pid, B, nid, B, item_rows, keys, perm, &key_base, sort_ws, sort_ws_bytes, span_a);
         if (rc) return rc;
         rc = occ_flags(ctx, s, keys, perm, B, 3 * B, 4, flags, hv, B <= kCountMaxB);
         if (rc) return rc;
@@ -2932,8 +3188,9 @@ extern "C" int cdr_bpr_shard_plan(cdr_ctx* ctx, void* stream, const int64_t* rec
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = 3 * Bl;
     const heads_view hv(heads, Bl);
-    rc = sort_ids_with(ctx, s, n, (int64_t)kb.key_base * 2, keys, perm, ws, ws_bytes, [&](uint32_t* keys_in, uint32_t* vals_in) {
-        shard_keys_kernel<<<dim3(grid_for(Bl, kBlock)), dim3(kBlock), 0, s>>>(recv3, Bl, (uint32_t)world, kb.lb, kb.key_base, u_loc, keys_in, vals_in, hv.cnt);
+    rc = sort_ids_with(ctx, s, n, (int64_t)kb.key_base * 2, keys, perm, ws, ws_bytes, [&](uint32_t* keys_in, uint32_t* vals_in, sort_clear z) {
+        shard_keys_kernel<<<dim3(grid_for(Bl, kBlock)), dim3(kBlock), 0, s>>>(recv3, Bl, (uint32_t)world, kb.lb, kb.key_base, u_loc, keys_in, vals_in, hv.cnt,
+                                                                             z.p, z.words);
     });
     if (rc) return rc;
     rc = occ_flags(ctx, s, keys, perm, Bl, n, 4, flags, hv);
@@ -3096,7 +3353,9 @@ namespace {
 __global__ __launch_bounds__(kBlock) void make_keys_pair_kernel(const int64_t* __restrict__ a0, int64_t na0, const int64_t* __restrict__ a1,
                                                                 int64_t na1, const int64_t* __restrict__ b0, int64_t nb0,
                                                                 const int64_t* __restrict__ b1, int64_t nb1, uint32_t key_base,
-                                                                uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+                                                                uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                                uint32_t* __restrict__ zspan, int64_t zwords) {
+    sort_state_clear(zspan, zwords);
     const int64_t na = na0 + na1, n = na + nb0 + nb1, stride = (int64_t)gridDim.x * kBlock;
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride) {
         if (e < na) { keys[e] = (uint32_t)(e < na0 ? a0[e] : a1[e - na0]); vals[e] = (uint32_t)e; }
@@ -3319,8 +3578,8 @@ extern "C" int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int los
     const unsigned hb = two_table_bits(user_rows, item_rows);
     CDR_CHECK_ARG(hb < 31);
     const uint32_t key_base = 1u << hb;
-    int rc = sort_ids_with(ctx, s, 2 * N, (int64_t)key_base * 2, keys, perm, sort_ws, sort_ws_bytes, [&](uint32_t* keys_in, uint32_t* vals_in) {
-        make_keys_pair_kernel<<<dim3(grid_for(2 * N, kBlock)), dim3(kBlock), 0, s>>>(su, B_s, tu, B_t, si, B_s, ti, B_t, key_base, keys_in, vals_in);
+    int rc = sort_ids_with(ctx, s, 2 * N, (int64_t)key_base * 2, keys, perm, sort_ws, sort_ws_bytes, [&](uint32_t* keys_in, uint32_t* vals_in, sort_clear z) {
+        make_keys_pair_kernel<<<dim3(grid_for(2 * N, kBlock)), dim3(kBlock), 0, s>>>(su, B_s, tu, B_t, si, B_s, ti, B_t, key_base, keys_in, vals_in, z.p, z.words);
     });
     if (rc) return rc;
     rc = occ_flags(ctx, s, keys, perm, N, 2 * N, 4, flags, hv);
