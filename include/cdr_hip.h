@@ -66,7 +66,7 @@ int cdr_id_count_workspace_bytes(int64_t B, size_t* bytes);
 int cdr_norm_rec_floats(void);
 int cdr_row_norms_build(void* stream, const float* table, int64_t rows, int D, float* n2);
 int cdr_ctx_set_norm_cache(cdr_ctx* ctx, float* user_n2, int64_t user_rows, float* item_n2, int64_t item_rows);
-#define CDR_ABI_VERSION 63
+#define CDR_ABI_VERSION 64
 int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the header the library was built from; bumped on any signature change */
 
 /* Optional measurement aid: HIP-event brackets around the hot kernels, recorded on the stream each kernel is launched
@@ -94,6 +94,7 @@ int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the
 #define CDR_TAG_BATCH_NORMS 19          /* batch_norms_kernel: EmbLoss norms of the batch's user and positive rows */
 #define CDR_TAG_CONET_FB 20             /* conet_fb_kernel: conet_fwd_kernel's and conet_bwd_kernel's passes over a row block in one launch */
 #define CDR_TAG_TRIPLET_FWD_GRAD 21   /* triplet_fwd_grad_kernel: SSCDR's triplet loss + compact gradient rows */
+#define CDR_TAG_CLFM_FWD_GRAD 22      /* clfm_fwd_grad_kernel: CLFM's factor map, BCE and the three gradient contractions of one domain */
 int cdr_timing_enable(cdr_ctx* ctx, int capacity);
 int cdr_timing_collect(cdr_ctx* ctx, int* tags, float* ms, int max_n, int* n_out);
 
@@ -677,6 +678,25 @@ int cdr_triplet_fwd_grad(cdr_ctx* ctx, void* stream, const float* user_tab, cons
                          const int64_t* uid, const int64_t* pid, const int64_t* nid, int64_t B,
                          float margin, float eps, float* out3 /* {mean hinge loss, active triples, 0} */,
                          float* GU /* [B, D] */, float* GI /* [2B, D]: rows [0,B) positives, [B,2B) negatives */);
+/* CLFM's domain step, forward half (clfm.py:74-101 forward, 103-124 loss) for one domain of B rows: u = user_tab[uid] [Du],
+ * i = item_tab[iid] [Di], f = W u with W [Di, Du] row-major -- the stacked weight cat([shared_linear ; <domain>_only_linear]) --,
+ * p = sigmoid(<f, i>), bce = mean BCE(p, label) with torch's -100 clamp of both logs, and `weight` the domain's share of the total
+ * (alpha for the source, 1 - alpha for the target).  With g_b = weight (p_b - y_b) / B (the 1e-12 clamp of cdr_point_fwd_grad's BCE
+ * branch) it leaves one compact gradient row per occurrence, GU[b] = g_b W^T i_b and GI[b] = g_b f_b, and the weight gradient
+ * dW = sum_b g_b i_b u_b^T [Di, Du].  out8 = {weight (bce + reg_weight (nU + nI) / B), bce, (nU + nI) / B, nU, nI, c_u, c_i, 0} with
+ * nU / nI the Frobenius norms of the GATHERED rows (every occurrence counts) and c = weight reg_weight / (B norm), 0 for a zero norm:
+ * the EmbLoss gradient does not pass through W.  Apply the rows with cdr_sort_ids_two_tables(uid | iid) and two cdr_rowwise_apply
+ * (D = Du, G = GU, reg_coef = out8 + 5) / (D = Di, G = GI, reg_coef = out8 + 6), neg_start = reg_limit = B.  The three contractions run
+ * on v_mfma_f32_32x32x2_f32 out of LDS (widths zero-padded to 32 there); dW is accumulated per workgroup and the partials -- one
+ * [Di, Du] block per workgroup in `workspace`, cdr_clfm_fwd_grad_workspace_bytes -- are added in workgroup order; loss and norm sums
+ * go through fp64 block partials.  No float atomics: a rerun is bit-equal.  Du % 4 == 0, Di % 4 == 0, 4 <= Du, Di <= CDR_CLFM_MAX_DIM,
+ * B > 0, 16-byte aligned tables, W, GU, GI (CDR_EINVAL before any launch otherwise).                                              */
+#define CDR_CLFM_MAX_DIM 128
+int cdr_clfm_fwd_grad_workspace_bytes(int64_t B, int Du, int Di, size_t* bytes);
+int cdr_clfm_fwd_grad(cdr_ctx* ctx, void* stream, const float* user_tab, const float* item_tab, int Du, int Di,
+                      const float* W /* [Di, Du] */, const int64_t* uid, const int64_t* iid, const float* label, int64_t B,
+                      float weight, float reg_weight, float* out8, float* GU /* [B, Du] */, float* GI /* [B, Di] */,
+                      float* dW /* [Di, Du] */, void* workspace, size_t workspace_bytes);
 /* The same step with the optimizer of every row that occurs ONCE in the batch applied by the forward kernel itself (round 3;
  * replaces cdr_bpr_fwd_grad + cdr_sort_ids_two_tables + 2 x cdr_rowwise_apply for emcdr.py:123-131,146-154 + Adam): the EmbLoss
  * norms of the batch are gathered first (the gradient coefficient reg_weight / (B ||rows||) is needed before the first row is

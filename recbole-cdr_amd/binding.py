@@ -34,7 +34,7 @@ def capturing(graph, stream):
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('CDR_LIB_PATH') or os.path.join(_HERE, 'lib', 'libcdrhip.so')   # env: A/B builds only
-ABI_VERSION = 63
+ABI_VERSION = 64
 SIGNIN_WORDS = 288          # CDR_SIGNIN_WORDS: the sign-in words cdr_adam_multi_dev's ``ticket`` points at
 
 CDR_LOSS_MSE, CDR_LOSS_BCE = 0, 1
@@ -103,6 +103,9 @@ _SIGNATURES = {
                          _c_ptr, _c_ptr, _c_int],
     'cdr_loss_finish_sums': [_c_ptr, _c_ptr, _c_i64, _c_f32, _c_ptr],
     'cdr_triplet_fwd_grad': [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_f32, _c_ptr, _c_ptr, _c_ptr],
+    'cdr_clfm_fwd_grad_workspace_bytes': [_c_i64, _c_int, _c_int, ctypes.POINTER(ctypes.c_size_t)],
+    'cdr_clfm_fwd_grad': [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_f32, _c_ptr, _c_ptr,
+                          _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
     'cdr_bpr_step_fused_heads_words': [_c_i64, ctypes.POINTER(_c_i64)],
     'cdr_bpr_step_fused_kmajor_sizes': [_c_i64, _c_int, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)],
     'cdr_bpr_step_fused_kmajor': [_c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_int,
@@ -439,7 +442,8 @@ TAGS = {1: 'bpr_fwd_kernel', 2: 'point_fwd_kernel', 3: 'bpr_fwd_grad_kernel', 4:
         8: 'bpr_partial_diff_kernel', 9: 'bpr_grad_from_diff_kernel',
         10: 'point_partial_dot_kernel', 11: 'point_grad_from_dot_kernel',
         12: 'conet_fwd_kernel', 13: 'conet_bwd_kernel', 14: 'conet_wgrad_kernel', 15: 'bpr_fwd_kmajor_kernel', 16: 'map_step_kernel',
-        17: 'occ_flags_kernel', 18: 'bpr_fwd_apply_kernel', 19: 'batch_norms_kernel', 20: 'conet_fb_kernel', 21: 'triplet_fwd_grad_kernel'}
+        17: 'occ_flags_kernel', 18: 'bpr_fwd_apply_kernel', 19: 'batch_norms_kernel', 20: 'conet_fb_kernel', 21: 'triplet_fwd_grad_kernel',
+        22: 'clfm_fwd_grad_kernel'}
 
 
 _timing_cap = {}     # device index -> ring capacity requested for every context (= stream) of that device

@@ -1,5 +1,5 @@
 // Row-wise kernels of the five models SURVEY.md 8f-4 lists after the BASELINE configs (DTCDR, DeepAPF, NATR, DCDCSR; CLFM needs none
-// of its own).  Their tables are small (they sit in L2 / Infinity Cache) and their dense layers go through the fp32-MFMA
+// of its own in dense mode -- its O(batch) training step has its kernel in cdr_clfm.hip).  Their tables are small (they sit in L2 / Infinity Cache) and their dense layers go through the fp32-MFMA
 // contraction (cdr_gemm_f32_ex); what is left are per-row fusions of the reference's elementwise chains: one wave per batch row,
 // lanes across the embedding dimension, wave reductions by DPP / permlane swaps (cdr_common.h), no atomics except the
 // embedding-gradient scatter (same as cdr_scatter_add_rows), parameter-gradient reductions over the batch through per-row

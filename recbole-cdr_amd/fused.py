@@ -1,6 +1,7 @@
 """Fused row-wise training steps: forward + backward + optimizer for one batch without table-sized gradients
 (FusedBPRStep: pairwise BPR; FusedPointStep: pointwise MSE / BCE; FusedPointPairStep: CMF's two domains on shared tables;
-FusedTripletStep: SSCDR's triplet margin loss; FusedMapStep / SSCDRMapStep: EMCDR's / SSCDR's OVERLAP-phase mapping loss).
+FusedTripletStep: SSCDR's triplet margin loss; FusedCLFMStep: CLFM's two domains, four tables and stacked factor weights;
+FusedMapStep / SSCDRMapStep: EMCDR's / SSCDR's OVERLAP-phase mapping loss).
 
 This is the large-table counterpart of ``loss.backward(); optimizer.step()`` in the reference's loop
 (recbole_cdr/trainer/trainer.py:59-73 -> recbole ``Trainer._train_epoch``): dense ``[rows, D]`` gradients and a dense
@@ -706,6 +707,116 @@ class FusedTripletStep(_TwoTableStep):
                     B_.raw(self.keys[lo:lo + n]), B_.raw(self.perm[lo:lo + n]), n, B_.f32(G), n, 0, None, *self._hp(), st.step, None,
                     int(base))
         return self.out3
+
+
+class FusedCLFMStep(_Step):
+    """CLFM's BOTH-phase step (clfm.py:74-124): per domain  p = sigmoid(<W_d U_d[uid], I_d[iid]>)  with the stacked weight
+    W_d = [shared_linear ; <domain>_only_linear] [Di, Du], loss = alpha (BCE_s + reg EmbLoss_s) + (1 - alpha) (BCE_t + reg EmbLoss_t).  The
+    four tables (user and item table of each domain, widths Du and Di) are updated row-wise on the batch's rows; the three small
+    weights keep the exact dense Adam (plain SGD with opt='sgd'), as in SSCDRMapStep.  Per domain: cdr_clfm_fwd_grad (csrc/cdr_clfm.hip:
+    the factor map, the loss and the three gradient contractions in one pass, + its finishing launch), one sort for both tables, two
+    segmented applies; both forwards run before anything is updated, so both domains see the pre-step weights.  The shared weight's
+    gradient is the sum of the two domains' first ``share`` rows of dW.  The update counts are the host's: not capturable.
+
+    ``weights``: (shared_linear.weight or None, source_only_linear.weight or None, target_only_linear.weight or None) -- the
+    parameters themselves: the step sets their ``.grad`` and updates them in place."""
+
+    MAX_DIM = 128                                                                # CDR_CLFM_MAX_DIM
+
+    @classmethod
+    def check_widths(cls, Du, Di):
+        if not (4 <= Du <= cls.MAX_DIM and 4 <= Di <= cls.MAX_DIM and Du % 4 == 0 and Di % 4 == 0):
+            raise ValueError(f'FusedCLFMStep: user_embedding_size and item embedding size must be multiples of 4 in 4..{cls.MAX_DIM} '
+                             f'(the weight tile lives in LDS), got {Du} and {Di}')
+
+    def __init__(self, source_user, source_item, target_user, target_item, weights, max_source, max_target, alpha, reg_weight, opt='adam',
+                 lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, states=None):
+        from .trainer.trainer import DenseAdam
+        tables = (source_user, source_item, target_user, target_item)
+        assert all(t.is_cuda for t in tables), 'FusedCLFMStep needs ROCm device tensors'
+        Du, Di = source_user.shape[1], source_item.shape[1]
+        if target_user.shape[1] != Du or target_item.shape[1] != Di:
+            raise ValueError(f'FusedCLFMStep: the domains\' tables differ in width ({tuple(t.shape[1] for t in tables)})')
+        self.check_widths(Du, Di)                                                # (before anything is allocated)
+        shared, s_only, t_only = weights
+        self.share = 0 if shared is None else shared.shape[0]
+        for w, rows in ((shared, self.share), (s_only, Di - self.share), (t_only, Di - self.share)):
+            if (w is None) != (rows == 0) or (w is not None and tuple(w.shape) != (rows, Du)):
+                raise ValueError(f'FusedCLFMStep: the stacked weights must be [{self.share} ; {Di - self.share}] x {Du}')
+        super().__init__(opt, lr, betas, eps, weight_decay)
+        self.Du, self.Di = Du, Di
+        self.tables = tables
+        self.weights = (shared, s_only, t_only)
+        self.alpha, self.reg_weight = float(alpha), float(reg_weight)
+        states = states if states is not None else (None,) * 4
+        self.states = tuple(st if st is not None else RowwiseState(t, self.opt) for st, t in zip(states, tables))
+        self.params = [w for w in self.weights if w is not None]
+        self.w_opt = DenseAdam(self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.opt == OPT_ADAM else None
+        dev = source_user.device
+        self.max_source, self.max_target = int(max_source), int(max_target)
+        Bm = max(self.max_source, self.max_target)
+        self.GU = tuple(torch.empty(n, Du, device=dev, dtype=torch.float32) for n in (self.max_source, self.max_target))
+        self.GI = tuple(torch.empty(n, Di, device=dev, dtype=torch.float32) for n in (self.max_source, self.max_target))
+        self.dW = torch.zeros(2, Di, Du, device=dev, dtype=torch.float32)
+        self.out16 = torch.zeros(16, device=dev, dtype=torch.float32)           # out8 of the source, out8 of the target
+        need = ctypes.c_size_t(0)
+        B_._check(B_.load().cdr_clfm_fwd_grad_workspace_bytes(Bm, Du, Di, ctypes.byref(need)), 'cdr_clfm_fwd_grad_workspace_bytes')
+        self.fws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)   # (the grid, and with it the size, grows with B)
+        self.keys = torch.empty(2 * Bm, device=dev, dtype=torch.int32)           # one sort per domain: user keys, then item keys
+        self.perm = torch.empty(2 * Bm, device=dev, dtype=torch.int32)
+        rows = 2 << (max(t.shape[0] for t in tables) - 1).bit_length()
+        # (the sort switches configuration at 2^18 keys: a short tail batch may need more scratch than a full one)
+        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (2 * Bm, min(2 * Bm, (1 << 18) - 1))), device=dev, dtype=torch.uint8)
+        self._key_base = ctypes.c_uint32(0)
+
+    def _states(self):
+        return self.states
+
+    def _stacked(self, only):
+        """[shared ; only] as one contiguous [Di, Du] matrix, exactly as ``CLFM._factors`` stacks it."""
+        ws = [w.data for w in (self.weights[0], only) if w is not None]
+        return ws[0].contiguous() if len(ws) == 1 else torch.cat(ws, dim=0)
+
+    @torch.no_grad()
+    def step(self, su, si, ys, tu, ti, yt):
+        """su / si int64 [B_s], ys fp32 [B_s] (source rows); tu / ti int64 [B_t], yt fp32 [B_t] (target rows).  Returns the total loss
+        (device [1]); ``out16`` keeps each domain's {weighted total, BCE, EmbLoss, ||U rows||, ||I rows||, c_u, c_i, 0}."""
+        Bs, Bt = su.numel(), tu.numel()
+        if not (1 <= Bs <= self.max_source and 1 <= Bt <= self.max_target):
+            raise ValueError(f'FusedCLFMStep: batches of {Bs} + {Bt} rows, sized for 1..{self.max_source} + 1..{self.max_target}')
+        if si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
+            raise ValueError('FusedCLFMStep: ids and labels of a domain must have the same length')
+        dev = self.tables[0].device
+        ctxh, s = B_.ctx(dev), B_.stream()
+        S, Du, Di = self.share, self.Du, self.Di
+        doms = ((0, su, si, ys, Bs, self.alpha, self._stacked(self.weights[1])),
+                (1, tu, ti, yt, Bt, 1.0 - self.alpha, self._stacked(self.weights[2])))
+        for d, uid, iid, y, n, w, W in doms:                       # both forwards first: both domains see the pre-step weights
+            B_.call('cdr_clfm_fwd_grad', ctxh, s, B_.f32(self.tables[2 * d]), B_.f32(self.tables[2 * d + 1]), Du, Di, B_.f32(W), B_.i64(uid),
+                    B_.i64(iid), B_.f32(y), n, w, self.reg_weight, B_.f32(self.out16[8 * d:8 * d + 8]), B_.f32(self.GU[d][:n]),
+                    B_.f32(self.GI[d][:n]), B_.f32(self.dW[d]), B_.raw(self.fws), self.fws.numel())
+        for d, uid, iid, y, n, w, W in doms:
+            ust, ist = self.states[2 * d], self.states[2 * d + 1]
+            B_.call('cdr_sort_ids_two_tables', ctxh, s, B_.i64(uid), n, ust.table.shape[0], B_.i64(iid), n, None, 0, ist.table.shape[0],
+                    B_.raw(self.keys), B_.raw(self.perm), ctypes.byref(self._key_base), B_.raw(self.ws), self.ws.numel())
+            # one gradient row per occurrence (neg_start = n), EmbLoss on every occurrence (reg_limit = n) with the domain's coefficient
+            for st, lo, D, G, coef, base in ((ust, 0, Du, self.GU[d], 8 * d + 5, 0), (ist, n, Di, self.GI[d], 8 * d + 6, self._key_base.value)):
+                st.advance()
+                B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), D,
+                        B_.raw(self.keys[lo:lo + n]), B_.raw(self.perm[lo:lo + n]), n, B_.f32(G[:n]), n, n, B_.f32(self.out16[coef:coef + 1]),
+                        *self._hp(), st.step, None, int(base))
+        shared, s_only, t_only = self.weights
+        if shared is not None:
+            shared.grad = self.dW[0, :S] + self.dW[1, :S]
+        if s_only is not None:
+            s_only.grad = self.dW[0, S:]
+            t_only.grad = self.dW[1, S:]
+        if self.w_opt is not None:
+            self.w_opt.step()
+        else:
+            for p in self.params:
+                p.add_(p.grad + self.wd * p if self.wd else p.grad, alpha=-self.lr)
+        return self.out16[0:1] + self.out16[8:9]
 
 
 class SSCDRMapStep(_Step):

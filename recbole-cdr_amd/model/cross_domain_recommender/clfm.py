@@ -3,7 +3,11 @@
 Per domain: user rows [B, Du] -> factors = user_e [shared_linear ; <domain>_only_linear]^T (ONE fp32-MFMA contraction over the stacked
 weight) -> sigmoid(factors . item_row) -> BCE in the fused gather-dot-loss kernel (the factors play the "user table", addressed
 by row number) + reg_weight * EmbLoss of the gathered ego rows.  Scoring: factors x item slab on the MFMA full-sort kernel.
-Quirk kept: ``target_item_embedding_size`` is read from ``config['source_item_embedding_size']`` (clfm.py:39)."""
+Quirk kept: ``target_item_embedding_size`` is read from ``config['source_item_embedding_size']`` (clfm.py:39).
+
+``fused_train_step`` (``optimizer_mode='rowwise'``): the BOTH-phase step without table-sized gradients -- fused.FusedCLFMStep, the four
+tables updated row-wise from csrc/cdr_clfm.hip's compact gradient rows, the three small weights by the exact dense Adam; ``adam='exact'``
+puts the catch-up of the reference's dense Adam in front of it (fused.rowwise_catch_up over the four tables)."""
 import torch
 import torch.nn as nn
 
@@ -11,9 +15,10 @@ from ... import binding as B_
 from ... import functional as F_
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
+from ..rowwise import RowwiseTraining
 
 
-class CLFM(CrossDomainRecommender):
+class CLFM(RowwiseTraining, CrossDomainRecommender):
     input_type = InputType.POINTWISE
 
     def __init__(self, config, dataset):
@@ -42,6 +47,11 @@ class CLFM(CrossDomainRecommender):
             self.target_only_linear = nn.Linear(self.user_embedding_size,
                                                 self.target_item_embedding_size - self.share_embedding_size, bias=False)
         self.apply(xavier_normal_initialization)
+        self.phase = 'BOTH'
+        self.__dict__['_dist_cfg'] = config['dist_group'] if 'dist_group' in config else None
+
+    def set_phase(self, phase):
+        self.phase = phase
 
     def _tables(self, domain):
         return getattr(self, f'{domain}_user_embedding').weight, getattr(self, f'{domain}_item_embedding').weight
@@ -103,6 +113,86 @@ class CLFM(CrossDomainRecommender):
             bce_t, _ = F_.PointGatherLoss.apply(B_.CDR_LOSS_BCE, ft, It, None, None, self._rows(ft.shape[0], ft.device), ti, tl, 0.0)
         out = [bce_s + self.reg_weight * self._emb_loss(su, si, 'source'), bce_t + self.reg_weight * self._emb_loss(tu, ti, 'target')]
         return out[0] * self.alpha + out[1] * (1 - self.alpha)
+
+    # ---- O(batch) training step (large tables) ------------------------------------------------------------------
+    _TABLES = ('source_user_embedding', 'source_item_embedding', 'target_user_embedding', 'target_item_embedding')
+
+    def _pair_fields(self, interaction):
+        fields = (self.SOURCE_USER_ID, self.SOURCE_ITEM_ID, self.SOURCE_LABEL, self.TARGET_USER_ID, self.TARGET_ITEM_ID, self.TARGET_LABEL)
+        missing = [f for f in fields if f not in interaction]
+        if missing:
+            raise ValueError(f'CLFM.fused_train_step trains on BOTH-phase batches (source and target rows); the {self.phase} batch '
+                             f'has no {", ".join(missing)}')
+        return [interaction[f].reshape(-1) for f in fields]
+
+    def _weights(self):
+        return (self.shared_linear.weight if self.share_embedding_size > 0 else None,
+                self.source_only_linear.weight if hasattr(self, 'source_only_linear') else None,
+                self.target_only_linear.weight if hasattr(self, 'target_only_linear') else None)
+
+    def fused_train_step(self, interaction, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam='lazy'):
+        """``calculate_loss -> backward -> optimizer.step`` on a BOTH-phase batch without table-sized gradients or a dense optimizer
+        sweep over the four tables (fused.FusedCLFMStep): what ``CrossDomainTrainer`` runs when ``config['optimizer_mode'] ==
+        'rowwise'``.  Same loss and gradients as ``calculate_loss``; each table advances once per step, and the three linears take the
+        exact dense Adam (the reference has one ``torch.optim.Adam`` over every parameter).  Returns the total loss (device [1]).
+
+        ``adam='lazy'`` (default): table rows the batch does not touch do not move.  ``adam='exact'``: the reference's dense Adam -- one
+        catch-up launch in front of every step (fused.rowwise_catch_up) replays the gradient-free updates the step's rows missed; the
+        tables hold what ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run.  One mode per model."""
+        from ...fused import FusedCLFMStep, rowwise_catch_up
+        exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            raise NotImplementedError("CLFM.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
+        try:
+            FusedCLFMStep.check_widths(self.user_embedding_size, self.source_item_embedding_size)
+        except ValueError as e:
+            raise ValueError(f'CLFM.fused_train_step: user_embedding_size = {self.user_embedding_size}, source_item_embedding_size = '
+                             f'{self.source_item_embedding_size}: {e}; use optimizer_mode=dense') from None
+        su, si, ys, tu, ti, yt = self._pair_fields(interaction)
+        Bs, Bt = su.numel(), tu.numel()
+        if Bs == 0 or Bt == 0 or si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
+            raise ValueError(f'CLFM.fused_train_step: the {self.phase} batch needs at least one row per domain and ids and labels of equal '
+                             f'length, got {Bs} / {si.numel()} / {ys.numel()} source and {Bt} / {ti.numel()} / {yt.numel()} target entries')
+        old = self._fused_cache(exact)['steps'].get('clfm')
+        states = tuple(self._fused_state(n, code, exact) for n in self._TABLES)
+        ms, mt = (Bs, Bt) if old is None else (max(Bs, old.max_source), max(Bt, old.max_target))
+
+        def build():
+            step = FusedCLFMStep(*(getattr(self, n).weight.data for n in self._TABLES), self._weights(), ms, mt, self.alpha, self.reg_weight,
+                                 states=states, **hp)
+            # the weights' Adam state outlives a re-sized step object, and a checkpoint's is handed over when the first one is built
+            carry = old.w_opt.state_dict() if old is not None and old.w_opt is not None else self.__dict__.pop('_pending_weight_state', None)
+            if carry is not None and step.w_opt is not None:
+                step.w_opt.load_state_dict(carry)
+                for g in step.w_opt.param_groups:
+                    g.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+            return step
+
+        step = self._fused_step('clfm', lambda s: s.max_source >= Bs and s.max_target >= Bt and s.hp == hp, build)
+        step.hp = hp
+        ys = ys if ys.dtype == torch.float32 else ys.float()
+        yt = yt if yt.dtype == torch.float32 else yt.float()
+        if exact:
+            rowwise_catch_up([(st, [ids]) for st, ids in zip(states, (su, si, tu, ti))], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        return step.step(su.contiguous(), si.contiguous(), ys.contiguous(), tu.contiguous(), ti.contiguous(), yt.contiguous())
+
+    def _fused_phase_step(self):
+        return self._fused['steps']['clfm']
+
+    def fused_optimizer_state(self):
+        """The shared per-table state, plus the dense Adam state of the three linears."""
+        out = super().fused_optimizer_state()
+        step = self.__dict__.get('_fused', {}).get('steps', {}).get('clfm')
+        if step is not None and step.w_opt is not None:
+            out['weights'] = step.w_opt.state_dict()
+        return out
+
+    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
+        """The shared per-table restore; the linears' Adam state is handed to the step when it is built."""
+        super().load_fused_optimizer_state(state, opt=opt, adam=adam)
+        if 'weights' in state:
+            self.__dict__['_pending_weight_state'] = state['weights']
+        self.__dict__.get('_fused', {}).get('steps', {}).pop('clfm', None)
 
     @torch.no_grad()
     def predict(self, interaction):
