@@ -95,6 +95,7 @@ int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the
 #define CDR_TAG_CONET_FB 20             /* conet_fb_kernel: conet_fwd_kernel's and conet_bwd_kernel's passes over a row block in one launch */
 #define CDR_TAG_TRIPLET_FWD_GRAD 21   /* triplet_fwd_grad_kernel: SSCDR's triplet loss + compact gradient rows */
 #define CDR_TAG_CLFM_FWD_GRAD 22      /* clfm_fwd_grad_kernel: CLFM's factor map, BCE and the three gradient contractions of one domain */
+#define CDR_TAG_DTCDR_FWD_GRAD 23     /* dtcdr_fwd_grad_kernel: DTCDR's NeuMF tower of one domain, forward and backward, with the max routing */
 int cdr_timing_enable(cdr_ctx* ctx, int capacity);
 int cdr_timing_collect(cdr_ctx* ctx, int* tags, float* ms, int max_n, int* n_out);
 
@@ -697,6 +698,35 @@ int cdr_clfm_fwd_grad(cdr_ctx* ctx, void* stream, const float* user_tab, const f
                       const float* W /* [Di, Du] */, const int64_t* uid, const int64_t* iid, const float* label, int64_t B,
                       float weight, float reg_weight, float* out8, float* GU /* [B, Du] */, float* GI /* [B, Di] */,
                       float* dW /* [Di, Du] */, void* workspace, size_t workspace_bytes);
+/* DTCDR's domain step, forward half (dtcdr.py:112-126 the NeuMF tower, 182-199 the loss) for one domain of B rows:
+ * x = [max(src_user[uid], tgt_user[uid]) | max(src_item[iid], tgt_item[iid])] (width 2 D), h_0 = x, h_{l+1} = relu(W_l drop_l(h_l) + b_l)
+ * for the n_hidden layers of widths hidden[] (a HOST array), z = w_out . h_L + b_out, p = sigmoid(z), bce = mean BCE(p, label) with
+ * torch's -100 clamp of both logs, and `weight` the domain's share of the total (alpha for the source, 1 - alpha for the target).
+ * `params` is the domain's tower packed as [W_0 (hidden[0] x 2 D, row-major), b_0, W_1, b_1, ..., w_out (hidden[L-1]), b_out (1)];
+ * `dparams` receives the gradient of weight * bce in the same layout.  With g_b = weight (p_b - y_b) / B (the 1e-12 clamp of
+ * cdr_point_fwd_grad's BCE branch) the gradient goes back through the same ReLU and dropout masks to gx [2 D] and leaves FOUR compact
+ * gradient rows per occurrence at row row0 + b of the joint buffers: element c of the user half goes to GUs where src_user[uid][c] >
+ * tgt_user[uid][c], to GUt where it is smaller, half to each on an exact tie (cdr_gather_max2_bwd's rule, on the exact table values);
+ * the loser's element is +0.0; the item half likewise to GIs / GIt.  Dropout (p_drop > 0): the counter-based mask of cdr_dropout_dev with
+ * the seed read from seed_dev, salt salt0 + l for layer l and element index b * width_l + c -- the masks MLPLayers.forward draws with
+ * the same seed (salt0 = 0 source, 64 target); p_drop = 0: no mask, seed_dev may be NULL.  Apply the rows of both domains with one sort
+ * of [source uid | target uid] and one of the item ids (cdr_sort_ids_two_tables) and four cdr_rowwise_apply (n = B_s + B_t, neg_start = n,
+ * reg_limit = 0): each sorted list serves both tables of its id space.  out8 = {weight bce, bce, 0, ...}: DTCDR has no EmbLoss.
+ * The contractions run on v_mfma_f32_32x32x2_f32 out of LDS (widths zero-padded to 32 there); the parameter gradients are accumulated per
+ * workgroup and the partials -- one packed vector per workgroup in `workspace`, cdr_dtcdr_fwd_grad_workspace_bytes = grid x parameters
+ * x 4 -- are added in workgroup order; the loss goes through fp64 block partials.  No float atomics: a rerun is bit-equal.
+ * D % 4 == 0, 4 <= D <= CDR_DTCDR_MAX_DIM, 1 <= n_hidden <= CDR_DTCDR_MAX_LAYERS, 1 <= hidden[l] <= CDR_DTCDR_MAX_HIDDEN, B > 0,
+ * 0 <= p_drop < 1, 16-byte aligned tables and gradient buffers (CDR_EINVAL before any launch otherwise).  The widest shape needs
+ * 161,920 B of LDS (one workgroup per CU); nothing spills.                                                                        */
+#define CDR_DTCDR_MAX_DIM 128
+#define CDR_DTCDR_MAX_HIDDEN 64
+#define CDR_DTCDR_MAX_LAYERS 3
+int cdr_dtcdr_fwd_grad_workspace_bytes(int64_t B, int D, int n_hidden, const int* hidden, size_t* bytes);
+int cdr_dtcdr_fwd_grad(cdr_ctx* ctx, void* stream, const float* src_user, const float* tgt_user, const float* src_item,
+                       const float* tgt_item, int D, int n_hidden, const int* hidden, const float* params, const int64_t* uid,
+                       const int64_t* iid, const float* label, int64_t B, float weight, float p_drop, const int64_t* seed_dev,
+                       uint64_t salt0, int64_t row0, float* out8, float* GUs, float* GUt, float* GIs, float* GIt,
+                       float* dparams, void* workspace, size_t workspace_bytes);
 /* The same step with the optimizer of every row that occurs ONCE in the batch applied by the forward kernel itself (round 3;
  * replaces cdr_bpr_fwd_grad + cdr_sort_ids_two_tables + 2 x cdr_rowwise_apply for emcdr.py:123-131,146-154 + Adam): the EmbLoss
  * norms of the batch are gathered first (the gradient coefficient reg_weight / (B ||rows||) is needed before the first row is

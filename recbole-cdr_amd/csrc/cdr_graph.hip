@@ -8,6 +8,7 @@
 // One lane group of LPR = D/4 lanes per output row (float4 per lane): 64/LPR rows per wave-instruction; the gather of
 // E[col] rows is the HBM/L2 traffic that bounds the kernel (4D+12 bytes per non-zero).
 #include "cdr_common.h"
+#include "cdr_dropout.h"
 
 namespace {
 
@@ -431,11 +432,7 @@ __global__ __launch_bounds__(kBlock) void dropout_kernel(const float* __restrict
     const float scale = 1.0f / (1.0f - p);
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride) {
-        uint64_t z = seed + (uint64_t)(e + 1) * 0x9E3779B97F4A7C15ull;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z = z ^ (z >> 31);
-        const float u = (float)(z >> 40) * (1.0f / 16777216.0f);      // 24 uniform bits in [0,1)
+        const float u = cdr_drop_uniform(seed, e);
         out[e] = u >= p ? x[e] * scale : 0.0f;
     }
 }
@@ -446,18 +443,11 @@ __global__ __launch_bounds__(kBlock) void dropout_kernel(const float* __restrict
 __global__ __launch_bounds__(kBlock) void dropout_dev_kernel(const float* __restrict__ x, int64_t n, float p,
                                                              const int64_t* __restrict__ seed_dev, uint64_t salt,
                                                              float* __restrict__ out) {
-    uint64_t s0 = (uint64_t)seed_dev[0] * 0xD1342543DE82EF95ull + 0x9E3779B97F4A7C15ull;      // consecutive counters -> unrelated seeds
-    s0 = (s0 ^ (s0 >> 30)) * 0xBF58476D1CE4E5B9ull;
-    s0 = (s0 ^ (s0 >> 27)) * 0x94D049BB133111EBull;
-    const uint64_t seed = (s0 ^ (s0 >> 31)) + salt * 0xA24BAED4963EE407ull;
+    const uint64_t seed = cdr_drop_seed_dev(seed_dev, salt);
     const float scale = 1.0f / (1.0f - p);
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride) {
-        uint64_t z = seed + (uint64_t)(e + 1) * 0x9E3779B97F4A7C15ull;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z = z ^ (z >> 31);
-        const float u = (float)(z >> 40) * (1.0f / 16777216.0f);
+        const float u = cdr_drop_uniform(seed, e);
         out[e] = u >= p ? x[e] * scale : 0.0f;
     }
 }
@@ -469,17 +459,10 @@ __global__ __launch_bounds__(kBlock) void dropout_dev_kernel(const float* __rest
 struct drop_arg { float p; uint64_t seed; const int64_t* seed_dev; uint64_t salt_s, salt_t; int64_t elem0; };
 __device__ __forceinline__ uint64_t drop_seed_of(const drop_arg& d, uint64_t salt) {
     if (!d.seed_dev) return d.seed + salt;
-    uint64_t s0 = (uint64_t)d.seed_dev[0] * 0xD1342543DE82EF95ull + 0x9E3779B97F4A7C15ull;
-    s0 = (s0 ^ (s0 >> 30)) * 0xBF58476D1CE4E5B9ull;
-    s0 = (s0 ^ (s0 >> 27)) * 0x94D049BB133111EBull;
-    return (s0 ^ (s0 >> 31)) + salt * 0xA24BAED4963EE407ull;
+    return cdr_drop_seed_dev(d.seed_dev, salt);
 }
 __device__ __forceinline__ float drop_factor(uint64_t seed, int64_t e, float p, float scale) {
-    uint64_t z = seed + (uint64_t)(e + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
-    return (float)(z >> 40) * (1.0f / 16777216.0f) >= p ? scale : 0.0f;
+    return cdr_drop_uniform(seed, e) >= p ? scale : 0.0f;
 }
 
 __global__ __launch_bounds__(kBlock) void transfer_drop_fwd_kernel(const float* __restrict__ S, const float* __restrict__ T,

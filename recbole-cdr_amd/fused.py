@@ -1,6 +1,7 @@
 """Fused row-wise training steps: forward + backward + optimizer for one batch without table-sized gradients
 (FusedBPRStep: pairwise BPR; FusedPointStep: pointwise MSE / BCE; FusedPointPairStep: CMF's two domains on shared tables;
 FusedTripletStep: SSCDR's triplet margin loss; FusedCLFMStep: CLFM's two domains, four tables and stacked factor weights;
+FusedDTCDRStep: DTCDR's two NeuMF towers over the maximum of both domains' rows, four tables fed by both batches;
 FusedMapStep / SSCDRMapStep: EMCDR's / SSCDR's OVERLAP-phase mapping loss).
 
 This is the large-table counterpart of ``loss.backward(); optimizer.step()`` in the reference's loop
@@ -816,6 +817,140 @@ class FusedCLFMStep(_Step):
         else:
             for p in self.params:
                 p.add_(p.grad + self.wd * p if self.wd else p.grad, alpha=-self.lr)
+        return self.out16[0:1] + self.out16[8:9]
+
+
+class FusedDTCDRStep(_Step):
+    """DTCDR's BOTH-phase step with the NeuMF tower (dtcdr.py:112-126, 182-199): per domain  p = sigmoid(head_d(mlp_d([max(Us[u], Ut[u]) |
+    max(Is[i], It[i])])))  with dropout in front of every hidden layer, loss = alpha BCE_s + (1 - alpha) BCE_t.  Every occurrence feeds
+    BOTH domains' tables (the maximum routes each element's gradient to the table that won it, half to each on an exact tie) and each of
+    the four tables receives rows from both batches, so the gradient rows of both domains go into joint [B_s + B_t, D] buffers (source rows
+    at 0, target rows at B_s) and each table advances ONCE per step, from the sum of a row's contributions, as in FusedPointPairStep.
+    Per step: cdr_dtcdr_fwd_grad per domain (csrc/cdr_dtcdr.hip: the tower forward and backward, the routing and every parameter gradient in
+    one pass, + its finishing launch) -- both before anything is updated --, ONE cdr_sort_ids_two_tables over ([su | tu], si ++ ti) (the
+    user list is concatenated on the host side: one copy launch and one sort, against two cdr_sort_ids), four segmented applies (each
+    sorted list serves both tables of its id space), then the exact dense Adam on the 12 tower parameters (plain SGD with opt='sgd'), as in
+    FusedCLFMStep.  The update counts are the host's: not capturable.
+
+    ``towers``: ((W_0, b_0, ..., w_out, b_out) of the source, the same of the target) -- the parameters themselves: the step sets their
+    ``.grad`` and updates them in place."""
+
+    MAX_DIM, MAX_HIDDEN, MAX_LAYERS = 128, 64, 3                                 # CDR_DTCDR_MAX_*
+
+    @classmethod
+    def check_widths(cls, D, hidden):
+        hidden = list(hidden)
+        if not (4 <= D <= cls.MAX_DIM and D % 4 == 0):
+            raise ValueError(f'FusedDTCDRStep: embedding_size must be a multiple of 4 in 4..{cls.MAX_DIM}, got {D}')
+        if not (1 <= len(hidden) <= cls.MAX_LAYERS and all(isinstance(h, int) and 1 <= h <= cls.MAX_HIDDEN for h in hidden)):
+            raise ValueError(f'FusedDTCDRStep: mlp_hidden_size must be 1..{cls.MAX_LAYERS} layers of 1..{cls.MAX_HIDDEN} units '
+                             f'(the tower lives in LDS), got {hidden}')
+
+    def __init__(self, source_user, source_item, target_user, target_item, towers, max_source, max_target, alpha, dropout_prob=0.0,
+                 opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, states=None):
+        from .trainer.trainer import DenseAdam
+        tables = (source_user, source_item, target_user, target_item)
+        assert all(t.is_cuda for t in tables), 'FusedDTCDRStep needs ROCm device tensors'
+        D = source_user.shape[1]
+        if any(t.shape[1] != D for t in tables) or source_user.shape[0] != target_user.shape[0] or source_item.shape[0] != target_item.shape[0]:
+            raise ValueError(f'FusedDTCDRStep: the four tables must share one width and the domains one id space '
+                             f'({tuple(tuple(t.shape) for t in tables)})')
+        hidden = [int(towers[0][2 * l].shape[0]) for l in range(len(towers[0]) // 2 - 1)]
+        self.check_widths(D, hidden)                                             # (before anything is allocated)
+        shapes = [s for i, o in zip([2 * D] + hidden, hidden) for s in ((o, i), (o,))] + [(1, hidden[-1]), (1,)]
+        for tw in towers:
+            if [tuple(p.shape) for p in tw] != shapes:
+                raise ValueError(f'FusedDTCDRStep: a tower must be {shapes}, got {[tuple(p.shape) for p in tw]}')
+        if not 0.0 <= float(dropout_prob) < 1.0:
+            raise ValueError(f'FusedDTCDRStep: dropout_prob must be in [0, 1), got {dropout_prob}')
+        super().__init__(opt, lr, betas, eps, weight_decay)
+        self.D, self.hidden = D, hidden
+        self._hidden_c = (ctypes.c_int * len(hidden))(*hidden)
+        self.tables = tables
+        self.towers = tuple(tuple(tw) for tw in towers)
+        self.alpha, self.p = float(alpha), float(dropout_prob)
+        states = states if states is not None else (None,) * 4
+        self.states = tuple(st if st is not None else RowwiseState(t, self.opt) for st, t in zip(states, tables))
+        self.params = [p for tw in self.towers for p in tw]
+        self.w_opt = DenseAdam(self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.opt == OPT_ADAM else None
+        dev = source_user.device
+        self.max_source, self.max_target = int(max_source), int(max_target)
+        Nm = self.max_source + self.max_target
+        self.G = tuple(torch.empty(Nm, D, device=dev, dtype=torch.float32) for _ in range(4))      # rows for Us, Is, Ut, It
+        self.n_params = sum(p.numel() for p in self.towers[0])
+        self.dP = torch.zeros(2, self.n_params, device=dev, dtype=torch.float32)
+        self.out16 = torch.zeros(16, device=dev, dtype=torch.float32)           # out8 of the source, out8 of the target
+        self.zero = torch.zeros(1, device=dev, dtype=torch.float32)             # the applies' EmbLoss coefficient: none
+        need = ctypes.c_size_t(0)
+        B_._check(B_.load().cdr_dtcdr_fwd_grad_workspace_bytes(max(self.max_source, self.max_target), D, len(hidden), self._hidden_c,
+                                                               ctypes.byref(need)), 'cdr_dtcdr_fwd_grad_workspace_bytes')
+        self.fws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)   # (the grid, and with it the size, grows with B)
+        self.keys = torch.empty(2 * Nm, device=dev, dtype=torch.int32)           # one sort: user keys [su | tu], then item keys [si | ti]
+        self.perm = torch.empty(2 * Nm, device=dev, dtype=torch.int32)
+        rows = 2 << (max(t.shape[0] for t in tables) - 1).bit_length()
+        # (the sort switches configuration at 2^18 keys: a short tail batch may need more scratch than a full one)
+        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (2 * Nm, min(2 * Nm, (1 << 18) - 1))), device=dev, dtype=torch.uint8)
+        self._key_base = ctypes.c_uint32(0)
+
+    def _states(self):
+        return self.states
+
+    def grid(self, B):
+        """Workgroups cdr_dtcdr_fwd_grad launches for a batch of B rows (the workspace is one packed parameter vector per workgroup)."""
+        need = ctypes.c_size_t(0)
+        B_._check(B_.load().cdr_dtcdr_fwd_grad_workspace_bytes(B, self.D, len(self.hidden), self._hidden_c, ctypes.byref(need)),
+                  'cdr_dtcdr_fwd_grad_workspace_bytes')
+        return int(need.value) // (4 * self.n_params)
+
+    @torch.no_grad()
+    def forward_grads(self, su, si, ys, tu, ti, yt, seed=None):
+        """Both domains' cdr_dtcdr_fwd_grad: fills ``G`` (rows [0, B_s) source, [B_s, B_s + B_t) target), ``dP`` and ``out16``."""
+        Bs, Bt = su.numel(), tu.numel()
+        if not (1 <= Bs <= self.max_source and 1 <= Bt <= self.max_target):
+            raise ValueError(f'FusedDTCDRStep: batches of {Bs} + {Bt} rows, sized for 1..{self.max_source} + 1..{self.max_target}')
+        if si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
+            raise ValueError('FusedDTCDRStep: ids and labels of a domain must have the same length')
+        if seed is not None and (seed.dtype != torch.int64 or not seed.is_cuda):
+            raise ValueError('FusedDTCDRStep: the dropout seed is a device int64 [1]')
+        ctxh, s = B_.ctx(self.tables[0].device), B_.stream()
+        p = self.p if seed is not None else 0.0
+        Us, Is, Ut, It = self.tables
+        for d, uid, iid, y, n, w, salt, row0 in ((0, su, si, ys, Bs, self.alpha, 0, 0), (1, tu, ti, yt, Bt, 1.0 - self.alpha, 64, Bs)):
+            packed = torch.cat([q.data.reshape(-1) for q in self.towers[d]])
+            B_.call('cdr_dtcdr_fwd_grad', ctxh, s, B_.f32(Us), B_.f32(Ut), B_.f32(Is), B_.f32(It), self.D, len(self.hidden), self._hidden_c,
+                    B_.f32(packed), B_.i64(uid), B_.i64(iid), B_.f32(y), n, w, p, B_.i64(seed) if p > 0 else None, salt, row0,
+                    B_.f32(self.out16[8 * d:8 * d + 8]), B_.f32(self.G[0]), B_.f32(self.G[2]), B_.f32(self.G[1]), B_.f32(self.G[3]),
+                    B_.f32(self.dP[d]), B_.raw(self.fws), self.fws.numel())
+
+    @torch.no_grad()
+    def step(self, su, si, ys, tu, ti, yt, seed=None):
+        """su / si int64 [B_s], ys fp32 [B_s] (source rows); tu / ti int64 [B_t], yt fp32 [B_t] (target rows); ``seed``: device int64 [1],
+        the step's dropout counter (None: no dropout).  Returns the total loss (device [1]); ``out16`` keeps each domain's {weighted BCE,
+        BCE, 0, ...}."""
+        self.forward_grads(su, si, ys, tu, ti, yt, seed)            # both forwards first: both domains see the pre-step state
+        Bs, Bt = su.numel(), tu.numel()
+        n = Bs + Bt
+        ctxh, s = B_.ctx(self.tables[0].device), B_.stream()
+        users = torch.cat([su, tu])
+        B_.call('cdr_sort_ids_two_tables', ctxh, s, B_.i64(users), n, self.tables[0].shape[0], B_.i64(si), Bs, B_.i64(ti), Bt,
+                self.tables[1].shape[0], B_.raw(self.keys), B_.raw(self.perm), ctypes.byref(self._key_base), B_.raw(self.ws), self.ws.numel())
+        # one gradient row per occurrence (neg_start = n), no EmbLoss (reg_limit = 0); table order: Us, Is, Ut, It
+        for st, G, lo, base in ((self.states[0], self.G[0], 0, 0), (self.states[2], self.G[2], 0, 0),
+                                (self.states[1], self.G[1], n, self._key_base.value), (self.states[3], self.G[3], n, self._key_base.value)):
+            st.advance()
+            B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
+                    B_.raw(self.keys[lo:lo + n]), B_.raw(self.perm[lo:lo + n]), n, B_.f32(G[:n]), n, 0, B_.f32(self.zero), *self._hp(),
+                    st.step, None, int(base))
+        for d, tw in enumerate(self.towers):
+            off = 0
+            for q in tw:
+                q.grad = self.dP[d, off:off + q.numel()].view(q.shape)
+                off += q.numel()
+        if self.w_opt is not None:
+            self.w_opt.step()
+        else:
+            for q in self.params:
+                q.add_(q.grad + self.wd * q if self.wd else q.grad, alpha=-self.lr)
         return self.out16[0:1] + self.out16[8:9]
 
 

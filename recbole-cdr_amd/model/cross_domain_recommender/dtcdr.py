@@ -9,7 +9,12 @@ not bit-comparable with torch's Philox stream, golden parity i
 ``base_model = 'DMF'`` (dtcdr.py:128-180) is NOT provided: the reference's DMF path indexes the source history with the wrong
 batch (``source_history_user_value[user]`` for an item matrix, :156-160), shifts source-only ids with ``>`` instead of ``>=``
 (:131,151: id == target_num_items lands outside the [B, source_num_items] matrix whenever target-only >= source-only ids) and
-scores the target batch with the source tower (:194); it cannot run on an id space with target-only ids and has no oracle."""
+scores the target batch with the source tower (:194); it cannot run on an id space with target-only ids and has no oracle.
+
+``fused_train_step`` (``optimizer_mode='rowwise'``): the BOTH-phase step without table-sized gradients -- fused.FusedDTCDRStep, the four
+tables updated row-wise from csrc/cdr_dtcdr.hip's compact gradient rows (each table advances once per step, from both batches), the 12
+tower parameters by the exact dense Adam; ``adam='exact'`` puts the catch-up of the reference's dense Adam in front of it
+(fused.rowwise_catch_up over the four tables).  Same masks as ``calculate_loss`` under the same seed."""
 import torch
 import torch.nn as nn
 
@@ -17,6 +22,7 @@ from ... import binding as B_
 from ... import functional as F_
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
+from ..rowwise import RowwiseTraining
 
 
 class MLPLayers(nn.Module):
@@ -61,7 +67,7 @@ class _Dropout(torch.autograd.Function):
         return g, None, None, None
 
 
-class DTCDR(CrossDomainRecommender):
+class DTCDR(RowwiseTraining, CrossDomainRecommender):
     input_type = InputType.POINTWISE
 
     def __init__(self, config, dataset):
@@ -88,6 +94,11 @@ class DTCDR(CrossDomainRecommender):
         self.target_mlp_layers = MLPLayers([2 * self.embedding_size] + self.mlp_hidden_size, self.dropout_prob)
         self.target_predict_layer = nn.Linear(self.mlp_hidden_size[-1], 1)
         self.apply(xavier_normal_initialization)
+        self.phase = 'BOTH'
+        self.__dict__['_dist_cfg'] = config['dist_group'] if 'dist_group' in config else None
+
+    def set_phase(self, phase):
+        self.phase = phase
 
     def _drop_seed(self):
         """Device-resident seed of this step's dropout masks: re-drawn from torch's CPU generator when run eagerly, advanced by a
@@ -124,6 +135,106 @@ class DTCDR(CrossDomainRecommender):
         loss_s = F_.BCEProbLoss.apply(ps, interaction[self.SOURCE_LABEL])
         loss_t = F_.BCEProbLoss.apply(pt, interaction[self.TARGET_LABEL])
         return loss_s * self.alpha + loss_t * (1 - self.alpha)
+
+    # ---- O(batch) training step (large tables) ------------------------------------------------------------------
+    _TABLES = ('source_user_embedding', 'source_item_embedding', 'target_user_embedding', 'target_item_embedding')
+
+    def _pair_fields(self, interaction):
+        fields = (self.SOURCE_USER_ID, self.SOURCE_ITEM_ID, self.SOURCE_LABEL, self.TARGET_USER_ID, self.TARGET_ITEM_ID, self.TARGET_LABEL)
+        missing = [f for f in fields if f not in interaction]
+        if missing:
+            raise ValueError(f'DTCDR.fused_train_step trains on BOTH-phase batches (source and target rows); the {self.phase} batch '
+                             f'has no {", ".join(missing)}')
+        return [interaction[f].reshape(-1) for f in fields]
+
+    def _towers(self):
+        """((W_0, b_0, ..., w_out, b_out) of the source tower, the same of the target): the 12 parameters at the default depth."""
+        out = []
+        for d in ('source', 'target'):
+            lin = [m for m in getattr(self, f'{d}_mlp_layers').mlp_layers if isinstance(m, nn.Linear)] + [getattr(self, f'{d}_predict_layer')]
+            out.append(tuple(p for m in lin for p in (m.weight, m.bias)))
+        return tuple(out)
+
+    def fused_train_step(self, interaction, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam='lazy'):
+        """``calculate_loss -> backward -> optimizer.step`` on a BOTH-phase batch without table-sized gradients or a dense optimizer
+        sweep over the four tables (fused.FusedDTCDRStep): what ``CrossDomainTrainer`` runs when ``config['optimizer_mode'] ==
+        'rowwise'``.  Same loss, masks and gradients as ``calculate_loss`` (the dropout seed is ``_drop_seed()``, drawn once per step);
+        each table advances once per step -- a row named by both batches gets one update from the sum of its contributions -- and the
+        towers' parameters take the exact dense Adam (the reference has one ``torch.optim.Adam`` over every parameter).  Returns the total
+        loss (device [1]).
+
+        ``adam='lazy'`` (default): table rows the batch does not touch do not move.  ``adam='exact'``: the reference's dense Adam -- one
+        catch-up launch in front of every step (fused.rowwise_catch_up) replays the gradient-free updates the step's rows missed; the
+        tables hold what ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run.  One mode per model.
+
+        Refused before any state is created: a batch without the BOTH-phase fields, empty or unequal-length domain batches,
+        ``config['dist_group']``, and widths outside ``FusedDTCDRStep.check_widths`` (use optimizer_mode=dense for those)."""
+        from ...fused import FusedDTCDRStep, rowwise_catch_up
+        exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            raise NotImplementedError("DTCDR.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
+        try:
+            FusedDTCDRStep.check_widths(self.embedding_size, self.mlp_hidden_size)
+        except ValueError as e:
+            raise ValueError(f'DTCDR.fused_train_step: embedding_size = {self.embedding_size}, mlp_hidden_size = {self.mlp_hidden_size}: '
+                             f'{e}; use optimizer_mode=dense') from None
+        su, si, ys, tu, ti, yt = self._pair_fields(interaction)
+        Bs, Bt = su.numel(), tu.numel()
+        if Bs == 0 or Bt == 0 or si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
+            raise ValueError(f'DTCDR.fused_train_step: the {self.phase} batch needs at least one row per domain and ids and labels of equal '
+                             f'length, got {Bs} / {si.numel()} / {ys.numel()} source and {Bt} / {ti.numel()} / {yt.numel()} target entries')
+        old = self._fused_cache(exact)['steps'].get('dtcdr')
+        states = tuple(self._fused_state(n, code, exact) for n in self._TABLES)
+        ms, mt = (Bs, Bt) if old is None else (max(Bs, old.max_source), max(Bt, old.max_target))
+
+        def build():
+            step = FusedDTCDRStep(*(getattr(self, n).weight.data for n in self._TABLES), self._towers(), ms, mt, self.alpha,
+                                  dropout_prob=self.dropout_prob, states=states, **hp)
+            # the towers' Adam state outlives a re-sized step object, and a checkpoint's is handed over when the first one is built
+            carry = old.w_opt.state_dict() if old is not None and old.w_opt is not None else self.__dict__.pop('_pending_weight_state', None)
+            if carry is not None and step.w_opt is not None:
+                step.w_opt.load_state_dict(carry)
+                for g in step.w_opt.param_groups:
+                    g.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+            return step
+
+        step = self._fused_step('dtcdr', lambda s: s.max_source >= Bs and s.max_target >= Bt and s.hp == hp, build)
+        step.hp = hp
+        ys = ys if ys.dtype == torch.float32 else ys.float()
+        yt = yt if yt.dtype == torch.float32 else yt.float()
+        seed = self._drop_seed()                                       # None in eval mode or without dropout: p = 0
+        if exact:
+            # [su, tu] names the rows of both user tables, [si, ti] those of both item tables
+            rowwise_catch_up([(st, ids) for st, ids in zip(states, ([su, tu], [si, ti], [su, tu], [si, ti]))], lr=lr, betas=betas, eps=eps,
+                             weight_decay=weight_decay)
+        return step.step(su.contiguous(), si.contiguous(), ys.contiguous(), tu.contiguous(), ti.contiguous(), yt.contiguous(), seed=seed)
+
+    def _fused_phase_step(self):
+        return self._fused['steps']['dtcdr']
+
+    def fused_optimizer_state(self):
+        """The shared per-table state, plus the dense Adam state of the towers and the state of the dropout seed (the generator
+        ``_drop_seed`` draws from and the device counter), so that a resumed run draws the masks the uninterrupted one would."""
+        out = super().fused_optimizer_state()
+        step = self.__dict__.get('_fused', {}).get('steps', {}).get('dtcdr')
+        if step is not None and step.w_opt is not None:
+            out['weights'] = step.w_opt.state_dict()
+        if out and self.dropout_prob:
+            st = self.__dict__.get('_drop_state')
+            out['dropout'] = {'rng': torch.get_rng_state(), 'counter': None if st is None else int(st.item())}
+        return out
+
+    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
+        """The shared per-table restore; the towers' Adam state is handed to the step when it is built."""
+        super().load_fused_optimizer_state(state, opt=opt, adam=adam)
+        if 'weights' in state:
+            self.__dict__['_pending_weight_state'] = state['weights']
+        if 'dropout' in state:
+            torch.set_rng_state(state['dropout']['rng'].cpu())
+            st = self.__dict__.get('_drop_state')
+            if st is not None and state['dropout']['counter'] is not None:
+                st.fill_(int(state['dropout']['counter']))
+        self.__dict__.get('_fused', {}).get('steps', {}).pop('dtcdr', None)
 
     @torch.no_grad()
     def predict(self, interaction):
