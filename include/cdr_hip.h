@@ -96,6 +96,7 @@ int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the
 #define CDR_TAG_TRIPLET_FWD_GRAD 21   /* triplet_fwd_grad_kernel: SSCDR's triplet loss + compact gradient rows */
 #define CDR_TAG_CLFM_FWD_GRAD 22      /* clfm_fwd_grad_kernel: CLFM's factor map, BCE and the three gradient contractions of one domain */
 #define CDR_TAG_DTCDR_FWD_GRAD 23     /* dtcdr_fwd_grad_kernel: DTCDR's NeuMF tower of one domain, forward and backward, with the max routing */
+#define CDR_TAG_DEEPAPF_FWD_GRAD 24   /* deepapf_fwd_grad_kernel: DeepAPF's two-candidate attention of one domain, forward and backward */
 int cdr_timing_enable(cdr_ctx* ctx, int capacity);
 int cdr_timing_collect(cdr_ctx* ctx, int* tags, float* ms, int max_n, int* n_out);
 
@@ -727,6 +728,31 @@ int cdr_dtcdr_fwd_grad(cdr_ctx* ctx, void* stream, const float* src_user, const 
                        const int64_t* iid, const float* label, int64_t B, float weight, float p_drop, const int64_t* seed_dev,
                        uint64_t salt0, int64_t row0, float* out8, float* GUs, float* GUt, float* GIs, float* GIt,
                        float* dparams, void* workspace, size_t workspace_bytes);
+/* DeepAPF's domain step, forward half (deepapf.py:69-152 the two domain forwards, 163-175 the loss) for one domain of B rows.  `key` names
+ * the overlapped side (user ids in overlap_users mode, item ids in overlap_items mode), `oid` the other side; three tables of width D:
+ * s = share_tab[key], o = only_tab[key], t = other_tab[oid].  xs = s (.) t, xo = o (.) t, hs = relu(W1 xs + b1), ho = relu(W1 xo + b1),
+ * a_s = w2 . hs -- replaced by -1e31 where key > n_overlap, STRICTLY: key == n_overlap keeps its share row --, a_o = w2 . ho,
+ * (al_s, al_o) = softmax(a_s, a_o), e = al_s s + al_o o, p = sigmoid(wp . (e (.) t)), bce = mean BCE(p, label) with torch's -100 clamp of
+ * both logs; `weight` is the domain's share of the total (1 for both domains of this model).  `params` is the attention MLP and the
+ * predict layer packed as [W1 (D x D, row-major), b1 (D), w2 (D), wp (D)]; `dparams` receives the gradient of weight * bce in the same
+ * layout.  With g_b = weight (p_b - y_b) / B (the 1e-12 clamp of cdr_point_fwd_grad's BCE branch) the gradient goes back through the
+ * sigmoid and the merge, the pair softmax (ga_s = al_s (d_s - dot): exactly 0 on masked rows, as cdr_apf_combine_bwd), the same ReLU
+ * decisions, W1 and the two products, and leaves THREE compact gradient rows per occurrence: GS[row0 + b] for the share row (row0 places
+ * a domain in the joint [B_s + B_t, D] buffer of the share table, which both domains feed), GO[b] and GT[b].  A masked occurrence does
+ * not read its share row; its GS row is +0.0.  Apply with cdr_sort_ids([key_s | key_t]) for the share table and per domain
+ * cdr_sort_ids_two_tables(key | oid) for the only and other tables, cdr_rowwise_apply with neg_start = n, reg_limit = 0: DeepAPF has no
+ * EmbLoss.  out8 = {weight bce, bce, 0, ...}.  The three contractions (H = X W1^T on the 64-row operand of 32 share and 32 only
+ * candidates, gX = gH W1, dW1 += gH^T X) run on v_mfma_f32_32x32x2_f32 out of LDS (widths zero-padded to 32 there); the parameter
+ * gradients are accumulated per workgroup and the partials -- one packed vector per workgroup in `workspace`,
+ * cdr_deepapf_fwd_grad_workspace_bytes = grid x (D D + 3 D) x 4 -- are added in workgroup order; the loss goes through fp64 block
+ * partials.  No float atomics: a rerun is bit-equal.  D % 4 == 0, 4 <= D <= CDR_DEEPAPF_MAX_DIM, B > 0, 16-byte aligned tables and
+ * gradient buffers (CDR_EINVAL before any launch otherwise).  D = 128 needs 136,960 B of LDS (one workgroup per CU); nothing spills. */
+#define CDR_DEEPAPF_MAX_DIM 128
+int cdr_deepapf_fwd_grad_workspace_bytes(int64_t B, int D, size_t* bytes);
+int cdr_deepapf_fwd_grad(cdr_ctx* ctx, void* stream, const float* share_tab, const float* only_tab, const float* other_tab, int D,
+                         const float* params, const int64_t* key, const int64_t* oid, const float* label, int64_t B,
+                         int64_t n_overlap, float weight, int64_t row0, float* out8, float* GS, float* GO, float* GT,
+                         float* dparams, void* workspace, size_t workspace_bytes);
 /* The same step with the optimizer of every row that occurs ONCE in the batch applied by the forward kernel itself (round 3;
  * replaces cdr_bpr_fwd_grad + cdr_sort_ids_two_tables + 2 x cdr_rowwise_apply for emcdr.py:123-131,146-154 + Adam): the EmbLoss
  * norms of the batch are gathered first (the gradient coefficient reg_weight / (B ||rows||) is needed before the first row is

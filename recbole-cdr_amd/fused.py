@@ -2,6 +2,7 @@
 (FusedBPRStep: pairwise BPR; FusedPointStep: pointwise MSE / BCE; FusedPointPairStep: CMF's two domains on shared tables;
 FusedTripletStep: SSCDR's triplet margin loss; FusedCLFMStep: CLFM's two domains, four tables and stacked factor weights;
 FusedDTCDRStep: DTCDR's two NeuMF towers over the maximum of both domains' rows, four tables fed by both batches;
+FusedDeepAPFStep: DeepAPF's two-candidate attention, a share table fed by both batches and two tables per domain;
 FusedMapStep / SSCDRMapStep: EMCDR's / SSCDR's OVERLAP-phase mapping loss).
 
 This is the large-table counterpart of ``loss.backward(); optimizer.step()`` in the reference's loop
@@ -946,6 +947,139 @@ class FusedDTCDRStep(_Step):
             for q in tw:
                 q.grad = self.dP[d, off:off + q.numel()].view(q.shape)
                 off += q.numel()
+        if self.w_opt is not None:
+            self.w_opt.step()
+        else:
+            for q in self.params:
+                q.add_(q.grad + self.wd * q if self.wd else q.grad, alpha=-self.lr)
+        return self.out16[0:1] + self.out16[8:9]
+
+
+class FusedDeepAPFStep(_Step):
+    """DeepAPF's BOTH-phase step (deepapf.py:69-152, 163-175): per domain the key id's share row and domain-only row, each multiplied with
+    the other side's row and scored by the two-layer attention MLP (W1, b1, w2), the pair softmax with the share score masked where
+    key > n_overlap (strictly), the merged row through the predict layer wp, loss = BCE_s + BCE_t.  Five live tables, named by role: the
+    share table (fed by BOTH domains: their rows go into one joint [B_s + B_t, D] buffer, source rows at 0, target rows at B_s), and per
+    domain the only table (indexed by the key id) and the other table.  ``key`` is the user in overlap_users mode and the item in
+    overlap_items mode; the step itself does not know which.
+    Per step: cdr_deepapf_fwd_grad per domain (csrc/cdr_deepapf.hip: the forward, the backward and every parameter gradient in one pass,
+    + its finishing launch) -- both before anything is updated, so both domains see the pre-step state --, one cdr_sort_ids over
+    [key_s | key_t] (two lists: no host concatenation) and one apply for the share table, per domain one cdr_sort_ids_two_tables(key |
+    other) and two applies: three sorts, five applies, each table advances exactly ONCE per step and a share row named by both domains
+    gets one update from the sum.  The four parameters are shared by the domains: their gradient is dP_source + dP_target, applied by the
+    exact dense Adam (plain SGD with opt='sgd'), as in FusedCLFMStep.  The MLP the mode does not use and the share table of the other side
+    are not given to the step: they get no gradient and do not move (torch.optim.Adam skips a parameter whose .grad is None).
+    Lazy mode touches every row a batch names, masked share rows included: a masked occurrence contributes a zero gradient row, and its
+    row takes the moment decay (and weight decay) of a zero-gradient update -- the rule DTCDR's losing rows follow.
+    The update counts are the host's: not capturable.
+
+    ``params``: (W1 [D, D], b1 [D], w2 [1, D], wp [1, D]) -- the parameters themselves: the step sets their ``.grad`` and updates them in
+    place."""
+
+    MAX_DIM = 128                                                                # CDR_DEEPAPF_MAX_DIM
+
+    @classmethod
+    def check_widths(cls, D):
+        if not (isinstance(D, int) and 4 <= D <= cls.MAX_DIM and D % 4 == 0):
+            raise ValueError(f'FusedDeepAPFStep: embedding_size must be a multiple of 4 in 4..{cls.MAX_DIM} (W1 lives in LDS), got {D}')
+
+    def __init__(self, share, source_only, source_other, target_only, target_other, params, n_overlap, max_source, max_target, opt='adam',
+                 lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, states=None):
+        from .trainer.trainer import DenseAdam
+        tables = (share, source_only, source_other, target_only, target_other)
+        assert all(t.is_cuda for t in tables), 'FusedDeepAPFStep needs ROCm device tensors'
+        D = int(share.shape[1])
+        if any(t.shape[1] != D for t in tables) or not (share.shape[0] == source_only.shape[0] == target_only.shape[0]) or \
+                source_other.shape[0] != target_other.shape[0]:
+            raise ValueError(f'FusedDeepAPFStep: the five tables must share one width, share and only tables the key id space and the other '
+                             f'tables theirs ({tuple(tuple(t.shape) for t in tables)})')
+        self.check_widths(D)                                                     # (before anything is allocated)
+        shapes = [(D, D), (D,), (1, D), (1, D)]
+        if [tuple(p.shape) for p in params] != shapes:
+            raise ValueError(f'FusedDeepAPFStep: (W1, b1, w2, wp) must be {shapes}, got {[tuple(p.shape) for p in params]}')
+        super().__init__(opt, lr, betas, eps, weight_decay)
+        self.D = D
+        self.tables = tables
+        self.params = list(params)
+        self.n_overlap = int(n_overlap)
+        states = states if states is not None else (None,) * 5
+        self.states = tuple(st if st is not None else RowwiseState(t, self.opt) for st, t in zip(states, tables))
+        self.w_opt = DenseAdam(self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.opt == OPT_ADAM else None
+        dev = share.device
+        self.max_source, self.max_target = int(max_source), int(max_target)
+        Nm = self.max_source + self.max_target
+        self.GS = torch.empty(Nm, D, device=dev, dtype=torch.float32)           # the share table's rows of both domains
+        self.GO = tuple(torch.empty(n, D, device=dev, dtype=torch.float32) for n in (self.max_source, self.max_target))
+        self.GT = tuple(torch.empty(n, D, device=dev, dtype=torch.float32) for n in (self.max_source, self.max_target))
+        self.n_params = D * D + 3 * D
+        self.dP = torch.zeros(2, self.n_params, device=dev, dtype=torch.float32)
+        self.out16 = torch.zeros(16, device=dev, dtype=torch.float32)           # out8 of the source, out8 of the target
+        self.zero = torch.zeros(1, device=dev, dtype=torch.float32)             # the applies' EmbLoss coefficient: none
+        self.fws = torch.empty(self._workspace_bytes(max(self.max_source, self.max_target)), device=dev, dtype=torch.uint8)
+        self.keys = torch.empty(2 * Nm, device=dev, dtype=torch.int32)           # one sort at a time: at most 2 max(B_s, B_t) or B_s + B_t keys
+        self.perm = torch.empty(2 * Nm, device=dev, dtype=torch.int32)
+        rows = 2 << (max(t.shape[0] for t in tables) - 1).bit_length()
+        # (the sort switches configuration at 2^18 keys: a short tail batch may need more scratch than a full one)
+        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (2 * Nm, min(2 * Nm, (1 << 18) - 1))), device=dev, dtype=torch.uint8)
+        self._key_base = ctypes.c_uint32(0)
+
+    def _states(self):
+        return self.states
+
+    def _workspace_bytes(self, B):
+        need = ctypes.c_size_t(0)
+        B_._check(B_.load().cdr_deepapf_fwd_grad_workspace_bytes(B, self.D, ctypes.byref(need)), 'cdr_deepapf_fwd_grad_workspace_bytes')
+        return int(need.value)
+
+    def grid(self, B):
+        """Workgroups cdr_deepapf_fwd_grad launches for a batch of B rows (the workspace is one packed parameter vector per workgroup)."""
+        return self._workspace_bytes(B) // (4 * self.n_params)
+
+    @torch.no_grad()
+    def forward_grads(self, ks, os_, ys, kt, ot, yt):
+        """Both domains' cdr_deepapf_fwd_grad: fills ``GS`` (rows [0, B_s) source, [B_s, B_s + B_t) target), ``GO``, ``GT``, ``dP`` and
+        ``out16``."""
+        Bs, Bt = ks.numel(), kt.numel()
+        if not (1 <= Bs <= self.max_source and 1 <= Bt <= self.max_target):
+            raise ValueError(f'FusedDeepAPFStep: batches of {Bs} + {Bt} rows, sized for 1..{self.max_source} + 1..{self.max_target}')
+        if os_.numel() != Bs or ys.numel() != Bs or ot.numel() != Bt or yt.numel() != Bt:
+            raise ValueError('FusedDeepAPFStep: ids and labels of a domain must have the same length')
+        ctxh, s = B_.ctx(self.tables[0].device), B_.stream()
+        packed = torch.cat([q.data.reshape(-1) for q in self.params])
+        for d, key, oid, y, n, row0 in ((0, ks, os_, ys, Bs, 0), (1, kt, ot, yt, Bt, Bs)):
+            B_.call('cdr_deepapf_fwd_grad', ctxh, s, B_.f32(self.tables[0]), B_.f32(self.tables[1 + 2 * d]), B_.f32(self.tables[2 + 2 * d]),
+                    self.D, B_.f32(packed), B_.i64(key), B_.i64(oid), B_.f32(y), n, self.n_overlap, 1.0, row0,
+                    B_.f32(self.out16[8 * d:8 * d + 8]), B_.f32(self.GS), B_.f32(self.GO[d]), B_.f32(self.GT[d]), B_.f32(self.dP[d]),
+                    B_.raw(self.fws), self.fws.numel())
+
+    def _apply(self, ctxh, s, st, lo, n, G, base):
+        st.advance()
+        # one gradient row per occurrence (neg_start = n), no EmbLoss (reg_limit = 0)
+        B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
+                B_.raw(self.keys[lo:lo + n]), B_.raw(self.perm[lo:lo + n]), n, B_.f32(G[:n]), n, 0, B_.f32(self.zero), *self._hp(), st.step,
+                None, int(base))
+
+    @torch.no_grad()
+    def step(self, ks, os_, ys, kt, ot, yt):
+        """ks / os_ int64 [B_s] (key and other ids of the source rows), ys fp32 [B_s]; kt / ot int64 [B_t], yt fp32 [B_t] (target rows).
+        Returns the total loss (device [1]); ``out16`` keeps each domain's {BCE, BCE, 0, ...}."""
+        self.forward_grads(ks, os_, ys, kt, ot, yt)                 # both forwards first: both domains see the pre-step state
+        Bs, Bt = ks.numel(), kt.numel()
+        ctxh, s = B_.ctx(self.tables[0].device), B_.stream()
+        B_.call('cdr_sort_ids', ctxh, s, B_.i64(ks), Bs, B_.i64(kt), Bt, self.tables[0].shape[0], B_.raw(self.keys), B_.raw(self.perm),
+                B_.raw(self.ws), self.ws.numel())
+        self._apply(ctxh, s, self.states[0], 0, Bs + Bt, self.GS, 0)
+        for d, key, oid, n in ((0, ks, os_, Bs), (1, kt, ot, Bt)):
+            ost, tst = self.states[1 + 2 * d], self.states[2 + 2 * d]
+            B_.call('cdr_sort_ids_two_tables', ctxh, s, B_.i64(key), n, ost.table.shape[0], B_.i64(oid), n, None, 0, tst.table.shape[0],
+                    B_.raw(self.keys), B_.raw(self.perm), ctypes.byref(self._key_base), B_.raw(self.ws), self.ws.numel())
+            self._apply(ctxh, s, ost, 0, n, self.GO[d], 0)
+            self._apply(ctxh, s, tst, n, n, self.GT[d], self._key_base.value)
+        dP = self.dP[0] + self.dP[1]                                # the towers are shared by the domains
+        off = 0
+        for q in self.params:
+            q.grad = dP[off:off + q.numel()].view(q.shape)
+            off += q.numel()
         if self.w_opt is not None:
             self.w_opt.step()
         else:

@@ -5,7 +5,12 @@ side's row, scored by the two-layer attention MLP (ONE [2B, D] operand through t
 of scores goes through a masked softmax, the rows are merged and scored by the predict layer (cdr_apf_combine), BCE natively.
 Quirks kept: the share score is masked where id > overlapped_num (strictly), i.e. the first non-overlapped id still uses its
 share row; ``self.user_mlp = self.seq = ...; self.item_mlp = self.seq = ...`` -- the item MLP is ALSO registered as ``seq`` and
-``named_parameters()`` reports it under that name (reference checkpoints carry user_mlp.*, seq.* and item_mlp.*)."""
+``named_parameters()`` reports it under that name (reference checkpoints carry user_mlp.*, seq.* and item_mlp.*).
+
+``fused_train_step`` (``optimizer_mode='rowwise'``): the BOTH-phase step without table-sized gradients -- fused.FusedDeepAPFStep, the five
+live tables (the overlapped side's share table, fed by both batches, and per domain the only table and the other side's table) updated
+row-wise from csrc/cdr_deepapf.hip's compact gradient rows, the attention MLP of the mode and the predict layer by the exact dense Adam;
+``adam='exact'`` puts the catch-up of the reference's dense Adam in front of it (fused.rowwise_catch_up over the five tables)."""
 import torch
 import torch.nn as nn
 
@@ -13,9 +18,10 @@ from ... import binding as B_
 from ... import functional as F_
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
+from ..rowwise import RowwiseTraining
 
 
-class DeepAPF(CrossDomainRecommender):
+class DeepAPF(RowwiseTraining, CrossDomainRecommender):
     input_type = InputType.POINTWISE
 
     def __init__(self, config, dataset):
@@ -38,6 +44,11 @@ class DeepAPF(CrossDomainRecommender):
                                                  nn.Linear(self.embedding_size, 1, bias=False))
         self.predict_layer = nn.Linear(self.embedding_size, 1, bias=False)
         self.apply(xavier_normal_initialization)
+        self.phase = 'BOTH'
+        self.__dict__['_dist_cfg'] = config['dist_group'] if 'dist_group' in config else None
+
+    def set_phase(self, phase):
+        self.phase = phase
 
     def _forward(self, user, item, domain):
         if self.mode == 'overlap_users':
@@ -75,3 +86,101 @@ class DeepAPF(CrossDomainRecommender):
         p_target = self.target_forward(interaction[self.TARGET_USER_ID], interaction[self.TARGET_ITEM_ID])
         return F_.BCEProbLoss.apply(p_source, interaction[self.SOURCE_LABEL]) + \
             F_.BCEProbLoss.apply(p_target, interaction[self.TARGET_LABEL])
+
+    # ---- O(batch) training step (large tables) ------------------------------------------------------------------
+    def _roles(self):
+        """(table attribute names by role: share, source only, source other, target only, target other; the attention MLP; n_overlap;
+        key field kind) of the mode -- ``_forward``'s choice.  The other share table and the other MLP are not part of the step."""
+        if self.mode == 'overlap_users':
+            return (('share_user_embedding', 'source_user_embedding', 'source_item_embedding', 'target_user_embedding',
+                     'target_item_embedding'), self.user_mlp, int(self.overlapped_num_users), 'user')
+        return (('share_item_embedding', 'source_item_embedding', 'source_user_embedding', 'target_item_embedding',
+                 'target_user_embedding'), self.item_mlp, int(self.overlapped_num_items), 'item')
+
+    def _attention_params(self):
+        """(W1, b1, w2, wp): the attention MLP of the mode and the predict layer."""
+        mlp = self._roles()[1]
+        return mlp[0].weight, mlp[0].bias, mlp[2].weight, self.predict_layer.weight
+
+    def _pair_fields(self, interaction):
+        fields = (self.SOURCE_USER_ID, self.SOURCE_ITEM_ID, self.SOURCE_LABEL, self.TARGET_USER_ID, self.TARGET_ITEM_ID, self.TARGET_LABEL)
+        missing = [f for f in fields if f not in interaction]
+        if missing:
+            raise ValueError(f'DeepAPF.fused_train_step trains on BOTH-phase batches (source and target rows); the {self.phase} batch '
+                             f'has no {", ".join(missing)}')
+        return [interaction[f].reshape(-1) for f in fields]
+
+    def fused_train_step(self, interaction, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam='lazy'):
+        """``calculate_loss -> backward -> optimizer.step`` on a BOTH-phase batch without table-sized gradients or a dense optimizer
+        sweep over the tables (fused.FusedDeepAPFStep): what ``CrossDomainTrainer`` runs when ``config['optimizer_mode'] == 'rowwise'``.
+        Same loss and gradients as ``calculate_loss``; each of the five live tables advances once per step -- a share row named by both
+        batches gets one update from the sum of its contributions -- and the attention MLP and the predict layer take the exact dense
+        Adam (the reference has one ``torch.optim.Adam`` over every parameter).  The MLP the mode does not use and the share table of the
+        other side have no gradient in the reference either and do not move.  Returns the total loss (device [1]).
+
+        ``adam='lazy'`` (default): table rows the batch does not touch do not move; every row a batch names is touched, a masked
+        occurrence's share row included (with a zero gradient row).  ``adam='exact'``: the reference's dense Adam -- two catch-up launches in
+        front of every step (fused.rowwise_catch_up takes up to four tables; there are five) replays the gradient-free updates the step's rows missed; the tables hold what
+        ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run.  One mode per model.
+
+        Refused before any state is created: a batch without the BOTH-phase fields, empty or unequal-length domain batches,
+        ``config['dist_group']``, and widths outside ``FusedDeepAPFStep.check_widths`` (use optimizer_mode=dense for those)."""
+        from ...fused import FusedDeepAPFStep, rowwise_catch_up
+        exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            raise NotImplementedError("DeepAPF.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
+        try:
+            FusedDeepAPFStep.check_widths(self.embedding_size)
+        except ValueError as e:
+            raise ValueError(f'DeepAPF.fused_train_step: embedding_size = {self.embedding_size}: {e}; use optimizer_mode=dense') from None
+        su, si, ys, tu, ti, yt = self._pair_fields(interaction)
+        Bs, Bt = su.numel(), tu.numel()
+        if Bs == 0 or Bt == 0 or si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
+            raise ValueError(f'DeepAPF.fused_train_step: the {self.phase} batch needs at least one row per domain and ids and labels of equal '
+                             f'length, got {Bs} / {si.numel()} / {ys.numel()} source and {Bt} / {ti.numel()} / {yt.numel()} target entries')
+        names, _mlp, n_over, kind = self._roles()
+        ks, os_, kt, ot = (su, si, tu, ti) if kind == 'user' else (si, su, ti, tu)
+        old = self._fused_cache(exact)['steps'].get('deepapf')
+        states = tuple(self._fused_state(n, code, exact) for n in names)
+        ms, mt = (Bs, Bt) if old is None else (max(Bs, old.max_source), max(Bt, old.max_target))
+
+        def build():
+            step = FusedDeepAPFStep(*(getattr(self, n).weight.data for n in names), self._attention_params(), n_over, ms, mt, states=states,
+                                    **hp)
+            # the parameters' Adam state outlives a re-sized step object, and a checkpoint's is handed over when the first one is built
+            carry = old.w_opt.state_dict() if old is not None and old.w_opt is not None else self.__dict__.pop('_pending_weight_state', None)
+            if carry is not None and step.w_opt is not None:
+                step.w_opt.load_state_dict(carry)
+                for g in step.w_opt.param_groups:
+                    g.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+            return step
+
+        step = self._fused_step('deepapf', lambda s: s.max_source >= Bs and s.max_target >= Bt and s.hp == hp, build)
+        step.hp = hp
+        ys = ys if ys.dtype == torch.float32 else ys.float()
+        yt = yt if yt.dtype == torch.float32 else yt.float()
+        ks, os_, kt, ot = ks.contiguous(), os_.contiguous(), kt.contiguous(), ot.contiguous()
+        if exact:
+            # [ks, kt] names the share table's rows; each domain's key list its only table's, its other list its other table's
+            named = list(zip(states, ([ks, kt], [ks], [os_], [kt], [ot])))
+            for part in (named[:3], named[3:]):                         # (a catch-up launch takes up to four tables)
+                rowwise_catch_up(part, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        return step.step(ks, os_, ys.contiguous(), kt, ot, yt.contiguous())
+
+    def _fused_phase_step(self):
+        return self._fused['steps']['deepapf']
+
+    def fused_optimizer_state(self):
+        """The shared per-table state, plus the dense Adam state of (W1, b1, w2, wp) under ``'weights'``."""
+        out = super().fused_optimizer_state()
+        step = self.__dict__.get('_fused', {}).get('steps', {}).get('deepapf')
+        if step is not None and step.w_opt is not None:
+            out['weights'] = step.w_opt.state_dict()
+        return out
+
+    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
+        """The shared per-table restore; the parameters' Adam state is handed to the step when it is built."""
+        super().load_fused_optimizer_state(state, opt=opt, adam=adam)
+        if 'weights' in state:
+            self.__dict__['_pending_weight_state'] = state['weights']
+        self.__dict__.get('_fused', {}).get('steps', {}).pop('deepapf', None)
