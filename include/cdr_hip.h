@@ -97,6 +97,7 @@ int cdr_abi_version(void);                          /* == CDR_ABI_VERSION of the
 #define CDR_TAG_CLFM_FWD_GRAD 22      /* clfm_fwd_grad_kernel: CLFM's factor map, BCE and the three gradient contractions of one domain */
 #define CDR_TAG_DTCDR_FWD_GRAD 23     /* dtcdr_fwd_grad_kernel: DTCDR's NeuMF tower of one domain, forward and backward, with the max routing */
 #define CDR_TAG_DEEPAPF_FWD_GRAD 24   /* deepapf_fwd_grad_kernel: DeepAPF's two-candidate attention of one domain, forward and backward */
+#define CDR_TAG_DCDCSR_MAP_FWD_GRAD 25 /* dcdcsr_map_kernel: DCDCSR's max-min normalised tanh-MLP map loss, forward and backward */
 int cdr_timing_enable(cdr_ctx* ctx, int capacity);
 int cdr_timing_collect(cdr_ctx* ctx, int* tags, float* ms, int max_n, int* n_out);
 
@@ -753,6 +754,31 @@ int cdr_deepapf_fwd_grad(cdr_ctx* ctx, void* stream, const float* share_tab, con
                          const float* params, const int64_t* key, const int64_t* oid, const float* label, int64_t B,
                          int64_t n_overlap, float weight, int64_t row0, float* out8, float* GS, float* GO, float* GT,
                          float* dparams, void* workspace, size_t workspace_bytes);
+/* DCDCSR's BOTH-phase map step, forward half (dcdcsr.py:172-187; the max-min normalisation is dcdcsr.py:167-172) for n sampled unit ids,
+ * repeats allowed.  x = table[ids[i]], e = maxmin(x), b = maxmin(bench[ids[i]]) (no gradient), maxmin(x) = (x - mean) / (max - mean) with
+ * mean = (max + min) / 2; m = the L-layer MLP of e with tanh after EVERY layer, the last included; mse = sum (m - b)^2 / (n D).
+ * `dims` = [L + 1] widths with dims[0] == dims[L] == D (the row width of both tables); `params` packs W1 (dims[1] x dims[0], row-major),
+ * b1, ..., WL, bL, and `dparams` receives the gradient of mse in the same layout.  From g = 2 (m - b) / (n D) the gradient goes back
+ * through 1 - a^2 and W_l of every layer and through the normalisation, whose arg-max and arg-min elements receive the extra terms split
+ * EVENLY over ties, as torch's amax / amin do (the formula above maxmin_bwd_kernel in csrc/cdr_rowmodels.hip), and leaves ONE gradient
+ * row G[i] per occurrence: apply with cdr_sort_ids(ids) and cdr_rowwise_apply(neg_start = n, reg_limit = 0), which adds the rows of a
+ * repeated id in occurrence order.  out8 = {mse, 0, ...}.  One launch (+ its finishing launch): a persistent grid walks tiles of 32
+ * occurrences, every layer's activation stays in LDS, the three contractions per layer (a_l = tanh(a_{l-1} W_l^T + b_l),
+ * gpre_{l-1} = gpre_l W_l (.) (1 - a_{l-1}^2), dW_l += gpre_l^T a_{l-1} in registers across a workgroup's tiles) run on
+ * v_mfma_f32_32x32x2_f32 with widths zero-padded to 32.  The padded weights are staged in LDS where they fit beside the activations
+ * (the default 64-[128]-64: 104,448 B); wider shapes (128-[128]-128) read the weight operand through L2.  The parameter-gradient
+ * partials -- one packed vector per workgroup in `workspace`, cdr_dcdcsr_map_fwd_grad_workspace_bytes = grid x packed-parameter-count
+ * x 4 -- are added in workgroup order, the loss goes through fp64 block partials.  No float atomics: a rerun is bit-equal.
+ * 1 <= L <= CDR_DCDCSR_MAX_LAYERS, every width % 4 == 0 and in 4..CDR_DCDCSR_MAX_DIM, dims[0] == dims[L], n > 0, no NULL pointer (bench
+ * and ids included), 16-byte aligned table, bench, params and G: CDR_EINVAL before any launch otherwise, from the workspace query too.
+ * A constant row (max == min) divides by zero exactly as the reference does.  Nothing spills. */
+#define CDR_DCDCSR_MAX_DIM 128
+#define CDR_DCDCSR_MAX_LAYERS 3
+int cdr_dcdcsr_map_fwd_grad_workspace_bytes(int64_t n, int L, const int* dims, size_t* bytes);
+int cdr_dcdcsr_map_fwd_grad(cdr_ctx* ctx, void* stream, const float* table, const float* bench, const int64_t* ids, int64_t n,
+                            int L, const int* dims /* [L+1], dims[0] == dims[L] == D */, const float* params /* W1,b1,...,WL,bL packed */,
+                            float* out8, float* G /* [n, D] */, float* dparams /* packed like params */,
+                            void* workspace, size_t workspace_bytes);
 /* The same step with the optimizer of every row that occurs ONCE in the batch applied by the forward kernel itself (round 3;
  * replaces cdr_bpr_fwd_grad + cdr_sort_ids_two_tables + 2 x cdr_rowwise_apply for emcdr.py:123-131,146-154 + Adam): the EmbLoss
  * norms of the batch are gathered first (the gradient coefficient reg_weight / (B ||rows||) is needed before the first row is

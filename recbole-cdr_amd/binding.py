@@ -113,6 +113,9 @@ _SIGNATURES = {
     'cdr_deepapf_fwd_grad_workspace_bytes': [_c_i64, _c_int, ctypes.POINTER(ctypes.c_size_t)],
     'cdr_deepapf_fwd_grad': [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_f32, _c_i64,
                              _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
+    'cdr_dcdcsr_map_fwd_grad_workspace_bytes': [_c_i64, _c_int, ctypes.POINTER(_c_int), ctypes.POINTER(ctypes.c_size_t)],
+    'cdr_dcdcsr_map_fwd_grad': [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_int, ctypes.POINTER(_c_int), _c_ptr, _c_ptr, _c_ptr, _c_ptr,
+                                _c_ptr, ctypes.c_size_t],
     'cdr_bpr_step_fused_heads_words': [_c_i64, ctypes.POINTER(_c_i64)],
     'cdr_bpr_step_fused_kmajor_sizes': [_c_i64, _c_int, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)],
     'cdr_bpr_step_fused_kmajor': [_c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_int,
@@ -450,7 +453,7 @@ TAGS = {1: 'bpr_fwd_kernel', 2: 'point_fwd_kernel', 3: 'bpr_fwd_grad_kernel', 4:
         10: 'point_partial_dot_kernel', 11: 'point_grad_from_dot_kernel',
         12: 'conet_fwd_kernel', 13: 'conet_bwd_kernel', 14: 'conet_wgrad_kernel', 15: 'bpr_fwd_kmajor_kernel', 16: 'map_step_kernel',
         17: 'occ_flags_kernel', 18: 'bpr_fwd_apply_kernel', 19: 'batch_norms_kernel', 20: 'conet_fb_kernel', 21: 'triplet_fwd_grad_kernel',
-        22: 'clfm_fwd_grad_kernel', 23: 'dtcdr_fwd_grad_kernel', 24: 'deepapf_fwd_grad_kernel'}
+        22: 'clfm_fwd_grad_kernel', 23: 'dtcdr_fwd_grad_kernel', 24: 'deepapf_fwd_grad_kernel', 25: 'dcdcsr_map_kernel'}
 
 
 _timing_cap = {}     # device index -> ring capacity requested for every context (= stream) of that device

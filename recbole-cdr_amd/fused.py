@@ -3,6 +3,8 @@
 FusedTripletStep: SSCDR's triplet margin loss; FusedCLFMStep: CLFM's two domains, four tables and stacked factor weights;
 FusedDTCDRStep: DTCDR's two NeuMF towers over the maximum of both domains' rows, four tables fed by both batches;
 FusedDeepAPFStep: DeepAPF's two-candidate attention, a share table fed by both batches and two tables per domain;
+FusedDCDCSRMapStep: DCDCSR's max-min normalised tanh-MLP map loss on sampled unit ids; FusedFrozenSideBPRStep: DCDCSR's second TARGET
+visit, BPR against a detached operand;
 FusedMapStep / SSCDRMapStep: EMCDR's / SSCDR's OVERLAP-phase mapping loss).
 
 This is the large-table counterpart of ``loss.backward(); optimizer.step()`` in the reference's loop
@@ -1086,6 +1088,184 @@ class FusedDeepAPFStep(_Step):
             for q in self.params:
                 q.add_(q.grad + self.wd * q if self.wd else q.grad, alpha=-self.lr)
         return self.out16[0:1] + self.out16[8:9]
+
+
+class FusedDCDCSRMapStep(_Step):
+    """DCDCSR's BOTH-phase step (dcdcsr.py:172-187): ``n`` unit ids drawn with repeats, e = maxmin(table[idx]), m = the tanh MLP of e (tanh
+    after every layer, the last included), b = maxmin(bench[idx]) without a gradient, loss = MSE(m, b) as a mean over n D.  One live table
+    (the target table of the overlapped unit kind) and the MLP.
+    Per step: cdr_dcdcsr_map_fwd_grad (csrc/cdr_dcdcsr.hip: the normalisation, the forward, the backward with the even tie split and every
+    parameter gradient in one pass, + its finishing launch) leaves one gradient row per occurrence; cdr_sort_ids(idx) and ONE
+    cdr_rowwise_apply(neg_start = n, reg_limit = 0) add the rows of a repeated id in occurrence order and update the table's rows; the
+    MLP's parameters take the exact dense Adam (plain SGD with opt='sgd') from ``dparams``, as in FusedDeepAPFStep.
+    The update count is the host's: not capturable.
+
+    ``layers``: [(weight [d_l, d_{l-1}], bias [d_l])] -- the parameters themselves: the step sets their ``.grad`` and updates them in
+    place.  ``bench`` may be replaced between BOTH visits (the ``bench`` attribute, or ``step(idx, bench=...)``)."""
+
+    MAX_DIM, MAX_LAYERS = 128, 3                                                 # CDR_DCDCSR_MAX_DIM, CDR_DCDCSR_MAX_LAYERS
+
+    @classmethod
+    def check_widths(cls, dims):
+        dims = list(dims)
+        if not (2 <= len(dims) <= cls.MAX_LAYERS + 1):
+            raise ValueError(f'FusedDCDCSRMapStep: 1..{cls.MAX_LAYERS} layers, got widths {dims}')
+        if not all(isinstance(d, int) and 4 <= d <= cls.MAX_DIM and d % 4 == 0 for d in dims):
+            raise ValueError(f'FusedDCDCSRMapStep: every width must be a multiple of 4 in 4..{cls.MAX_DIM} (the activations live in LDS), '
+                             f'got {dims}')
+        if dims[0] != dims[-1]:
+            raise ValueError(f'FusedDCDCSRMapStep: the MLP must map the row width onto itself, got {dims}')
+
+    def __init__(self, table, bench, layers, max_batch, state=None, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        from .trainer.trainer import DenseAdam
+        assert table.is_cuda, 'FusedDCDCSRMapStep needs ROCm device tensors'
+        layers = [tuple(l) for l in layers]
+        dims = [int(layers[0][0].shape[1])] + [int(W.shape[0]) for W, _ in layers] if layers else []
+        self.check_widths(dims)                                                  # (before anything is allocated)
+        for l, (W, b) in enumerate(layers):
+            if tuple(W.shape) != (dims[l + 1], dims[l]) or b is None or tuple(b.shape) != (dims[l + 1],):
+                raise ValueError(f'FusedDCDCSRMapStep: layer {l + 1} must be a [{dims[l + 1]}, {dims[l]}] weight with a bias')
+        if table.shape[1] != dims[0]:
+            raise ValueError(f'FusedDCDCSRMapStep: the table is {table.shape[1]} wide, the MLP {dims[0]}')
+        super().__init__(opt, lr, betas, eps, weight_decay)
+        self.table, self.D, self.dims = table, dims[0], dims
+        self.bench = bench
+        self.params = [q for pair in layers for q in pair]
+        self.state = state if state is not None else RowwiseState(table, self.opt)
+        self.w_opt = DenseAdam(self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.opt == OPT_ADAM else None
+        dev = table.device
+        self.max_batch = int(max_batch)
+        self._dims_c = (ctypes.c_int * len(dims))(*dims)
+        self.n_params = sum(q.numel() for q in self.params)
+        self.G = torch.empty(self.max_batch, self.D, device=dev, dtype=torch.float32)
+        self.dP = torch.zeros(self.n_params, device=dev, dtype=torch.float32)
+        self.out8 = torch.zeros(8, device=dev, dtype=torch.float32)
+        self.zero = torch.zeros(1, device=dev, dtype=torch.float32)             # the apply's EmbLoss coefficient: none
+        self.fws = torch.empty(self._workspace_bytes(self.max_batch), device=dev, dtype=torch.uint8)
+        self.keys = torch.empty(self.max_batch, device=dev, dtype=torch.int32)
+        self.perm = torch.empty(self.max_batch, device=dev, dtype=torch.int32)
+        rows = 2 << (table.shape[0] - 1).bit_length()
+        # (the sort switches configuration at 2^18 keys: a short batch may need more scratch than a full one)
+        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (self.max_batch, min(self.max_batch, (1 << 18) - 1))), device=dev,
+                              dtype=torch.uint8)
+
+    def _states(self):
+        return (self.state,)
+
+    def _workspace_bytes(self, n):
+        need = ctypes.c_size_t(0)
+        B_._check(B_.load().cdr_dcdcsr_map_fwd_grad_workspace_bytes(n, len(self.dims) - 1, self._dims_c, ctypes.byref(need)),
+                  'cdr_dcdcsr_map_fwd_grad_workspace_bytes')
+        return int(need.value)
+
+    def grid(self, n):
+        """Workgroups cdr_dcdcsr_map_fwd_grad launches for n ids (the workspace is one packed parameter vector per workgroup)."""
+        return self._workspace_bytes(n) // (4 * self.n_params)
+
+    @torch.no_grad()
+    def forward_grads(self, idx, bench=None):
+        """cdr_dcdcsr_map_fwd_grad alone: fills ``G[:n]``, ``dP`` and ``out8``."""
+        bench = self.bench if bench is None else bench
+        n = idx.numel()
+        if not 1 <= n <= self.max_batch:
+            raise ValueError(f'FusedDCDCSRMapStep: {n} ids, sized for 1..{self.max_batch}')
+        if bench is None or not bench.is_cuda or bench.dtype != torch.float32 or bench.dim() != 2 or bench.shape[1] != self.D or \
+                not bench.is_contiguous():
+            raise ValueError(f'FusedDCDCSRMapStep: bench must be a contiguous fp32 device tensor [rows, {self.D}]')
+        if idx.dtype != torch.int64 or idx.device != self.table.device or not idx.is_contiguous():
+            raise ValueError(f'FusedDCDCSRMapStep: idx must be contiguous int64 on {self.table.device}')
+        packed = torch.cat([q.data.reshape(-1) for q in self.params])
+        B_.call('cdr_dcdcsr_map_fwd_grad', B_.ctx(self.table.device), B_.stream(), B_.f32(self.table), B_.f32(bench), B_.i64(idx), n,
+                len(self.dims) - 1, self._dims_c, B_.f32(packed), B_.f32(self.out8), B_.f32(self.G), B_.f32(self.dP), B_.raw(self.fws),
+                self.fws.numel())
+
+    @torch.no_grad()
+    def step(self, idx, bench=None):
+        """idx: int64 device tensor [n], repeats allowed.  Returns the loss (device scalar)."""
+        self.forward_grads(idx, bench)
+        n = idx.numel()
+        ctxh, s, st = B_.ctx(self.table.device), B_.stream(), self.state
+        B_.call('cdr_sort_ids', ctxh, s, B_.i64(idx), n, None, 0, self.table.shape[0], B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.ws),
+                self.ws.numel())
+        st.advance()
+        # one gradient row per occurrence (neg_start = n), no EmbLoss (reg_limit = 0)
+        B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
+                B_.raw(self.keys[:n]), B_.raw(self.perm[:n]), n, B_.f32(self.G[:n]), n, 0, B_.f32(self.zero), *self._hp(), st.step, None, 0)
+        off = 0
+        for q in self.params:
+            q.grad = self.dP[off:off + q.numel()].view(q.shape)
+            off += q.numel()
+        if self.w_opt is not None:
+            self.w_opt.step()
+        else:
+            for q in self.params:
+                q.add_(q.grad + self.wd * q if self.wd else q.grad, alpha=-self.lr)
+        return self.out8[0]
+
+
+class FusedFrozenSideBPRStep(_Step):
+    """DCDCSR's second TARGET visit (dcdcsr.py:98-110, 204-213): BPR without a regulariser in which one operand is a detached table (the
+    affine embedding stands in for the overlapped side's table) and only the OTHER side's table trains.  Composed from existing entry
+    points: cdr_bpr_fwd_grad(reg_weight = 0) reads both operands; the trained side's ids are sorted -- cdr_sort_ids(pid, nid) with
+    G = GP, neg_start = B for items, cdr_sort_ids(uid) with G = GU, neg_start = B for users -- and ONE cdr_rowwise_apply updates its rows.
+    Only the trained table's ``RowwiseState`` advances; the frozen operand is read only and has no state.  It may have fewer rows than
+    the table it stands in for (the affine table has target_num rows): the batch's ids on that side must be below its row count.
+    The frozen side's gradient buffer is written and never read (B D 4 bytes per step; DESIGN.md names a one-sided forward as the next step).
+
+    ``frozen``: 'user' (``user_rows`` is the frozen operand, the item table trains) or 'item'."""
+
+    def __init__(self, user_rows, item_rows, frozen, max_batch, state=None, gamma=1e-10, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=0.0):
+        if frozen not in ('user', 'item'):
+            raise ValueError(f"FusedFrozenSideBPRStep: frozen must be 'user' or 'item', got {frozen!r}")
+        assert user_rows.is_cuda and item_rows.is_cuda, 'FusedFrozenSideBPRStep needs ROCm device tensors'
+        D = int(user_rows.shape[1])
+        if item_rows.shape[1] != D or D % 4 != 0 or not 4 <= D <= 256:
+            raise ValueError(f'FusedFrozenSideBPRStep: both operands must share a width that is a multiple of 4 in 4..256, got '
+                             f'{tuple(user_rows.shape)} and {tuple(item_rows.shape)}')
+        super().__init__(opt, lr, betas, eps, weight_decay)
+        self.U, self.I, self.D, self.frozen, self.gamma = user_rows, item_rows, D, frozen, gamma
+        trained = item_rows if frozen == 'user' else user_rows
+        self.state = state if state is not None else RowwiseState(trained, self.opt)
+        if self.state.table.data_ptr() != trained.data_ptr():
+            raise ValueError('FusedFrozenSideBPRStep: state belongs to another table than the trained operand')
+        dev = trained.device
+        self.max_batch = Bm = int(max_batch)
+        self.GU = torch.empty(Bm, D, device=dev, dtype=torch.float32)
+        self.GP = torch.empty(Bm, D, device=dev, dtype=torch.float32)
+        self.out6 = torch.zeros(12, device=dev, dtype=torch.float32)
+        self.zero = torch.zeros(1, device=dev, dtype=torch.float32)
+        nk = 2 * Bm if frozen == 'user' else Bm
+        self.keys = torch.empty(nk, device=dev, dtype=torch.int32)
+        self.perm = torch.empty(nk, device=dev, dtype=torch.int32)
+        rows = 2 << (trained.shape[0] - 1).bit_length()
+        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (nk, min(nk, (1 << 18) - 1))), device=dev, dtype=torch.uint8)
+
+    def _states(self):
+        return (self.state,)
+
+    @torch.no_grad()
+    def step(self, uid, pid, nid):
+        """uid / pid / nid: int64 device tensors [B].  Returns the device tensor out6 (view; [0] = the loss)."""
+        B = uid.numel()
+        if not 1 <= B <= self.max_batch or pid.numel() != B or nid.numel() != B:
+            raise ValueError(f'FusedFrozenSideBPRStep: {B} / {pid.numel()} / {nid.numel()} ids, sized for 1..{self.max_batch} triples')
+        ctxh, s, st = B_.ctx(self.U.device), B_.stream(), self.state
+        B_.call('cdr_bpr_fwd_grad', ctxh, s, B_.f32(self.U), B_.f32(self.I), self.D, B_.i64(uid), B_.i64(pid), B_.i64(nid), B, 0,
+                float(self.gamma), 0.0, B_.f32(self.out6), B_.f32(self.GU), B_.f32(self.GP), 0)
+        if self.frozen == 'user':
+            n, G = 2 * B, self.GP
+            B_.call('cdr_sort_ids', ctxh, s, B_.i64(pid), B, B_.i64(nid), B, st.table.shape[0], B_.raw(self.keys), B_.raw(self.perm),
+                    B_.raw(self.ws), self.ws.numel())
+        else:
+            n, G = B, self.GU
+            B_.call('cdr_sort_ids', ctxh, s, B_.i64(uid), B, None, 0, st.table.shape[0], B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.ws),
+                    self.ws.numel())
+        st.advance()
+        # occurrences [B, 2 B) of the item list are the negatives: -GP[o - B]; no EmbLoss (reg_limit = 0)
+        B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
+                B_.raw(self.keys[:n]), B_.raw(self.perm[:n]), n, B_.f32(G), B, 0, B_.f32(self.zero), *self._hp(), st.step, None, 0)
+        return self.out6
 
 
 class SSCDRMapStep(_Step):

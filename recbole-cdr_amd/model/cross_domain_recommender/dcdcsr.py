@@ -9,7 +9,14 @@ DCDCSRTrainer: SOURCE -> TARGET -> BOTH -> TARGET).
 * BOTH (dcdcsr.py:174-182): numpy-sampled unit ids -> gather -> max-min row normalisation (cdr_maxmin_norm, native backward) ->
   tanh MLP on the MFMA contraction -> MSE against the normalised benchmark rows.
 * second TARGET: BPR with the detached affine table standing in for the overlapped side's table (dcdcsr.py:98-110, 204-213).
-``predict`` / ``full_sort_predict`` follow the reference's phase table, including full_sort_predict returning [U, N]."""
+``predict`` / ``full_sort_predict`` follow the reference's phase table, including full_sort_predict returning [U, N].
+
+``fused_train_step`` (``optimizer_mode='rowwise'``): every phase without table-sized gradients -- the first SOURCE / TARGET visit on the
+fused BPR step of the domain's two tables, BOTH on fused.FusedDCDCSRMapStep (csrc/cdr_dcdcsr.hip: the normalisation, the tanh MLP, the MSE
+and the whole backward in one pass; the unit table row-wise, the MLP by the exact dense Adam), the second TARGET visit on
+fused.FusedFrozenSideBPRStep (the affine table read only, the other side's table row-wise).  One optimizer state per table across the
+phases; ``adam='exact'`` puts the catch-up of the reference's dense Adam in front of every step, and ``set_phase`` syncs the tables
+before it builds the benchmark or the affine table from them."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -18,10 +25,11 @@ from ... import binding as B_
 from ... import functional as F_
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
+from ..rowwise import RowwiseTraining
 from .sscdr import MLPLayers
 
 
-class DCDCSR(CrossDomainRecommender):
+class DCDCSR(RowwiseTraining, CrossDomainRecommender):
     input_type = InputType.PAIRWISE
 
     def __init__(self, config, dataset):
@@ -53,6 +61,7 @@ class DCDCSR(CrossDomainRecommender):
         # (zero fills of dcdcsr.py:72-76 are overwritten by the initialisation below, :86)
         self.mapping_mlp_layers = MLPLayers([self.embedding_size] + self.mlp_hidden_size + [self.embedding_size])
         self.apply(xavier_normal_initialization)
+        self.__dict__['_dist_cfg'] = config['dist_group'] if 'dist_group' in config else None
 
     @staticmethod
     def build_unit2pop(dataset, unit='user', domain='source'):
@@ -68,6 +77,8 @@ class DCDCSR(CrossDomainRecommender):
     def set_phase(self, phase):
         self.phase = phase
         self.phase2count[phase] += 1
+        # exact row-wise Adam: the rows lag behind their tables' update counts, and both builds below read whole tables
+        self.fused_sync()
         if self.phase == 'BOTH':
             self.build_benchmark_embedding()
         if self.phase == 'TARGET' and self.phase2count[self.phase] == 2:
@@ -162,6 +173,140 @@ class DCDCSR(CrossDomainRecommender):
             return self.calculate_rec_loss(interaction, U, I, getattr(self, f'{tag}_USER_ID'), getattr(self, f'{tag}_ITEM_ID'),
                                            getattr(self, f'{tag}_NEG_ITEM_ID'), getattr(self, f'{tag}_LABEL'))
         return None
+
+    # ---- O(batch) training step (large tables) ------------------------------------------------------------------
+    def _mlp_pairs(self):
+        """[(weight, bias)] of the mapping MLP's linear layers, first layer first."""
+        return [(m.weight, m.bias) for m in self.mapping_mlp_layers.mlp_layers if isinstance(m, nn.Linear)]
+
+    def _triple_fields(self, interaction, tag):
+        fields = [getattr(self, f'{tag}_{f}') for f in ('USER_ID', 'ITEM_ID', 'NEG_ITEM_ID')]
+        missing = [f for f in fields if f not in interaction]
+        if missing:
+            raise ValueError(f'DCDCSR.fused_train_step trains the {self.phase} phase on {tag} triples; the batch has no {", ".join(missing)}')
+        uid, pid, nid = (interaction[f].reshape(-1).contiguous() for f in fields)
+        if uid.numel() == 0 or pid.numel() != uid.numel() or nid.numel() != uid.numel():
+            raise ValueError(f'DCDCSR.fused_train_step: the {self.phase} batch needs at least one triple and id lists of equal length, got '
+                             f'{uid.numel()} / {pid.numel()} / {nid.numel()} entries')
+        return uid, pid, nid
+
+    def fused_train_step(self, interaction, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam='lazy'):
+        """``calculate_loss -> backward -> optimizer.step`` of the current (phase, visit) without table-sized gradients or a dense optimizer
+        sweep over the tables: what ``DCDCSRTrainer`` runs when ``config['optimizer_mode'] == 'rowwise'``.  Same loss and gradients as
+        ``calculate_loss``:
+
+        * first SOURCE / TARGET visit: the fused BPR step of the domain's two tables (fused.FusedBPRStep / KMajorBPRStep by the batch
+          layout, reg_weight 0, gamma 1e-10);
+        * BOTH: ``map_batch_size`` unit ids drawn with ONE ``np.random.randint`` per step exactly as ``calculate_unit_map_loss`` draws them
+          (the dense and the row-wise mode consume the same numpy stream), then fused.FusedDCDCSRMapStep on the live benchmark table: the
+          target table of the overlapped unit kind row-wise, the mapping MLP by the exact dense Adam;
+        * second TARGET visit: fused.FusedFrozenSideBPRStep with the affine table on the overlapped side; only the other side's table trains.
+
+        One optimizer state per table, shared by the phases (the reference has one ``torch.optim.Adam`` over every parameter).  Returns the
+        loss (device scalar or [1]).  ``adam='lazy'`` (default): table rows a step does not name do not move.  ``adam='exact'``: the
+        reference's dense Adam -- one catch-up launch in front of every step (fused.rowwise_catch_up); the tables hold what
+        ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run, which ``set_phase`` does before it reads them.
+        One mode per model.  Every phase runs eagerly: there is no ``fused_graph_key`` (BOTH draws on the host; replaying the BPR phases
+        is left for later).
+
+        Refused before any state is created: ``adam`` other than 'lazy' / 'exact', ``adam='exact'`` with SGD, a second Adam mode
+        (ValueError); ``config['dist_group']`` (NotImplementedError); an embedding_size the fused BPR step does not take, MLP widths outside
+        ``FusedDCDCSRMapStep.check_widths`` (ValueError, use optimizer_mode=dense); a batch without the phase's triple fields, empty or
+        unequal-length id lists, and a (phase, visit) pair ``calculate_loss`` has no loss for (ValueError)."""
+        from ...fused import FusedDCDCSRMapStep, FusedFrozenSideBPRStep, rowwise_catch_up
+        exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            raise NotImplementedError("DCDCSR.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
+        D = self.embedding_size
+        if D % 4 != 0 or D > 256:
+            raise ValueError(f'DCDCSR.fused_train_step needs embedding_size % 4 == 0 and embedding_size <= 256 (one float4 per lane, '
+                             f'at most 64 lanes per row), got {D}; use optimizer_mode=dense')
+        dims = [D] + [int(h) for h in self.mlp_hidden_size] + [D]
+        try:
+            FusedDCDCSRMapStep.check_widths(dims)
+        except ValueError as e:
+            raise ValueError(f'DCDCSR.fused_train_step: mapping MLP widths {dims}: {e}; use optimizer_mode=dense') from None
+        count = self.phase2count.get(self.phase, 0)
+        unit = self._unit()
+
+        def catch_up(st, ids):
+            if exact:
+                rowwise_catch_up([(st, ids)], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+        if self.phase == 'BOTH':
+            n = int(self.map_batch_size)
+            if n < 1 or self.benchmark_embedding is None:
+                raise ValueError(f'DCDCSR.fused_train_step: the BOTH phase needs map_batch_size >= 1 (got {n}) and the benchmark table '
+                                 f"set_phase('BOTH') builds")
+            name = f'target_{unit}_embedding'
+            old = self._fused_cache(exact)['steps'].get('map')
+            st = self._fused_state(name, code, exact)
+
+            def build():
+                step = FusedDCDCSRMapStep(getattr(self, name).weight.data, self.benchmark_embedding, self._mlp_pairs(),
+                                          n if old is None else max(n, old.max_batch), state=st, **hp)
+                # the MLP's Adam state outlives a re-sized step object, and a checkpoint's is handed over when the first one is built
+                carry = old.w_opt.state_dict() if old is not None and old.w_opt is not None else self.__dict__.pop('_pending_weight_state', None)
+                if carry is not None and step.w_opt is not None:
+                    step.w_opt.load_state_dict(carry)
+                    for g in step.w_opt.param_groups:
+                        g.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+                return step
+
+            step = self._fused_step('map', lambda s: s.max_batch >= n and s.hp == hp, build)
+            step.hp = hp
+            sampled_index = np.random.randint(0, getattr(self, f'target_num_{unit}s'), n)        # host draw, as the reference (:175)
+            idx = torch.from_numpy(sampled_index).to(st.table.device)
+            catch_up(st, [idx])
+            return step.step(idx, bench=self.benchmark_embedding)
+        if self.phase in ('SOURCE', 'TARGET') and count == 1:
+            uid, pid, nid = self._triple_fields(interaction, self.phase)
+            self._fused_cache(exact)
+            return self._fused_bpr_domain_step(self.phase.lower(), getattr(interaction, 'k_major', None), uid, pid, nid, 0.0, 1e-10, code,
+                                               exact, hp)
+        if self.phase == 'TARGET' and count == 2:
+            uid, pid, nid = self._triple_fields(interaction, 'TARGET')
+            if self.affine_embedding is None:
+                raise ValueError("DCDCSR.fused_train_step: the second TARGET visit needs the affine table set_phase('TARGET') builds")
+            trained = 'item' if unit == 'user' else 'user'
+            self._fused_cache(exact)
+            st = self._fused_state(f'target_{trained}_embedding', code, exact)
+            affine, B = self.affine_embedding, uid.numel()
+            old = self._fused['steps'].get('frozen')
+
+            def build_frozen():
+                U, I = (affine, st.table) if unit == 'user' else (st.table, affine)
+                return FusedFrozenSideBPRStep(U, I, unit, B if old is None else max(B, old.max_batch), state=st, gamma=1e-10, **hp)
+
+            step = self._fused_step('frozen', lambda s: s.max_batch >= B and s.hp == hp and (s.U if unit == 'user' else s.I) is affine,
+                                    build_frozen)
+            step.hp = hp
+            catch_up(st, [pid, nid] if trained == 'item' else [uid])
+            return step.step(uid, pid, nid)[0]
+        raise ValueError(f'DCDCSR.fused_train_step: no loss for visit {count} of phase {self.phase!r} (calculate_loss returns None there): '
+                         f'the phases are SOURCE, TARGET, BOTH, TARGET')
+
+    def _fused_phase_step(self):
+        if self.phase == 'BOTH':
+            return self._fused['steps']['map']
+        if self.phase == 'TARGET' and self.phase2count.get('TARGET', 0) == 2:
+            return self._fused['steps']['frozen']
+        return self._fused['steps'][('bpr', self.phase.lower())]
+
+    def fused_optimizer_state(self):
+        """The shared per-table state, plus the dense Adam state of the mapping MLP under ``'weights'``."""
+        out = super().fused_optimizer_state()
+        step = self.__dict__.get('_fused', {}).get('steps', {}).get('map')
+        if step is not None and step.w_opt is not None:
+            out['weights'] = step.w_opt.state_dict()
+        return out
+
+    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
+        """The shared per-table restore; the MLP's Adam state is handed to the map step when it is built."""
+        super().load_fused_optimizer_state(state, opt=opt, adam=adam)
+        if 'weights' in state:
+            self.__dict__['_pending_weight_state'] = state['weights']
+        self.__dict__.get('_fused', {}).get('steps', {}).pop('map', None)
 
     @torch.no_grad()
     def full_sort_predict(self, interaction):

@@ -174,11 +174,7 @@ class EMCDR(RowwiseTraining, CrossDomainRecommender):
         item = interaction[getattr(self, f'{domain.upper()}_ITEM_ID')].reshape(-1)
 
         def domain_step(key, cls, size, sized_by, **kw):
-            # this domain's ``cls`` object for ``size`` rows or positives, rebuilt when its ``sized_by`` attribute says it is too small
-            return self._fused_step(key, lambda s: getattr(s, sized_by) >= size, lambda: cls(
-                getattr(self, f'{domain}_user_embedding').weight.data, getattr(self, f'{domain}_item_embedding').weight.data, size,
-                reg_weight=self.reg_weight, user_state=state(f'{domain}_user_embedding'), item_state=state(f'{domain}_item_embedding'),
-                **kw, **hp))
+            return self._fused_domain_step(domain, key, cls, size, sized_by, code, exact, hp, reg_weight=self.reg_weight, **kw)
 
         if self.latent_factor_model == 'MF':
             label = interaction[getattr(self, f'{domain.upper()}_LABEL')].reshape(-1).float()
@@ -195,19 +191,9 @@ class EMCDR(RowwiseTraining, CrossDomainRecommender):
             catch_up((step.ustate, [user]), (step.istate, [item]))
             return step.step(user, item, label)[0]
         neg = interaction[getattr(self, f'{domain.upper()}_NEG_ITEM_ID')].reshape(-1)
-        # recbole's pairwise batches tile S positives k times with k-major negatives (crossdomain_sampler.py:148-152); the loader
-        # says so (Interaction.k_major).  Then the per-positive step serves k >= 2 (u, p gathered once per positive) and every
-        # batch small enough for its four-launch form (the reference default of 2,048 rows); k = 1 at large batches stays on the
-        # per-triple step, which is faster there.
-        k = getattr(interaction, 'k_major', None)
-        rows = user.numel()
-        if k is not None and rows % k == 0 and (k >= 2 or rows + rows // k <= 8192):
-            step = domain_step(('bprk', domain, k), KMajorBPRStep, rows // k, 'max_positives', k=k, gamma=self.bpr_gamma)
-            catch_up((step.ustate, [user[:rows // k]]), (step.istate, [item[:rows // k], neg]))
-            return step.step(user, item, neg)[0]
-        step = domain_step(('bpr', domain), FusedBPRStep, rows, 'max_batch', gamma=self.bpr_gamma)
-        catch_up((step.ustate, [user]), (step.istate, [item, neg]))
-        return step.step(user, item, neg)[0]
+        # per-triple or per-positive form by the batch layout (Interaction.k_major): RowwiseTraining._fused_bpr_domain_step
+        return self._fused_bpr_domain_step(domain, getattr(interaction, 'k_major', None), user, item, neg, self.reg_weight, self.bpr_gamma,
+                                           code, exact, hp)
 
     def fused_graph_key(self, interaction, adam='lazy'):
         """Hashable tag of the launches ``fused_train_step(interaction)`` would make, or None when they must not be captured in a

@@ -2,7 +2,7 @@
 ``fused_train_step``: the cache of per-table optimizer states and step objects, the checks of the (opt, adam) arguments, and the
 methods the trainer calls around the step (``fused_replayed``, ``fused_sync``, ``fused_optimizer_state``,
 ``load_fused_optimizer_state``).  Which step class a batch gets stays with the model."""
-from ..fused import RowwiseState, OPT_ADAM, OPT_SGD, rowwise_bound_lag
+from ..fused import FusedBPRStep, KMajorBPRStep, RowwiseState, OPT_ADAM, OPT_SGD, rowwise_bound_lag, rowwise_catch_up
 
 
 class RowwiseTraining:
@@ -44,6 +44,36 @@ class RowwiseTraining:
         if step is None or not fits(step):
             step = steps[key] = build()
         return step
+
+    def _fused_domain_step(self, domain, key, cls, size, sized_by, code, exact, hp, **kw):
+        """This domain's ``cls`` object on (``<domain>_user_embedding``, ``<domain>_item_embedding``) for ``size`` rows or positives,
+        rebuilt when its ``sized_by`` attribute says it is too small.  The tables' states are the model's shared ones."""
+        return self._fused_step(key, lambda s: getattr(s, sized_by) >= size, lambda: cls(
+            getattr(self, f'{domain}_user_embedding').weight.data, getattr(self, f'{domain}_item_embedding').weight.data, size,
+            user_state=self._fused_state(f'{domain}_user_embedding', code, exact),
+            item_state=self._fused_state(f'{domain}_item_embedding', code, exact), **kw, **hp))
+
+    def _fused_bpr_domain_step(self, domain, k_major, user, item, neg, reg_weight, gamma, code, exact, hp):
+        """One BPR step on a domain's two tables, in the form the batch layout calls for (EMCDR's BPR branch, DCDCSR's first SOURCE /
+        TARGET visit).  recbole's pairwise batches tile S positives k times with k-major negatives (crossdomain_sampler.py:148-152); the
+        loader says so (``Interaction.k_major``).  Then the per-positive step serves k >= 2 (u, p gathered once per positive) and every
+        batch small enough for its four-launch form (the reference default of 2,048 rows); k = 1 at large batches stays on the
+        per-triple step, which is faster there.  In exact mode the catch-up runs in front on (user, [uid]) and
+        (item, [pid, nid]).  Returns the loss (device [1] view)."""
+        def catch_up(*tables):
+            if exact:
+                rowwise_catch_up(tables, lr=hp['lr'], betas=hp['betas'], eps=hp['eps'], weight_decay=hp['weight_decay'])
+
+        k, rows = k_major, user.numel()
+        if k is not None and rows % k == 0 and (k >= 2 or rows + rows // k <= 8192):
+            step = self._fused_domain_step(domain, ('bprk', domain, k), KMajorBPRStep, rows // k, 'max_positives', code, exact, hp,
+                                           reg_weight=reg_weight, k=k, gamma=gamma)
+            catch_up((step.ustate, [user[:rows // k]]), (step.istate, [item[:rows // k], neg]))
+            return step.step(user, item, neg)[0]
+        step = self._fused_domain_step(domain, ('bpr', domain), FusedBPRStep, rows, 'max_batch', code, exact, hp, reg_weight=reg_weight,
+                                       gamma=gamma)
+        catch_up((step.ustate, [user]), (step.istate, [item, neg]))
+        return step.step(user, item, neg)[0]
 
     def fused_replayed(self, n=1):
         """Host bookkeeping of ``n`` hipGraph replays of the current phase's ``fused_train_step`` (the update counts' host mirrors)."""
