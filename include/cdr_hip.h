@@ -505,6 +505,20 @@ int cdr_conet_fullsort_users(void* stream, const float* P, int64_t ldp, const fl
                              const float* W1u, int64_t ldw1, const float* b1, int D, int64_t U, int64_t N, int h1, int n_tail,
                              const int* tail_dims, const float* const* W, const float* const* b, const float* wo, const float* bo,
                              float* out, int64_t ldo);
+/* The same tower with the evaluation mask + top-k as the kernel's epilogue instead of the [U, N] store (recbole
+ * trainer.py Trainer._full_sort_batch_eval: scores[:, 0] = -inf, scores[history_index] = -inf, torch.topk; the scores are those of
+ * conet.py:222-242 / dtcdr.py:112-126 over every target item).  Contract of cdr_fullsort_topk_f32: out_vals [U, k] descending and bit-equal
+ * to the k largest unmasked values cdr_conet_fullsort writes, out_idx [U, k] their columns, (-inf, -1) where fewer than k unmasked columns
+ * are left, ties to the column met first; hist_* = per-user CSR of masked columns (ascending) or NULL, exclude_first_col masks column 0.
+ * 1 <= k <= 64, N < 2^31, tower range of cdr_conet_fullsort_supported (CDR_EINVAL with an error text outside either; nothing is launched
+ * for a refused call).  workspace: caller-owned, at least cdr_conet_fullsort_topk_workspace_bytes(U, N, k) -- the partial lists
+ * [item stripes <= 2,048][U][k] (values + columns) and their first merge level; a smaller one is refused.                                */
+int cdr_conet_fullsort_topk_workspace_bytes(int64_t U, int64_t N, int k, size_t* bytes);
+int cdr_conet_fullsort_topk(void* stream, const float* P, int64_t ldp, const float* Q, int64_t ldq, int64_t U, int64_t N, int h1,
+                            int n_tail, const int* tail_dims, const float* const* W, const float* const* b,
+                            const float* wo, const float* bo, int k,
+                            const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                            float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes);
 
 /* ---- SSCDR helpers (sscdr.py:120-187) -------------------------------------------------------------------------- */
 /* embedding_normalize: len = sum x^2, y = x / (len > 1 ? len : 1)  -- the squared-length quirk is kept */

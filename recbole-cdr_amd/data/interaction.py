@@ -48,5 +48,9 @@ class Interaction(dict):
     def repeat(self, times):
         return Interaction({k: v.repeat(times, *([1] * (v.dim() - 1))) for k, v in self.items()})
 
+    def repeat_interleave(self, repeats, dim=0):
+        """recbole ``Interaction.repeat_interleave``: every row ``repeats`` times in a row (row 0, row 0, ..., row 1, ...)."""
+        return Interaction({k: v.repeat_interleave(repeats, dim=dim) for k, v in self.items()})
+
     def index_select(self, idx):
         return Interaction({k: v[idx] for k, v in self.items()})

@@ -1024,6 +1024,63 @@ def conet_fullsort(P, Q, weights, biases, wo, bo, out=None):
     return out
 
 
+_tower_topk_ws = {}
+# Catalogue size from which the models' ``full_sort_topk`` takes the fused launch.  Measured (tools/mb_tower_topk.py, k = 10, U = 64 and
+# 1,024, both default towers): fused / unfused = 0.88-0.93 at 250,000 items and 0.89-0.91 at 1 M, but 1.06-1.15 at 81,920 (the smallest
+# catalogue whose thresholds are seeded from a sample) and 1.7-10 below that, where every list fills from -inf.  Below it the [U, N]
+# matrix is small and ``conet_fullsort`` + mask + ``torch.topk`` is the faster route.  A model's ``fullsort_topk_min_items`` overrides it.
+TOWER_TOPK_MIN_ITEMS = 250_000
+
+
+@torch.no_grad()
+def conet_fullsort_topk(P, Q, weights, biases, wo, bo, k, hist_indptr=None, hist_cols=None, exclude_first_col=True):
+    """(values [U,k] descending, columns [U,k] int64) of ``conet_fullsort(P, Q, ...)`` after the evaluation mask -- column 0 (PAD) and, per
+    user, the ascending columns ``hist_cols[hist_indptr[u]:hist_indptr[u+1]]`` -- without the [U, N] matrix: the tower kernel's second
+    epilogue (cdr_conet_fullsort_topk).  Values are bit-equal to the unfused scores; (-inf, -1) pads a row with fewer than k columns left."""
+    _dev_check(P, Q, wo, bo, hist_indptr, hist_cols, *weights, *biases)
+    U, N, h1 = Q.shape[0], P.shape[0], P.shape[1]
+    assert Q.shape[1] == h1 and P.stride(1) == 1 and Q.stride(1) == 1
+    T = len(weights)
+    ws = [w.contiguous() for w in weights]
+    bs = [b.contiguous() for b in biases]
+    wo_, bo_ = wo.reshape(-1).contiguous(), bo.reshape(-1).contiguous()
+    dev = P.device
+    need = ctypes.c_size_t(0)
+    B_._check(B_.load().cdr_conet_fullsort_topk_workspace_bytes(U, N, int(k), ctypes.byref(need)), 'cdr_conet_fullsort_topk_workspace_bytes')
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    wsp = _tower_topk_ws.get(key)
+    if wsp is None or wsp.numel() < need.value:
+        wsp = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+        _tower_topk_ws[key] = wsp
+    vals = torch.empty(U, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(U, k, device=dev, dtype=torch.int64)
+    dims = (ctypes.c_int * max(T, 1))(*[int(w.shape[0]) for w in ws])
+    B_._alive.extend(ws + bs + [P, Q])
+    B_.call('cdr_conet_fullsort_topk', B_.stream(), B_._c_ptr(P.data_ptr()), P.stride(0), B_._c_ptr(Q.data_ptr()), Q.stride(0), U, N, h1, T, dims,
+            (ctypes.c_void_p * max(T, 1))(*[w.data_ptr() for w in ws]), (ctypes.c_void_p * max(T, 1))(*[b.data_ptr() for b in bs]),
+            B_.f32(wo_), B_.f32(bo_), int(k), B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals), B_.i64(idx),
+            B_.raw(wsp), wsp.numel())
+    return vals, idx
+
+
+def masked_topk(scores, k, hist_indptr=None, hist_cols=None, exclude_first_col=True):
+    """The unfused route of the same contract, in torch: mask ``scores`` [U, N] in place (column 0; the per-user CSR of history columns),
+    ``torch.topk``; a row with fewer than k columns left is padded with (-inf, -1)."""
+    U, N = scores.shape
+    if exclude_first_col:
+        scores[:, 0] = -float('inf')
+    if hist_indptr is not None and hist_cols is not None and hist_cols.numel():
+        rows = torch.repeat_interleave(torch.arange(U, device=scores.device), hist_indptr[1:] - hist_indptr[:-1])
+        scores[rows, hist_cols] = -float('inf')
+    kk = min(int(k), N)
+    vals, idx = torch.topk(scores, kk, dim=-1)
+    if kk < k:
+        vals = torch.cat([vals, vals.new_full((U, k - kk), -float('inf'))], 1)
+        idx = torch.cat([idx, idx.new_full((U, k - kk), -1)], 1)
+    idx = torch.where(vals == -float('inf'), torch.full_like(idx, -1), idx)
+    return vals, idx
+
+
 class ConetFullsortFewUsers:
     """CoNet.full_sort_predict for a FEW users as one launch (cdr_conet_fullsort_users): everything that does not change between calls --
     P, the tower, the table and first-layer pointers -- is packed into ctypes arguments ONCE; a call allocates the [U, N] scores and fills in

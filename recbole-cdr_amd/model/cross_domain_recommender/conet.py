@@ -234,6 +234,39 @@ class CoNet(CrossDomainRecommender):
                                    interaction[self.TARGET_USER_ID], interaction[self.TARGET_ITEM_ID])
         return self._target_tower_tail(x, 0)                        # [B,1]
 
+    def _item_half(self, items, W1, caching):
+        """P = items x W1i^T [N, h1], kept for the length of a freeze_for_eval() bracket."""
+        P = self.__dict__.get('_eval_P') if caching else None
+        if P is None:
+            P = F_.gemm(items, W1[:, self.latent_dim:], trans_b=True)   # (the callers run under no_grad: no graph is kept with it)
+            if caching:
+                self.__dict__['_eval_P'] = P
+        return P
+
+    @torch.no_grad()
+    def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
+        """(values [U,k], item ids [U,k]) of ``full_sort_predict`` after the evaluation mask (PAD column, per-user history CSR) without the
+        [U, N] score matrix: P and Q exactly as ``full_sort_predict`` forms them, then the tower kernel with the mask + top-k as its epilogue
+        (F_.conet_fullsort_topk; values bit-equal to the unfused scores).  A tower outside that kernel's range, or ``fullsort_fused = False``,
+        and a catalogue below ``F_.TOWER_TOPK_MIN_ITEMS`` (where the unfused route measures faster; ``self.fullsort_topk_min_items`` overrides)
+        take ``full_sort_predict`` + mask + ``torch.topk``: the method always exists and always agrees with the unfused path."""
+        D = self.latent_dim
+        lin1, lo = self.target_crossunit_linear[0], self.target_outputunit[0]
+        W1 = lin1.weight
+        tail = list(self.target_crossunit_linear)[1:]
+        uid = interaction[self.TARGET_USER_ID]
+        if not (self.__dict__.get('fullsort_fused', True) and tail
+                and self.target_num_items >= self.__dict__.get('fullsort_topk_min_items', F_.TOWER_TOPK_MIN_ITEMS)
+                and F_.conet_fullsort_supported(W1.shape[0], [l.weight.shape[0] for l in tail])):
+            scores = self.full_sort_predict(interaction).view(uid.numel(), -1)
+            return F_.masked_topk(scores, k, hist_indptr, hist_cols)
+        self.sync_tables()
+        user_e = F_.gather_rows(self.target_user_embedding.weight, uid)
+        P = self._item_half(self.target_item_embedding.weight[:self.target_num_items], W1, self._eval_caching())
+        Q = F_.gemm(user_e, W1[:, :D], trans_b=True, bias=lin1.bias)
+        return F_.conet_fullsort_topk(P, Q, [l.weight for l in tail], [l.bias for l in tail], lo.weight, lo.bias, k,
+                                      hist_indptr=hist_indptr, hist_cols=hist_cols)
+
     @torch.no_grad()
     def full_sort_predict(self, interaction):
         """[U,N].  The first layer is separable, W1 [u ; i] = W1u u + W1i i: the item part P = items x W1i^T is computed
@@ -258,11 +291,7 @@ class CoNet(CrossDomainRecommender):
         W1 = lin1.weight                                              # [h1, 2D]
         # P depends on the item table and W1 only: inside a freeze_for_eval() bracket (recbole's evaluate calls full_sort_predict once per
         # user batch -- one user per call at the default eval_batch_size) it is formed once and kept until the bracket closes
-        P = self.__dict__.get('_eval_P') if caching else None
-        if P is None:
-            P = F_.gemm(items, W1[:, D:], trans_b=True)                # [N, h1]  (this method runs under no_grad: no graph is kept with it)
-            if caching:
-                self.__dict__['_eval_P'] = P
+        P = self._item_half(items, W1, caching)
         Q = F_.gemm(user_e, W1[:, :D], trans_b=True, bias=lin1.bias)    # [U, h1]
         tail = list(self.target_crossunit_linear)[1:]
         if (self.__dict__.get('fullsort_fused', True) and tail

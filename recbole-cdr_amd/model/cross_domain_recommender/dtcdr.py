@@ -170,6 +170,7 @@ class DTCDR(RowwiseTraining, CrossDomainRecommender):
         Refused before any state is created: a batch without the BOTH-phase fields, empty or unequal-length domain batches,
         ``config['dist_group']``, and widths outside ``FusedDTCDRStep.check_widths`` (use optimizer_mode=dense for those)."""
         from ...fused import FusedDTCDRStep, rowwise_catch_up
+        self.unfreeze_eval()                                           # the step writes the tables in place: no evaluation cache outlives it
         exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
         if self.__dict__.get('_dist_cfg') not in (None, False):
             raise NotImplementedError("DTCDR.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
@@ -239,3 +240,94 @@ class DTCDR(RowwiseTraining, CrossDomainRecommender):
     @torch.no_grad()
     def predict(self, interaction):
         return self.neumf_forward(interaction[self.TARGET_USER_ID], interaction[self.TARGET_ITEM_ID], 'target')
+
+    # ---- full-sort evaluation (the reference defines ``predict`` only; recbole's evaluation scores every pair through it) ------------
+    # The target tower's first layer is separable over the [B, 2D] operand of dtcdr.py:112-125: with M_u = max of the two user rows and
+    # M_i = max of the two item rows, W0 [M_u ; M_i] + b0 = (M_u W0[:, :D]^T + b0) + M_i W0[:, D:]^T =: Q[u] + P[i]; behind it ReLU layers and
+    # a sigmoid unit -- the algebra of CoNet's evaluation tower, so the same kernels score it (csrc/cdr_conet_fullsort.hip).  Dropout is the
+    # identity (eval mode, as in ``predict``).
+    # P [N, h1] is cached only between ``freeze_for_eval()`` and ``unfreeze_eval()`` (CrossDomainTrainer.evaluate brackets its loop with the
+    # pair: nothing trains in between); outside a bracket every call recomputes from the live parameters.
+    def freeze_for_eval(self):
+        self.__dict__.pop('_eval_P', None)
+        self.__dict__['_eval_frozen'] = True
+        return self
+
+    def unfreeze_eval(self):
+        self.__dict__.pop('_eval_frozen', None)
+        self.__dict__.pop('_eval_P', None)
+        return self
+
+    def train(self, mode=True):
+        if mode:
+            self.unfreeze_eval()
+        return super().train(mode)
+
+    def on_train_steps(self):
+        self.unfreeze_eval()
+
+    def load_state_dict(self, *args, **kwargs):
+        self.unfreeze_eval()
+        return super().load_state_dict(*args, **kwargs)
+
+    def __getstate__(self):
+        # pickle / copy.deepcopy / torch.save(model): the cache is table-sized and cheap to rebuild
+        st = dict(self.__dict__)
+        for k in ('_eval_P', '_eval_frozen'):
+            st.pop(k, None)
+        return st
+
+    def _fullsort_operands(self, uid):
+        """(P [N, h1], Q [U, h1], tail linears, predict layer) of the target tower over every target item."""
+        D = self.embedding_size
+        lins = [m for m in self.target_mlp_layers.mlp_layers if isinstance(m, nn.Linear)]
+        W0, b0 = lins[0].weight, lins[0].bias
+        caching = (not self.training) and bool(self.__dict__.get('_eval_frozen', False))
+        P = self.__dict__.get('_eval_P') if caching else None
+        if P is None:
+            N = self.target_num_items
+            M_i = torch.maximum(self.source_item_embedding.weight[:N], self.target_item_embedding.weight[:N])
+            P = F_.gemm(M_i, W0[:, D:], trans_b=True)
+            if caching:
+                self.__dict__['_eval_P'] = P
+        uid = uid.reshape(-1)
+        M_u = torch.maximum(F_.gather_rows(self.source_user_embedding.weight, uid), F_.gather_rows(self.target_user_embedding.weight, uid))
+        Q = F_.gemm(M_u, W0[:, :D], trans_b=True, bias=b0)
+        return P, Q, lins[1:], self.target_predict_layer
+
+    def _fullsort_kernel_ok(self, tail):
+        h1 = self.mlp_hidden_size[0]
+        return bool(self.__dict__.get('fullsort_fused', True)) and len(tail) >= 1 and \
+            F_.conet_fullsort_supported(h1, [l.weight.shape[0] for l in tail])
+
+    @torch.no_grad()
+    def full_sort_predict(self, interaction):
+        """[U, N]: ``predict`` for every evaluated user against every target item, in one launch for towers the full-sort kernel takes;
+        otherwise (a one-layer ``mlp_hidden_size`` has no tail layer; widths beyond the kernel's) one broadcast-add-ReLU pass and the
+        remaining contractions per user."""
+        P, Q, tail, head = self._fullsort_operands(interaction[self.TARGET_USER_ID])
+        if self._fullsort_kernel_ok(tail):
+            return F_.conet_fullsort(P, Q, [l.weight for l in tail], [l.bias for l in tail], head.weight, head.bias)
+        rows = []
+        for u in range(Q.shape[0]):
+            h = F_.bcast_add_act(P, Q[u], B_.ACT_RELU)
+            for lin in tail:
+                h = F_.linear(h, lin.weight, lin.bias, B_.ACT_RELU)
+            rows.append(F_.linear(h, head.weight, head.bias, B_.ACT_SIGMOID).view(1, -1))
+        return torch.cat(rows, dim=0)
+
+    @torch.no_grad()
+    def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
+        """(values [U,k], item ids [U,k]) of ``full_sort_predict`` after the evaluation mask (PAD column, per-user history CSR), without the
+        [U, N] matrix where the kernel takes the tower and the catalogue has at least ``F_.TOWER_TOPK_MIN_ITEMS`` items (below it the unfused
+        route measures faster; ``self.fullsort_topk_min_items`` overrides) -- values bit-equal to the unfused scores; mask + ``torch.topk``
+        of ``full_sort_predict`` otherwise."""
+        uid = interaction[self.TARGET_USER_ID]
+        lins = [m for m in self.target_mlp_layers.mlp_layers if isinstance(m, nn.Linear)]
+        if not self._fullsort_kernel_ok(lins[1:]) or \
+                self.target_num_items < self.__dict__.get('fullsort_topk_min_items', F_.TOWER_TOPK_MIN_ITEMS):
+            scores = self.full_sort_predict(interaction).view(uid.numel(), -1)
+            return F_.masked_topk(scores, k, hist_indptr, hist_cols)
+        P, Q, tail, head = self._fullsort_operands(uid)
+        return F_.conet_fullsort_topk(P, Q, [l.weight for l in tail], [l.bias for l in tail], head.weight, head.bias, k,
+                                      hist_indptr=hist_indptr, hist_cols=hist_cols)

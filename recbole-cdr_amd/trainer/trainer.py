@@ -504,6 +504,18 @@ class Trainer:
             if restore is not None:
                 eval_data.rebatch(restore)
 
+    def _predict_all_pairs(self, interaction, n_user):
+        """[U, N] scores of a model that defines ``predict`` only (DeepAPF, NATR, as in the reference), the way recbole's
+        ``Trainer._full_sort_batch_eval`` / ``_spilt_predict`` get them: every user row repeated ``target_num_items`` times, item ids
+        0..N-1 attached, ``predict`` in chunks of at most ``eval_batch_size`` pairs (recbole's default 4,096).  Plumbing in torch: correct
+        for any model, one ``predict`` per chunk -- slow by construction."""
+        N = int(self.model.target_num_items)
+        chunk = int(self.config['eval_batch_size']) if 'eval_batch_size' in self.config else 4096
+        pairs = interaction.repeat_interleave(N)
+        pairs.update({self.model.TARGET_ITEM_ID: torch.arange(N, device=self.device).repeat(n_user)})
+        out = [self.model.predict(pairs[s:s + chunk]).reshape(-1) for s in range(0, n_user * N, max(chunk, 1))]
+        return torch.cat(out).view(n_user, N).float()
+
     def _evaluate_batches(self, eval_data, fused, kmax):
         hits, pos_len = [], []
         for interaction, history_index, positive_u, positive_i in eval_data:
@@ -513,7 +525,10 @@ class Trainer:
                 h, npos = self._topk_hits(interaction, n_user, history_index, positive_u, positive_i, kmax)
                 hits.append(h); pos_len.append(npos)
                 continue
-            scores = self.model.full_sort_predict(interaction).view(n_user, -1)
+            try:
+                scores = self.model.full_sort_predict(interaction).view(n_user, -1)
+            except NotImplementedError:
+                scores = self._predict_all_pairs(interaction, n_user)
             scores[:, 0] = -np.inf
             if history_index is not None:
                 scores[history_index] = -np.inf
