@@ -520,6 +520,32 @@ int cdr_conet_fullsort_topk(void* stream, const float* P, int64_t ldp, const flo
                             const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
                             float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes);
 
+/* ---- DeepAPF full-sort scoring, all evaluated users x all target items in one launch (deepapf.py:111-161: target_forward / predict
+ * over every pair, which the reference reaches through repeat()ed user rows and chunked predict calls) ---------------------------
+ *      out[u, i] = sigmoid(wp . ((al_s s + al_o o) (.) t)),  (al_s, al_o) = softmax(a_s, a_o),  a_c = w2 . relu(W1 (c (.) t) + b1),
+ *      a_s = -1e31 where key > n_overlap (strictly)
+ * key_is_item = 0 (overlap_users): s / o = share_tab / only_tab rows of uid[u] (the share and the target user table), t = row i of
+ * other_tab (the target item table), key = uid[u].  key_is_item = 1 (overlap_items): s / o = rows i of share_tab / only_tab (the share
+ * and the target item table), t = other_tab row of uid[u] (the target user table), key = i.  Items are rows [0, N) of the item-side
+ * tables.  W1 [D, D] row-major, b1 / w2 / wp [D].  Tables and W1 16-byte aligned, row strides multiples of 4 floats.
+ * Range (deepapf.py:111-161 at any embedding_size the row-wise step takes): D in 4..128, a multiple of 4
+ * (cdr_deepapf_fullsort_supported returns 1 / 0); 1 <= U, 1 <= N < 2^31.  Outside it CDR_EINVAL with an error text, nothing launched. */
+int cdr_deepapf_fullsort_supported(int D);
+int cdr_deepapf_fullsort(void* stream, int key_is_item, const float* share_tab, int64_t ld_share, const float* only_tab, int64_t ld_only,
+                         const float* other_tab, int64_t ld_other, const int64_t* uid, int64_t U, int64_t N, int D, int64_t n_overlap,
+                         const float* W1, const float* b1, const float* w2, const float* wp, float* out, int64_t ldo);
+/* The same scores (deepapf.py:111-161) with the evaluation mask + top-k as the kernel's epilogue; contract of cdr_conet_fullsort_topk:
+ * out_vals [U, k] descending and bit-equal to the k largest unmasked values cdr_deepapf_fullsort writes, out_idx [U, k] their columns,
+ * (-inf, -1) padding, hist_* = per-user CSR of masked columns (ascending) or NULL, exclude_first_col masks column 0.  1 <= k <= 64.
+ * workspace: caller-owned, at least cdr_deepapf_fullsort_topk_workspace_bytes(U, N, k) (deepapf.py:111-161 has no counterpart: the
+ * partial lists [item stripes <= 2,048][U][k] and their first merge level; never U x N); a smaller one is refused before any launch. */
+int cdr_deepapf_fullsort_topk_workspace_bytes(int64_t U, int64_t N, int k, size_t* bytes);
+int cdr_deepapf_fullsort_topk(void* stream, int key_is_item, const float* share_tab, int64_t ld_share, const float* only_tab,
+                              int64_t ld_only, const float* other_tab, int64_t ld_other, const int64_t* uid, int64_t U, int64_t N, int D,
+                              int64_t n_overlap, const float* W1, const float* b1, const float* w2, const float* wp, int k,
+                              const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                              float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes);
+
 /* ---- SSCDR helpers (sscdr.py:120-187) -------------------------------------------------------------------------- */
 /* embedding_normalize: len = sum x^2, y = x / (len > 1 ? len : 1)  -- the squared-length quirk is kept */
 int cdr_sqnorm_normalize_fwd(void* stream, const float* x, int64_t rows, int D, float* y, float* len_out);

@@ -1063,6 +1063,78 @@ def conet_fullsort_topk(P, Q, weights, biases, wo, bo, k, hist_indptr=None, hist
     return vals, idx
 
 
+def deepapf_fullsort_supported(D):
+    """True when csrc/cdr_deepapf_fullsort.hip takes this embedding width (4..128, a multiple of 4)."""
+    return B_.load().cdr_deepapf_fullsort_supported(int(D)) == 1
+
+
+def _deepapf_fullsort_args(key_is_item, share, only, other, uid, N, n_overlap, W1, b1, w2, wp):
+    _dev_check(share, only, other, uid, W1, b1, w2, wp)
+    D = share.shape[1]
+    assert only.shape[1] == D and other.shape[1] == D and tuple(W1.shape) == (D, D)
+    item_side = (share, only) if key_is_item else (other,)
+    assert all(t.shape[0] >= N for t in item_side), 'the item-side tables need at least N rows'
+    share, only, other = share.contiguous(), only.contiguous(), other.contiguous()
+    uid = _ids(uid)
+    vec = [t.reshape(-1).contiguous() for t in (b1, w2, wp)]
+    assert all(v.numel() == D for v in vec)
+    return uid.numel(), D, (B_.stream(), 1 if key_is_item else 0, B_.f32(share), share.stride(0), B_.f32(only), only.stride(0), B_.f32(other),
+                            other.stride(0), B_.i64(uid), uid.numel(), int(N), D, int(n_overlap), B_.f32(W1.contiguous()), B_.f32(vec[0]),
+                            B_.f32(vec[1]), B_.f32(vec[2]))
+
+
+@torch.no_grad()
+def deepapf_fullsort(key_is_item, share, only, other, uid, N, n_overlap, W1, b1, w2, wp, out=None):
+    """[U, N] scores of DeepAPF's target_forward (deepapf.py:111-161) for the users ``uid`` against items [0, N) in one launch
+    (csrc/cdr_deepapf_fullsort.hip).  ``key_is_item`` False (overlap_users): ``share`` / ``only`` = the share and the target USER table,
+    ``other`` = the target item table, the key is the user id.  True (overlap_items): ``share`` / ``only`` = the share and the target ITEM
+    table, ``other`` = the target user table, the key is the item id.  The share score is masked where key > ``n_overlap`` (strictly).
+    ``W1`` [D, D], ``b1``, ``w2``: the mode's attention MLP; ``wp``: the predict layer."""
+    U, D, args = _deepapf_fullsort_args(key_is_item, share, only, other, uid, N, n_overlap, W1, b1, w2, wp)
+    if out is None:
+        out = torch.empty(U, int(N), device=share.device, dtype=torch.float32)
+    B_.call('cdr_deepapf_fullsort', *args, B_.f32(out), out.stride(0))
+    return out
+
+
+_deepapf_topk_ws = {}
+# Catalogue size from which DeepAPF.full_sort_topk takes the fused launch.  Measured (tools/mb_deepapf_fullsort.py, k = 10, U = 64 and 1,024,
+# D = 64 and 128, both modes; DESIGN.md 4.4.2): fused / unfused = 1.19-1.55 at 81,920 items, 1.03-1.40 at 250,000 and 1.00-1.37 at 1 M -- the
+# scoring is compute bound (0.7 of the MFMA peak), so the [U, N] round trip the fusion saves is worth less than the sample call and the
+# merges it adds: at no measured size is the fused launch faster.  The default therefore lies above every catalogue the kernel takes
+# (N < 2^31) and ``deepapf_fullsort`` + mask + ``torch.topk`` is the route; the fused launch is for callers that cannot hold [U, N]
+# (4 GB at 1,024 users x 1 M items): a model's ``fullsort_topk_min_items`` overrides it.
+DEEPAPF_TOPK_MIN_ITEMS = 1 << 31
+
+
+@torch.no_grad()
+def deepapf_fullsort_topk(key_is_item, share, only, other, uid, N, n_overlap, W1, b1, w2, wp, k, hist_indptr=None, hist_cols=None,
+                          exclude_first_col=True):
+    """(values [U,k] descending, item ids [U,k] int64) of ``deepapf_fullsort(...)`` after the evaluation mask -- column 0 (PAD) and, per
+    user, the ascending columns ``hist_cols[hist_indptr[u]:hist_indptr[u+1]]`` -- without the [U, N] matrix: the scoring kernel's second
+    epilogue (cdr_deepapf_fullsort_topk).  Values are bit-equal to the unfused scores; (-inf, -1) pads a row with fewer than k columns left."""
+    _dev_check(hist_indptr, hist_cols)
+    U, D, args = _deepapf_fullsort_args(key_is_item, share, only, other, uid, N, n_overlap, W1, b1, w2, wp)
+    dev = share.device
+    need = ctypes.c_size_t(0)
+    try:
+        B_._check(B_.load().cdr_deepapf_fullsort_topk_workspace_bytes(U, int(N), int(k), ctypes.byref(need)),
+                  'cdr_deepapf_fullsort_topk_workspace_bytes')
+    except RuntimeError:
+        B_._alive.clear()
+        raise
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    wsp = _deepapf_topk_ws.get(key)
+    if wsp is None or wsp.numel() < need.value:
+        wsp = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+        _deepapf_topk_ws[key] = wsp
+    vals = torch.empty(U, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(U, k, device=dev, dtype=torch.int64)
+    B_.call('cdr_deepapf_fullsort_topk', *args, int(k), B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals),
+            B_.i64(idx), B_.raw(wsp), wsp.numel())
+    return vals, idx
+
+
 def masked_topk(scores, k, hist_indptr=None, hist_cols=None, exclude_first_col=True):
     """The unfused route of the same contract, in torch: mask ``scores`` [U, N] in place (column 0; the per-user CSR of history columns),
     ``torch.topk``; a row with fewer than k columns left is padded with (-inf, -1)."""

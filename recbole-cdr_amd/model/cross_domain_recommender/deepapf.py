@@ -10,7 +10,12 @@ share row; ``self.user_mlp = self.seq = ...; self.item_mlp = self.seq = ...`` --
 ``fused_train_step`` (``optimizer_mode='rowwise'``): the BOTH-phase step without table-sized gradients -- fused.FusedDeepAPFStep, the five
 live tables (the overlapped side's share table, fed by both batches, and per domain the only table and the other side's table) updated
 row-wise from csrc/cdr_deepapf.hip's compact gradient rows, the attention MLP of the mode and the predict layer by the exact dense Adam;
-``adam='exact'`` puts the catch-up of the reference's dense Adam in front of it (fused.rowwise_catch_up over the five tables)."""
+``adam='exact'`` puts the catch-up of the reference's dense Adam in front of it (fused.rowwise_catch_up over the five tables).
+
+Evaluation.  The reference defines ``predict`` only (deepapf.py:157-161), so ``full_sort_predict`` raises NotImplementedError and there is
+no ``full_sort_topk``: the trainer scores every (user, item) pair through chunked ``predict``.  ``config['native_full_sort']`` (opt-in)
+adds both on csrc/cdr_deepapf_fullsort.hip -- every evaluated user against every target item in one launch, with the evaluation mask +
+top-k as the kernel's second epilogue; ``predict`` always scores the target domain, so does the full sort in every phase."""
 import torch
 import torch.nn as nn
 
@@ -45,6 +50,7 @@ class DeepAPF(RowwiseTraining, CrossDomainRecommender):
         self.predict_layer = nn.Linear(self.embedding_size, 1, bias=False)
         self.apply(xavier_normal_initialization)
         self.phase = 'BOTH'
+        self.__dict__['_native_full_sort'] = bool(config['native_full_sort']) if 'native_full_sort' in config else False
         self.__dict__['_dist_cfg'] = config['dist_group'] if 'dist_group' in config else None
 
     def set_phase(self, phase):
@@ -80,6 +86,61 @@ class DeepAPF(RowwiseTraining, CrossDomainRecommender):
 
     def graph_key(self):
         return ('DeepAPF',)
+
+    # ---- full-sort evaluation, opt-in (config['native_full_sort']) ------------------------------------------------
+    # Properties: with the flag off ``full_sort_topk`` raises AttributeError (nn.Module.__getattr__ then reports the attribute missing, so
+    # ``hasattr`` is False) and ``full_sort_predict`` is the base class's, which raises NotImplementedError -- the reference's contract, on
+    # which the trainer's chunked-``predict`` route rests.  The flag is a plain bool in ``__dict__``: pickle and deepcopy carry it.
+    @property
+    def full_sort_predict(self):
+        if self.__dict__.get('_native_full_sort', False):
+            return self._native_full_sort_predict
+        return super().full_sort_predict
+
+    @property
+    def full_sort_topk(self):
+        if self.__dict__.get('_native_full_sort', False):
+            return self._native_full_sort_topk
+        raise AttributeError("'DeepAPF' object has no attribute 'full_sort_topk' (config['native_full_sort'] is off)")
+
+    def _fullsort_operands(self):
+        """(key_is_item, share, only, other, n_overlap, W1, b1, w2, wp) of ``target_forward`` in the dataset's mode."""
+        W1, b1, w2, wp = self._attention_params()
+        if self.mode == 'overlap_users':
+            return (False, self.share_user_embedding.weight, self.target_user_embedding.weight, self.target_item_embedding.weight,
+                    int(self.overlapped_num_users), W1, b1, w2, wp)
+        return (True, self.share_item_embedding.weight, self.target_item_embedding.weight, self.target_user_embedding.weight,
+                int(self.overlapped_num_items), W1, b1, w2, wp)
+
+    @torch.no_grad()
+    def _native_full_sort_predict(self, interaction):
+        """[U * N]: ``predict`` for every evaluated user against every target item -- one launch for the widths the kernel takes
+        (4..128, a multiple of 4); chunked ``predict`` over all pairs otherwise."""
+        uid = interaction[self.TARGET_USER_ID].reshape(-1)
+        N = int(self.target_num_items)
+        if F_.deepapf_fullsort_supported(self.embedding_size):
+            ki, share, only, other, n_over, W1, b1, w2, wp = self._fullsort_operands()
+            return F_.deepapf_fullsort(ki, share, only, other, uid, N, n_over, W1, b1, w2, wp).view(-1)
+        items = torch.arange(N, device=uid.device)
+        per = max(1, (1 << 20) // N)                                       # users per ``predict`` call
+        rows = [self.target_forward(uid[s:s + per].repeat_interleave(N), items.repeat(min(per, uid.numel() - s))).reshape(-1)
+                for s in range(0, uid.numel(), per)]
+        return torch.cat(rows).float()
+
+    @torch.no_grad()
+    def _native_full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
+        """(values [U,k], item ids [U,k]) of ``full_sort_predict`` after the evaluation mask (PAD column, per-user history CSR): the fused
+        launch from ``F_.DEEPAPF_TOPK_MIN_ITEMS`` target items on (``self.fullsort_topk_min_items`` overrides) -- values bit-equal to the
+        unfused scores; mask + ``torch.topk`` of ``full_sort_predict`` below it and for widths outside the kernel's range."""
+        uid = interaction[self.TARGET_USER_ID].reshape(-1)
+        N = int(self.target_num_items)
+        if not F_.deepapf_fullsort_supported(self.embedding_size) or \
+                N < self.__dict__.get('fullsort_topk_min_items', F_.DEEPAPF_TOPK_MIN_ITEMS):
+            scores = self._native_full_sort_predict(interaction).view(uid.numel(), -1)
+            return F_.masked_topk(scores, k, hist_indptr, hist_cols)
+        ki, share, only, other, n_over, W1, b1, w2, wp = self._fullsort_operands()
+        return F_.deepapf_fullsort_topk(ki, share, only, other, uid, N, n_over, W1, b1, w2, wp, k, hist_indptr=hist_indptr,
+                                        hist_cols=hist_cols)
 
     def calculate_loss(self, interaction):
         p_source = self.source_forward(interaction[self.SOURCE_USER_ID], interaction[self.SOURCE_ITEM_ID])
