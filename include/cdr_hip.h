@@ -546,6 +546,37 @@ int cdr_deepapf_fullsort_topk(void* stream, int key_is_item, const float* share_
                               const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
                               float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes);
 
+/* ---- NATR full-sort scoring of phase 2, all evaluated users x all target items in one launch (natr.py:112-156: phase2_forward;
+ * natr.py:178-191: predict, which the reference reaches through repeat()ed user rows and chunked calls) -------------------------
+ * With a = su row of the key (functional.natr_history_summary: history gather, transfer layer, unit attention, weighted sum -- everything
+ * of natr.py:112-156 that depends on the key alone), p = the key's row of key_tab, q = the other side's row of other_tab and
+ * w = domain_attention_layer.weight [Dt]:
+ *      g = (w/2 (.) (a - p)) . q + (w/2 (.) (|a| - |p|)) . |q|        out[u, i] = sigmoid(p . q + sigmoid(g) ((a - p) . q))
+ * -- natr.py:139-156 rewritten as three dot products (beta = e^b_s / (e^b_s + e^b_p) = sigmoid(b_s - b_p) = sigmoid(g); the gate's bias
+ * cancels).  The kernel evaluates sigmoid(g): the same number wherever the reference's form is finite, and finite where the reference's
+ * is NaN (a gate logit beyond ~88).
+ * key_is_item = 0 (overlap_items): the key is the user -- su [U, Dt] by position u, p = key_tab row uid[u] (the target user table),
+ * q = row i of other_tab (the target item table).  key_is_item = 1 (overlap_users): the key is the item -- su [N, Dt] by item id,
+ * p = row i of key_tab (the target item table), q = other_tab row uid[u] (the target user table).  Items are rows [0, N).  su and the
+ * tables 16-byte aligned, row strides multiples of 4 floats.
+ * Range (natr.py:112-156): Dt in 4..128, a multiple of 4 (cdr_natr_fullsort_supported returns 1 / 0); 1 <= U, 1 <= N < 2^31.  Outside it
+ * CDR_EINVAL with an error text, nothing launched. */
+int cdr_natr_fullsort_supported(int Dt);
+int cdr_natr_fullsort(void* stream, int key_is_item, const float* su, int64_t ld_su, const float* key_tab, int64_t ld_key,
+                      const float* other_tab, int64_t ld_other, const int64_t* uid, int64_t U, int64_t N, int Dt, const float* w,
+                      float* out, int64_t ldo);
+/* The same scores (natr.py:112-156 / :178-191) with the evaluation mask + top-k as the kernel's epilogue; contract of
+ * cdr_deepapf_fullsort_topk: out_vals [U, k] descending and bit-equal to the k largest unmasked values cdr_natr_fullsort writes,
+ * out_idx [U, k] their columns, (-inf, -1) padding, hist_* = per-user CSR of masked columns (ascending) or NULL, exclude_first_col masks
+ * column 0.  1 <= k <= 64.  workspace: caller-owned, at least cdr_natr_fullsort_topk_workspace_bytes(U, N, k) (natr.py:178-191 has no
+ * counterpart: the partial lists [item stripes <= 2,048][U][k] and their first merge level; never U x N); a smaller one is refused
+ * before any launch. */
+int cdr_natr_fullsort_topk_workspace_bytes(int64_t U, int64_t N, int k, size_t* bytes);
+int cdr_natr_fullsort_topk(void* stream, int key_is_item, const float* su, int64_t ld_su, const float* key_tab, int64_t ld_key,
+                           const float* other_tab, int64_t ld_other, const int64_t* uid, int64_t U, int64_t N, int Dt, const float* w, int k,
+                           const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                           float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes);
+
 /* ---- SSCDR helpers (sscdr.py:120-187) -------------------------------------------------------------------------- */
 /* embedding_normalize: len = sum x^2, y = x / (len > 1 ? len : 1)  -- the squared-length quirk is kept */
 int cdr_sqnorm_normalize_fwd(void* stream, const float* x, int64_t rows, int D, float* y, float* len_out);

@@ -324,6 +324,11 @@ _SIGNATURES = {
     'cdr_deepapf_fullsort_topk_workspace_bytes': [_c_i64, _c_i64, _c_int, _c_ptr],
     'cdr_deepapf_fullsort_topk': [_c_ptr, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int, _c_i64,
                                   _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
+    'cdr_natr_fullsort_supported': [_c_int],
+    'cdr_natr_fullsort': [_c_ptr, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_i64],
+    'cdr_natr_fullsort_topk_workspace_bytes': [_c_i64, _c_i64, _c_int, _c_ptr],
+    'cdr_natr_fullsort_topk': [_c_ptr, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr,
+                               _c_int, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
     'cdr_overlap_remap': [ctypes.c_char_p, _c_ptr, _c_ptr, _c_i64, ctypes.c_char_p, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr],
     'cdr_revoke_map': [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr],
     'cdr_adam_dense': [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _c_i64],

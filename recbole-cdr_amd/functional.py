@@ -1135,6 +1135,112 @@ def deepapf_fullsort_topk(key_is_item, share, only, other, uid, N, n_overlap, W1
     return vals, idx
 
 
+NATR_SUMMARY_BYTES = 64 << 20        # budget of one [chunk, L, max(Ds, Dt)] intermediate of natr_history_summary
+
+
+@torch.no_grad()
+def natr_history_summary(src, hist, mask_mat, key_tab, keys, Wt, bt, wu, bu, wd, bd, chunk_rows=None):
+    """su [K, Dt] of NATR's phase 2 for the keys ``keys`` (natr.py:112-136 / :139-148): the source rows of hist[key] through the transfer
+    layer, unit-level attention against the key's own target row, masked softmax, weighted sum -- everything of ``phase2_forward`` that
+    depends on the key alone.  Composed of ``gather_rows``, the transfer layer on the general fp32-MFMA contraction (``gemm``: what
+    ``linear`` runs on above its small-batch threshold) and cdr_natr_att_fwd (whose ``su`` output does not depend on the ``qi`` operand:
+    the key rows stand in for it, the gate and the score it also writes are dropped).  Runs in key chunks of
+    ``chunk_rows`` (default: as many as keep one [chunk, L, max(Ds, Dt)] intermediate under NATR_SUMMARY_BYTES); every row is computed
+    from its own operands alone, so the result is bit-equal for every chunking."""
+    _dev_check(src, hist, mask_mat, key_tab, keys, Wt, bt, wu, bu, wd, bd)
+    keys = _ids(keys)
+    K, L, Dt = keys.numel(), hist.shape[1], Wt.shape[0]
+    per = int(chunk_rows) if chunk_rows else max(1, NATR_SUMMARY_BYTES // (4 * L * max(Wt.shape[1], Dt)))
+    wu_, wd_ = wu.reshape(-1).contiguous(), wd.reshape(-1).contiguous()
+    Wt_, bt_ = Wt.contiguous(), bt.contiguous()
+    dev = src.device
+    su = torch.empty(K, Dt, device=dev, dtype=torch.float32)
+    n0 = min(per, K)
+    att = torch.empty(n0, L, device=dev, dtype=torch.float32)
+    beta, p = torch.empty(n0, device=dev, dtype=torch.float32), torch.empty(n0, device=dev, dtype=torch.float32)
+    for s in range(0, K, per):
+        ids = keys[s:s + per]
+        n = ids.numel()
+        # (always the general contraction: ``linear`` picks its kernel by the row count, and two kernels need not round alike)
+        he = gemm(gather_rows(src, hist[ids]).view(n * L, -1), Wt_, trans_b=True, bias=bt_)  # [n * L, Dt]
+        pu = gather_rows(key_tab, ids).contiguous()
+        mask = mask_mat[ids].contiguous()
+        B_.call('cdr_natr_att_fwd', B_.stream(), B_.f32(he), B_.f32(pu), B_.f32(pu), B_.f32(mask), B_.f32(wu_), B_.f32(bu), B_.f32(wd_),
+                B_.f32(bd), n, L, Dt, B_.f32(att), B_.f32(su[s:s + n]), B_.f32(beta), B_.f32(p))
+    return su
+
+
+def natr_fullsort_supported(Dt):
+    """True when csrc/cdr_natr_fullsort.hip takes this target embedding width (4..128, a multiple of 4)."""
+    return B_.load().cdr_natr_fullsort_supported(int(Dt)) == 1
+
+
+def _natr_fullsort_args(key_is_item, su, key_tab, other_tab, uid, N, w):
+    _dev_check(su, key_tab, other_tab, uid, w)
+    Dt = su.shape[1]
+    assert key_tab.shape[1] == Dt and other_tab.shape[1] == Dt
+    uid = _ids(uid)
+    item_side = (su, key_tab) if key_is_item else (other_tab,)
+    assert all(t.shape[0] >= N for t in item_side), 'the item-side operands need at least N rows'
+    assert key_is_item or su.shape[0] == uid.numel(), 'overlap_items: one su row per evaluated user'
+    su, key_tab, other_tab = su.contiguous(), key_tab.contiguous(), other_tab.contiguous()
+    w_ = w.reshape(-1).contiguous()
+    assert w_.numel() == Dt
+    return uid.numel(), (B_.stream(), 1 if key_is_item else 0, B_.f32(su), su.stride(0), B_.f32(key_tab), key_tab.stride(0), B_.f32(other_tab),
+                         other_tab.stride(0), B_.i64(uid), uid.numel(), int(N), Dt, B_.f32(w_))
+
+
+@torch.no_grad()
+def natr_fullsort(key_is_item, su, key_tab, other_tab, uid, N, w, out=None):
+    """[U, N] scores of NATR's phase2_forward (natr.py:112-156; predict :178-191) for the users ``uid`` against items [0, N) in one launch
+    (csrc/cdr_natr_fullsort.hip).  ``su``: the key side's ``natr_history_summary``.  ``key_is_item`` False (overlap_items): the key is the
+    user -- ``su`` [U, Dt] by position, ``key_tab`` = the target USER table, ``other_tab`` = the target item table.  True (overlap_users):
+    the key is the item -- ``su`` [>= N, Dt] by item id, ``key_tab`` = the target ITEM table, ``other_tab`` = the target user table.
+    ``w``: domain_attention_layer.weight (its bias cancels out of the gate)."""
+    U, args = _natr_fullsort_args(key_is_item, su, key_tab, other_tab, uid, N, w)
+    if out is None:
+        out = torch.empty(U, int(N), device=su.device, dtype=torch.float32)
+    B_.call('cdr_natr_fullsort', *args, B_.f32(out), out.stride(0))
+    return out
+
+
+_natr_topk_ws = {}
+# Catalogue size from which NATR.full_sort_topk takes the fused launch: the smallest measured N from which the fused launch beats
+# scores + mask + torch.topk at every measured U by more than the run-to-run spread (tools/mb_natr_fullsort.py topk, k = 10, U = 64 and
+# 1,024, Dt = 64, both modes; table in DESIGN.md 4.4.3).  fused / unfused = 1.11-1.13 at U = 64 and 0.82-0.83 at U = 1,024 for 100,000
+# items, 0.70-0.74 at 1 M and 0.55-0.66 at 10 M, every arm's spread (max - min of five runs) under 5 % at 1 M and beyond: the scoring is cheap enough here
+# (8 Dt FLOP per pair) that writing [U, N] and torch.topk's passes over it cost more than the scoring.  A model's
+# ``fullsort_topk_min_items`` overrides it.
+NATR_TOPK_MIN_ITEMS = 1_000_000
+
+
+@torch.no_grad()
+def natr_fullsort_topk(key_is_item, su, key_tab, other_tab, uid, N, w, k, hist_indptr=None, hist_cols=None, exclude_first_col=True):
+    """(values [U,k] descending, item ids [U,k] int64) of ``natr_fullsort(...)`` after the evaluation mask -- column 0 (PAD) and, per
+    user, the ascending columns ``hist_cols[hist_indptr[u]:hist_indptr[u+1]]`` -- without the [U, N] matrix: the scoring kernel's second
+    epilogue (cdr_natr_fullsort_topk).  Values are bit-equal to the unfused scores; (-inf, -1) pads a row with fewer than k columns left."""
+    _dev_check(hist_indptr, hist_cols)
+    U, args = _natr_fullsort_args(key_is_item, su, key_tab, other_tab, uid, N, w)
+    dev = su.device
+    need = ctypes.c_size_t(0)
+    try:
+        B_._check(B_.load().cdr_natr_fullsort_topk_workspace_bytes(U, int(N), int(k), ctypes.byref(need)),
+                  'cdr_natr_fullsort_topk_workspace_bytes')
+    except RuntimeError:
+        B_._alive.clear()
+        raise
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    wsp = _natr_topk_ws.get(key)
+    if wsp is None or wsp.numel() < need.value:
+        wsp = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+        _natr_topk_ws[key] = wsp
+    vals = torch.empty(U, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(U, k, device=dev, dtype=torch.int64)
+    B_.call('cdr_natr_fullsort_topk', *args, int(k), B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals),
+            B_.i64(idx), B_.raw(wsp), wsp.numel())
+    return vals, idx
+
+
 def masked_topk(scores, k, hist_indptr=None, hist_cols=None, exclude_first_col=True):
     """The unfused route of the same contract, in torch: mask ``scores`` [U, N] in place (column 0; the per-user CSR of history columns),
     ``torch.topk``; a row with fewer than k columns left is padded with (-inf, -1)."""
