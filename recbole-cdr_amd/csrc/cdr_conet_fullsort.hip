@@ -27,7 +27,7 @@
 #include "cdr_common.h"
 #include "cdr_mfma.h"
 #include "cdr_topk.h"
-#include <type_traits>
+#include "cdr_fullsort_tile.h"
 
 namespace {
 
@@ -54,24 +54,10 @@ struct fs_args {
 struct fs_args_topk : fs_args { topk_out tk; };
 template <bool TOPK> using fs_kargs = std::conditional_t<TOPK, fs_args_topk, fs_args>;
 
-constexpr int kFsQueue = 128;                    // TOPK: candidates a wave parks before their mask test (a tile adds at most 32 per user)
-// LDS a TOPK workgroup may use: 160 KB per CU, two workgroups resident (the two-waves-per-SIMD bound) with room to spare
-constexpr size_t kFsTopkLds = (size_t)64 * 1024;
-constexpr int64_t kFsTopkGrid = 2 * CDR_NUM_CU;  // TOPK workgroups per launch: what is resident at once, so that no partial round trails
-// TOPK: columns of the sample that seeds the thresholds (catalogues of >= 8 x this): the real call then inserts ~k N / sample entries per user
-constexpr int64_t fs_seed_cols(int k) { return (int64_t)1024 * (k < 8 ? 8 : k); }
-constexpr int64_t kFsSeedGx = 8;                 // ... and the workgroups along x of the sample call: 32 stripes
-// dynamic LDS floats of a TOPK workgroup: per wave, the k-th values [upb] | list values [upb][k] | list columns [upb][k] | queue [3][kFsQueue]
-__host__ __device__ constexpr size_t fs_topk_wave_words(int upb, int k) { return (size_t)upb * (1 + 2 * k) + 3 * kFsQueue; }
-
-#define FS_MFMA(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0)
-
-__device__ __forceinline__ f32x16 fs_zero() {
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.f;
-    return z;
-}
+// TOPK launch geometry (cdr_topk.h).  The lists share the 64 KB budget with the 8 KB Q chunk: 160 KB per CU, two workgroups resident (the
+// two-waves-per-SIMD bound) with room to spare -- 152 users per workgroup at k = 10, 24 at k = 64; P is re-read once per user group.  Two
+// workgroups per CU, four stripes each: at most 2,048 stripes, reached only by a single user group.  The sample call runs 8 x 4 = 32 stripes.
+constexpr topk_stripe_geom kFsTopkGeom{kFsBlock / 64, sizeof(float) * kFsUsers * 64, 2 * CDR_NUM_CU, 8, 0};
 
 // feature held by (register r, lane half h) of a 32x32 accumulator
 __device__ __forceinline__ int fs_feat(int r, int h) { return 8 * (r >> 2) + 4 * h + (r & 3); }
@@ -147,22 +133,8 @@ __global__ __launch_bounds__(kFsBlock, (G3 <= 2 && G4 <= 1) ? 2 : 1) void conet_
     // row, a dependent pair) are in flight under the ~100 weight-fragment loads below
     const bool one_chunk = u_hi - u_lo <= kFsUsers;
     if (one_chunk) fs_stage_q<S1, QF>(a, Ql, u_lo, (int)(u_hi - u_lo));
-    // TOPK: this wave's lists of the workgroup's users (private to the wave: no other wave reads or writes them, so they need no barrier),
-    // all empty: entries (-inf, -1), the k-th value -inf or just below the user's seed
-    volatile float* thr_l = nullptr; volatile float* lv = nullptr; volatile int* lc = nullptr;
-    volatile float* qv = nullptr; volatile int* qc = nullptr; volatile int* qu = nullptr;
-    int qn = 0;
-    if constexpr (TOPK) {
-        const int upb = a.users_per_block, k = a.tk.k;
-        thr_l = fs_dyn + (size_t)wave * fs_topk_wave_words(upb, k);
-        lv = thr_l + upb;
-        lc = reinterpret_cast<volatile int*>(lv + (size_t)upb * k);
-        qv = reinterpret_cast<volatile float*>(lc + (size_t)upb * k);
-        qc = reinterpret_cast<volatile int*>(qv + kFsQueue);
-        qu = qc + kFsQueue;
-        for (int i = lane; i < upb; i += 64) thr_l[i] = topk_seed_thr(a.tk, u_lo + i, a.U);      // (-inf without a seed)
-        for (int i = lane; i < upb * k; i += 64) { lv[i] = -INFINITY; lc[i] = -1; }
-    }
+    topk_wave_lists lists;                                           // TOPK: this wave's lists of the workgroup's users, all empty
+    if constexpr (TOPK) lists.init(fs_dyn, wave, a.users_per_block, a.tk.k, a.tk, u_lo, a.U);
 
     // ---- static per-lane weight fragments, in the K order of the register chain ------------------------------------------------
     // (every address is clamped into its array and the value masked afterwards: straight-line loads -- a bounds BRANCH per element made
@@ -242,24 +214,24 @@ __global__ __launch_bounds__(kFsBlock, (G3 <= 2 && G4 <= 1) ? 2 : 1) void conet_
             for (int uu = 0; uu < nu; ++uu) {
                 const float* q = Ql + uu * 2 * S1 + h * S1;
                 float thr_u = 0.f;                                  // TOPK: this user's k-th value, read ahead of the MFMA chain
-                if constexpr (TOPK) thr_u = thr_l[(int)(u0 - u_lo) + uu];
-                f32x16 acc = fs_zero();
+                if constexpr (TOPK) thr_u = lists.thr((int)(u0 - u_lo) + uu);
+                f32x16 acc = zero16();
 #pragma unroll
                 for (int s = 0; s < S1; s += 4) {
                     const float4 qv = *reinterpret_cast<const float4*>(q + s);
-                    FS_MFMA(acc, w2[s], fmaxf(p[s] + qv.x, 0.f));
-                    FS_MFMA(acc, w2[s + 1], fmaxf(p[s + 1] + qv.y, 0.f));
-                    FS_MFMA(acc, w2[s + 2], fmaxf(p[s + 2] + qv.z, 0.f));
-                    FS_MFMA(acc, w2[s + 3], fmaxf(p[s + 3] + qv.w, 0.f));
+                    MF1(acc, w2[s], fmaxf(p[s] + qv.x, 0.f));
+                    MF1(acc, w2[s + 1], fmaxf(p[s + 1] + qv.y, 0.f));
+                    MF1(acc, w2[s + 2], fmaxf(p[s + 2] + qv.z, 0.f));
+                    MF1(acc, w2[s + 3], fmaxf(p[s + 3] + qv.w, 0.f));
                 }
                 if (G3) {
-                    f32x16 a3 = fs_zero();
+                    f32x16 a3 = zero16();
 #pragma unroll
-                    for (int r = 0; r < R2; ++r) FS_MFMA(a3, w3[r], fmaxf(acc[r] + b2[r], 0.f));
+                    for (int r = 0; r < R2; ++r) MF1(a3, w3[r], fmaxf(acc[r] + b2[r], 0.f));
                     if (G4) {
-                        f32x16 a4 = fs_zero();
+                        f32x16 a4 = zero16();
 #pragma unroll
-                        for (int r = 0; r < R3; ++r) FS_MFMA(a4, w4[r], fmaxf(a3[r] + b3[r], 0.f));
+                        for (int r = 0; r < R3; ++r) MF1(a4, w4[r], fmaxf(a3[r] + b3[r], 0.f));
 #pragma unroll
                         for (int r = 0; r < R4; ++r) acc[r] = fmaxf(a4[r] + b4[r], 0.f);
                     } else {
@@ -278,36 +250,14 @@ __global__ __launch_bounds__(kFsBlock, (G3 <= 2 && G4 <= 1) ? 2 : 1) void conet_
                 if constexpr (!TOPK) {
                     if (h == 0 && iv) a.out[(u0 + uu) * a.ldo + item] = 1.0f / (1.0f + expf(-(z + bo)));
                 } else {
-                    // the same score, offered to user (u0 + uu)'s list: almost every tile fails the k-th-value test as a whole; the
-                    // survivors wait in the wave's queue for their mask test (topk_flush: 64 history searches in flight)
+                    // the same score, offered to user (u0 + uu)'s list (only the h == 0 half carries candidates: at most 32 per call)
                     const float sc = 1.0f / (1.0f + expf(-(z + bo)));
-                    const int ul = (int)(u0 - u_lo) + uu;
-                    const bool pass = h == 0 && iv && sc > thr_u;
-                    const unsigned long long m = __ballot(pass);
-                    if (m) {
-                        if (qn + 32 > kFsQueue) { topk_flush(qv, qc, qu, qn, thr_l, lv, lc, a.tk, u_lo); qn = 0; }
-                        if (pass) {
-                            const int at = qn + __popcll(m & ((1ull << lane) - 1));
-                            qv[at] = sc; qc[at] = (int)item; qu[at] = ul;
-                        }
-                        qn += __popcll(m);
-                    }
+                    lists.template offer<32>(h == 0 && iv && sc > thr_u, sc, (int)item, (int)(u0 - u_lo) + uu, a.tk, u_lo);
                 }
             }
         }
     }
-    if constexpr (TOPK) {
-        if (qn) topk_flush(qv, qc, qu, qn, thr_l, lv, lc, a.tk, u_lo);
-        // one partial list per (this wave, user of the workgroup); a wave that met no tile writes its empty lists
-        const int k = a.tk.k;
-        const int64_t prod = (int64_t)blockIdx.x * 4 + wave;
-        const int n = (int)(u_hi - u_lo) * k;
-        for (int i = lane; i < n; i += 64) {
-            const int64_t o = (prod * a.U + u_lo) * k + i;
-            a.tk.pv[o] = lv[i];
-            a.tk.pc[o] = lc[i];
-        }
-    }
+    if constexpr (TOPK) lists.finish(a.tk, kFsBlock / 64, u_lo, u_hi, a.U);
 }
 
 template <int S1, int G2, int G3, int G4, bool QF>
@@ -330,80 +280,23 @@ int fs_launch_q(const fs_args& a, hipStream_t s) {
     return 0;
 }
 
-// ---- TOPK launch geometry (from U, N and k alone: the workspace is sized without the tower) -------------------------------------
-// A workgroup's lists live across all of its item tiles, so its users are bounded by LDS: 4 waves x (4 + 8 k) B per user next to the 8 KB
-// Q chunk and the queues -- 152 users at k = 10, 24 at k = 64.  P is re-read once per user group.  The workgroups are equally long (the
-// same users x tile rounds each), so the grid is what is resident at once -- two per CU -- and never a partial round more (one
-// workgroup beyond what fits trails as long as a whole round).  That also caps the item stripes (4 per workgroup along x, one per wave) and with them the
-// partial lists [stripes][U][k]: at most 2,048 stripes, reached only by a single user group (<= 152 users).
-// `sample`: the call that seeds the thresholds.  Its lists fill from -inf -- k (1 + ln(n_stripe / k)) insertions per user and stripe, each
-// worth a third of a (tile, user) of CoNet's tower (~1,300 cycles) -- so it runs FEW stripes (kFsSeedGx workgroups along x) and spreads the users over
-// the rest of the grid instead (the first form -- 32,768 columns, as many stripes as the real call -- made the whole call 3.4 ms longer at
-// 1,024 users x 1 M items and 1.0 ms longer at 64).
-struct fs_topk_plan { int upb; int64_t gx, gy, stripes; size_t lds; };
-
-fs_topk_plan fs_make_topk_plan(int64_t U, int64_t N, int k, bool sample = false) {
-    fs_topk_plan p{};
-    const size_t fixed = sizeof(float) * ((size_t)kFsUsers * 64 + 4 * 3 * kFsQueue);      // the widest Q chunk + the four queues
-    int64_t upb = (int64_t)((kFsTopkLds - fixed) / (4 * sizeof(float) * (1 + 2 * (size_t)k)));
-    if (upb > U) upb = U;
-    if (sample) {
-        const int64_t spread = (U + kFsTopkGrid / kFsSeedGx - 1) / (kFsTopkGrid / kFsSeedGx);
-        if (upb > spread) upb = spread;
-    }
-    p.gy = (U + upb - 1) / upb;
-    p.upb = (int)((U + p.gy - 1) / p.gy);                                // the groups evened out
-    p.gy = (U + p.upb - 1) / p.upb;
-    const int64_t n_tiles = (N + 31) >> 5;
-    int64_t gx = kFsTopkGrid / p.gy;
-    if (gx < 1) gx = 1;
-    if (sample && gx > kFsSeedGx) gx = kFsSeedGx;
-    if (gx > (n_tiles + 3) / 4) gx = (n_tiles + 3) / 4;
-    p.gx = gx;
-    p.stripes = 4 * gx;
-    p.lds = 4 * sizeof(float) * fs_topk_wave_words(p.upb, k);
-    return p;
-}
-
-// stripes the workspace is laid out for: those of the real call, or of the sample call in front of it when that has more
-int64_t fs_topk_ws_stripes(int64_t U, int64_t N, int k) {
-    const int64_t s = fs_make_topk_plan(U, N, k).stripes;
-    const int64_t ss = N >= 8 * fs_seed_cols(k) ? fs_make_topk_plan(U, fs_seed_cols(k), k, true).stripes : 0;
-    return s > ss ? s : ss;
-}
-
-// level-0 lists (values | columns) | level-1 lists (one per kTopkMergeGroup level-0 lists)
-size_t fs_topk_ws_bytes(int64_t stripes, int64_t U, int k) {
-    const int64_t l1 = (stripes + kTopkMergeGroup - 1) / kTopkMergeGroup;
-    return 2 * topk_part_bytes(stripes, U, k) + 2 * topk_part_bytes(l1, U, k);
-}
-
 template <int S1, int G2, int G3, int G4>
-int fs_launch_topk(const fs_args_topk& a, const fs_topk_plan& p, hipStream_t s) {
+int fs_launch_topk(const fs_args_topk& a, const topk_stripe_plan& p, hipStream_t s) {
     fs_args_topk b = a;
     b.users_per_block = p.upb;
-    const auto kern = conet_fullsort_kernel<S1, G2, G3, G4, false, true>;
-    if (p.lds > (size_t)48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        if (e != hipSuccess) { cdr_set_error("cdr_conet_fullsort_topk: %zu B of LDS refused: %s", p.lds, hipGetErrorString(e)); return CDR_EINVAL; }
-    }
-    kern<<<dim3((unsigned)p.gx, (unsigned)p.gy), dim3(kFsBlock), p.lds, s>>>(b);
-    return 0;
+    return tile_launch_one("cdr_conet_fullsort_topk", conet_fullsort_kernel<S1, G2, G3, G4, false, true>, b,
+                           dim3((unsigned)p.gx, (unsigned)p.gy), kFsBlock, p.lds, s);
 }
 
 // the instantiations of fs_dispatch, with the top-k epilogue
-int fs_dispatch_topk(const fs_args_topk& a, const fs_topk_plan& p, hipStream_t s) {
+int fs_dispatch_topk(const fs_args_topk& a, const topk_stripe_plan& p, hipStream_t s) {
     const int n_tail = a.n_tail;
     const int g2 = (a.d[0] + 7) / 8, g3 = n_tail > 1 ? (a.d[1] + 7) / 8 : 0, g4 = n_tail > 2 ? (a.d[2] + 7) / 8 : 0;
     const bool small1 = a.h1 <= 32;
-    int rc;
-    if (!small1 && n_tail == 3 && g2 <= 4 && g3 <= 2 && g4 <= 1) rc = fs_launch_topk<32, 4, 2, 1>(a, p, s);
-    else if (n_tail == 3) rc = small1 ? fs_launch_topk<16, 4, 4, 4>(a, p, s) : fs_launch_topk<32, 4, 4, 4>(a, p, s);
-    else if (n_tail == 2) rc = small1 ? fs_launch_topk<16, 4, 4, 0>(a, p, s) : fs_launch_topk<32, 4, 4, 0>(a, p, s);
-    else rc = small1 ? fs_launch_topk<16, 4, 0, 0>(a, p, s) : fs_launch_topk<32, 4, 0, 0>(a, p, s);
-    if (rc) return rc;
-    CDR_LAUNCH_CHECK();
-    return CDR_OK;
+    if (!small1 && n_tail == 3 && g2 <= 4 && g3 <= 2 && g4 <= 1) return fs_launch_topk<32, 4, 2, 1>(a, p, s);
+    if (n_tail == 3) return small1 ? fs_launch_topk<16, 4, 4, 4>(a, p, s) : fs_launch_topk<32, 4, 4, 4>(a, p, s);
+    if (n_tail == 2) return small1 ? fs_launch_topk<16, 4, 4, 0>(a, p, s) : fs_launch_topk<32, 4, 4, 0>(a, p, s);
+    return small1 ? fs_launch_topk<16, 4, 0, 0>(a, p, s) : fs_launch_topk<32, 4, 0, 0>(a, p, s);
 }
 
 template <int S1, int G2, int G3, int G4>
@@ -481,9 +374,7 @@ extern "C" int cdr_conet_fullsort_users(void* stream, const float* P, int64_t ld
 // -inf at the PAD column and the user's history -> torch.topk).  Contract of cdr_fullsort_topk_f32; the values are bit-equal to what
 // cdr_conet_fullsort writes (one tower, two epilogues).
 extern "C" int cdr_conet_fullsort_topk_workspace_bytes(int64_t U, int64_t N, int k, size_t* bytes) {
-    CDR_CHECK_ARG(bytes && U > 0 && N > 0 && N < ((int64_t)1 << 31) && k >= 1 && k <= 64);
-    *bytes = fs_topk_ws_bytes(fs_topk_ws_stripes(U, N, k), U, k);
-    return CDR_OK;
+    return topk_stripe_ws_query("cdr_conet_fullsort_topk_workspace_bytes", kFsTopkGeom, U, N, k, bytes);
 }
 
 extern "C" int cdr_conet_fullsort_topk(void* stream, const float* P, int64_t ldp, const float* Q, int64_t ldq, int64_t U, int64_t N, int h1,
@@ -493,52 +384,22 @@ extern "C" int cdr_conet_fullsort_topk(void* stream, const float* P, int64_t ldp
     CDR_CHECK_ARG(P && Q && out_vals && out_idx && workspace && W && b && wo && bo && tail_dims && U > 0 && N > 0 && ldp >= h1 && ldq >= h1);
     CDR_CHECK_ARG(N < ((int64_t)1 << 31) && U < ((int64_t)1 << 31));
     CDR_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));
-    if (k < 1 || k > 64) { cdr_set_error("cdr_conet_fullsort_topk: k = %d outside 1..64", k); return CDR_EINVAL; }
+    if (const int rc = topk_check_k("cdr_conet_fullsort_topk", k)) return rc;
     if (!cdr_conet_fullsort_supported(h1, n_tail, tail_dims)) {
         cdr_set_error("cdr_conet_fullsort_topk: tower [%d -> %d layers] outside the kernel's range (first width <= 64, 1..3 further layers of width <= 32)",
                       h1, n_tail);
         return CDR_EINVAL;
     }
-    const fs_topk_plan p = fs_make_topk_plan(U, N, k);
-    if (p.gy > 65535 || fs_make_topk_plan(U, fs_seed_cols(k), k, true).gy > 65535) {
-        cdr_set_error("cdr_conet_fullsort_topk: %lld users at k = %d need more than 65,535 user groups; evaluate them in batches", (long long)U, k);
-        return CDR_EINVAL;
-    }
-    const int64_t ws_stripes = fs_topk_ws_stripes(U, N, k);
-    const size_t need = fs_topk_ws_bytes(ws_stripes, U, k);
-    if (workspace_bytes < need) { cdr_set_error("cdr_conet_fullsort_topk: workspace %zu < %zu bytes", workspace_bytes, need); return CDR_EINVAL; }
-    const size_t part = topk_part_bytes(ws_stripes, U, k);
-    const size_t part1 = topk_part_bytes((ws_stripes + kTopkMergeGroup - 1) / kTopkMergeGroup, U, k);
-    float* pv = (float*)workspace;
-    int* pc = (int*)((char*)workspace + part);
-    float* pv1 = (float*)((char*)workspace + 2 * part);
-    int* pc1 = (int*)((char*)workspace + 2 * part + part1);
     fs_args_topk a{};
     a.P = P; a.ldp = ldp; a.Q = Q; a.ldq = ldq; a.U = U; a.N = N; a.h1 = h1; a.n_tail = n_tail; a.wo = wo; a.bo = bo;
-    for (int t = 0; t < n_tail; ++t) {
-        CDR_CHECK_ARG(W[t] && b[t]);
-        a.d[t] = tail_dims[t]; a.W[t] = W[t]; a.b[t] = b[t];
-    }
-    a.tk = topk_out{k, 0, pv, pc, topk_mask{hist_indptr, hist_cols, exclude_first_col}};
+    for (int t = 0; t < n_tail; ++t) { a.d[t] = tail_dims[t]; a.W[t] = W[t]; a.b[t] = b[t]; }
     hipStream_t s = (hipStream_t)stream;
-    // SEEDED thresholds, as in cdr_fullsort_topk_f32: every stripe that fills its lists from -inf pays k (1 + ln(n_stripe / k)) insertions per
-    // user -- with ~1,000 items per stripe that was ~2 insertions per (tile, user), +45 % (CoNet's tower) to +160 % (DTCDR's) on the
-    // launch.  A first call over a SAMPLE (the first fs_seed_cols(k) columns, same mask) leaves each user's k-th value over the sample in
-    // out_vals[:, k - 1]: a lower bound of the final one, the starting threshold (one float below: ties still enter) of every stripe of
-    // the real call.  Results are unchanged: every entry of the final top-k is >= its user's seed; short lists are padded with (-inf, -1),
-    // which the merge never takes.
-    if (N >= 8 * fs_seed_cols(k)) {
-        fs_args_topk sa = a;
-        sa.N = fs_seed_cols(k);
-        const fs_topk_plan sp = fs_make_topk_plan(U, sa.N, k, true);          // (32 stripes; the workspace is laid out for the larger of the two calls)
-        int rc = fs_dispatch_topk(sa, sp, s);
-        if (rc) return rc;
-        rc = topk_merge_launch(s, pv, pc, sp.stripes, U, k, pv1, pc1, out_vals, out_idx);
-        if (rc) return rc;
-        a.tk.seed = out_vals + (k - 1);
-        a.tk.seed_stride = k;
-    }
-    int rc = fs_dispatch_topk(a, p, s);
-    if (rc) return rc;
-    return topk_merge_launch(s, pv, pc, p.stripes, U, k, pv1, pc1, out_vals, out_idx);
+    return topk_seeded_run("cdr_conet_fullsort_topk", kFsTopkGeom, s, U, N, k, topk_mask{hist_indptr, hist_cols, exclude_first_col}, out_vals,
+                           out_idx, workspace, workspace_bytes, [&](int64_t n_cols, const topk_stripe_plan& p, const topk_out& tk) -> int {
+                               for (int t = 0; t < n_tail; ++t)                 // (refused behind the workspace, ahead of any launch)
+                                   if (!W[t] || !b[t]) { cdr_set_error("cdr_conet_fullsort_topk: invalid argument: W[t] && b[t]"); return CDR_EINVAL; }
+                               fs_args_topk c = a;
+                               c.N = n_cols; c.tk = tk;
+                               return fs_dispatch_topk(c, p, s);
+                           });
 }

@@ -29,19 +29,16 @@
 #include "cdr_common.h"
 #include "cdr_mfma.h"
 #include "cdr_topk.h"
-#include <type_traits>
+#include "cdr_fullsort_tile.h"
 
 namespace {
 
 constexpr int kApWaves = 8;                      // item tiles per workgroup pass: W1 is staged once for eight waves (two per SIMD)
 constexpr int kApBlock = 64 * kApWaves;
 constexpr int kApUsers = 8;                      // users per LDS chunk (four rows of 128 floats each at most: 16 KB)
-constexpr int kApQueue = 128;                    // TOPK: candidates a wave parks before their mask test (a tile adds at most 32 per user)
-constexpr size_t kApListLds = (size_t)64 * 1024; // TOPK: LDS of the lists and queues, next to at most 81 KB of W1, vectors and chunk
-constexpr int64_t kApTopkGrid = CDR_NUM_CU;      // TOPK workgroups per launch: what is resident at once (one per CU), never a partial round
-constexpr int64_t ap_seed_cols(int k) { return (int64_t)1024 * (k < 8 ? 8 : k); }
-constexpr int64_t kApSeedGx = 4;                 // workgroups along x of the sample call: 32 stripes
-__host__ __device__ constexpr size_t ap_topk_wave_words(int upb, int k) { return (size_t)upb * (1 + 2 * k) + 3 * kApQueue; }
+// TOPK launch geometry (cdr_topk.h): the 64 KB of lists and queues lie next to at most 81 KB of W1, vectors and chunk -- 79 users per
+// workgroup at k = 10, 12 at k = 64.  One workgroup per CU, eight stripes each (at most 8 x 256); the sample call runs 4 x 8 = 32 stripes.
+constexpr topk_stripe_geom kApTopkGeom{kApWaves, 0, CDR_NUM_CU, 4, 0};
 
 struct ap_args {
     const float* key_s; const float* key_o;      // the key side's share / target-only tables
@@ -82,18 +79,6 @@ __device__ __forceinline__ void ap_stage_users(const ap_args& a, float* __restri
     }
     if (!ITEMKEY)
         for (int e = threadIdx.x; e < nu; e += kApBlock) mflag[e] = a.uid[u0 + e] > a.n_overlap ? 1 : 0;
-}
-
-// one item row's features h S .. h S + S - 1 (zero beyond D, or for a lane without an item)
-template <int S>
-__device__ __forceinline__ void ap_load_row(float (&p)[S], const float* __restrict__ row, bool iv, int h, int D) {
-#pragma unroll
-    for (int s = 0; s < S; s += 4) {
-        const int f = h * S + s;
-        const bool ok = iv && f < D;
-        const float4 v = ld4(row + (ok ? f : 0));
-        p[s] = ok ? v.x : 0.f; p[s + 1] = ok ? v.y : 0.f; p[s + 2] = ok ? v.z : 0.f; p[s + 3] = ok ? v.w : 0.f;
-    }
 }
 
 // an offset the optimiser cannot see through: the chunk rows are re-read in every 32-feature pass instead of being kept (hoisted out of the
@@ -204,21 +189,8 @@ __global__ __launch_bounds__(kApBlock) void deepapf_fullsort_kernel(ap_kargs<TOP
         const float vb = a.b1[ok ? t : 0], v2 = a.w2[ok ? t : 0];
         b1l[t] = ok ? vb : 0.f; w2l[t] = ok ? v2 : 0.f;
     }
-    // TOPK: this wave's lists of the workgroup's users (private to the wave), all empty
-    volatile float* thr_l = nullptr; volatile float* lv = nullptr; volatile int* lc = nullptr;
-    volatile float* qv = nullptr; volatile int* qc = nullptr; volatile int* qu = nullptr;
-    int qn = 0;
-    if constexpr (TOPK) {
-        const int upb = a.users_per_block, k = a.tk.k;
-        thr_l = dyn + (size_t)wave * ap_topk_wave_words(upb, k);
-        lv = thr_l + upb;
-        lc = reinterpret_cast<volatile int*>(lv + (size_t)upb * k);
-        qv = reinterpret_cast<volatile float*>(lc + (size_t)upb * k);
-        qc = reinterpret_cast<volatile int*>(qv + kApQueue);
-        qu = qc + kApQueue;
-        for (int i = lane; i < upb; i += 64) thr_l[i] = topk_seed_thr(a.tk, u_lo + i, a.U);
-        for (int i = lane; i < upb * k; i += 64) { lv[i] = -INFINITY; lc[i] = -1; }
-    }
+    topk_wave_lists lists;                                    // TOPK: this wave's lists of the workgroup's users, all empty
+    if constexpr (TOPK) lists.init(dyn, wave, a.users_per_block, a.tk.k, a.tk, u_lo, a.U);
     // this lane's views: A fragments of row c (K features h S ..), the vectors' and the chunk rows' half
     const float* const wa0 = Wl + ((size_t)(h * (S / 4)) * DP + c) * 4;
     const float* const b1h = b1l + 4 * h;
@@ -239,10 +211,10 @@ __global__ __launch_bounds__(kApBlock) void deepapf_fullsort_kernel(ap_kargs<TOP
         const bool imask = ITEMKEY && item > a.n_overlap;                   // this lane's item takes al_S = 0
         const bool tile_masked = ITEMKEY && tile * 32 > a.n_overlap;        // ... and so does every item of the tile
         if constexpr (ITEMKEY) {
-            ap_load_row<S>(r0, a.key_s + (iv ? item : 0) * a.ld_s, iv && !imask, h, D);
-            ap_load_row<S>(r1, a.key_o + (iv ? item : 0) * a.ld_o, iv, h, D);
+            tile_load_row<S>(r0, a.key_s + (iv ? item : 0) * a.ld_s, iv && !imask, h, D);
+            tile_load_row<S>(r1, a.key_o + (iv ? item : 0) * a.ld_o, iv, h, D);
         } else {
-            ap_load_row<S>(r0, a.oth + (iv ? item : 0) * a.ld_t, iv, h, D);
+            tile_load_row<S>(r0, a.oth + (iv ? item : 0) * a.ld_t, iv, h, D);
         }
         for (int64_t u0 = u_lo; u0 < u_hi; u0 += kApUsers) {
             const int nu = (int)(u_hi - u0 < kApUsers ? u_hi - u0 : kApUsers);
@@ -257,7 +229,7 @@ __global__ __launch_bounds__(kApBlock) void deepapf_fullsort_kernel(ap_kargs<TOP
                 const float* const lo = l0 + (ITEMKEY ? 0 : DP);            // the row the only candidate multiplies: O_u / T_u
                 const bool skip_s = ITEMKEY ? tile_masked : mflag[uu] != 0;  // wave-uniform
                 float thr_u = 0.f;
-                if constexpr (TOPK) thr_u = thr_l[(int)(u0 - u_lo) + uu];
+                if constexpr (TOPK) thr_u = lists.thr((int)(u0 - u_lo) + uu);
                 // z_c = wp . x_c, then a_c = w2 . relu(W1 x_c + b1), 32 output features per pass
                 float as = 0.f, ao = 0.f, zs = 0.f, zo = 0.f;
                 if (!skip_s) {
@@ -287,127 +259,31 @@ __global__ __launch_bounds__(kApBlock) void deepapf_fullsort_kernel(ap_kargs<TOP
                 if constexpr (!TOPK) {
                     if (h == 0 && iv) a.out[(u0 + uu) * a.ldo + item] = sc;
                 } else {
-                    const int ul = (int)(u0 - u_lo) + uu;
-                    const bool pass = h == 0 && iv && sc > thr_u;
-                    const unsigned long long mm = __ballot(pass);
-                    if (mm) {
-                        if (qn + 32 > kApQueue) { topk_flush(qv, qc, qu, qn, thr_l, lv, lc, a.tk, u_lo); qn = 0; }
-                        if (pass) {
-                            const int at = qn + __popcll(mm & ((1ull << lane) - 1));
-                            qv[at] = sc; qc[at] = (int)item; qu[at] = ul;
-                        }
-                        qn += __popcll(mm);
-                    }
+                    // (only the h == 0 half carries candidates: at most 32 per call)
+                    lists.template offer<32>(h == 0 && iv && sc > thr_u, sc, (int)item, (int)(u0 - u_lo) + uu, a.tk, u_lo);
                 }
             }
         }
     }
-    if constexpr (TOPK) {
-        if (qn) topk_flush(qv, qc, qu, qn, thr_l, lv, lc, a.tk, u_lo);
-        // one partial list per (this wave, user of the workgroup); a wave that met no tile writes its empty lists
-        const int k = a.tk.k;
-        const int64_t prod = (int64_t)blockIdx.x * kApWaves + wave;
-        const int n = (int)(u_hi - u_lo) * k;
-        for (int i = lane; i < n; i += 64) {
-            const int64_t o = (prod * a.U + u_lo) * k + i;
-            a.tk.pv[o] = lv[i];
-            a.tk.pc[o] = lc[i];
-        }
-    }
-}
-
-template <int NB, bool ITEMKEY, bool TOPK>
-int ap_launch_one(const ap_kargs<TOPK>& a, dim3 grid, size_t lds, hipStream_t s) {
-    const auto kern = deepapf_fullsort_kernel<NB, ITEMKEY, TOPK>;
-    if (lds > (size_t)48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { cdr_set_error("cdr_deepapf_fullsort: %zu B of LDS refused: %s", lds, hipGetErrorString(e)); return CDR_EINVAL; }
-    }
-    kern<<<grid, dim3(kApBlock), lds, s>>>(a);
-    CDR_LAUNCH_CHECK();
-    return CDR_OK;
+    if constexpr (TOPK) lists.finish(a.tk, kApWaves, u_lo, u_hi, a.U);
 }
 
 template <bool TOPK>
 int ap_dispatch(const ap_kargs<TOPK>& a, bool itemkey, dim3 grid, size_t list_bytes, hipStream_t s) {
-    const int nb = (a.D + 31) / 32;
-    const size_t lds = sizeof(float) * ap_fixed_words(32 * nb, itemkey) + list_bytes;
-    switch (nb * 2 + (itemkey ? 1 : 0)) {
-        case 2: return ap_launch_one<1, false, TOPK>(a, grid, lds, s);
-        case 3: return ap_launch_one<1, true, TOPK>(a, grid, lds, s);
-        case 4: return ap_launch_one<2, false, TOPK>(a, grid, lds, s);
-        case 5: return ap_launch_one<2, true, TOPK>(a, grid, lds, s);
-        case 6: return ap_launch_one<3, false, TOPK>(a, grid, lds, s);
-        case 7: return ap_launch_one<3, true, TOPK>(a, grid, lds, s);
-        case 8: return ap_launch_one<4, false, TOPK>(a, grid, lds, s);
-        case 9: return ap_launch_one<4, true, TOPK>(a, grid, lds, s);
-    }
-    cdr_set_error("cdr_deepapf_fullsort: D = %d outside the kernel's range", a.D);
-    return CDR_EINVAL;
+    const size_t lds = sizeof(float) * ap_fixed_words(32 * ((a.D + 31) / 32), itemkey) + list_bytes;
+    const int rc = tile_dispatch(a.D, itemkey, [&](auto nb, auto ik) {
+        return tile_launch_one("cdr_deepapf_fullsort", deepapf_fullsort_kernel<nb(), ik(), TOPK>, a, grid, kApBlock, lds, s);
+    });
+    if (rc < 0) { cdr_set_error("cdr_deepapf_fullsort: D = %d outside the kernel's range", a.D); return CDR_EINVAL; }
+    return rc;
 }
 
-// score epilogue: every workgroup stages W1 once, so the grid is a few workgroups per CU and the waves walk the remaining tiles; the users
-// are split over blockIdx.y only while the item tiles alone do not fill the chip
+// score epilogue: every workgroup stages W1 once, so the grid is a few workgroups per CU (cdr_fullsort_tile.h)
 int ap_launch_scores(const ap_args& a, bool itemkey, hipStream_t s) {
-    const int64_t n_tiles = (a.N + 31) >> 5;
     ap_args b = a;
-    int64_t gx = (n_tiles + kApWaves - 1) / kApWaves;
-    const int64_t groups = (a.U + kApUsers - 1) / kApUsers;
-    int64_t gy = 1;
-    while (gx * gy < 2 * CDR_NUM_CU && gy < groups) gy *= 2;
-    if (gy > groups) gy = groups;
-    const int64_t per = (groups + gy - 1) / gy;
-    gy = (groups + per - 1) / per;
-    if (gy > 65535) { cdr_set_error("cdr_deepapf_fullsort: %lld users need more than 65,535 user groups", (long long)a.U); return CDR_EINVAL; }
-    b.users_per_block = (int)(per * kApUsers);
-    if (gx > 4 * CDR_NUM_CU) gx = 4 * CDR_NUM_CU;
-    return ap_dispatch<false>(b, itemkey, dim3((unsigned)gx, (unsigned)gy), 0, s);
-}
-
-// ---- TOPK launch geometry, from U, N and k alone (the workspace is sized without the model): cdr_conet_fullsort's, with eight stripes
-// per workgroup.  A workgroup's lists live across all of its item tiles, so its users are bounded by the lists' LDS: 8 waves x (4 + 8 k) B
-// per user next to the queues -- 79 users at k = 10, 12 at k = 64.  The grid is what is resident at once, which also caps the item
-// stripes (at most 8 x 256) and with them the partial lists [stripes][U][k].
-struct ap_topk_plan { int upb; int64_t gx, gy, stripes; size_t list_bytes; };
-
-ap_topk_plan ap_make_topk_plan(int64_t U, int64_t N, int k, bool sample = false) {
-    ap_topk_plan p{};
-    const size_t fixed = sizeof(float) * (size_t)kApWaves * 3 * kApQueue;
-    int64_t upb = (int64_t)((kApListLds - fixed) / (kApWaves * sizeof(float) * (1 + 2 * (size_t)k)));
-    if (upb > U) upb = U;
-    if (sample) {
-        const int64_t spread = (U + kApTopkGrid / kApSeedGx - 1) / (kApTopkGrid / kApSeedGx);
-        if (upb > spread) upb = spread;
-    }
-    p.gy = (U + upb - 1) / upb;
-    p.upb = (int)((U + p.gy - 1) / p.gy);
-    p.gy = (U + p.upb - 1) / p.upb;
-    const int64_t n_tiles = (N + 31) >> 5;
-    int64_t gx = kApTopkGrid / p.gy;
-    if (gx < 1) gx = 1;
-    if (sample && gx > kApSeedGx) gx = kApSeedGx;
-    if (gx > (n_tiles + kApWaves - 1) / kApWaves) gx = (n_tiles + kApWaves - 1) / kApWaves;
-    p.gx = gx;
-    p.stripes = kApWaves * gx;
-    p.list_bytes = kApWaves * sizeof(float) * ap_topk_wave_words(p.upb, k);
-    return p;
-}
-
-int64_t ap_topk_ws_stripes(int64_t U, int64_t N, int k) {
-    const int64_t s = ap_make_topk_plan(U, N, k).stripes;
-    const int64_t ss = N >= 8 * ap_seed_cols(k) ? ap_make_topk_plan(U, ap_seed_cols(k), k, true).stripes : 0;
-    return s > ss ? s : ss;
-}
-
-size_t ap_topk_ws_bytes(int64_t stripes, int64_t U, int k) {
-    const int64_t l1 = (stripes + kTopkMergeGroup - 1) / kTopkMergeGroup;
-    return 2 * topk_part_bytes(stripes, U, k) + 2 * topk_part_bytes(l1, U, k);
-}
-
-int ap_launch_topk(const ap_args_topk& a, bool itemkey, const ap_topk_plan& p, hipStream_t s) {
-    ap_args_topk b = a;
-    b.users_per_block = p.upb;
-    return ap_dispatch<true>(b, itemkey, dim3((unsigned)p.gx, (unsigned)p.gy), p.list_bytes, s);
+    dim3 grid;
+    if (const int rc = tile_score_grid("cdr_deepapf_fullsort", a.U, a.N, kApWaves, kApUsers, &grid, &b.users_per_block)) return rc;
+    return ap_dispatch<false>(b, itemkey, grid, 0, s);
 }
 
 // the arguments both entries share; nothing is launched for a refused call
@@ -458,9 +334,7 @@ extern "C" int cdr_deepapf_fullsort(void* stream, int key_is_item, const float* 
 }
 
 extern "C" int cdr_deepapf_fullsort_topk_workspace_bytes(int64_t U, int64_t N, int k, size_t* bytes) {
-    CDR_CHECK_ARG(bytes && U > 0 && N > 0 && N < ((int64_t)1 << 31) && U < ((int64_t)1 << 31) && k >= 1 && k <= 64);
-    *bytes = ap_topk_ws_bytes(ap_topk_ws_stripes(U, N, k), U, k);
-    return CDR_OK;
+    return topk_stripe_ws_query("cdr_deepapf_fullsort_topk_workspace_bytes", kApTopkGeom, U, N, k, bytes);
 }
 
 extern "C" int cdr_deepapf_fullsort_topk(void* stream, int key_is_item, const float* share_tab, int64_t ld_share, const float* only_tab,
@@ -468,46 +342,20 @@ extern "C" int cdr_deepapf_fullsort_topk(void* stream, int key_is_item, const fl
                                          int64_t N, int D, int64_t n_overlap, const float* W1, const float* b1, const float* w2,
                                          const float* wp, int k, const int64_t* hist_indptr, const int64_t* hist_cols,
                                          int exclude_first_col, float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes) {
-    if (k < 1 || k > 64) { cdr_set_error("cdr_deepapf_fullsort_topk: k = %d outside 1..64", k); return CDR_EINVAL; }
+    if (const int rc = topk_check_k("cdr_deepapf_fullsort_topk", k)) return rc;
     const int rc0 = ap_check("cdr_deepapf_fullsort_topk", share_tab, ld_share, only_tab, ld_only, other_tab, ld_other, uid, U, N, D, W1, b1,
                              w2, wp);
     if (rc0) return rc0;
     CDR_CHECK_ARG(out_vals && out_idx && workspace);
     CDR_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));
-    const bool itemkey = key_is_item != 0;
-    const ap_topk_plan p = ap_make_topk_plan(U, N, k);
-    if (p.gy > 65535 || ap_make_topk_plan(U, ap_seed_cols(k), k, true).gy > 65535) {
-        cdr_set_error("cdr_deepapf_fullsort_topk: %lld users at k = %d need more than 65,535 user groups; evaluate them in batches", (long long)U, k);
-        return CDR_EINVAL;
-    }
-    const int64_t ws_stripes = ap_topk_ws_stripes(U, N, k);
-    const size_t need = ap_topk_ws_bytes(ws_stripes, U, k);
-    if (workspace_bytes < need) { cdr_set_error("cdr_deepapf_fullsort_topk: workspace %zu < %zu bytes", workspace_bytes, need); return CDR_EINVAL; }
-    const size_t part = topk_part_bytes(ws_stripes, U, k);
-    const size_t part1 = topk_part_bytes((ws_stripes + kTopkMergeGroup - 1) / kTopkMergeGroup, U, k);
-    float* pv = (float*)workspace;
-    int* pc = (int*)((char*)workspace + part);
-    float* pv1 = (float*)((char*)workspace + 2 * part);
-    int* pc1 = (int*)((char*)workspace + 2 * part + part1);
     ap_args_topk a{};
     static_cast<ap_args&>(a) = ap_fill(key_is_item, share_tab, ld_share, only_tab, ld_only, other_tab, ld_other, uid, U, N, D, n_overlap, W1,
                                        b1, w2, wp);
-    a.tk = topk_out{k, 0, pv, pc, topk_mask{hist_indptr, hist_cols, exclude_first_col}};
     hipStream_t s = (hipStream_t)stream;
-    // SEEDED thresholds, as in cdr_conet_fullsort_topk: a first call over the first ap_seed_cols(k) columns (same mask) leaves each user's
-    // k-th value over the sample in out_vals[:, k - 1], a lower bound of the final one and the starting threshold of every stripe
-    if (N >= 8 * ap_seed_cols(k)) {
-        ap_args_topk sa = a;
-        sa.N = ap_seed_cols(k);
-        const ap_topk_plan sp = ap_make_topk_plan(U, sa.N, k, true);
-        int rc = ap_launch_topk(sa, itemkey, sp, s);
-        if (rc) return rc;
-        rc = topk_merge_launch(s, pv, pc, sp.stripes, U, k, pv1, pc1, out_vals, out_idx);
-        if (rc) return rc;
-        a.tk.seed = out_vals + (k - 1);
-        a.tk.seed_stride = k;
-    }
-    int rc = ap_launch_topk(a, itemkey, p, s);
-    if (rc) return rc;
-    return topk_merge_launch(s, pv, pc, p.stripes, U, k, pv1, pc1, out_vals, out_idx);
+    return topk_seeded_run("cdr_deepapf_fullsort_topk", kApTopkGeom, s, U, N, k, topk_mask{hist_indptr, hist_cols, exclude_first_col},
+                           out_vals, out_idx, workspace, workspace_bytes, [&](int64_t n_cols, const topk_stripe_plan& p, const topk_out& tk) {
+                               ap_args_topk b = a;
+                               b.N = n_cols; b.users_per_block = p.upb; b.tk = tk;
+                               return ap_dispatch<true>(b, key_is_item != 0, dim3((unsigned)p.gx, (unsigned)p.gy), p.lds, s);
+                           });
 }

@@ -30,19 +30,17 @@
 #include "cdr_common.h"
 #include "cdr_mfma.h"
 #include "cdr_topk.h"
-#include <type_traits>
+#include "cdr_fullsort_tile.h"
 
 namespace {
 
 constexpr int kNfWaves = 8;                      // item tiles per workgroup pass (two waves per SIMD)
 constexpr int kNfBlock = 64 * kNfWaves;
 constexpr int kNfUsers = 32;                     // users per LDS chunk: the rows of one MFMA tile
-constexpr int kNfQueue = 128;                    // TOPK: candidates a wave parks before their mask test (a register adds at most 64)
-constexpr size_t kNfListLds = (size_t)64 * 1024; // TOPK: LDS of the lists and queues, next to at most 64 KB of chunk
-constexpr int64_t kNfTopkGrid = CDR_NUM_CU;      // TOPK workgroups per launch: what is resident at once (one per CU), never a partial round
-constexpr int64_t nf_seed_cols(int k) { return (int64_t)1024 * (k < 8 ? 8 : k); }
-constexpr int64_t kNfSeedGx = 4;                 // workgroups along x of the sample call: 32 stripes
-__host__ __device__ constexpr size_t nf_topk_wave_words(int upb, int k) { return (size_t)upb * (1 + 2 * k) + 3 * kNfQueue; }
+// TOPK launch geometry (cdr_topk.h): the 64 KB of lists and queues lie next to at most 64 KB of chunk -- 64 users per workgroup at k = 10
+// (a multiple of the 32-user chunk where that many fit), 12 at k = 64.  One workgroup per CU, eight stripes each (at most 8 x 256); the
+// sample call runs 4 x 8 = 32 stripes.
+constexpr topk_stripe_geom kNfTopkGeom{kNfWaves, 0, CDR_NUM_CU, 4, kNfUsers};
 
 struct nf_args {
     const float* su;                             // [keys, D]: the key side's history summary, by POSITION (user u / item i)
@@ -97,18 +95,6 @@ __device__ __forceinline__ void nf_stage_users(const nf_args& a, float* __restri
     }
 }
 
-// one item row's features h S .. h S + S - 1 (zero beyond D, or for a lane without an item)
-template <int S>
-__device__ __forceinline__ void nf_load_row(float (&p)[S], const float* __restrict__ row, bool iv, int h, int D) {
-#pragma unroll
-    for (int s = 0; s < S; s += 4) {
-        const int f = h * S + s;
-        const bool ok = iv && f < D;
-        const float4 v = ld4(row + (ok ? f : 0));
-        p[s] = ok ? v.x : 0.f; p[s + 1] = ok ? v.y : 0.f; p[s + 2] = ok ? v.z : 0.f; p[s + 3] = ok ? v.w : 0.f;
-    }
-}
-
 template <int NB, bool ITEMKEY, bool TOPK>
 __global__ __launch_bounds__(kNfBlock) void natr_fullsort_kernel(nf_kargs<TOPK> a) {
     constexpr int DP = 32 * NB, S = 16 * NB, Q = DP / 4, S1 = ITEMKEY ? S : 1;
@@ -124,21 +110,8 @@ __global__ __launch_bounds__(kNfBlock) void natr_fullsort_kernel(nf_kargs<TOPK> 
     const bool one_chunk = u_hi - u_lo <= kNfUsers;           // staged once, not once per tile round
     if (one_chunk) nf_stage_users<NB, ITEMKEY>(a, Ul, u_lo, (int)(u_hi - u_lo));
     for (int t = threadIdx.x; t < DP; t += kNfBlock) wl[t] = t < D ? 0.5f * a.w[t] : 0.f;
-    // TOPK: this wave's lists of the workgroup's users (private to the wave), all empty
-    volatile float* thr_l = nullptr; volatile float* lv = nullptr; volatile int* lc = nullptr;
-    volatile float* qv = nullptr; volatile int* qc = nullptr; volatile int* qu = nullptr;
-    int qn = 0;
-    if constexpr (TOPK) {
-        const int upb = a.users_per_block, k = a.tk.k;
-        thr_l = dyn + (size_t)wave * nf_topk_wave_words(upb, k);
-        lv = thr_l + upb;
-        lc = reinterpret_cast<volatile int*>(lv + (size_t)upb * k);
-        qv = reinterpret_cast<volatile float*>(lc + (size_t)upb * k);
-        qc = reinterpret_cast<volatile int*>(qv + kNfQueue);
-        qu = qc + kNfQueue;
-        for (int i = lane; i < upb; i += 64) thr_l[i] = topk_seed_thr(a.tk, u_lo + i, a.U);
-        for (int i = lane; i < upb * k; i += 64) { lv[i] = -INFINITY; lc[i] = -1; }
-    }
+    topk_wave_lists lists;                                    // TOPK: this wave's lists of the workgroup's users, all empty
+    if constexpr (TOPK) lists.init(dyn, wave, a.users_per_block, a.tk.k, a.tk, u_lo, a.U);
     // this lane's view of the chunk: user row c, K groups h S / 4 ..
     const float* const ua = Ul + ((size_t)(h * (S / 4)) * kNfUsers + c) * 4;
     const float* const wh = wl + h * S;
@@ -155,10 +128,10 @@ __global__ __launch_bounds__(kNfBlock) void natr_fullsort_kernel(nf_kargs<TOPK> 
         // the tile's rows.  overlap_items: r0 = q.  overlap_users: r0 = a (su of the item), r1 = p
         float r0[S], r1[S1];
         if constexpr (ITEMKEY) {
-            nf_load_row<S>(r0, a.su + (iv ? item : 0) * a.ld_su, iv, h, D);
-            nf_load_row<S>(r1, a.ptab + (iv ? item : 0) * a.ld_p, iv, h, D);
+            tile_load_row<S>(r0, a.su + (iv ? item : 0) * a.ld_su, iv, h, D);
+            tile_load_row<S>(r1, a.ptab + (iv ? item : 0) * a.ld_p, iv, h, D);
         } else {
-            nf_load_row<S>(r0, a.qtab + (iv ? item : 0) * a.ld_q, iv, h, D);
+            tile_load_row<S>(r0, a.qtab + (iv ? item : 0) * a.ld_q, iv, h, D);
         }
         for (int64_t u0 = u_lo; u0 < u_hi; u0 += kNfUsers) {
             const int nu = (int)(u_hi - u0 < kNfUsers ? u_hi - u0 : kNfUsers);
@@ -215,127 +188,31 @@ __global__ __launch_bounds__(kNfBlock) void natr_fullsort_kernel(nf_kargs<TOPK> 
                 if constexpr (!TOPK) {
                     if (ok) a.out[(u0 + row) * a.ldo + item] = sc;
                 } else {
-                    const int ul = (int)(u0 - u_lo) + row;
-                    const bool pass = ok && sc > thr_l[ok ? ul : 0];
-                    const unsigned long long mm = __ballot(pass);
-                    if (mm) {
-                        if (qn + 64 > kNfQueue) { topk_flush(qv, qc, qu, qn, thr_l, lv, lc, a.tk, u_lo); qn = 0; }
-                        if (pass) {
-                            const int at = qn + __popcll(mm & ((1ull << lane) - 1));
-                            qv[at] = sc; qc[at] = (int)item; qu[at] = ul;
-                        }
-                        qn += __popcll(mm);
-                    }
+                    const int ul = (int)(u0 - u_lo) + row;                  // (every lane may carry a candidate: at most 64 per call)
+                    lists.template offer<64>(ok && sc > lists.thr(ok ? ul : 0), sc, (int)item, ul, a.tk, u_lo);
                 }
             }
         }
     }
-    if constexpr (TOPK) {
-        if (qn) topk_flush(qv, qc, qu, qn, thr_l, lv, lc, a.tk, u_lo);
-        // one partial list per (this wave, user of the workgroup); a wave that met no tile writes its empty lists
-        const int k = a.tk.k;
-        const int64_t prod = (int64_t)blockIdx.x * kNfWaves + wave;
-        const int n = (int)(u_hi - u_lo) * k;
-        for (int i = lane; i < n; i += 64) {
-            const int64_t o = (prod * a.U + u_lo) * k + i;
-            a.tk.pv[o] = lv[i];
-            a.tk.pc[o] = lc[i];
-        }
-    }
-}
-
-template <int NB, bool ITEMKEY, bool TOPK>
-int nf_launch_one(const nf_kargs<TOPK>& a, dim3 grid, size_t lds, hipStream_t s) {
-    const auto kern = natr_fullsort_kernel<NB, ITEMKEY, TOPK>;
-    if (lds > (size_t)48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { cdr_set_error("cdr_natr_fullsort: %zu B of LDS refused: %s", lds, hipGetErrorString(e)); return CDR_EINVAL; }
-    }
-    kern<<<grid, dim3(kNfBlock), lds, s>>>(a);
-    CDR_LAUNCH_CHECK();
-    return CDR_OK;
+    if constexpr (TOPK) lists.finish(a.tk, kNfWaves, u_lo, u_hi, a.U);
 }
 
 template <bool TOPK>
 int nf_dispatch(const nf_kargs<TOPK>& a, bool itemkey, dim3 grid, size_t list_bytes, hipStream_t s) {
-    const int nb = (a.D + 31) / 32;
-    const size_t lds = sizeof(float) * nf_fixed_words(32 * nb, itemkey) + list_bytes;
-    switch (nb * 2 + (itemkey ? 1 : 0)) {
-        case 2: return nf_launch_one<1, false, TOPK>(a, grid, lds, s);
-        case 3: return nf_launch_one<1, true, TOPK>(a, grid, lds, s);
-        case 4: return nf_launch_one<2, false, TOPK>(a, grid, lds, s);
-        case 5: return nf_launch_one<2, true, TOPK>(a, grid, lds, s);
-        case 6: return nf_launch_one<3, false, TOPK>(a, grid, lds, s);
-        case 7: return nf_launch_one<3, true, TOPK>(a, grid, lds, s);
-        case 8: return nf_launch_one<4, false, TOPK>(a, grid, lds, s);
-        case 9: return nf_launch_one<4, true, TOPK>(a, grid, lds, s);
-    }
-    cdr_set_error("cdr_natr_fullsort: Dt = %d outside the kernel's range", a.D);
-    return CDR_EINVAL;
+    const size_t lds = sizeof(float) * nf_fixed_words(32 * ((a.D + 31) / 32), itemkey) + list_bytes;
+    const int rc = tile_dispatch(a.D, itemkey, [&](auto nb, auto ik) {
+        return tile_launch_one("cdr_natr_fullsort", natr_fullsort_kernel<nb(), ik(), TOPK>, a, grid, kNfBlock, lds, s);
+    });
+    if (rc < 0) { cdr_set_error("cdr_natr_fullsort: Dt = %d outside the kernel's range", a.D); return CDR_EINVAL; }
+    return rc;
 }
 
-// score epilogue: a few workgroups per CU, the waves walk the remaining tiles; the users are split over blockIdx.y only while the item
-// tiles alone do not fill the chip
+// score epilogue: a few workgroups per CU (cdr_fullsort_tile.h)
 int nf_launch_scores(const nf_args& a, bool itemkey, hipStream_t s) {
-    const int64_t n_tiles = (a.N + 31) >> 5;
     nf_args b = a;
-    int64_t gx = (n_tiles + kNfWaves - 1) / kNfWaves;
-    const int64_t groups = (a.U + kNfUsers - 1) / kNfUsers;
-    int64_t gy = 1;
-    while (gx * gy < 2 * CDR_NUM_CU && gy < groups) gy *= 2;
-    if (gy > groups) gy = groups;
-    const int64_t per = (groups + gy - 1) / gy;
-    gy = (groups + per - 1) / per;
-    if (gy > 65535) { cdr_set_error("cdr_natr_fullsort: %lld users need more than 65,535 user groups", (long long)a.U); return CDR_EINVAL; }
-    b.users_per_block = (int)(per * kNfUsers);
-    if (gx > 4 * CDR_NUM_CU) gx = 4 * CDR_NUM_CU;
-    return nf_dispatch<false>(b, itemkey, dim3((unsigned)gx, (unsigned)gy), 0, s);
-}
-
-// ---- TOPK launch geometry, from U, N and k alone (the workspace is sized without the model): cdr_deepapf_fullsort's.  A workgroup's
-// lists live across all of its item tiles, so its users are bounded by the lists' LDS: 8 waves x (4 + 8 k) B per user next to the queues
-// -- 64 users at k = 10 (a multiple of the 32-user chunk where that many fit), 12 at k = 64.  The grid is what is resident at once, which
-// also caps the item stripes (at most 8 x 256) and with them the partial lists [stripes][U][k].
-struct nf_topk_plan { int upb; int64_t gx, gy, stripes; size_t list_bytes; };
-
-nf_topk_plan nf_make_topk_plan(int64_t U, int64_t N, int k, bool sample = false) {
-    nf_topk_plan p{};
-    const size_t fixed = sizeof(float) * (size_t)kNfWaves * 3 * kNfQueue;
-    int64_t upb = (int64_t)((kNfListLds - fixed) / (kNfWaves * sizeof(float) * (1 + 2 * (size_t)k)));
-    if (upb > kNfUsers) upb -= upb % kNfUsers;
-    if (upb > U) upb = U;
-    if (sample) {
-        const int64_t spread = (U + kNfTopkGrid / kNfSeedGx - 1) / (kNfTopkGrid / kNfSeedGx);
-        if (upb > spread) upb = spread;
-    }
-    p.gy = (U + upb - 1) / upb;
-    p.upb = (int)upb;
-    const int64_t n_tiles = (N + 31) >> 5;
-    int64_t gx = kNfTopkGrid / p.gy;
-    if (gx < 1) gx = 1;
-    if (sample && gx > kNfSeedGx) gx = kNfSeedGx;
-    if (gx > (n_tiles + kNfWaves - 1) / kNfWaves) gx = (n_tiles + kNfWaves - 1) / kNfWaves;
-    p.gx = gx;
-    p.stripes = kNfWaves * gx;
-    p.list_bytes = kNfWaves * sizeof(float) * nf_topk_wave_words(p.upb, k);
-    return p;
-}
-
-int64_t nf_topk_ws_stripes(int64_t U, int64_t N, int k) {
-    const int64_t s = nf_make_topk_plan(U, N, k).stripes;
-    const int64_t ss = N >= 8 * nf_seed_cols(k) ? nf_make_topk_plan(U, nf_seed_cols(k), k, true).stripes : 0;
-    return s > ss ? s : ss;
-}
-
-size_t nf_topk_ws_bytes(int64_t stripes, int64_t U, int k) {
-    const int64_t l1 = (stripes + kTopkMergeGroup - 1) / kTopkMergeGroup;
-    return 2 * topk_part_bytes(stripes, U, k) + 2 * topk_part_bytes(l1, U, k);
-}
-
-int nf_launch_topk(const nf_args_topk& a, bool itemkey, const nf_topk_plan& p, hipStream_t s) {
-    nf_args_topk b = a;
-    b.users_per_block = p.upb;
-    return nf_dispatch<true>(b, itemkey, dim3((unsigned)p.gx, (unsigned)p.gy), p.list_bytes, s);
+    dim3 grid;
+    if (const int rc = tile_score_grid("cdr_natr_fullsort", a.U, a.N, kNfWaves, kNfUsers, &grid, &b.users_per_block)) return rc;
+    return nf_dispatch<false>(b, itemkey, grid, 0, s);
 }
 
 // the arguments both entries share; nothing is launched for a refused call
@@ -382,53 +259,25 @@ extern "C" int cdr_natr_fullsort(void* stream, int key_is_item, const float* su,
 }
 
 extern "C" int cdr_natr_fullsort_topk_workspace_bytes(int64_t U, int64_t N, int k, size_t* bytes) {
-    CDR_CHECK_ARG(bytes && U > 0 && N > 0 && N < ((int64_t)1 << 31) && U < ((int64_t)1 << 31) && k >= 1 && k <= 64);
-    *bytes = nf_topk_ws_bytes(nf_topk_ws_stripes(U, N, k), U, k);
-    return CDR_OK;
+    return topk_stripe_ws_query("cdr_natr_fullsort_topk_workspace_bytes", kNfTopkGeom, U, N, k, bytes);
 }
 
 extern "C" int cdr_natr_fullsort_topk(void* stream, int key_is_item, const float* su, int64_t ld_su, const float* key_tab, int64_t ld_key,
                                       const float* other_tab, int64_t ld_other, const int64_t* uid, int64_t U, int64_t N, int Dt,
                                       const float* w, int k, const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
                                       float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes) {
-    if (k < 1 || k > 64) { cdr_set_error("cdr_natr_fullsort_topk: k = %d outside 1..64", k); return CDR_EINVAL; }
+    if (const int rc = topk_check_k("cdr_natr_fullsort_topk", k)) return rc;
     const int rc0 = nf_check("cdr_natr_fullsort_topk", su, ld_su, key_tab, ld_key, other_tab, ld_other, uid, U, N, Dt, w);
     if (rc0) return rc0;
     CDR_CHECK_ARG(out_vals && out_idx && workspace);
     CDR_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));
-    const bool itemkey = key_is_item != 0;
-    const nf_topk_plan p = nf_make_topk_plan(U, N, k);
-    if (p.gy > 65535 || nf_make_topk_plan(U, nf_seed_cols(k), k, true).gy > 65535) {
-        cdr_set_error("cdr_natr_fullsort_topk: %lld users at k = %d need more than 65,535 user groups; evaluate them in batches", (long long)U, k);
-        return CDR_EINVAL;
-    }
-    const int64_t ws_stripes = nf_topk_ws_stripes(U, N, k);
-    const size_t need = nf_topk_ws_bytes(ws_stripes, U, k);
-    if (workspace_bytes < need) { cdr_set_error("cdr_natr_fullsort_topk: workspace %zu < %zu bytes", workspace_bytes, need); return CDR_EINVAL; }
-    const size_t part = topk_part_bytes(ws_stripes, U, k);
-    const size_t part1 = topk_part_bytes((ws_stripes + kTopkMergeGroup - 1) / kTopkMergeGroup, U, k);
-    float* pv = (float*)workspace;
-    int* pc = (int*)((char*)workspace + part);
-    float* pv1 = (float*)((char*)workspace + 2 * part);
-    int* pc1 = (int*)((char*)workspace + 2 * part + part1);
     nf_args_topk a{};
     static_cast<nf_args&>(a) = nf_fill(su, ld_su, key_tab, ld_key, other_tab, ld_other, uid, U, N, Dt, w);
-    a.tk = topk_out{k, 0, pv, pc, topk_mask{hist_indptr, hist_cols, exclude_first_col}};
     hipStream_t s = (hipStream_t)stream;
-    // SEEDED thresholds, as in cdr_conet_fullsort_topk: a first call over the first nf_seed_cols(k) columns (same mask) leaves each user's
-    // k-th value over the sample in out_vals[:, k - 1], a lower bound of the final one and the starting threshold of every stripe
-    if (N >= 8 * nf_seed_cols(k)) {
-        nf_args_topk sa = a;
-        sa.N = nf_seed_cols(k);
-        const nf_topk_plan sp = nf_make_topk_plan(U, sa.N, k, true);
-        int rc = nf_launch_topk(sa, itemkey, sp, s);
-        if (rc) return rc;
-        rc = topk_merge_launch(s, pv, pc, sp.stripes, U, k, pv1, pc1, out_vals, out_idx);
-        if (rc) return rc;
-        a.tk.seed = out_vals + (k - 1);
-        a.tk.seed_stride = k;
-    }
-    int rc = nf_launch_topk(a, itemkey, p, s);
-    if (rc) return rc;
-    return topk_merge_launch(s, pv, pc, p.stripes, U, k, pv1, pc1, out_vals, out_idx);
+    return topk_seeded_run("cdr_natr_fullsort_topk", kNfTopkGeom, s, U, N, k, topk_mask{hist_indptr, hist_cols, exclude_first_col}, out_vals,
+                           out_idx, workspace, workspace_bytes, [&](int64_t n_cols, const topk_stripe_plan& p, const topk_out& tk) {
+                               nf_args_topk b = a;
+                               b.N = n_cols; b.users_per_block = p.upb; b.tk = tk;
+                               return nf_dispatch<true>(b, key_is_item != 0, dim3((unsigned)p.gx, (unsigned)p.gy), p.lds, s);
+                           });
 }

@@ -1024,7 +1024,30 @@ def conet_fullsort(P, Q, weights, biases, wo, bo, out=None):
     return out
 
 
-_tower_topk_ws = {}
+_stripe_topk_ws = {}
+
+
+def _stripe_topk_call(entry, dev, U, N, k, args, hist_indptr, hist_cols, exclude_first_col):
+    """The tail the three one-launch fused top-k entries share: the workspace query (a refusal drops what the caller parked in
+    ``B_._alive``), one workspace per (entry, device, stream) that only grows, the outputs, and the call's common trailing arguments."""
+    need = ctypes.c_size_t(0)
+    try:
+        B_._check(getattr(B_.load(), entry + '_workspace_bytes')(U, int(N), int(k), ctypes.byref(need)), entry + '_workspace_bytes')
+    except RuntimeError:
+        B_._alive.clear()
+        raise
+    key = (entry, dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    wsp = _stripe_topk_ws.get(key)
+    if wsp is None or wsp.numel() < need.value:
+        wsp = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+        _stripe_topk_ws[key] = wsp
+    vals = torch.empty(U, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(U, k, device=dev, dtype=torch.int64)
+    B_.call(entry, *args, int(k), B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals), B_.i64(idx),
+            B_.raw(wsp), wsp.numel())
+    return vals, idx
+
+
 # Catalogue size from which the models' ``full_sort_topk`` takes the fused launch.  Measured (tools/mb_tower_topk.py, k = 10, U = 64 and
 # 1,024, both default towers): fused / unfused = 0.88-0.93 at 250,000 items and 0.89-0.91 at 1 M, but 1.06-1.15 at 81,920 (the smallest
 # catalogue whose thresholds are seeded from a sample) and 1.7-10 below that, where every list fills from -inf.  Below it the [U, N]
@@ -1044,23 +1067,12 @@ def conet_fullsort_topk(P, Q, weights, biases, wo, bo, k, hist_indptr=None, hist
     ws = [w.contiguous() for w in weights]
     bs = [b.contiguous() for b in biases]
     wo_, bo_ = wo.reshape(-1).contiguous(), bo.reshape(-1).contiguous()
-    dev = P.device
-    need = ctypes.c_size_t(0)
-    B_._check(B_.load().cdr_conet_fullsort_topk_workspace_bytes(U, N, int(k), ctypes.byref(need)), 'cdr_conet_fullsort_topk_workspace_bytes')
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    wsp = _tower_topk_ws.get(key)
-    if wsp is None or wsp.numel() < need.value:
-        wsp = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
-        _tower_topk_ws[key] = wsp
-    vals = torch.empty(U, k, device=dev, dtype=torch.float32)
-    idx = torch.empty(U, k, device=dev, dtype=torch.int64)
     dims = (ctypes.c_int * max(T, 1))(*[int(w.shape[0]) for w in ws])
     B_._alive.extend(ws + bs + [P, Q])
-    B_.call('cdr_conet_fullsort_topk', B_.stream(), B_._c_ptr(P.data_ptr()), P.stride(0), B_._c_ptr(Q.data_ptr()), Q.stride(0), U, N, h1, T, dims,
+    args = (B_.stream(), B_._c_ptr(P.data_ptr()), P.stride(0), B_._c_ptr(Q.data_ptr()), Q.stride(0), U, N, h1, T, dims,
             (ctypes.c_void_p * max(T, 1))(*[w.data_ptr() for w in ws]), (ctypes.c_void_p * max(T, 1))(*[b.data_ptr() for b in bs]),
-            B_.f32(wo_), B_.f32(bo_), int(k), B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals), B_.i64(idx),
-            B_.raw(wsp), wsp.numel())
-    return vals, idx
+            B_.f32(wo_), B_.f32(bo_))
+    return _stripe_topk_call('cdr_conet_fullsort_topk', P.device, U, N, k, args, hist_indptr, hist_cols, exclude_first_col)
 
 
 def deepapf_fullsort_supported(D):
@@ -1097,7 +1109,6 @@ def deepapf_fullsort(key_is_item, share, only, other, uid, N, n_overlap, W1, b1,
     return out
 
 
-_deepapf_topk_ws = {}
 # Catalogue size from which DeepAPF.full_sort_topk takes the fused launch.  Measured (tools/mb_deepapf_fullsort.py, k = 10, U = 64 and 1,024,
 # D = 64 and 128, both modes): fused / unfused = 1.19-1.55 at 81,920 items, 1.03-1.40 at 250,000 and 1.00-1.37 at 1 M -- the
 # scoring is compute bound (0.7 of the MFMA peak), so the [U, N] round trip the fusion saves is worth less than the sample call and the
@@ -1115,24 +1126,7 @@ def deepapf_fullsort_topk(key_is_item, share, only, other, uid, N, n_overlap, W1
     epilogue (cdr_deepapf_fullsort_topk).  Values are bit-equal to the unfused scores; (-inf, -1) pads a row with fewer than k columns left."""
     _dev_check(hist_indptr, hist_cols)
     U, D, args = _deepapf_fullsort_args(key_is_item, share, only, other, uid, N, n_overlap, W1, b1, w2, wp)
-    dev = share.device
-    need = ctypes.c_size_t(0)
-    try:
-        B_._check(B_.load().cdr_deepapf_fullsort_topk_workspace_bytes(U, int(N), int(k), ctypes.byref(need)),
-                  'cdr_deepapf_fullsort_topk_workspace_bytes')
-    except RuntimeError:
-        B_._alive.clear()
-        raise
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    wsp = _deepapf_topk_ws.get(key)
-    if wsp is None or wsp.numel() < need.value:
-        wsp = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
-        _deepapf_topk_ws[key] = wsp
-    vals = torch.empty(U, k, device=dev, dtype=torch.float32)
-    idx = torch.empty(U, k, device=dev, dtype=torch.int64)
-    B_.call('cdr_deepapf_fullsort_topk', *args, int(k), B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals),
-            B_.i64(idx), B_.raw(wsp), wsp.numel())
-    return vals, idx
+    return _stripe_topk_call('cdr_deepapf_fullsort_topk', share.device, U, N, k, args, hist_indptr, hist_cols, exclude_first_col)
 
 
 NATR_SUMMARY_BYTES = 64 << 20        # budget of one [chunk, L, max(Ds, Dt)] intermediate of natr_history_summary
@@ -1204,7 +1198,6 @@ def natr_fullsort(key_is_item, su, key_tab, other_tab, uid, N, w, out=None):
     return out
 
 
-_natr_topk_ws = {}
 # Catalogue size from which NATR.full_sort_topk takes the fused launch: the smallest measured N from which the fused launch beats
 # scores + mask + torch.topk at every measured U by more than the run-to-run spread (tools/mb_natr_fullsort.py topk, k = 10, U = 64 and
 # 1,024, Dt = 64, both modes; table in DESIGN.md 4.4.3).  fused / unfused = 1.11-1.13 at U = 64 and 0.82-0.83 at U = 1,024 for 100,000
@@ -1221,24 +1214,7 @@ def natr_fullsort_topk(key_is_item, su, key_tab, other_tab, uid, N, w, k, hist_i
     epilogue (cdr_natr_fullsort_topk).  Values are bit-equal to the unfused scores; (-inf, -1) pads a row with fewer than k columns left."""
     _dev_check(hist_indptr, hist_cols)
     U, args = _natr_fullsort_args(key_is_item, su, key_tab, other_tab, uid, N, w)
-    dev = su.device
-    need = ctypes.c_size_t(0)
-    try:
-        B_._check(B_.load().cdr_natr_fullsort_topk_workspace_bytes(U, int(N), int(k), ctypes.byref(need)),
-                  'cdr_natr_fullsort_topk_workspace_bytes')
-    except RuntimeError:
-        B_._alive.clear()
-        raise
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    wsp = _natr_topk_ws.get(key)
-    if wsp is None or wsp.numel() < need.value:
-        wsp = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
-        _natr_topk_ws[key] = wsp
-    vals = torch.empty(U, k, device=dev, dtype=torch.float32)
-    idx = torch.empty(U, k, device=dev, dtype=torch.int64)
-    B_.call('cdr_natr_fullsort_topk', *args, int(k), B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals),
-            B_.i64(idx), B_.raw(wsp), wsp.numel())
-    return vals, idx
+    return _stripe_topk_call('cdr_natr_fullsort_topk', su.device, U, N, k, args, hist_indptr, hist_cols, exclude_first_col)
 
 
 def masked_topk(scores, k, hist_indptr=None, hist_cols=None, exclude_first_col=True):

@@ -30,6 +30,8 @@ CASES = [(8, 5, 77, 5, 3),                   # tail tile, one pass of 32 feature
          (12, 7, 100, 1, 4),                 # a width that is no multiple of 8, k = 1
          (64, 3, 300001, 10, 2),             # more than one round of tiles per workgroup; the seeded thresholds
          (64, 40, 9001, 20, 9001)]           # nobody masked
+TOPK_ONLY = [(64, 33, 1, 10, 0),             # a one-item catalogue: padding
+             (64, 160, 81921, 10, 40000)]    # the seeded path with three user groups, just over its threshold of 81,920 items; a partial last tile
 MODES = [False, True]                        # key_is_item: overlap_users, overlap_items
 
 
@@ -95,12 +97,12 @@ def _check(masked, k, got_v, got_i):
 
 
 @pytest.mark.parametrize('key_is_item', MODES)
-@pytest.mark.parametrize('D,U,N,k,n_overlap', CASES + [(64, 33, 1, 10, 0)])
+@pytest.mark.parametrize('D,U,N,k,n_overlap', CASES + TOPK_ONLY)
 def test_deepapf_fullsort_topk_matches_topk_of_masked_scores(D, U, N, k, n_overlap, key_is_item):
     """Fused mask + top-k == torch.topk over the evaluation-masked output of ``deepapf_fullsort`` on the same operands: one scoring body,
     two epilogues, so the values are bit-equal; columns may differ only between exactly tied scores.  The history holds each user's 7 best
     columns and 30 random ones, so the mask decides the result; a second call runs without history and keeps the PAD column.  The last
-    case is a one-item catalogue: the padding contract."""
+    two cases: a one-item catalogue (the padding contract), and seeded thresholds with several user groups."""
     from recbole_cdr_amd import functional as F_
     c, full = _case(D, U, N, n_overlap, key_is_item)
     g = torch.Generator().manual_seed(U + N)

@@ -30,7 +30,8 @@ CASES = [(8, 16, 3, 5, 77, 5),               # tail tile
          (64, 64, 50, 70, 4001, 10),         # the defaults; the summary chunked
          (128, 32, 9, 40, 4000, 50),         # the widest instantiation
          (64, 16, 4, 3, 300001, 10)]         # more than one round of tiles per workgroup; the seeded thresholds
-TOPK_ONLY = [(64, 8, 2, 33, 1, 10)]          # every column masked, all padding
+TOPK_ONLY = [(64, 8, 2, 33, 1, 10),          # every column masked, all padding
+             (64, 16, 4, 160, 81921, 10)]    # the seeded path with three user groups, just over its threshold of 81,920 items; a partial last tile
 MODES = [False, True]                        # key_is_item: overlap_items, overlap_users
 
 

@@ -64,7 +64,8 @@ CASES = [(16, [64, 32, 16, 8], 5, 77, 10),           # tail tile
          (16, [20, 32, 32, 32], 33, 2049, 64),       # k larger than a tile, k = 64 (24 users per workgroup: two user groups), widest tail
          (128, [64, 32, 16, 8], 130, 4000, 50),      # several user groups at a large k, C3's D
          (64, [32, 16], 3, 300001, 10),              # more than one round of tiles per workgroup (the top-k grid is at most 512 x 128 items; the seeded path)
-         (64, [64, 8], 33, 1, 10)]                   # a one-item catalogue: padding
+         (64, [64, 8], 33, 1, 10),                   # a one-item catalogue: padding
+         (64, [32, 16], 160, 81921, 10)]             # the seeded path with two user groups, just over its threshold of 81,920 items; a partial last tile
 
 
 @pytest.mark.parametrize('D,layers,U,N,k', CASES)
