@@ -221,6 +221,29 @@ int cdr_fullsort_topk_f32(void* stream, const float* user_e, int64_t U, int D,
 int cdr_fullsort_neg_sqdist_f32(void* stream, const float* user_e, int64_t U, int D,
                                 const float* items, int64_t N, float* norm_scratch, float* scores);
 
+/* out[r] = sum_d X[r,d]^2: the row norms the two distance entries form (the same kernel, so the same bits). */
+int cdr_row_sqnorm_f32(void* stream, const float* X, int64_t rows, int D, float* out /* [rows] */);
+
+/* Mask + top-k fused after SSCDR's distance scoring (sscdr.py:228-259: full_sort_predict, then the trainer's two masks and
+ * torch.topk): cdr_fullsort_topk_f32 with the score -(((-2 <u,i>) + |u|^2) + |i|^2), the item operand as <= 2 row ranges so
+ * that the reference's torch.cat never happens.  out_vals [U, k] descending and bit-equal to the k largest unmasked entries
+ * of the matrix cdr_fullsort_neg_sqdist_f32 writes for user_e against the concatenated slabs; out_idx their columns, or
+ * (-inf, -1) where fewer than k unmasked columns are left.  Ties between equal scores resolve to the column met first.  A NaN
+ * score never enters a list.  1 <= k <= 64, n0 + n1 < 2^31; out-of-range arguments get
+ * CDR_EINVAL with an error text and nothing is launched.
+ * col_sqnorm: [n0 + n1] from cdr_row_sqnorm_f32 of the slabs (what an evaluation computes once for all of its user batches),
+ * or NULL: computed into the workspace.  The user row norms are always computed into the workspace.
+ * Workspace: cdr_fullsort_topk_workspace_bytes(U, D, n0, n1, k) + ((4 * (U + n0 + n1) + 255) & ~255) bytes.
+ * U <= 8 with 16 <= D <= 256, D % 4 == 0 -- where the dot-product entry streams a GEMV, whose sums are not the MFMA's bits
+ * and whose workspace holds no score staging -- is refused with CDR_EINVAL: score those few rows with
+ * cdr_fullsort_neg_sqdist_f32.                                                                                          */
+int cdr_fullsort_neg_sqdist_topk_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int k, size_t* bytes);
+int cdr_fullsort_neg_sqdist_topk_f32(void* stream, const float* user_e, int64_t U, int D,
+                                     const float* slab0, int64_t n0, const float* slab1, int64_t n1,
+                                     const float* col_sqnorm, int k,
+                                     const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                                     float* out_vals /* [U,k] */, int64_t* out_idx /* [U,k] */, void* workspace, size_t workspace_bytes);
+
 /* ---- elementwise helpers used by the model mirrors --------------------------------------------------------- */
 /* d/dx of act given y = act(x): gx = gy * act'(y)  (tanh: 1-y^2, relu: y>0, sigmoid: y(1-y)) ; in place allowed */
 int cdr_act_bwd(void* stream, int act, const float* y, const float* gy, float* gx, int64_t n);

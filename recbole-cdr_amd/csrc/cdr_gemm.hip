@@ -13,6 +13,7 @@
 // A-operand rows = M side (users / batch rows), B-operand rows = N side (items / output features), so a lane's
 // accumulator column is an N index and every store instruction writes 32 consecutive floats per half-wave.
 #include <stdlib.h>
+#include <type_traits>
 #include "cdr_common.h"
 #include "cdr_mfma.h"
 #include "cdr_topk.h"
@@ -432,10 +433,20 @@ constexpr int kTopkQueue = 256;
 #define TOPK_TEST_FIRST_STEP 0
 #endif
 
-template <int MT, int K, bool TOPK>
+// SQDIST (with TOPK): the scores are SSCDR's distances -(((-2 <u,i>) + |u|^2) + |i|^2) (gemm_f32_kernel's EPI_SQDIST, same expression
+// and association), formed once behind the MFMA phase so that thresholds, queues and the LDS score tile only ever see distances.  The
+// two norm vectors ride behind the lists' arguments in these instantiations only: the others keep their argument block and their code.
+struct topk_out_sq : topk_out {
+    const float* rown;          // [M] squared norms of the user rows
+    const float* coln;          // squared norms of this slab's item rows (index 0 = the slab's first row)
+};
+
+template <int MT, int K, bool TOPK, bool SQDIST = false>
 __global__ __launch_bounds__(256, 1) void score_persistent_kernel(const float* __restrict__ A, int M,
                                                                   const float* __restrict__ B, int NT,
-                                                                  float* __restrict__ C, int64_t ldc, topk_out tk) {
+                                                                  float* __restrict__ C, int64_t ldc,
+                                                                  std::conditional_t<SQDIST, topk_out_sq, topk_out> tk) {
+    static_assert(TOPK || !SQDIST, "the distance epilogue exists in the top-k form only");
     constexpr int BM = 64 * MT;            // 2 waves along M, MT 32-row tiles each
     constexpr int BN = 64;                 // 2 waves along N, one 32-col tile each
     constexpr int KS = K / 8;              // K steps of 8 (one float4 per lane per step feeds 4 MFMAs)
@@ -489,6 +500,9 @@ __global__ __launch_bounds__(256, 1) void score_persistent_kernel(const float* _
     volatile int* qc = reinterpret_cast<volatile int*>(qv + QC);
     volatile int* qu = qc + QC;
     int* qcnt = reinterpret_cast<int*>(const_cast<float*>(q0) + 4 * QC * 3);                  // [4] queue fills, [4] = overflow flag, [5] = attention flag (a queue half full / overflowed)
+    // SQDIST: the user block's BM row norms behind everything else (16-byte aligned: every region in front is a multiple of four words).
+    // Not in registers: the wave's 16 MT of them across the phase would cost what the 4 MT thresholds did (see below)
+    [[maybe_unused]] float* rn_l = reinterpret_cast<float*>(qcnt + 8);
 
     for (int mb = mslot; mb < MB; mb += MBc) {
         const int m0 = mb * BM + wm * 32 * MT;
@@ -498,6 +512,12 @@ __global__ __launch_bounds__(256, 1) void score_persistent_kernel(const float* _
             for (int i = tid; i < BM; i += 256) thr_l[i] = topk_seed_thr(tk, (int64_t)mb * BM + i, M);
             for (int i = tid; i < BM * tk.k; i += 256) { lv[i] = -INFINITY; lc[i] = -1; }
             if (tid < 6) qcnt[tid] = 0;
+            if constexpr (SQDIST) {            // rows past M: 0 (never read from memory; validmask / the scans drop them anyway)
+                for (int i = tid; i < BM; i += 256) {
+                    const int64_t u = (int64_t)mb * BM + i;
+                    rn_l[i] = u < M ? tk.rown[u] : 0.f;
+                }
+            }
         }
         // this wave's user rows, whole K, in registers (loaded once per user block)
         float4 a[MT][KS];
@@ -518,6 +538,9 @@ __global__ __launch_bounds__(256, 1) void score_persistent_kernel(const float* _
 #pragma unroll
             for (int q = 0; q < NQ; ++q) st4(smem + st_lds[q], ld4(bp + st_gl[q]));
         }
+        // SQDIST: the norm of this lane's column of the tile in the phase, and of the prefetched tile (loaded with its rows)
+        [[maybe_unused]] float cn_cur = 0.f, cn_next = 0.f;
+        if constexpr (SQDIST) { if (tile < tile_end) cn_cur = tk.coln[(int64_t)tile * BN + wn * 32 + li]; }
         __syncthreads();
         // PIPE (score output, two accumulator tiles per wave): the scores of tile i are written while tile i+1's MFMAs run
         // (they wait in `prev`), not between two MFMA phases.  Same-box A/B: +4 % (D = 128) / +17 % (D = 64) at U = 1,024; with
@@ -575,6 +598,7 @@ __global__ __launch_bounds__(256, 1) void score_persistent_kernel(const float* _
                 const float* bp = B + (int64_t)(has_next ? next : tile) * BN * K;
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) stage[q] = ld4(bp + st_gl[q]);
+                if constexpr (SQDIST) cn_next = tk.coln[(int64_t)(has_next ? next : tile) * BN + wn * 32 + li];
             }
             // hipcc otherwise SINKS these loads below the MFMA phase (register pressure heuristic) and serialises
             // load -> wait -> ds_write after it: 1.7x slower end to end.  Pin the issue point.
@@ -703,6 +727,23 @@ __global__ __launch_bounds__(256, 1) void score_persistent_kernel(const float* _
                 float* dst = smem + (buf ^ 1) * BUF;
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) st4(dst + st_lds[q], stage[q]);
+            }
+            if constexpr (SQDIST) {
+                // dot products -> distances, once: the hand-over to `prev`, slow_scan and the tail group all read them from `acc` / `prev`.
+                // Register r is user row (r & 3) + 8 (r >> 2) + 4 lh of its 32-row tile: four consecutive rows per 16-byte LDS read, the
+                // addressing test_group uses for the thresholds.  (A NaN score fails every `>` below: it never enters a queue, a list or a threshold.)
+                const float* rn_base = rn_l + wm * 32 * MT + 4 * lh;
+#pragma unroll
+                for (int t = 0; t < MT; ++t)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const float4 rn = *reinterpret_cast<const float4*>(rn_base + 32 * t + 8 * g);
+                        acc[t][4 * g] = -(((-2.0f * acc[t][4 * g]) + rn.x) + cn_cur);
+                        acc[t][4 * g + 1] = -(((-2.0f * acc[t][4 * g + 1]) + rn.y) + cn_cur);
+                        acc[t][4 * g + 2] = -(((-2.0f * acc[t][4 * g + 2]) + rn.z) + cn_cur);
+                        acc[t][4 * g + 3] = -(((-2.0f * acc[t][4 * g + 3]) + rn.w) + cn_cur);
+                    }
+                cn_cur = cn_next;
             }
             // epilogue: lane column = item ; register r -> user row (r&3) + 8*(r>>2) + 4*lh
             if (!TOPK) {
@@ -970,9 +1011,12 @@ static int64_t topk_small_u() {
     return v;
 }
 
-static size_t fused_lds_bytes(int D, int MT, int k) {
+// `sqdist`: BM more floats, the user block's row norms.  (They never decide whether a slab is planned fused -- the limit below is passed
+// at k = 49 with MT = 2, D = 128 in either form, 49 x 1,024 B being the step -- so one plan, and one workspace layout, serves both scores.)
+static size_t fused_lds_bytes(int D, int MT, int k, bool sqdist = false) {
     const int BM = 64 * MT;
-    return sizeof(float) * ((size_t)2 * 64 * (D + 4) + (size_t)BM * 65 + BM + (size_t)BM * k * 2 + (size_t)4 * kTopkQueue * 3 + 8);
+    return sizeof(float) * ((size_t)2 * 64 * (D + 4) + (size_t)BM * 65 + BM + (size_t)BM * k * 2 + (size_t)4 * kTopkQueue * 3 + 8 +
+                            (sqdist ? BM : 0));
 }
 
 static topk_plan make_topk_plan(int64_t U, int D, const int64_t n[2], int k, const float* users, const float* const slab[2]) {
@@ -1024,7 +1068,14 @@ static size_t topk_ws_bytes(const topk_plan& p, int64_t U, int k) {
     return 2 * topk_part_bytes(p.producers, U, k) + 2 * topk_part_bytes(l1, U, k) + (((size_t)p.score_floats * 4 + 255) & ~(size_t)255);
 }
 
-static int score_block(hipStream_t s, const float* user_e, int64_t U, int D, const float* items, int64_t n, float* scores, int64_t ld) {
+// The score behind the top-k.  rown == nullptr: dot products.  Else SSCDR's distances from the squared row norms of the users and of the
+// concatenated slabs (coln[global column]).
+struct topk_epi { const float* rown; const float* coln; };
+
+// one block of columns into the staging buffer, dot products or distances (`coln`: the block's first column)
+static int score_block(hipStream_t s, const float* user_e, int64_t U, int D, const float* items, int64_t n, float* scores, int64_t ld,
+                       const float* rown = nullptr, const float* coln = nullptr) {
+    if (rown) return launch<false, true, true>(s, U, n, D, user_e, D, items, D, scores, ld, nullptr, CDR_ACT_NONE, 0, rown, coln);
     return gemv_ok(U, D, user_e, items) ? gemv_dispatch(s, user_e, (int)U, D, items, n, scores, ld)
            : score_persistent_ok(U, D, n, user_e, items) ? launch_score_persistent(s, user_e, U, D, items, n, scores, ld)
            : launch<false, true, false>(s, U, n, D, user_e, D, items, D, scores, ld, nullptr, CDR_ACT_NONE, 0, nullptr, nullptr);
@@ -1040,27 +1091,33 @@ extern "C" int cdr_fullsort_topk_workspace_bytes(int64_t U, int D, int64_t n0, i
     return CDR_OK;
 }
 
-static int fullsort_topk_impl(void* stream, const float* user_e, int64_t U, int D, const float* slab0, int64_t n0,
-                              const float* slab1, int64_t n1, int k, const int64_t* hist_indptr,
+// One top-k call over the slabs (`fn`: the entry it serves, for the error texts).  With `epi.rown` the score is the distance: the fused
+// kernel's SQDIST instantiations, and the distance GEMM in front of topk_rows_kernel wherever the dot-product form stages scores.  The
+// streaming GEMV has no distance form (its sums run in another order than the MFMA's: not the bits of cdr_fullsort_neg_sqdist_f32), and
+// the plan gives its shapes no score staging: the distance entry refuses them before it comes here.
+static int fullsort_topk_impl(const char* fn, const topk_epi& epi, void* stream, const float* user_e, int64_t U, int D, const float* slab0,
+                              int64_t n0, const float* slab1, int64_t n1, int k, const int64_t* hist_indptr,
                               const int64_t* hist_cols, int exclude_first_col, float* out_vals, int64_t* out_idx,
                               void* workspace, size_t workspace_bytes, const float* seed, int64_t seed_stride) {
-    CDR_CHECK_ARG(user_e && out_vals && out_idx && workspace && U > 0 && D > 0 && k >= 1 && k <= 64);
-    CDR_CHECK_ARG((slab0 && n0 > 0) || (slab1 && n1 > 0));
-    CDR_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));
+#define TOPK_CHECK_ARG(cond) do { if (!(cond)) { cdr_set_error("%s: invalid argument: %s", fn, #cond); return CDR_EINVAL; } } while (0)
+    TOPK_CHECK_ARG(user_e && out_vals && out_idx && workspace && U > 0 && D > 0 && k >= 1 && k <= 64);
+    TOPK_CHECK_ARG((slab0 && n0 > 0) || (slab1 && n1 > 0));
+    TOPK_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));
     hipStream_t s = (hipStream_t)stream;
     const int64_t n[2] = {slab0 ? n0 : 0, slab1 ? n1 : 0};
     const float* const slab[2] = {slab0, slab1};
-    CDR_CHECK_ARG(n[0] + n[1] < ((int64_t)1 << 31) && n[0] + n[1] >= k);
+    TOPK_CHECK_ARG(n[0] + n[1] < ((int64_t)1 << 31) && n[0] + n[1] >= k);
+#undef TOPK_CHECK_ARG
     // the workspace was sized without the pointers (alignment unknown): plan the same way, then demote unaligned slabs
     const float* const none[2] = {nullptr, nullptr};
     topk_plan p = make_topk_plan(U, D, n, k, nullptr, none);
     for (int i = 0; i < 2; ++i)
         if (p.fused[i] && ((((uintptr_t)user_e | (uintptr_t)slab[i]) & 15) != 0)) {
-            cdr_set_error("cdr_fullsort_topk_f32: operands must be 16-byte aligned");
+            cdr_set_error("%s: operands must be 16-byte aligned", fn);
             return CDR_EINVAL;
         }
     const size_t need = topk_ws_bytes(p, U, k);
-    if (workspace_bytes < need) { cdr_set_error("cdr_fullsort_topk_f32: workspace %zu < %zu bytes", workspace_bytes, need); return CDR_EINVAL; }
+    if (workspace_bytes < need) { cdr_set_error("%s: workspace %zu < %zu bytes", fn, workspace_bytes, need); return CDR_EINVAL; }
     const size_t part = topk_part_bytes(p.producers, U, k);
     const int64_t l1 = (p.producers + kTopkMergeGroup - 1) / kTopkMergeGroup;
     const size_t part1 = topk_part_bytes(l1, U, k);
@@ -1079,16 +1136,26 @@ static int fullsort_topk_impl(void* stream, const float* user_e, int64_t U, int 
             if (rc) return rc;
             prod += p.gemv_blocks[i];
         } else if (p.gemv[i]) {
-            cdr_set_error("cdr_fullsort_topk_f32: operands must be 16-byte aligned");
+            cdr_set_error("%s: operands must be 16-byte aligned", fn);
             return CDR_EINVAL;
         } else if (p.fused[i]) {
-            topk_out tk{k, (int)col_off, pv + prod * U * k, pc + prod * U * k, mk};
+            topk_out_sq tk{};
+            tk.k = k; tk.col_off = (int)col_off; tk.pv = pv + prod * U * k; tk.pc = pc + prod * U * k; tk.mk = mk;
             tk.seed = seed; tk.seed_stride = seed_stride;
+            tk.rown = epi.rown; tk.coln = epi.rown ? epi.coln + col_off : nullptr;
             const int NT = (int)(n[i] / 64);
             const unsigned grid = CDR_NUM_CU;
             const bool small = U <= topk_small_u();
-            const size_t lds = fused_lds_bytes(D, small ? 1 : 2, k);
-            if (D == 64) {
+            const size_t lds = fused_lds_bytes(D, small ? 1 : 2, k, epi.rown != nullptr);
+            if (epi.rown) {
+                if (D == 64) {
+                    if (small) score_persistent_kernel<1, 64, true, true><<<dim3(grid), dim3(256), lds, s>>>(user_e, (int)U, slab[i], NT, nullptr, 0, tk);
+                    else score_persistent_kernel<2, 64, true, true><<<dim3(grid), dim3(256), lds, s>>>(user_e, (int)U, slab[i], NT, nullptr, 0, tk);
+                } else {
+                    if (small) score_persistent_kernel<1, 128, true, true><<<dim3(grid), dim3(256), lds, s>>>(user_e, (int)U, slab[i], NT, nullptr, 0, tk);
+                    else score_persistent_kernel<2, 128, true, true><<<dim3(grid), dim3(256), lds, s>>>(user_e, (int)U, slab[i], NT, nullptr, 0, tk);
+                }
+            } else if (D == 64) {
                 if (small) score_persistent_kernel<1, 64, true><<<dim3(grid), dim3(256), lds, s>>>(user_e, (int)U, slab[i], NT, nullptr, 0, tk);
                 else score_persistent_kernel<2, 64, true><<<dim3(grid), dim3(256), lds, s>>>(user_e, (int)U, slab[i], NT, nullptr, 0, tk);
             } else {
@@ -1099,8 +1166,10 @@ static int fullsort_topk_impl(void* stream, const float* user_e, int64_t U, int 
             prod += p.stripes[i];
             const int64_t tail = n[i] - p.fused_cols[i];
             if (tail > 0) {
-                int rc = launch<false, true, false>(s, U, tail, D, user_e, D, slab[i] + p.fused_cols[i] * D, D, sbuf, tail, nullptr,
-                                                    CDR_ACT_NONE, 0, nullptr, nullptr);
+                const int64_t c = p.fused_cols[i];
+                int rc = epi.rown ? score_block(s, user_e, U, D, slab[i] + c * D, tail, sbuf, tail, epi.rown, epi.coln + col_off + c)
+                                  : launch<false, true, false>(s, U, tail, D, user_e, D, slab[i] + c * D, D, sbuf, tail, nullptr,
+                                                               CDR_ACT_NONE, 0, nullptr, nullptr);
                 if (rc) return rc;
                 topk_rows_kernel<<<dim3((unsigned)((U + 3) / 4)), dim3(256), 0, s>>>(sbuf, tail, U, tail, tail, (int)(col_off + p.fused_cols[i]),
                                                                                     k, mk, pv, pc, prod);
@@ -1110,7 +1179,7 @@ static int fullsort_topk_impl(void* stream, const float* user_e, int64_t U, int 
         } else {
             for (int64_t c = 0; c < n[i]; c += p.pass_cols) {
                 const int64_t cn = n[i] - c < p.pass_cols ? n[i] - c : p.pass_cols;
-                int rc = score_block(s, user_e, U, D, slab[i] + c * D, cn, sbuf, cn);
+                int rc = score_block(s, user_e, U, D, slab[i] + c * D, cn, sbuf, cn, epi.rown, epi.rown ? epi.coln + col_off + c : nullptr);
                 if (rc) return rc;
                 const int64_t chunks = (cn + kTopkSub - 1) / kTopkSub;
                 topk_rows_kernel<<<dim3((unsigned)((U * chunks + 3) / 4)), dim3(256), 0, s>>>(sbuf, cn, U, cn, kTopkSub, (int)(col_off + c), k,
@@ -1132,25 +1201,45 @@ static int fullsort_topk_impl(void* stream, const float* user_e, int64_t U, int 
 // entry of the final top-k is >= its user's seed and passes in its own stripe; a stripe's list may end up shorter than k, which the
 // merges already handle (-inf / -1 fillers never enter).
 constexpr int64_t kTopkSeedCols = 65536;
+// The sample is a subset of the columns whatever the score is, so the distance entry shares the driver.
+static int fullsort_topk_seeded(const char* fn, const topk_epi& epi, void* stream, const float* user_e, int64_t U, int D, const float* slab0,
+                                int64_t n0, const float* slab1, int64_t n1, int k, const int64_t* hist_indptr,
+                                const int64_t* hist_cols, int exclude_first_col, float* out_vals, int64_t* out_idx,
+                                void* workspace, size_t workspace_bytes) {
+    static const bool seeding = [] { const char* e = getenv("CDR_TOPK_SEED"); return !(e && e[0] == '0'); }();
+    const bool first0 = slab0 && n0 > 0;
+    const float* fs = first0 ? slab0 : slab1;
+    const int64_t fn_cols = first0 ? n0 : n1;
+    if (seeding && fs && U > 32 && (D == 64 || D == 128) && fn_cols >= 16 * kTopkSeedCols && k <= kTopkSeedCols / 64 &&
+        ((((uintptr_t)user_e | (uintptr_t)fs) & 15) == 0)) {
+        // the sample call: same users, same mask, the first columns of the first slab (global columns [0, kTopkSeedCols))
+        int rc = fullsort_topk_impl(fn, epi, stream, user_e, U, D, fs, kTopkSeedCols, nullptr, 0, k, hist_indptr, hist_cols, exclude_first_col, out_vals,
+                                    out_idx, workspace, workspace_bytes, nullptr, 0);
+        if (rc) return rc;
+        return fullsort_topk_impl(fn, epi, stream, user_e, U, D, slab0, n0, slab1, n1, k, hist_indptr, hist_cols, exclude_first_col, out_vals, out_idx,
+                                  workspace, workspace_bytes, out_vals + (k - 1), k);
+    }
+    return fullsort_topk_impl(fn, epi, stream, user_e, U, D, slab0, n0, slab1, n1, k, hist_indptr, hist_cols, exclude_first_col, out_vals, out_idx,
+                              workspace, workspace_bytes, nullptr, 0);
+}
+
 extern "C" int cdr_fullsort_topk_f32(void* stream, const float* user_e, int64_t U, int D, const float* slab0, int64_t n0,
                                      const float* slab1, int64_t n1, int k, const int64_t* hist_indptr,
                                      const int64_t* hist_cols, int exclude_first_col, float* out_vals, int64_t* out_idx,
                                      void* workspace, size_t workspace_bytes) {
-    static const bool seeding = [] { const char* e = getenv("CDR_TOPK_SEED"); return !(e && e[0] == '0'); }();
-    const bool first0 = slab0 && n0 > 0;
-    const float* fs = first0 ? slab0 : slab1;
-    const int64_t fn = first0 ? n0 : n1;
-    if (seeding && fs && U > 32 && (D == 64 || D == 128) && fn >= 16 * kTopkSeedCols && k <= kTopkSeedCols / 64 &&
-        ((((uintptr_t)user_e | (uintptr_t)fs) & 15) == 0)) {
-        // the sample call: same users, same mask, the first columns of the first slab (global columns [0, kTopkSeedCols))
-        int rc = fullsort_topk_impl(stream, user_e, U, D, fs, kTopkSeedCols, nullptr, 0, k, hist_indptr, hist_cols, exclude_first_col, out_vals, out_idx,
-                                    workspace, workspace_bytes, nullptr, 0);
-        if (rc) return rc;
-        return fullsort_topk_impl(stream, user_e, U, D, slab0, n0, slab1, n1, k, hist_indptr, hist_cols, exclude_first_col, out_vals, out_idx, workspace,
-                                  workspace_bytes, out_vals + (k - 1), k);
-    }
-    return fullsort_topk_impl(stream, user_e, U, D, slab0, n0, slab1, n1, k, hist_indptr, hist_cols, exclude_first_col, out_vals, out_idx, workspace,
-                              workspace_bytes, nullptr, 0);
+    return fullsort_topk_seeded(__func__, topk_epi{nullptr, nullptr}, stream, user_e, U, D, slab0, n0, slab1, n1, k, hist_indptr, hist_cols,
+                                exclude_first_col, out_vals, out_idx, workspace, workspace_bytes);
+}
+
+static int row_sqnorm_launch(hipStream_t s, const float* X, int64_t rows, int D, float* out) {
+    row_sqnorm_kernel<<<dim3((unsigned)((rows + 3) / 4 > 2048 ? 2048 : (rows + 3) / 4)), dim3(256), 0, s>>>(X, rows, D, out);
+    CDR_LAUNCH_CHECK();
+    return CDR_OK;
+}
+
+extern "C" int cdr_row_sqnorm_f32(void* stream, const float* X, int64_t rows, int D, float* out) {
+    CDR_CHECK_ARG(X && out && rows > 0 && D > 0);
+    return row_sqnorm_launch((hipStream_t)stream, X, rows, D, out);
 }
 
 extern "C" int cdr_fullsort_neg_sqdist_f32(void* stream, const float* user_e, int64_t U, int D, const float* items,
@@ -1159,7 +1248,54 @@ extern "C" int cdr_fullsort_neg_sqdist_f32(void* stream, const float* user_e, in
     hipStream_t s = (hipStream_t)stream;
     float* rown = norm_scratch;
     float* coln = norm_scratch + U;
-    row_sqnorm_kernel<<<dim3((unsigned)((U + 3) / 4 > 2048 ? 2048 : (U + 3) / 4)), dim3(256), 0, s>>>(user_e, U, D, rown);
-    row_sqnorm_kernel<<<dim3((unsigned)((N + 3) / 4 > 2048 ? 2048 : (N + 3) / 4)), dim3(256), 0, s>>>(items, N, D, coln);
+    if (int rc = row_sqnorm_launch(s, user_e, U, D, rown)) return rc;
+    if (int rc = row_sqnorm_launch(s, items, N, D, coln)) return rc;
     return launch<false, true, true>(s, U, N, D, user_e, D, items, D, scores, N, nullptr, CDR_ACT_NONE, 0, rown, coln);
+}
+
+// ---- SSCDR's distances under the fused mask + top-k --------------------------------------------------------------------------------
+// workspace = the dot-product entry's (same plan, same lists) | user row norms [U] | column norms [n0 + n1]
+static size_t sqdist_norm_bytes(int64_t U, int64_t N) { return ((size_t)4 * (size_t)(U + N) + 255) & ~(size_t)255; }
+
+extern "C" int cdr_fullsort_neg_sqdist_topk_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int k, size_t* bytes) {
+    CDR_CHECK_ARG(bytes && U > 0 && D > 0 && k >= 1 && k <= 64 && n0 >= 0 && n1 >= 0 && n0 + n1 > 0);
+    const int64_t n[2] = {n0, n1};
+    const float* const slab[2] = {nullptr, nullptr};
+    *bytes = topk_ws_bytes(make_topk_plan(U, D, n, k, nullptr, slab), U, k) + sqdist_norm_bytes(U, n0 + n1);
+    return CDR_OK;
+}
+
+extern "C" int cdr_fullsort_neg_sqdist_topk_f32(void* stream, const float* user_e, int64_t U, int D, const float* slab0, int64_t n0,
+                                                const float* slab1, int64_t n1, const float* col_sqnorm, int k,
+                                                const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                                                float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes) {
+    CDR_CHECK_ARG(user_e && out_vals && out_idx && workspace && U > 0 && D > 0 && k >= 1 && k <= 64);
+    CDR_CHECK_ARG((slab0 && n0 > 0) || (slab1 && n1 > 0));
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n[2] = {slab0 ? n0 : 0, slab1 ? n1 : 0};
+    CDR_CHECK_ARG(n[0] >= 0 && n[1] >= 0 && n[0] + n[1] < ((int64_t)1 << 31));
+    const float* const none[2] = {nullptr, nullptr};
+    const topk_plan p = make_topk_plan(U, D, n, k, nullptr, none);
+    const size_t lists = topk_ws_bytes(p, U, k), need = lists + sqdist_norm_bytes(U, n[0] + n[1]);
+    if (workspace_bytes < need) { cdr_set_error("%s: workspace %zu < %zu bytes", __func__, workspace_bytes, need); return CDR_EINVAL; }
+    CDR_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));
+    CDR_CHECK_ARG(n[0] + n[1] >= k);
+    for (int i = 0; i < 2; ++i)
+        if (p.fused[i] && ((((uintptr_t)user_e | (uintptr_t)(i ? slab1 : slab0)) & 15) != 0)) {
+            cdr_set_error("%s: operands must be 16-byte aligned", __func__);
+            return CDR_EINVAL;
+        }
+    if (p.gemv[0] || p.gemv[1]) {          // (fullsort_topk_impl says why)
+        cdr_set_error("%s: U = %lld <= 8 users has no top-k form for distances (score them with cdr_fullsort_neg_sqdist_f32)", __func__, (long long)U);
+        return CDR_EINVAL;
+    }
+    float* rown = (float*)((char*)workspace + lists);
+    float* coln = rown + U;
+    if (int rc = row_sqnorm_launch(s, user_e, U, D, rown)) return rc;
+    if (!col_sqnorm) {
+        if (n[0] > 0) { if (int rc = row_sqnorm_launch(s, slab0, n[0], D, coln)) return rc; }
+        if (n[1] > 0) { if (int rc = row_sqnorm_launch(s, slab1, n[1], D, coln + n[0])) return rc; }
+    }
+    return fullsort_topk_seeded(__func__, topk_epi{rown, col_sqnorm ? col_sqnorm : coln}, stream, user_e, U, D, slab0, n0, slab1, n1, k, hist_indptr,
+                                hist_cols, exclude_first_col, out_vals, out_idx, workspace, lists);
 }

@@ -816,6 +816,64 @@ def fullsort_neg_sqdist(user_e, items):
     return out
 
 
+def row_sqnorm(x):
+    """out[r] = sum_d x[r, d]^2 by the kernel both distance entries take their norms from (cdr_row_sqnorm_f32): the ``col_sqnorm`` of
+    ``fullsort_neg_sqdist_topk``, computed once per evaluation instead of once per user batch."""
+    _dev_check(x)
+    x = x.detach().contiguous()
+    out = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
+    if x.shape[0]:
+        B_.call('cdr_row_sqnorm_f32', B_.stream(), B_.f32(x), x.shape[0], x.shape[1], B_.f32(out))
+    return out
+
+
+# Catalogue size from which SSCDR's ``full_sort_topk`` takes the fused launch: the smallest N of the sweep at and above which the fused
+# form won for every (U, D).  Measured (tools/mb_sqdist_topk.py, profiles/mb_sqdist_topk.txt; k = 10, U = 64 and 1,024, D = 64 and 128),
+# fused / unfused with both arms forming their norms per call: 0.31-0.33 (U = 1,024) and 0.76-0.83 (U = 64) at 1,052,673 items; at 250,000
+# items 0.70-0.78 at U = 1,024 but 2.0-2.2 at U = 64; 1.4-3.2 at 81,920 and 3.0-3.5 at 20,000, where the [U, N] matrix is small and
+# ``fullsort_neg_sqdist`` + mask + ``torch.topk`` is the faster route.  Nothing was measured between 250,000 and 1,052,673 items.  A
+# model's ``fullsort_topk_min_items`` overrides it (an evaluation that only runs 1,024-user batches wins from 250,000 items on).
+SQDIST_TOPK_MIN_ITEMS = 1_052_673
+
+
+def fullsort_neg_sqdist_topk(user_e, slab0, slab1=None, k=10, hist_indptr=None, hist_cols=None, exclude_first_col=True, col_sqnorm=None):
+    """(values [U,k] descending, columns [U,k] int64) of ``fullsort_neg_sqdist(user_e, cat(slab0, slab1))`` after the evaluation mask --
+    column 0 (PAD) and, per user, the ascending columns ``hist_cols[hist_indptr[u]:hist_indptr[u+1]]`` -- without the cat copy and,
+    when U > 32 and D is 64 or 128, without the [U, N] matrix (cdr_fullsort_neg_sqdist_topk_f32).  Values are bit-equal to the matrix's
+    entries; (-inf, -1) pads a row with fewer than k columns left.  ``col_sqnorm``: ``row_sqnorm`` of the concatenated slabs when the caller
+    keeps it (an evaluation's item operand does not change between user batches); computed per call otherwise."""
+    _dev_check(user_e, slab0, slab1, hist_indptr, hist_cols, col_sqnorm)
+    user_e = user_e.detach().contiguous()
+    U, D = user_e.shape
+    n0 = slab0.shape[0] if slab0 is not None else 0
+    n1 = slab1.shape[0] if slab1 is not None else 0
+    dev = user_e.device
+    if col_sqnorm is not None:
+        assert col_sqnorm.dtype == torch.float32 and col_sqnorm.numel() == n0 + n1
+    rows = U
+    if U <= 8:
+        # The entry has no form for these few rows (the dot-product plan streams a GEMV there and sizes no score staging).  Nine rows
+        # take the unfused passes -- the distance GEMM's 32-row tile either way -- and the padding rows are cut off again.
+        rows = 9
+        user_e = torch.cat([user_e, user_e.new_zeros(rows - U, D)])
+        if hist_indptr is not None:
+            hist_indptr = torch.cat([hist_indptr, hist_indptr[-1:].expand(rows - U)])
+    need = ctypes.c_size_t(0)
+    B_._check(B_.load().cdr_fullsort_neg_sqdist_topk_workspace_bytes(rows, D, n0, n1, int(k), ctypes.byref(need)),
+              'cdr_fullsort_neg_sqdist_topk_workspace_bytes')
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _topk_ws.get(key)                  # (the dot-product form's: one per device and stream, it only grows)
+    if ws is None or ws.numel() < need.value:
+        ws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+        _topk_ws[key] = ws
+    vals = torch.empty(rows, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(rows, k, device=dev, dtype=torch.int64)
+    B_.call('cdr_fullsort_neg_sqdist_topk_f32', B_.stream(), B_.f32(user_e), rows, D, B_.f32(slab0.detach()) if n0 else None, n0,
+            B_.f32(slab1.detach()) if n1 else None, n1, B_.f32(col_sqnorm), int(k), B_.i64(hist_indptr), B_.i64(hist_cols),
+            1 if exclude_first_col else 0, B_.f32(vals), B_.i64(idx), B_.raw(ws), ws.numel())
+    return (vals[:U], idx[:U]) if rows != U else (vals, idx)
+
+
 # ---------------------------------------------------------------------------------------------------- CoNet pieces
 class GatherConcat2(Function):
     """cat([A[ida], B[idb]], dim=1) in one buffer (conet.py:106-111) with the dense scatter-add backward."""

@@ -203,3 +203,12 @@ class CLFM(RowwiseTraining, CrossDomainRecommender):
         user_e = F_.gather_rows(self.target_user_embedding.weight, interaction[self.TARGET_USER_ID])
         fac = self._factors(user_e, 'target')
         return F_.fullsort_scores(fac, self.target_item_embedding.weight[:self.target_num_items]).view(-1)
+
+    @torch.no_grad()
+    def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
+        """Evaluation without the [U, N] matrix: (values [U,k], columns [U,k]) of ``full_sort_predict`` after the evaluation mask (column 0
+        and the per-user history columns, CSR with ascending columns), on the dot-product kernel's fused mask + top-k (F_.fullsort_topk;
+        values bit-equal to the unfused scores)."""
+        user_e = F_.gather_rows(self.target_user_embedding.weight, interaction[self.TARGET_USER_ID])
+        return F_.fullsort_topk(self._factors(user_e, 'target'), self.target_item_embedding.weight[:self.target_num_items], None, k=k,
+                                hist_indptr=hist_indptr, hist_cols=hist_cols, exclude_first_col=True)

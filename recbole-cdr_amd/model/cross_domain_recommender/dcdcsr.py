@@ -319,6 +319,21 @@ class DCDCSR(RowwiseTraining, CrossDomainRecommender):
         return F_.fullsort_scores(user_e, I[:self.target_num_items])
 
     @torch.no_grad()
+    def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
+        """Evaluation without the [U, N] matrix: (values [U,k], columns [U,k]) of ``full_sort_predict`` after the evaluation mask (column 0
+        and the per-user history columns, CSR with ascending columns) -- the same three table cases, on the dot-product kernel's fused
+        mask + top-k (F_.fullsort_topk, as EMCDR's: values bit-equal to the unfused scores, no catalogue threshold of its own)."""
+        U, I, tag = self._tables()
+        user_e = F_.gather_rows(U, interaction[getattr(self, f'{tag}_USER_ID')])
+        if tag == 'SOURCE':
+            slab0, slab1 = I[:self.overlapped_num_items], I[self.target_num_items:]
+        elif I is self.affine_embedding:
+            slab0, slab1 = I, None
+        else:
+            slab0, slab1 = I[:self.target_num_items], None
+        return F_.fullsort_topk(user_e, slab0, slab1, k=k, hist_indptr=hist_indptr, hist_cols=hist_cols, exclude_first_col=True)
+
+    @torch.no_grad()
     def predict(self, interaction):
         U, I, tag = self._tables()
         user, item = interaction[getattr(self, f'{tag}_USER_ID')], interaction[getattr(self, f'{tag}_ITEM_ID')]

@@ -11,6 +11,10 @@ distribution and constraints, counter-based RNG, no host work inside the loss, s
 ``fused_train_step`` (``optimizer_mode='rowwise'``): every phase without table-sized gradients -- fused.FusedTripletStep on a domain's
 pair of tables, fused.SSCDRMapStep on the three tables of the OVERLAP phase; ``adam='exact'`` puts the catch-up of the reference's dense
 Adam in front of each (fused.rowwise_catch_up).
+
+``full_sort_topk``: evaluation without the [U, N] distance matrix from ``F_.SQDIST_TOPK_MIN_ITEMS`` items on (the scoring kernel's distance
+epilogue under the fused mask + top-k); ``freeze_for_eval()`` ... ``unfreeze_eval()`` keep the normalised item operand and its norms for the
+length of an evaluation.
 """
 import numpy as np
 import torch
@@ -145,9 +149,6 @@ class SSCDR(RowwiseTraining, CrossDomainRecommender):
         return pos, neg
 
     embedding_normalize = staticmethod(F_.sqnorm_normalize)
-
-    def set_phase(self, phase):
-        self.phase = phase
 
     def _domain_loss(self, interaction, domain):
         U = getattr(self, f'{domain}_user_embedding').weight
@@ -345,25 +346,102 @@ class SSCDR(RowwiseTraining, CrossDomainRecommender):
             ie = self._mapped_rows('item', item, self.overlapped_num_items)
         return self._neg_rowdist(F_.sqnorm_normalize(ue), F_.sqnorm_normalize(ie))
 
-    @torch.no_grad()
-    def full_sort_predict(self, interaction):
+    # ---- full-sort evaluation ---------------------------------------------------------------------------------------------------
+    # The item operand -- the phase's item rows, normalised -- does not depend on the evaluated users.  Between ``freeze_for_eval()`` and
+    # ``unfreeze_eval()`` (CrossDomainTrainer.evaluate brackets its loop with the pair: nothing trains in between) it is kept, as ONE buffer,
+    # with its squared row norms; outside a bracket every call recomputes from the live parameters, as the reference does (sscdr.py:228-259).
+    def freeze_for_eval(self):
+        self.__dict__.pop('_eval_items', None)
+        self.__dict__['_eval_frozen'] = True
+        return self
+
+    def unfreeze_eval(self):
+        self.__dict__.pop('_eval_frozen', None)
+        self.__dict__.pop('_eval_items', None)
+        return self
+
+    def set_phase(self, phase):
+        self.__dict__.pop('_eval_items', None)
+        self.phase = phase
+
+    def train(self, mode=True):
+        if mode:
+            self.unfreeze_eval()
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        self.unfreeze_eval()
+        return super().load_state_dict(*args, **kwargs)
+
+    def __getstate__(self):
+        # pickle / copy.deepcopy / torch.save(model): the cache is table-sized and cheap to rebuild
+        st = dict(self.__dict__)
+        for k in ('_eval_items', '_eval_frozen'):
+            st.pop(k, None)
+        return st
+
+    def _item_slabs(self):
+        """The normalised item rows the current phase scores against, as one or two row ranges (normalising is row-wise: the ranges of the
+        reference's ``torch.cat`` can be normalised apart, and an empty range drops out)."""
         OI, TI = self.overlapped_num_items, self.target_num_items
         if self.phase == 'SOURCE':
-            ue = F_.sqnorm_normalize(F_.gather_rows(self.source_user_embedding.weight, interaction[self.SOURCE_USER_ID]))
             W = self.source_item_embedding.weight
-            all_item = torch.cat([F_.sqnorm_normalize(W[:OI]), F_.sqnorm_normalize(W[TI:])], dim=0)
-        elif self.phase == 'TARGET':
-            ue = F_.sqnorm_normalize(F_.gather_rows(self.target_user_embedding.weight, interaction[self.TARGET_USER_ID]))
-            all_item = F_.sqnorm_normalize(self.target_item_embedding.weight[:TI])
+            parts = [W[:OI], W[TI:]]
+        elif self.phase == 'TARGET' or self.mode == 'overlap_users':
+            parts = [self.target_item_embedding.weight[:TI]]
         else:
-            user = interaction[self.TARGET_USER_ID]
-            if self.mode == 'overlap_users':
-                ue = self._mapped_rows('user', user, self.overlapped_num_users)
-                all_item = self.target_item_embedding.weight[:TI]
-            else:
-                ue = F_.gather_rows(self.target_user_embedding.weight, user)
-                ov = self.mapping_layer(self.source_item_embedding.weight[:OI])
-                all_item = torch.cat([ov, self.target_item_embedding.weight[OI:TI]], dim=0)
-            ue = F_.sqnorm_normalize(ue)
-            all_item = F_.sqnorm_normalize(all_item)
-        return F_.fullsort_neg_sqdist(ue, all_item).view(-1)
+            parts = [self.mapping_layer(self.source_item_embedding.weight[:OI]), self.target_item_embedding.weight[OI:TI]]
+        slabs = [F_.sqnorm_normalize(x) for x in parts if x.shape[0]]
+        return slabs[0], (slabs[1] if len(slabs) > 1 else None)
+
+    def _eval_item_cache(self):
+        """Inside an evaluation bracket: {'items': the normalised item operand as one buffer, 'sqnorm': its squared row norms, formed when
+        ``full_sort_topk`` first asks}.  None outside."""
+        if self.training or not self.__dict__.get('_eval_frozen', False):
+            return None
+        cache = self.__dict__.get('_eval_items')
+        if cache is None:
+            s0, s1 = self._item_slabs()
+            cache = self.__dict__['_eval_items'] = {'items': s0 if s1 is None else torch.cat([s0, s1], dim=0), 'sqnorm': None}
+        return cache
+
+    def _full_sort_users(self, interaction):
+        if self.phase == 'SOURCE':
+            ue = F_.gather_rows(self.source_user_embedding.weight, interaction[self.SOURCE_USER_ID])
+        elif self.phase == 'TARGET' or self.mode != 'overlap_users':
+            ue = F_.gather_rows(self.target_user_embedding.weight, interaction[self.TARGET_USER_ID])
+        else:
+            ue = self._mapped_rows('user', interaction[self.TARGET_USER_ID], self.overlapped_num_users)
+        return F_.sqnorm_normalize(ue)
+
+    def _full_sort_operands(self, interaction):
+        """(user_e, slab0, slab1) of ``full_sort_predict``: the normalised user rows and the normalised item rows as one or two row ranges
+        (``slab1`` None: one) -- all three phase cases, both modes.  Inside an evaluation bracket the item operand is the cached buffer."""
+        cache = self._eval_item_cache()
+        s0, s1 = (cache['items'], None) if cache is not None else self._item_slabs()
+        return self._full_sort_users(interaction), s0, s1
+
+    @torch.no_grad()
+    def full_sort_predict(self, interaction):
+        ue, s0, s1 = self._full_sort_operands(interaction)
+        return F_.fullsort_neg_sqdist(ue, s0 if s1 is None else torch.cat([s0, s1], dim=0)).view(-1)
+
+    @torch.no_grad()
+    def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
+        """(values [U,k], item columns [U,k]) of ``full_sort_predict`` after the evaluation mask (PAD column, per-user history CSR).  From
+        ``F_.SQDIST_TOPK_MIN_ITEMS`` items on (``self.fullsort_topk_min_items`` overrides) without the [U, N] matrix and without the cat of
+        the item ranges: the scoring kernel's distance epilogue under the fused mask + top-k (F_.fullsort_neg_sqdist_topk; values bit-equal
+        to the unfused scores).  Below it ``full_sort_predict`` + mask + ``torch.topk``."""
+        OI, TI = self.overlapped_num_items, self.target_num_items
+        N = OI + self.total_num_items - TI if self.phase == 'SOURCE' else TI
+        if N < self.__dict__.get('fullsort_topk_min_items', F_.SQDIST_TOPK_MIN_ITEMS):
+            uid = interaction[self.SOURCE_USER_ID if self.phase == 'SOURCE' else self.TARGET_USER_ID]
+            return F_.masked_topk(self.full_sort_predict(interaction).view(uid.numel(), -1), k, hist_indptr, hist_cols)
+        ue, s0, s1 = self._full_sort_operands(interaction)
+        cache = self._eval_item_cache()
+        sq = None
+        if cache is not None:
+            if cache['sqnorm'] is None:
+                cache['sqnorm'] = F_.row_sqnorm(cache['items'])
+            sq = cache['sqnorm']
+        return F_.fullsort_neg_sqdist_topk(ue, s0, s1, k=k, hist_indptr=hist_indptr, hist_cols=hist_cols, col_sqnorm=sq)
