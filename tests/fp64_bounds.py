@@ -125,9 +125,11 @@ def _occ_sums(n_rows, inv, terms, absum, cerr):
     return G, A, E, torch.bincount(inv, minlength=n_rows)
 
 
-def bpr_grads_fp64(U, I, uid, pid, nid, reg, go=None, detail=None):
+def bpr_grads_fp64(U, I, uid, pid, nid, reg, go=None, detail=None, k_reg_extra=0):
     """Loss and summed row gradients of  BPRLoss(u.p, u.n) + reg * EmbLoss(u, p)  (recbole; emcdr.py domain_loss) in float64.
-    Returns (loss, user part, item part)."""
+    Returns (loss, user part, item part).  ``k_reg_extra``: further fp32 roundings of the EmbLoss coefficient beyond K_REG (the row-sharded
+    step's per-rank norm sums and their all-reduce, test_gpu_shard_fp64.py); ``detail`` then also receives the coefficients and their
+    relative bound."""
     B, D = uid.numel(), U.shape[1]
     ru, inv_u = torch.unique(uid, return_inverse=True)
     ri, inv_i = torch.unique(torch.cat([pid, nid]), return_inverse=True)
@@ -147,12 +149,14 @@ def bpr_grads_fp64(U, I, uid, pid, nid, reg, go=None, detail=None):
     loss = main + reg * (nu + ni) / B
     if detail is not None:
         detail.update(main=float(main), nu=float(nu), ni=float(ni), g=g, delta=delta)
-    k_reg = K_REG
+    k_reg = K_REG + k_reg_extra
     if go is not None:
-        g, delta, k_reg = go * g, abs(go) * delta, K_REG + 1
+        g, delta, k_reg = go * g, abs(go) * delta, k_reg + 1
     cu = (1.0 if go is None else go) * reg / (B * nu) if reg else 0.0
     ci = (1.0 if go is None else go) * reg / (B * ni) if reg else 0.0
     gc = gam(D + k_reg)
+    if detail is not None:
+        detail.update(cu=float(cu), ci=float(ci), gc=gc)
     g1, delta = g.unsqueeze(1), delta.unsqueeze(1)
     ut = (g1 * (p - n) + cu * u, g1.abs() * (pa + na) + abs(cu) * ua, delta * (p - n).abs() + gc * abs(cu) * ua)
     del x, s, q, h, dgdx, dgds
