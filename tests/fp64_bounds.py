@@ -125,19 +125,21 @@ def _occ_sums(n_rows, inv, terms, absum, cerr):
     return G, A, E, torch.bincount(inv, minlength=n_rows)
 
 
-def bpr_grads_fp64(U, I, uid, pid, nid, reg, go=None, detail=None, k_reg_extra=0):
+def bpr_grads_fp64(U, I, uid, pid, nid, reg, go=None, detail=None, k_reg_extra=0, k_score=None):
     """Loss and summed row gradients of  BPRLoss(u.p, u.n) + reg * EmbLoss(u, p)  (recbole; emcdr.py domain_loss) in float64.
     Returns (loss, user part, item part).  ``k_reg_extra``: further fp32 roundings of the EmbLoss coefficient beyond K_REG (the row-sharded
     step's per-rank norm sums and their all-reduce, test_gpu_shard_fp64.py); ``detail`` then also receives the coefficients and their
-    relative bound."""
+    relative bound.  ``k_score``: the k of the score's gamma_k (default D + 2: two D-term dot products and their difference on one GPU;
+    the dimension layout passes its own, smaller count, test_gpu_dim_fp64.py)."""
     B, D = uid.numel(), U.shape[1]
+    k_score = D + 2 if k_score is None else k_score
     ru, inv_u = torch.unique(uid, return_inverse=True)
     ri, inv_i = torch.unique(torch.cat([pid, nid]), return_inverse=True)
     Ur, Ir = U[ru].double(), I[ri].double()
     u, p, n = Ur[inv_u], Ir[inv_i[:B]], Ir[inv_i[B:]]
     ua, pa, na = u.abs(), p.abs(), n.abs()
     x = (u * p).sum(1) - (u * n).sum(1)
-    ex = gam(D + 2) * ((ua * pa).sum(1) + (ua * na).sum(1)) + U32 * x.abs()
+    ex = gam(k_score) * ((ua * pa).sum(1) + (ua * na).sum(1)) + U32 * x.abs()
     s, q = torch.sigmoid(x), torch.sigmoid(-x)
     h = GAMMA + s
     g = -(s * q) / h / B
@@ -166,17 +168,19 @@ def bpr_grads_fp64(U, I, uid, pid, nid, reg, go=None, detail=None, k_reg_extra=0
     return float(loss), (ru, *_occ_sums(ru.numel(), inv_u, *ut)), (ri, *_occ_sums(ri.numel(), inv_i, *it))
 
 
-def point_grads_fp64(U, I, uid, iid, label, reg, kind, go=None, RU=None, RI=None, detail=None):
+def point_grads_fp64(U, I, uid, iid, label, reg, kind, go=None, RU=None, RI=None, detail=None, k_reg_extra=0, k_score=None):
     """Loss and summed row gradients of  MSE(u.i, y)  or  BCE(sigmoid(u.i), y)  + reg * EmbLoss(u, i)  in float64.  With ``RU`` / ``RI``
-    the EmbLoss rows come from those tables (same ids) and two more parts, the reg tables' gradients, are returned."""
+    the EmbLoss rows come from those tables (same ids) and two more parts, the reg tables' gradients, are returned.  ``k_reg_extra`` /
+    ``k_score``: as bpr_grads_fp64's (the score here is one D-term dot product; default D + 2)."""
     B, D = uid.numel(), U.shape[1]
+    k_score = D + 2 if k_score is None else k_score
     ru, inv_u = torch.unique(uid, return_inverse=True)
     ri, inv_i = torch.unique(iid, return_inverse=True)
     u, i = U[ru].double()[inv_u], I[ri].double()[inv_i]
     ua, ia = u.abs(), i.abs()
     y = label.double()
     x = (u * i).sum(1)
-    ex = gam(D + 2) * (ua * ia).sum(1) + U32 * x.abs()
+    ex = gam(k_score) * (ua * ia).sum(1) + U32 * x.abs()
     if kind == 'mse':
         d = x - y
         main = (d * d).mean()
@@ -193,12 +197,14 @@ def point_grads_fp64(U, I, uid, iid, label, reg, kind, go=None, RU=None, RI=None
     loss = main + reg * (nu + ni) / B
     if detail is not None:
         detail.update(main=float(main), nu=float(nu), ni=float(ni), g=g, delta=delta)
-    k_reg = K_REG
+    k_reg = K_REG + k_reg_extra
     if go is not None:
-        g, delta, k_reg = go * g, abs(go) * delta, K_REG + 1
+        g, delta, k_reg = go * g, abs(go) * delta, k_reg + 1
     cu = (1.0 if go is None else go) * reg / (B * nu) if reg else 0.0
     ci = (1.0 if go is None else go) * reg / (B * ni) if reg else 0.0
     gc = gam(D + k_reg)
+    if detail is not None:
+        detail.update(cu=float(cu), ci=float(ci), gc=gc)
     g1, d1 = g.unsqueeze(1), delta.unsqueeze(1)
     if sep:
         ut, it = (g1 * i, g1.abs() * ia, d1 * ia), (g1 * u, g1.abs() * ua, d1 * ua)

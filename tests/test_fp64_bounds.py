@@ -194,6 +194,12 @@ def test_rowmodels_case_table_covers_every_regime_without_a_gpu():
     T.test_case_table_covers_every_regime()
 
 
+def test_dim_case_table_covers_every_regime_without_a_gpu():
+    """test_gpu_dim_fp64.py's case tables: every lanes-per-row instantiation, both grid-stride capacities and the big sort, from the constants."""
+    import test_dim_loopback_host as T
+    T.test_case_table_covers_every_regime()
+
+
 def test_running_bounds_hold_for_fp32_on_the_cpu_and_reject_small_mutations():
     """fp64_bounds.EV without a GPU: torch's own fp32 results lie inside the bounds the two fp64 test files build (a product with a tanh
     epilogue; the oracle's max-min normalisation with tied extremes through autograd), and results that are subtly wrong do not."""

@@ -131,10 +131,11 @@ def _with_counts(lengths, total, pool, gen):
     """``total`` ids drawn from ``pool`` (distinct candidates): one id per entry of ``lengths`` with exactly that many occurrences, two
     of the rest twice, every other one once; shuffled."""
     rest = total - sum(lengths) - 4
-    counts = torch.tensor(lengths + [2, 2] + [1] * rest, device=DEV)
-    picked = pool[torch.randperm(pool.numel(), device=DEV, generator=gen)[:counts.numel()]]
+    dev = pool.device
+    counts = torch.tensor(lengths + [2, 2] + [1] * rest, device=dev)
+    picked = pool[torch.randperm(pool.numel(), device=dev, generator=gen)[:counts.numel()]]
     ids = torch.repeat_interleave(picked, counts)
-    return ids[torch.randperm(total, device=DEV, generator=gen)]
+    return ids[torch.randperm(total, device=dev, generator=gen)]
 
 
 def _batch_i(c, t, gen):

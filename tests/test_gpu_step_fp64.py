@@ -83,7 +83,7 @@ def _mark_edges(uid, pid, nid, nu, ni, gen):
 
 def _zipf(n, rows, gen, a=1.05):
     """Zipf(a) ids over [0, rows) by inverse transform, as tests/test_gpu_trainer_graph.py builds the C5 positives."""
-    r = torch.rand(n, device=DEV, generator=gen, dtype=torch.float64)
+    r = torch.rand(n, device=gen.device, generator=gen, dtype=torch.float64)
     return (((float(rows) ** (1 - a) - 1) * r + 1).pow(1 / (1 - a)).long().clamp_(1, rows) - 1)
 
 
