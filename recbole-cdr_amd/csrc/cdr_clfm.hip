@@ -9,23 +9,15 @@
 //   A  F = U W^T [32, Di] and T = I W [32, Du]: one 32x32 output tile per job, the nI + nU jobs dealt round-robin to the waves
 //   B  eight lanes per row: x_b from F and the row's I chunks still in registers, the loss term, g_b; GI[b] = g_b F[b], GU[b] = g_b T[b]
 //   C  dW += (g (.) I)^T U: the nI x nU output tiles dealt round-robin to the waves, accumulated in registers ACROSS the workgroup's tiles
-// and written once, as the workgroup's partial, when its tiles are done; clfm_finish_kernel adds the partials in workgroup order (no
+// and written once, as the workgroup's partial, when its tiles are done; rowstep_finish_kernel (cdr_rowstep.h) adds the partials in workgroup order (no
 // float atomics: a rerun is bit-equal) and turns the fp64 block partials of the loss and norm sums into out8.
 // At Du = Di = 64 a row is ~25 kFLOP against ~1 KB of HBM traffic: near the balance of the fp32 matrix pipe and HBM, which is why the
 // contractions are on the matrix pipe and not a per-lane matvec with wave reductions.
-#include "cdr_common.h"
-#include "cdr_loss_math.h"
-#include "cdr_mfma.h"
+#include "cdr_rowstep.h"
 
 namespace {
 
-constexpr int kRows = 32;                    // batch rows of a tile = M of the MFMA
-constexpr int kLdsPad = 4;                   // floats: a row stride of 4 (mod 32) keeps the float4 reads of 32 consecutive rows apart
-constexpr int kSub = kBlock / kRows;         // lanes per row in the staging and epilogue phases (8)
-constexpr int kChunks = CDR_CLFM_MAX_DIM / 4 / kSub;     // float4 chunks of a row one of them holds (4)
-constexpr size_t kLdsPerCu = 160 * 1024;
-
-__host__ __device__ inline int pad32(int d) { return (d + 31) & ~31; }
+constexpr int kChunks = CDR_CLFM_MAX_DIM / 4 / kSub;     // float4 chunks of a row one of the kSub lanes holds (4)
 
 struct clfm_plan {
     int grid;
@@ -39,10 +31,7 @@ inline clfm_plan clfm_plan_for(int64_t B, int Du, int Di) {
     clfm_plan p;
     p.lds = ((size_t)DiP * SU + 2 * (size_t)kRows * SU + 2 * (size_t)kRows * SI + kRows) * sizeof(float);
     p.tiles = (B + kRows - 1) / kRows;
-    int64_t per_cu = (int64_t)(kLdsPerCu / (p.lds + 512));
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const int64_t cap = CDR_NUM_CU * per_cu;
-    p.grid = (int)(p.tiles < cap ? p.tiles : cap);
+    p.grid = rowstep_grid(p.tiles, p.lds, 4);
     p.nq = ((DuP >> 5) * (DiP >> 5) + 3) / 4;
     return p;
 }
@@ -187,45 +176,11 @@ __global__ __launch_bounds__(kBlock) void clfm_fwd_grad_kernel(const float* __re
         const int ot = wave + (kBlock / 64) * q;
         if (ot < nI * nU) {
             const int ti = ot / nU, tu = ot - ti * nU;
-            const int du = tu * 32 + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int di = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (di < Di && du < Du) part[di * Du + du] = wacc[q][r];
-            }
+            STORE_TILE32(part, 0, Du, ti, tu, Di, Du, wacc[q], li, lh);
         }
     }
     block_sum_d<3>(acc, red);
     if (threadIdx.x == 0) store_partials(partials, acc);
-}
-
-// Block 0: out8 = {w (bce + reg (nU + nI) / B), bce, (nU + nI) / B, nU, nI, c_u, c_i, 0} with c = w reg / (B norm) (0 for a zero norm,
-// as step_finish_kernel).  Blocks 1..: one thread per element of dW adds the workgroups' partials in workgroup order.
-__global__ __launch_bounds__(kBlock) void clfm_finish_kernel(const double* __restrict__ partials, int nblocks, int64_t B, float weight,
-                                                             float reg_weight, float* __restrict__ out8,
-                                                             const float* __restrict__ dWpart, int n_elem, float* __restrict__ dW) {
-    if (blockIdx.x == 0) {
-        __shared__ double smem[3 * (kBlock / 64)];
-        double acc[3] = {0.0, 0.0, 0.0};
-        sum_partials<3, kBlock>(partials, nblocks, acc, smem);
-        if (threadIdx.x == 0) {
-            const float bce = (float)(acc[0] / (double)B);
-            const float nu = (float)sqrt(acc[1]), ni = (float)sqrt(acc[2]);
-            const float emb = (nu + ni) / (float)B;
-            out8[0] = weight * (bce + reg_weight * emb);
-            out8[1] = bce; out8[2] = emb; out8[3] = nu; out8[4] = ni;
-            out8[5] = weight * embloss_coef(reg_weight, B, nu);
-            out8[6] = weight * embloss_coef(reg_weight, B, ni);
-            out8[7] = 0.f;
-        }
-        return;
-    }
-    const int e = (blockIdx.x - 1) * kBlock + threadIdx.x;
-    if (e < n_elem) {
-        float s = 0.f;
-        for (int b = 0; b < nblocks; ++b) s += dWpart[(size_t)b * n_elem + e];
-        dW[e] = s;
-    }
 }
 
 inline bool clfm_dims_ok(int Du, int Di) {
@@ -264,20 +219,10 @@ extern "C" int cdr_clfm_fwd_grad(cdr_ctx* ctx, void* stream, const float* user_t
         default: CLFM_PICK(4); break;
     }
 #undef CLFM_PICK
-    if (p.lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        if (e != hipSuccess) { cdr_set_error("cdr_clfm_fwd_grad: %zu B of LDS refused: %s", p.lds, hipGetErrorString(e)); return (int)e; }
-    }
+    if (int e = rowstep_optin_lds((const void*)kern, p.lds, __func__)) return e;
     hipStream_t s = (hipStream_t)stream;
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_CLFM_FWD_GRAD, s);
+    return rowstep_run(ctx, s, CDR_TAG_CLFM_FWD_GRAD, __func__, [&] {
         kern<<<dim3(p.grid), dim3(kBlock), p.lds, s>>>(user_tab, item_tab, W, Du, Di, uid, iid, label, B, weight * (1.0f / (float)B), GU, GI,
                                                        (float*)workspace, ctx->partials);
-    }
-    CDR_LAUNCH_CHECK();
-    const int n_elem = Di * Du;
-    clfm_finish_kernel<<<dim3(1 + (n_elem + kBlock - 1) / kBlock), dim3(kBlock), 0, s>>>(ctx->partials, p.grid, B, weight, reg_weight, out8,
-                                                                                          (const float*)workspace, n_elem, dW);
-    CDR_LAUNCH_CHECK();
-    return CDR_OK;
+    }, p.grid, rowstep_bce_emb{B, weight, reg_weight}, out8, workspace, Di * Du, dW);
 }

@@ -20,24 +20,16 @@
 //          accumulators that live ACROSS the workgroup's tiles, then gpre_l W_l (1 - a_{l-1}^2) over a_{l-1} in place
 //   route  eight lanes per row: the max-min backward and the occurrence's gradient row G_i
 // Nothing but G leaves the CU per row.  The parameter gradients are written once, as the workgroup's partial, when its tiles are done;
-// dcdcsr_finish_kernel adds the partials in workgroup order (no float atomics: a rerun is bit-equal) and turns the fp64 block partials
+// rowstep_finish_kernel (cdr_rowstep.h) adds the partials in workgroup order (no float atomics: a rerun is bit-equal) and turns the fp64 block partials
 // of the loss into out8.  Duplicate ids get one gradient row per occurrence; the apply adds them in occurrence order.
 // A constant row (max == min) divides by zero exactly as the reference does.
 // LDS at the default 64-[128]-64: W 68,608 + activations 34,304 + biases and their gradients 1,536 = 104,448 B of the CU's 163,840.
-#include "cdr_common.h"
-#include "cdr_loss_math.h"
-#include "cdr_mfma.h"
+#include "cdr_rowstep.h"
 
 namespace {
 
-constexpr int kRows = 32;                    // occurrences of a tile = M of the MFMA
-constexpr int kLdsPad = 4;                   // floats: a row stride of 4 (mod 32) keeps the float4 reads of 32 consecutive rows apart
-constexpr int kSub = kBlock / kRows;         // lanes per row in the staging, loss and routing phases (8)
-constexpr int kChunks = CDR_DCDCSR_MAX_DIM / 4 / kSub;       // float4 chunks of a row one of them holds (4)
+constexpr int kChunks = CDR_DCDCSR_MAX_DIM / 4 / kSub;       // float4 chunks of a row one of the kSub lanes holds (4)
 constexpr int kMaxL = CDR_DCDCSR_MAX_LAYERS;
-constexpr size_t kLdsPerCu = 160 * 1024;
-
-__host__ __device__ inline int pad32(int d) { return (d + 31) & ~31; }
 
 struct dcdcsr_args {
     const float *table, *bench, *params;
@@ -113,10 +105,7 @@ inline dcdcsr_plan dcdcsr_plan_for(int64_t n, int L, const int* dims) {
     p.total = a.total = total;
     p.nq = (tiles + 3) / 4;
     const int64_t ntile = (n + kRows - 1) / kRows;
-    int64_t per_cu = (int64_t)(kLdsPerCu / (p.lds + 512));
-    per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);    // (the dW accumulators: two waves per SIMD at most)
-    const int64_t cap = CDR_NUM_CU * per_cu;
-    p.grid = (int)(ntile < cap ? ntile : cap);
+    p.grid = rowstep_grid(ntile, p.lds, 2);                 // (the dW accumulators: two waves per SIMD at most)
     return p;
 }
 
@@ -363,40 +352,14 @@ __global__ __launch_bounds__(kBlock) void dcdcsr_map_kernel(const dcdcsr_args a)
         for (int q = 0; q < NQ; ++q) {
             const int ot = wave + (kBlock / 64) * q;
             if (ot >= a.tb[l - 1] && ot < a.tb[l]) {
-                const int loc = ot - a.tb[l - 1], ti = loc / nI, tj = loc - ti * nI, cin = tj * 32 + li;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ro = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (ro < out && cin < in) pl[ro * in + cin] = wacc[q][r];
-                }
+                const int loc = ot - a.tb[l - 1], ti = loc / nI, tj = loc - ti * nI;
+                STORE_TILE32(pl, 0, in, ti, tj, out, in, wacc[q], li, lh);
             }
         }
         if (t < out) pl[out * in + t] = smem[a.dbs[l - 1] + t];     // (the thread that summed the column)
     }
     block_sum_d<1>(acc, red);
     if (threadIdx.x == 0) store_partials(a.partials, acc);
-}
-
-// Block 0: out8 = {mse, 0, ...}.  Blocks 1..: one thread per parameter adds the workgroups' partials in workgroup order.
-__global__ __launch_bounds__(kBlock) void dcdcsr_finish_kernel(const double* __restrict__ partials, int nblocks, double count,
-                                                               float* __restrict__ out8, const float* __restrict__ part, int n_elem,
-                                                               float* __restrict__ dparams) {
-    if (blockIdx.x == 0) {
-        __shared__ double smem[kBlock / 64];
-        double acc[1] = {0.0};
-        sum_partials<1, kBlock>(partials, nblocks, acc, smem);
-        if (threadIdx.x == 0) {
-            out8[0] = (float)(acc[0] / count);
-            for (int i = 1; i < 8; ++i) out8[i] = 0.f;
-        }
-        return;
-    }
-    const int e = (blockIdx.x - 1) * kBlock + threadIdx.x;
-    if (e < n_elem) {
-        float s = 0.f;
-        for (int b = 0; b < nblocks; ++b) s += part[(size_t)b * n_elem + e];
-        dparams[e] = s;
-    }
 }
 
 }  // namespace
@@ -431,22 +394,12 @@ extern "C" int cdr_dcdcsr_map_fwd_grad(cdr_ctx* ctx, void* stream, const float* 
     else if (p.nq <= 8) DCDCSR_PICK(8);
     else DCDCSR_PICK(12);
 #undef DCDCSR_PICK
-    if (p.lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        if (e != hipSuccess) { cdr_set_error("cdr_dcdcsr_map_fwd_grad: %zu B of LDS refused: %s", p.lds, hipGetErrorString(e)); return (int)e; }
-    }
+    if (int e = rowstep_optin_lds((const void*)kern, p.lds, __func__)) return e;
     dcdcsr_args& a = p.a;
     a.table = table; a.bench = bench; a.params = params; a.ids = ids; a.n = n;
     a.scale = (float)(2.0 / ((double)n * (double)dims[0]));
     a.G = G; a.part = (float*)workspace; a.partials = ctx->partials;
     hipStream_t s = (hipStream_t)stream;
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_DCDCSR_MAP_FWD_GRAD, s);
-        kern<<<dim3(p.grid), dim3(kBlock), p.lds, s>>>(a);
-    }
-    CDR_LAUNCH_CHECK();
-    dcdcsr_finish_kernel<<<dim3(1 + (p.total + kBlock - 1) / kBlock), dim3(kBlock), 0, s>>>(ctx->partials, p.grid, (double)n * (double)dims[0],
-                                                                                           out8, (const float*)workspace, p.total, dparams);
-    CDR_LAUNCH_CHECK();
-    return CDR_OK;
+    return rowstep_run(ctx, s, CDR_TAG_DCDCSR_MAP_FWD_GRAD, __func__, [&] { kern<<<dim3(p.grid), dim3(kBlock), p.lds, s>>>(a); }, p.grid,
+                       rowstep_mean{(double)n * (double)dims[0]}, out8, workspace, p.total, dparams);
 }

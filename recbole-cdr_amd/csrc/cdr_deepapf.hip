@@ -21,25 +21,17 @@
 //   gX     gX = gH W1 written over X
 //   route  eight lanes per row: the three compact gradient rows of the occurrence (a masked share row is +0.0)
 // H, gH and X never leave the CU.  The parameter gradients are written once, as the workgroup's partial, when its tiles are done;
-// deepapf_finish_kernel adds the partials in workgroup order (no float atomics: a rerun is bit-equal) and turns the fp64 block partials
+// rowstep_finish_kernel (cdr_rowstep.h) adds the partials in workgroup order (no float atomics: a rerun is bit-equal) and turns the fp64 block partials
 // of the loss into out8.
 // At D = 64 a row is ~50 kFLOP (three contractions over two candidates) against ~1.5 KB of HBM traffic: past the balance of the fp32
 // matrix pipe and HBM, which is why the contractions are on the matrix pipe.
 // LDS at the widest accepted shape (D = 128): W1 67,584 + X 33,792 + H 33,792 + b1, w2, wp 1,536 + ga 256 = 136,960 B of the CU's
 // 163,840: one workgroup per CU there, nothing spills.
-#include "cdr_common.h"
-#include "cdr_loss_math.h"
-#include "cdr_mfma.h"
+#include "cdr_rowstep.h"
 
 namespace {
 
-constexpr int kRows = 32;                    // batch rows of a tile = M of the MFMA; the operand has 2 kRows rows
-constexpr int kLdsPad = 4;                   // floats: a row stride of 4 (mod 32) keeps the float4 reads of 32 consecutive rows apart
-constexpr int kSub = kBlock / kRows;         // lanes per row in the staging, score and routing phases (8)
-constexpr int kChunks = CDR_DEEPAPF_MAX_DIM / 4 / kSub;      // float4 chunks of a row one of them holds (4)
-constexpr size_t kLdsPerCu = 160 * 1024;
-
-__host__ __device__ inline int pad32(int d) { return (d + 31) & ~31; }
+constexpr int kChunks = CDR_DEEPAPF_MAX_DIM / 4 / kSub;      // float4 chunks of a row one of the kSub lanes holds (4)
 
 struct deepapf_plan {
     int grid;
@@ -57,10 +49,7 @@ inline deepapf_plan deepapf_plan_for(int64_t B, int D) {
     p.total = D * D + 3 * D;
     p.lds = ((size_t)DP * S + 4 * (size_t)kRows * S + 3 * (size_t)DP + 2 * kRows) * sizeof(float);
     p.tiles = (B + kRows - 1) / kRows;
-    int64_t per_cu = (int64_t)(kLdsPerCu / (p.lds + 512));
-    per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);    // (190..216 VGPRs + 32..80 AGPRs: two waves per SIMD at most)
-    const int64_t cap = CDR_NUM_CU * per_cu;
-    p.grid = (int)(p.tiles < cap ? p.tiles : cap);
+    p.grid = rowstep_grid(p.tiles, p.lds, 2);               // (190..216 VGPRs + 32..80 AGPRs: two waves per SIMD at most)
     p.nq = ((DP >> 5) * (DP >> 5) + 3) / 4;
     return p;
 }
@@ -300,12 +289,8 @@ __global__ __launch_bounds__(kBlock) void deepapf_fwd_grad_kernel(const deepapf_
     for (int q = 0; q < NQ; ++q) {
         const int ot = wave + (kBlock / 64) * q;
         if (ot < nD * nD) {
-            const int ti = ot / nD, tj = ot - ti * nD, cin = tj * 32 + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ro = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (ro < D && cin < D) part[ro * D + cin] = wacc[q][r];
-            }
+            const int ti = ot / nD, tj = ot - ti * nD;
+            STORE_TILE32(part, 0, D, ti, tj, D, D, wacc[q], li, lh);
         }
     }
     // db1, dw2: the row slices' sums in slice order; dwp: the 32 row groups' sums in row order -- through the row buffers
@@ -330,30 +315,6 @@ __global__ __launch_bounds__(kBlock) void deepapf_fwd_grad_kernel(const deepapf_
     }
     block_sum_d<1>(acc, red);
     if (threadIdx.x == 0) store_partials(a.partials, acc);
-}
-
-// Block 0: out8 = {w bce, bce, 0, ...}.  Blocks 1..: one thread per parameter adds the workgroups' partials in workgroup order.
-__global__ __launch_bounds__(kBlock) void deepapf_finish_kernel(const double* __restrict__ partials, int nblocks, int64_t B, float weight,
-                                                                float* __restrict__ out8, const float* __restrict__ part, int n_elem,
-                                                                float* __restrict__ dparams) {
-    if (blockIdx.x == 0) {
-        __shared__ double smem[kBlock / 64];
-        double acc[1] = {0.0};
-        sum_partials<1, kBlock>(partials, nblocks, acc, smem);
-        if (threadIdx.x == 0) {
-            const float bce = (float)(acc[0] / (double)B);
-            out8[0] = weight * bce;
-            out8[1] = bce;
-            for (int i = 2; i < 8; ++i) out8[i] = 0.f;
-        }
-        return;
-    }
-    const int e = (blockIdx.x - 1) * kBlock + threadIdx.x;
-    if (e < n_elem) {
-        float s = 0.f;
-        for (int b = 0; b < nblocks; ++b) s += part[(size_t)b * n_elem + e];
-        dparams[e] = s;
-    }
 }
 
 }  // namespace
@@ -389,10 +350,7 @@ extern "C" int cdr_deepapf_fwd_grad(cdr_ctx* ctx, void* stream, const float* sha
         default: DEEPAPF_PICK(4); break;
     }
 #undef DEEPAPF_PICK
-    if (p.lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        if (e != hipSuccess) { cdr_set_error("cdr_deepapf_fwd_grad: %zu B of LDS refused: %s", p.lds, hipGetErrorString(e)); return (int)e; }
-    }
+    if (int e = rowstep_optin_lds((const void*)kern, p.lds, __func__)) return e;
     deepapf_args a;
     a.share = share_tab; a.only = only_tab; a.other = other_tab; a.D = D;
     a.params = params;
@@ -401,13 +359,6 @@ extern "C" int cdr_deepapf_fwd_grad(cdr_ctx* ctx, void* stream, const float* sha
     a.GS = GS + row0 * D; a.GO = GO; a.GT = GT;
     a.part = (float*)workspace; a.partials = ctx->partials;
     hipStream_t s = (hipStream_t)stream;
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_DEEPAPF_FWD_GRAD, s);
-        kern<<<dim3(p.grid), dim3(kBlock), p.lds, s>>>(a);
-    }
-    CDR_LAUNCH_CHECK();
-    deepapf_finish_kernel<<<dim3(1 + (p.total + kBlock - 1) / kBlock), dim3(kBlock), 0, s>>>(ctx->partials, p.grid, B, weight, out8,
-                                                                                             (const float*)workspace, p.total, dparams);
-    CDR_LAUNCH_CHECK();
-    return CDR_OK;
+    return rowstep_run(ctx, s, CDR_TAG_DEEPAPF_FWD_GRAD, __func__, [&] { kern<<<dim3(p.grid), dim3(kBlock), p.lds, s>>>(a); }, p.grid,
+                       rowstep_bce{B, weight}, out8, workspace, p.total, dparams);
 }

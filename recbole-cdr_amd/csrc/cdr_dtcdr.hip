@@ -16,29 +16,21 @@
 //   bwd    per layer, last first: dW_l += gz_l^T drop_l(H_l) into register accumulators that live ACROSS the workgroup's tiles, db_l on
 //          wave l, then gz_l W_l written over H_l in place (through the masks), for layer 0 over x
 //   route  eight lanes per row: gx through the keep bits to the four compact gradient rows of the occurrence
-// The weight gradients are written once, as the workgroup's partial, when its tiles are done; dtcdr_finish_kernel adds the partials
+// The weight gradients are written once, as the workgroup's partial, when its tiles are done; rowstep_finish_kernel (cdr_rowstep.h) adds the partials
 // in workgroup order (no float atomics: a rerun is bit-equal) and turns the fp64 block partials of the loss into out8.
 // At D = 64, hidden [32, 16] a row is ~28 kFLOP against ~2 KB of HBM traffic: near the balance of the fp32 matrix pipe and HBM, as in
 // cdr_clfm.hip, which is why the contractions are on the matrix pipe.
 // LDS at the widest accepted shape (D = 128, hidden [64, 64, 64]): W 101,376 + x 33,280 + H 26,112 + biases and g 1,152 = 161,920 B of
 // the CU's 163,840: one workgroup per CU there, nothing spills.
-#include "cdr_common.h"
-#include "cdr_loss_math.h"
-#include "cdr_mfma.h"
+#include "cdr_rowstep.h"
 #include "cdr_dropout.h"
 
 namespace {
 
-constexpr int kRows = 32;                    // batch rows of a tile = M of the MFMA
-constexpr int kLdsPad = 4;                   // floats: a row stride of 4 (mod 32) keeps the float4 reads of 32 consecutive rows apart
-constexpr int kSub = kBlock / kRows;         // lanes per row in the staging, output and routing phases (8)
 constexpr int kML = CDR_DTCDR_MAX_LAYERS;
 constexpr int kMH = CDR_DTCDR_MAX_HIDDEN;
 constexpr int kChunks = 2 * CDR_DTCDR_MAX_DIM / 4 / kSub;      // float4 chunks of x one lane holds (8)
 constexpr int SH = kMH + kLdsPad;            // row stride of the hidden buffers
-constexpr size_t kLdsPerCu = 160 * 1024;
-
-__host__ __device__ inline int pad32(int d) { return (d + 31) & ~31; }
 
 // the tower of one domain: widths, offsets into the packed parameter vector [W_0, b_0, ..., W_{L-1}, b_{L-1}, w_out, b_out] (the
 // layout of dparams and of a workgroup's partial too) and the LDS offsets of the staged weights
@@ -108,10 +100,7 @@ inline dtcdr_plan dtcdr_plan_for(int64_t B, int D, int n_hidden, const int* hidd
     N.lds_floats = lds;
     p.lds = (size_t)lds * sizeof(float);
     p.tiles = (B + kRows - 1) / kRows;
-    int64_t per_cu = (int64_t)(kLdsPerCu / (p.lds + 512));
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const int64_t cap = CDR_NUM_CU * per_cu;
-    p.grid = (int)(p.tiles < cap ? p.tiles : cap);
+    p.grid = rowstep_grid(p.tiles, p.lds, 4);
     p.nq0 = ((pad32(N.n[1]) >> 5) * (pad32(2 * D) >> 5) + 3) / 4;
     return p;
 }
@@ -371,12 +360,8 @@ __global__ __launch_bounds__(kBlock) void dtcdr_fwd_grad_kernel(const dtcdr_args
         for (int q = 0; q < NQ0; ++q) {
             const int ot = wave + (kBlock / 64) * q;
             if (ot < tO * tI) {
-                const int ti = ot / tI, tj = ot - ti * tI, cin = tj * 32 + li;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ro = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (ro < nout && cin < nin) part[N.woff[0] + ro * nin + cin] = w0[q][r];
-                }
+                const int ti = ot / tI, tj = ot - ti * tI;
+                STORE_TILE32(part, N.woff[0], nin, ti, tj, nout, nin, w0[q], li, lh);
             }
         }
     }
@@ -385,12 +370,8 @@ __global__ __launch_bounds__(kBlock) void dtcdr_fwd_grad_kernel(const dtcdr_args
         if (l < L) {
             const int nin = N.n[l], nout = N.n[l + 1], tI = pad32(nin) >> 5, tO = pad32(nout) >> 5;
             if (wave < tO * tI) {
-                const int ti = wave / tI, tj = wave - ti * tI, cin = tj * 32 + li;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ro = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (ro < nout && cin < nin) part[N.woff[l] + ro * nin + cin] = w12[l - 1][r];
-                }
+                const int ti = wave / tI, tj = wave - ti * tI;
+                STORE_TILE32(part, N.woff[l], nin, ti, tj, nout, nin, w12[l - 1], li, lh);
             }
         }
     }
@@ -403,30 +384,6 @@ __global__ __launch_bounds__(kBlock) void dtcdr_fwd_grad_kernel(const dtcdr_args
     }
     block_sum_d<1>(acc, red);
     if (threadIdx.x == 0) store_partials(a.partials, acc);
-}
-
-// Block 0: out8 = {w bce, bce, 0, ...}.  Blocks 1..: one thread per parameter adds the workgroups' partials in workgroup order.
-__global__ __launch_bounds__(kBlock) void dtcdr_finish_kernel(const double* __restrict__ partials, int nblocks, int64_t B, float weight,
-                                                              float* __restrict__ out8, const float* __restrict__ part, int n_elem,
-                                                              float* __restrict__ dparams) {
-    if (blockIdx.x == 0) {
-        __shared__ double smem[kBlock / 64];
-        double acc[1] = {0.0};
-        sum_partials<1, kBlock>(partials, nblocks, acc, smem);
-        if (threadIdx.x == 0) {
-            const float bce = (float)(acc[0] / (double)B);
-            out8[0] = weight * bce;
-            out8[1] = bce;
-            for (int i = 2; i < 8; ++i) out8[i] = 0.f;
-        }
-        return;
-    }
-    const int e = (blockIdx.x - 1) * kBlock + threadIdx.x;
-    if (e < n_elem) {
-        float s = 0.f;
-        for (int b = 0; b < nblocks; ++b) s += part[(size_t)b * n_elem + e];
-        dparams[e] = s;
-    }
 }
 
 }  // namespace
@@ -468,10 +425,7 @@ extern "C" int cdr_dtcdr_fwd_grad(cdr_ctx* ctx, void* stream, const float* src_u
         default: DTCDR_PICK(4); break;
     }
 #undef DTCDR_PICK
-    if (p.lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        if (e != hipSuccess) { cdr_set_error("cdr_dtcdr_fwd_grad: %zu B of LDS refused: %s", p.lds, hipGetErrorString(e)); return (int)e; }
-    }
+    if (int e = rowstep_optin_lds((const void*)kern, p.lds, __func__)) return e;
     dtcdr_args a;
     a.Us = src_user; a.Ut = tgt_user; a.Is = src_item; a.It = tgt_item; a.D = D;
     a.params = params; a.net = p.net;
@@ -481,14 +435,6 @@ extern "C" int cdr_dtcdr_fwd_grad(cdr_ctx* ctx, void* stream, const float* src_u
     a.GUs = GUs + row0 * D; a.GUt = GUt + row0 * D; a.GIs = GIs + row0 * D; a.GIt = GIt + row0 * D;
     a.part = (float*)workspace; a.partials = ctx->partials;
     hipStream_t s = (hipStream_t)stream;
-    {
-        cdr_time_scope ts(ctx, CDR_TAG_DTCDR_FWD_GRAD, s);
-        kern<<<dim3(p.grid), dim3(kBlock), p.lds, s>>>(a);
-    }
-    CDR_LAUNCH_CHECK();
-    const int n_elem = p.net.total;
-    dtcdr_finish_kernel<<<dim3(1 + (n_elem + kBlock - 1) / kBlock), dim3(kBlock), 0, s>>>(ctx->partials, p.grid, B, weight, out8,
-                                                                                           (const float*)workspace, n_elem, dparams);
-    CDR_LAUNCH_CHECK();
-    return CDR_OK;
+    return rowstep_run(ctx, s, CDR_TAG_DTCDR_FWD_GRAD, __func__, [&] { kern<<<dim3(p.grid), dim3(kBlock), p.lds, s>>>(a); }, p.grid,
+                       rowstep_bce{B, weight}, out8, workspace, p.net.total, dparams);
 }

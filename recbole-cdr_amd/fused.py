@@ -204,14 +204,9 @@ def rowwise_catch_up(tables, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay
     del keep
 
 
-def _sort_workspace_bytes(n_keys, rows):
-    need = ctypes.c_size_t(0)
-    B_._check(B_.load().cdr_sort_workspace_bytes(n_keys, rows, ctypes.byref(need)), 'cdr_sort_workspace_bytes')
-    return int(need.value)
-
-
 class _Step:
-    """What every step class keeps: the optimizer settings (and their native-call form) and the host side of a hipGraph replay."""
+    """What every step class keeps: the optimizer settings (and their native-call form), the host side of a hipGraph replay, and what
+    the steps composed of a forward, an id sort and segmented applies share: the size queries, the sort buffers, the states and the apply."""
 
     def __init__(self, opt, lr, betas, eps, weight_decay):
         self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
@@ -227,6 +222,80 @@ class _Step:
             for st in self._states():
                 st.advance(device_bumped=True)
 
+    @staticmethod
+    def _query_bytes(entry, *args):
+        """What the native size query ``entry(*args, &bytes)`` reports."""
+        need = ctypes.c_size_t(0)
+        B_._check(getattr(B_.load(), entry)(*args, ctypes.byref(need)), entry)
+        return int(need.value)
+
+    @staticmethod
+    def _sort_rows_of(*tables):
+        return 2 << (max(t.shape[0] for t in tables) - 1).bit_length()
+
+    @classmethod
+    def _sort_scratch(cls, dev, rows, *n_keys):
+        """uint8 scratch of an id sort over ``rows`` table rows: enough for each of the key counts given."""
+        return torch.empty(max(cls._query_bytes('cdr_sort_workspace_bytes', n, rows) for n in n_keys), device=dev, dtype=torch.uint8)
+
+    @classmethod
+    def _sort_buffers(cls, n_keys, rows, dev):
+        """(keys, perm, scratch) of an id sort of up to ``n_keys`` keys.  The sort switches configuration at 2^18 keys: a short tail
+        batch may need more scratch than a full one, so the scratch covers the full count and min(count, 2^18 - 1)."""
+        return (torch.empty(n_keys, device=dev, dtype=torch.int32), torch.empty(n_keys, device=dev, dtype=torch.int32),
+                cls._sort_scratch(dev, rows, n_keys, min(n_keys, (1 << 18) - 1)))
+
+    def _own_states(self, tables, states):
+        """One ``RowwiseState`` per table: the caller's where one is given, a fresh one otherwise."""
+        states = states if states is not None else (None,) * len(tables)
+        return tuple(st if st is not None else RowwiseState(t, self.opt) for st, t in zip(states, tables))
+
+    def _apply(self, ctxh, st, D, keys, perm, n, G, neg_start, reg_limit, coef, key_base, advance=True):
+        """One segmented update of ``st``'s table from the sorted occurrence list: occurrence o takes G[o] below ``neg_start`` and
+        -G[o - neg_start] from it on; EmbLoss with the device coefficient ``coef`` (None: none) on occurrences below ``reg_limit``.
+        ``advance=False``: the caller has counted the update already."""
+        if advance:
+            st.advance()
+        B_.call('cdr_rowwise_apply', ctxh, B_.stream(), self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), D,
+                B_.raw(keys), B_.raw(perm), n, B_.f32(G), neg_start, reg_limit, None if coef is None else B_.f32(coef), *self._hp(),
+                st.step, None, int(key_base))
+
+    def _check_pair_batch(self, source, target):
+        """(B_s, B_t) of a two-domain batch: every tensor of a domain of one length, within the sizes the step was built for."""
+        Bs, Bt = source[0].numel(), target[0].numel()
+        if not (1 <= Bs <= self.max_source and 1 <= Bt <= self.max_target):
+            raise ValueError(f'{type(self).__name__}: batches of {Bs} + {Bt} rows, sized for 1..{self.max_source} + 1..{self.max_target}')
+        if any(x.numel() != Bs for x in source) or any(x.numel() != Bt for x in target):
+            raise ValueError(f'{type(self).__name__}: ids and labels of a domain must have the same length')
+        return Bs, Bt
+
+
+class _DenseStep(_Step):
+    """A step that also owns small dense parameters: they keep the exact dense Adam (plain SGD with opt='sgd') while the tables are
+    updated row-wise.  ``params`` are the parameters themselves: the step sets their ``.grad`` and updates them in place."""
+
+    def _dense_init(self, params):
+        from .trainer.trainer import DenseAdam
+        self.params = list(params)
+        self.w_opt = DenseAdam(self.params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.wd) \
+            if self.opt == OPT_ADAM else None
+
+    def _dense_update(self, packed=None):
+        """``packed``: the gradients as one vector in ``params`` order, each ``.grad`` becomes a view of it (None: the caller has set
+        them).  Then the update; a parameter whose ``.grad`` is None does not move (torch.optim.Adam skips it too)."""
+        if packed is not None:
+            off = 0
+            for q in self.params:
+                q.grad = packed[off:off + q.numel()].view(q.shape)
+                off += q.numel()
+        if self.w_opt is not None:
+            self.w_opt.step()
+        else:
+            with torch.no_grad():
+                for q in self.params:
+                    if q.grad is not None:
+                        q.add_(q.grad + self.wd * q if self.wd else q.grad, alpha=-self.lr)
+
 
 class _TwoTableStep(_Step):
     """What the steps on one (user table, item table) pair share: the tables, one ``RowwiseState`` per table (the caller's, or a fresh
@@ -240,15 +309,15 @@ class _TwoTableStep(_Step):
         self.D = user_table.shape[1]
         self.ustate = user_state if user_state is not None else RowwiseState(user_table, self.opt)
         self.istate = item_state if item_state is not None else RowwiseState(item_table, self.opt)
-        self._sort_rows = 2 << (max(user_table.shape[0], item_table.shape[0]) - 1).bit_length()
+        self._sort_rows = self._sort_rows_of(user_table, item_table)
 
     def _states(self):
         return self.ustate, self.istate
 
     def _sort_workspace(self, *n_keys):
         """(uint8 scratch, its size in bytes) of the two-table id sort: enough for each of the key counts given."""
-        need = max(_sort_workspace_bytes(n, self._sort_rows) for n in n_keys)
-        return torch.empty(need, device=self.U.device, dtype=torch.uint8), need
+        ws = self._sort_scratch(self.U.device, self._sort_rows, *n_keys)
+        return ws, ws.numel()
 
     def _single_row_buffers(self, n):
         """(flags, heads) of the forward kernels that update single-occurrence rows themselves: four flag bytes per batch row."""
@@ -309,10 +378,9 @@ class FusedBPRStep(_TwoTableStep):
     def _count_buffers(self):
         if self._count is None:
             dev = self.U.device
-            need = ctypes.c_size_t(0)
-            B_._check(B_.load().cdr_id_count_workspace_bytes(min(self.max_batch, self.COUNT_MAX_B), ctypes.byref(need)), 'cdr_id_count_workspace_bytes')
+            need = self._query_bytes('cdr_id_count_workspace_bytes', min(self.max_batch, self.COUNT_MAX_B))
             self._count = (torch.zeros(self.U.shape[0], device=dev, dtype=torch.int32), torch.zeros(self.I.shape[0], device=dev, dtype=torch.int32),
-                           torch.empty(int(need.value), device=dev, dtype=torch.uint8))
+                           torch.empty(need, device=dev, dtype=torch.uint8))
         return self._count
 
     def _select_id_path(self, B):
@@ -438,16 +506,10 @@ class FusedBPRStep(_TwoTableStep):
 
     def apply_sorted(self, B):
         ctxh = B_.ctx(self.U.device)
-        self._apply(ctxh, self.ustate, self.keys[:B], self.perm[:B], B, self.GU, B, B, self.out6[4:5], 0)
-        self._apply(ctxh, self.istate, self.keys[B:3 * B], self.perm[B:3 * B], 2 * B, self.GP, B, B, self.out6[5:6],
+        self._apply(ctxh, self.ustate, self.D, self.keys[:B], self.perm[:B], B, self.GU, B, B, self.out6[4:5], 0)
+        self._apply(ctxh, self.istate, self.D, self.keys[B:3 * B], self.perm[B:3 * B], 2 * B, self.GP, B, B, self.out6[5:6],
                     self._key_base.value)
         return self.out6
-
-    def _apply(self, ctxh, st, keys, perm, n, G, neg_start, reg_limit, coef, key_base):
-        st.advance()
-        B_.call('cdr_rowwise_apply', ctxh, B_.stream(), self.opt, B_.f32(st.table), B_.f32(st.exp_avg),
-                B_.f32(st.exp_avg_sq), self.D, B_.raw(keys), B_.raw(perm), n, B_.f32(G), neg_start, reg_limit,
-                B_.f32(coef), *self._hp(), st.step, None, int(key_base))
 
 
 class KMajorBPRStep(_TwoTableStep):
@@ -657,14 +719,10 @@ class FusedPointStep(_TwoTableStep):
                 self.I.shape[0], B_.raw(self.keys), B_.raw(self.perm), ctypes.byref(self._key_base), B_.raw(self.ws), self.ws.numel())
 
     def apply_sorted(self, B):
-        s = B_.stream()
         ctxh = B_.ctx(self.U.device)
         for st, lo, G, coef, base in ((self.ustate, 0, self.GU, self.out6[4:5], 0),
                                       (self.istate, B, self.GI, self.out6[5:6], self._key_base.value)):
-            st.advance()
-            B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
-                    B_.raw(self.keys[lo:lo + B]), B_.raw(self.perm[lo:lo + B]), B, B_.f32(G), B, B, B_.f32(coef), *self._hp(), st.step, None,
-                    int(base))
+            self._apply(ctxh, st, self.D, self.keys[lo:lo + B], self.perm[lo:lo + B], B, G, B, B, coef, base)
         return self.out6
 
 
@@ -707,13 +765,11 @@ class FusedTripletStep(_TwoTableStep):
         self.ustate.advance(); self.istate.advance()
         # every occurrence has its own gradient row: neg_start = n (nothing is negated), reg_limit = 0 (no EmbLoss)
         for st, lo, n, G, base in ((self.ustate, 0, B, self.GU, 0), (self.istate, B, 2 * B, GI, self._key_base.value)):
-            B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
-                    B_.raw(self.keys[lo:lo + n]), B_.raw(self.perm[lo:lo + n]), n, B_.f32(G), n, 0, None, *self._hp(), st.step, None,
-                    int(base))
+            self._apply(ctxh, st, self.D, self.keys[lo:lo + n], self.perm[lo:lo + n], n, G, n, 0, None, base, advance=False)
         return self.out3
 
 
-class FusedCLFMStep(_Step):
+class FusedCLFMStep(_DenseStep):
     """CLFM's BOTH-phase step (clfm.py:74-124): per domain  p = sigmoid(<W_d U_d[uid], I_d[iid]>)  with the stacked weight
     W_d = [shared_linear ; <domain>_only_linear] [Di, Du], loss = alpha (BCE_s + reg EmbLoss_s) + (1 - alpha) (BCE_t + reg EmbLoss_t).  The
     four tables (user and item table of each domain, widths Du and Di) are updated row-wise on the batch's rows; the three small
@@ -735,7 +791,6 @@ class FusedCLFMStep(_Step):
 
     def __init__(self, source_user, source_item, target_user, target_item, weights, max_source, max_target, alpha, reg_weight, opt='adam',
                  lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, states=None):
-        from .trainer.trainer import DenseAdam
         tables = (source_user, source_item, target_user, target_item)
         assert all(t.is_cuda for t in tables), 'FusedCLFMStep needs ROCm device tensors'
         Du, Di = source_user.shape[1], source_item.shape[1]
@@ -752,10 +807,8 @@ class FusedCLFMStep(_Step):
         self.tables = tables
         self.weights = (shared, s_only, t_only)
         self.alpha, self.reg_weight = float(alpha), float(reg_weight)
-        states = states if states is not None else (None,) * 4
-        self.states = tuple(st if st is not None else RowwiseState(t, self.opt) for st, t in zip(states, tables))
-        self.params = [w for w in self.weights if w is not None]
-        self.w_opt = DenseAdam(self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.opt == OPT_ADAM else None
+        self.states = self._own_states(tables, states)
+        self._dense_init(w for w in self.weights if w is not None)
         dev = source_user.device
         self.max_source, self.max_target = int(max_source), int(max_target)
         Bm = max(self.max_source, self.max_target)
@@ -763,14 +816,10 @@ class FusedCLFMStep(_Step):
         self.GI = tuple(torch.empty(n, Di, device=dev, dtype=torch.float32) for n in (self.max_source, self.max_target))
         self.dW = torch.zeros(2, Di, Du, device=dev, dtype=torch.float32)
         self.out16 = torch.zeros(16, device=dev, dtype=torch.float32)           # out8 of the source, out8 of the target
-        need = ctypes.c_size_t(0)
-        B_._check(B_.load().cdr_clfm_fwd_grad_workspace_bytes(Bm, Du, Di, ctypes.byref(need)), 'cdr_clfm_fwd_grad_workspace_bytes')
-        self.fws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)   # (the grid, and with it the size, grows with B)
-        self.keys = torch.empty(2 * Bm, device=dev, dtype=torch.int32)           # one sort per domain: user keys, then item keys
-        self.perm = torch.empty(2 * Bm, device=dev, dtype=torch.int32)
-        rows = 2 << (max(t.shape[0] for t in tables) - 1).bit_length()
-        # (the sort switches configuration at 2^18 keys: a short tail batch may need more scratch than a full one)
-        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (2 * Bm, min(2 * Bm, (1 << 18) - 1))), device=dev, dtype=torch.uint8)
+        # (the grid, and with it the size, grows with B)
+        self.fws = torch.empty(self._query_bytes('cdr_clfm_fwd_grad_workspace_bytes', Bm, Du, Di), device=dev, dtype=torch.uint8)
+        # one sort per domain: user keys, then item keys
+        self.keys, self.perm, self.ws = self._sort_buffers(2 * Bm, self._sort_rows_of(*tables), dev)
         self._key_base = ctypes.c_uint32(0)
 
     def _states(self):
@@ -785,11 +834,7 @@ class FusedCLFMStep(_Step):
     def step(self, su, si, ys, tu, ti, yt):
         """su / si int64 [B_s], ys fp32 [B_s] (source rows); tu / ti int64 [B_t], yt fp32 [B_t] (target rows).  Returns the total loss
         (device [1]); ``out16`` keeps each domain's {weighted total, BCE, EmbLoss, ||U rows||, ||I rows||, c_u, c_i, 0}."""
-        Bs, Bt = su.numel(), tu.numel()
-        if not (1 <= Bs <= self.max_source and 1 <= Bt <= self.max_target):
-            raise ValueError(f'FusedCLFMStep: batches of {Bs} + {Bt} rows, sized for 1..{self.max_source} + 1..{self.max_target}')
-        if si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
-            raise ValueError('FusedCLFMStep: ids and labels of a domain must have the same length')
+        Bs, Bt = self._check_pair_batch((su, si, ys), (tu, ti, yt))
         dev = self.tables[0].device
         ctxh, s = B_.ctx(dev), B_.stream()
         S, Du, Di = self.share, self.Du, self.Di
@@ -805,25 +850,18 @@ class FusedCLFMStep(_Step):
                     B_.raw(self.keys), B_.raw(self.perm), ctypes.byref(self._key_base), B_.raw(self.ws), self.ws.numel())
             # one gradient row per occurrence (neg_start = n), EmbLoss on every occurrence (reg_limit = n) with the domain's coefficient
             for st, lo, D, G, coef, base in ((ust, 0, Du, self.GU[d], 8 * d + 5, 0), (ist, n, Di, self.GI[d], 8 * d + 6, self._key_base.value)):
-                st.advance()
-                B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), D,
-                        B_.raw(self.keys[lo:lo + n]), B_.raw(self.perm[lo:lo + n]), n, B_.f32(G[:n]), n, n, B_.f32(self.out16[coef:coef + 1]),
-                        *self._hp(), st.step, None, int(base))
+                self._apply(ctxh, st, D, self.keys[lo:lo + n], self.perm[lo:lo + n], n, G[:n], n, n, self.out16[coef:coef + 1], base)
         shared, s_only, t_only = self.weights
         if shared is not None:
             shared.grad = self.dW[0, :S] + self.dW[1, :S]
         if s_only is not None:
             s_only.grad = self.dW[0, S:]
             t_only.grad = self.dW[1, S:]
-        if self.w_opt is not None:
-            self.w_opt.step()
-        else:
-            for p in self.params:
-                p.add_(p.grad + self.wd * p if self.wd else p.grad, alpha=-self.lr)
+        self._dense_update()
         return self.out16[0:1] + self.out16[8:9]
 
 
-class FusedDTCDRStep(_Step):
+class FusedDTCDRStep(_DenseStep):
     """DTCDR's BOTH-phase step with the NeuMF tower (dtcdr.py:112-126, 182-199): per domain  p = sigmoid(head_d(mlp_d([max(Us[u], Ut[u]) |
     max(Is[i], It[i])])))  with dropout in front of every hidden layer, loss = alpha BCE_s + (1 - alpha) BCE_t.  Every occurrence feeds
     BOTH domains' tables (the maximum routes each element's gradient to the table that won it, half to each on an exact tie) and each of
@@ -851,7 +889,6 @@ class FusedDTCDRStep(_Step):
 
     def __init__(self, source_user, source_item, target_user, target_item, towers, max_source, max_target, alpha, dropout_prob=0.0,
                  opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, states=None):
-        from .trainer.trainer import DenseAdam
         tables = (source_user, source_item, target_user, target_item)
         assert all(t.is_cuda for t in tables), 'FusedDTCDRStep needs ROCm device tensors'
         D = source_user.shape[1]
@@ -872,10 +909,8 @@ class FusedDTCDRStep(_Step):
         self.tables = tables
         self.towers = tuple(tuple(tw) for tw in towers)
         self.alpha, self.p = float(alpha), float(dropout_prob)
-        states = states if states is not None else (None,) * 4
-        self.states = tuple(st if st is not None else RowwiseState(t, self.opt) for st, t in zip(states, tables))
-        self.params = [p for tw in self.towers for p in tw]
-        self.w_opt = DenseAdam(self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.opt == OPT_ADAM else None
+        self.states = self._own_states(tables, states)
+        self._dense_init(p for tw in self.towers for p in tw)
         dev = source_user.device
         self.max_source, self.max_target = int(max_source), int(max_target)
         Nm = self.max_source + self.max_target
@@ -884,35 +919,26 @@ class FusedDTCDRStep(_Step):
         self.dP = torch.zeros(2, self.n_params, device=dev, dtype=torch.float32)
         self.out16 = torch.zeros(16, device=dev, dtype=torch.float32)           # out8 of the source, out8 of the target
         self.zero = torch.zeros(1, device=dev, dtype=torch.float32)             # the applies' EmbLoss coefficient: none
-        need = ctypes.c_size_t(0)
-        B_._check(B_.load().cdr_dtcdr_fwd_grad_workspace_bytes(max(self.max_source, self.max_target), D, len(hidden), self._hidden_c,
-                                                               ctypes.byref(need)), 'cdr_dtcdr_fwd_grad_workspace_bytes')
-        self.fws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)   # (the grid, and with it the size, grows with B)
-        self.keys = torch.empty(2 * Nm, device=dev, dtype=torch.int32)           # one sort: user keys [su | tu], then item keys [si | ti]
-        self.perm = torch.empty(2 * Nm, device=dev, dtype=torch.int32)
-        rows = 2 << (max(t.shape[0] for t in tables) - 1).bit_length()
-        # (the sort switches configuration at 2^18 keys: a short tail batch may need more scratch than a full one)
-        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (2 * Nm, min(2 * Nm, (1 << 18) - 1))), device=dev, dtype=torch.uint8)
+        # (the grid, and with it the size, grows with B)
+        self.fws = torch.empty(self._workspace_bytes(max(self.max_source, self.max_target)), device=dev, dtype=torch.uint8)
+        # one sort: user keys [su | tu], then item keys [si | ti]
+        self.keys, self.perm, self.ws = self._sort_buffers(2 * Nm, self._sort_rows_of(*tables), dev)
         self._key_base = ctypes.c_uint32(0)
 
     def _states(self):
         return self.states
 
+    def _workspace_bytes(self, B):
+        return self._query_bytes('cdr_dtcdr_fwd_grad_workspace_bytes', B, self.D, len(self.hidden), self._hidden_c)
+
     def grid(self, B):
         """Workgroups cdr_dtcdr_fwd_grad launches for a batch of B rows (the workspace is one packed parameter vector per workgroup)."""
-        need = ctypes.c_size_t(0)
-        B_._check(B_.load().cdr_dtcdr_fwd_grad_workspace_bytes(B, self.D, len(self.hidden), self._hidden_c, ctypes.byref(need)),
-                  'cdr_dtcdr_fwd_grad_workspace_bytes')
-        return int(need.value) // (4 * self.n_params)
+        return self._workspace_bytes(B) // (4 * self.n_params)
 
     @torch.no_grad()
     def forward_grads(self, su, si, ys, tu, ti, yt, seed=None):
         """Both domains' cdr_dtcdr_fwd_grad: fills ``G`` (rows [0, B_s) source, [B_s, B_s + B_t) target), ``dP`` and ``out16``."""
-        Bs, Bt = su.numel(), tu.numel()
-        if not (1 <= Bs <= self.max_source and 1 <= Bt <= self.max_target):
-            raise ValueError(f'FusedDTCDRStep: batches of {Bs} + {Bt} rows, sized for 1..{self.max_source} + 1..{self.max_target}')
-        if si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
-            raise ValueError('FusedDTCDRStep: ids and labels of a domain must have the same length')
+        Bs, Bt = self._check_pair_batch((su, si, ys), (tu, ti, yt))
         if seed is not None and (seed.dtype != torch.int64 or not seed.is_cuda):
             raise ValueError('FusedDTCDRStep: the dropout seed is a device int64 [1]')
         ctxh, s = B_.ctx(self.tables[0].device), B_.stream()
@@ -940,24 +966,12 @@ class FusedDTCDRStep(_Step):
         # one gradient row per occurrence (neg_start = n), no EmbLoss (reg_limit = 0); table order: Us, Is, Ut, It
         for st, G, lo, base in ((self.states[0], self.G[0], 0, 0), (self.states[2], self.G[2], 0, 0),
                                 (self.states[1], self.G[1], n, self._key_base.value), (self.states[3], self.G[3], n, self._key_base.value)):
-            st.advance()
-            B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
-                    B_.raw(self.keys[lo:lo + n]), B_.raw(self.perm[lo:lo + n]), n, B_.f32(G[:n]), n, 0, B_.f32(self.zero), *self._hp(),
-                    st.step, None, int(base))
-        for d, tw in enumerate(self.towers):
-            off = 0
-            for q in tw:
-                q.grad = self.dP[d, off:off + q.numel()].view(q.shape)
-                off += q.numel()
-        if self.w_opt is not None:
-            self.w_opt.step()
-        else:
-            for q in self.params:
-                q.add_(q.grad + self.wd * q if self.wd else q.grad, alpha=-self.lr)
+            self._apply(ctxh, st, self.D, self.keys[lo:lo + n], self.perm[lo:lo + n], n, G[:n], n, 0, self.zero, base)
+        self._dense_update(self.dP.view(-1))                        # (params: the source tower, then the target tower, as dP's rows)
         return self.out16[0:1] + self.out16[8:9]
 
 
-class FusedDeepAPFStep(_Step):
+class FusedDeepAPFStep(_DenseStep):
     """DeepAPF's BOTH-phase step (deepapf.py:69-152, 163-175): per domain the key id's share row and domain-only row, each multiplied with
     the other side's row and scored by the two-layer attention MLP (W1, b1, w2), the pair softmax with the share score masked where
     key > n_overlap (strictly), the merged row through the predict layer wp, loss = BCE_s + BCE_t.  Five live tables, named by role: the
@@ -987,7 +1001,6 @@ class FusedDeepAPFStep(_Step):
 
     def __init__(self, share, source_only, source_other, target_only, target_other, params, n_overlap, max_source, max_target, opt='adam',
                  lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, states=None):
-        from .trainer.trainer import DenseAdam
         tables = (share, source_only, source_other, target_only, target_other)
         assert all(t.is_cuda for t in tables), 'FusedDeepAPFStep needs ROCm device tensors'
         D = int(share.shape[1])
@@ -1002,11 +1015,9 @@ class FusedDeepAPFStep(_Step):
         super().__init__(opt, lr, betas, eps, weight_decay)
         self.D = D
         self.tables = tables
-        self.params = list(params)
         self.n_overlap = int(n_overlap)
-        states = states if states is not None else (None,) * 5
-        self.states = tuple(st if st is not None else RowwiseState(t, self.opt) for st, t in zip(states, tables))
-        self.w_opt = DenseAdam(self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.opt == OPT_ADAM else None
+        self.states = self._own_states(tables, states)
+        self._dense_init(params)
         dev = share.device
         self.max_source, self.max_target = int(max_source), int(max_target)
         Nm = self.max_source + self.max_target
@@ -1018,20 +1029,15 @@ class FusedDeepAPFStep(_Step):
         self.out16 = torch.zeros(16, device=dev, dtype=torch.float32)           # out8 of the source, out8 of the target
         self.zero = torch.zeros(1, device=dev, dtype=torch.float32)             # the applies' EmbLoss coefficient: none
         self.fws = torch.empty(self._workspace_bytes(max(self.max_source, self.max_target)), device=dev, dtype=torch.uint8)
-        self.keys = torch.empty(2 * Nm, device=dev, dtype=torch.int32)           # one sort at a time: at most 2 max(B_s, B_t) or B_s + B_t keys
-        self.perm = torch.empty(2 * Nm, device=dev, dtype=torch.int32)
-        rows = 2 << (max(t.shape[0] for t in tables) - 1).bit_length()
-        # (the sort switches configuration at 2^18 keys: a short tail batch may need more scratch than a full one)
-        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (2 * Nm, min(2 * Nm, (1 << 18) - 1))), device=dev, dtype=torch.uint8)
+        # one sort at a time: at most 2 max(B_s, B_t) or B_s + B_t keys
+        self.keys, self.perm, self.ws = self._sort_buffers(2 * Nm, self._sort_rows_of(*tables), dev)
         self._key_base = ctypes.c_uint32(0)
 
     def _states(self):
         return self.states
 
     def _workspace_bytes(self, B):
-        need = ctypes.c_size_t(0)
-        B_._check(B_.load().cdr_deepapf_fwd_grad_workspace_bytes(B, self.D, ctypes.byref(need)), 'cdr_deepapf_fwd_grad_workspace_bytes')
-        return int(need.value)
+        return self._query_bytes('cdr_deepapf_fwd_grad_workspace_bytes', B, self.D)
 
     def grid(self, B):
         """Workgroups cdr_deepapf_fwd_grad launches for a batch of B rows (the workspace is one packed parameter vector per workgroup)."""
@@ -1041,11 +1047,7 @@ class FusedDeepAPFStep(_Step):
     def forward_grads(self, ks, os_, ys, kt, ot, yt):
         """Both domains' cdr_deepapf_fwd_grad: fills ``GS`` (rows [0, B_s) source, [B_s, B_s + B_t) target), ``GO``, ``GT``, ``dP`` and
         ``out16``."""
-        Bs, Bt = ks.numel(), kt.numel()
-        if not (1 <= Bs <= self.max_source and 1 <= Bt <= self.max_target):
-            raise ValueError(f'FusedDeepAPFStep: batches of {Bs} + {Bt} rows, sized for 1..{self.max_source} + 1..{self.max_target}')
-        if os_.numel() != Bs or ys.numel() != Bs or ot.numel() != Bt or yt.numel() != Bt:
-            raise ValueError('FusedDeepAPFStep: ids and labels of a domain must have the same length')
+        Bs, Bt = self._check_pair_batch((ks, os_, ys), (kt, ot, yt))
         ctxh, s = B_.ctx(self.tables[0].device), B_.stream()
         packed = torch.cat([q.data.reshape(-1) for q in self.params])
         for d, key, oid, y, n, row0 in ((0, ks, os_, ys, Bs, 0), (1, kt, ot, yt, Bt, Bs)):
@@ -1054,12 +1056,9 @@ class FusedDeepAPFStep(_Step):
                     B_.f32(self.out16[8 * d:8 * d + 8]), B_.f32(self.GS), B_.f32(self.GO[d]), B_.f32(self.GT[d]), B_.f32(self.dP[d]),
                     B_.raw(self.fws), self.fws.numel())
 
-    def _apply(self, ctxh, s, st, lo, n, G, base):
-        st.advance()
+    def _apply_rows(self, ctxh, st, lo, n, G, base):
         # one gradient row per occurrence (neg_start = n), no EmbLoss (reg_limit = 0)
-        B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
-                B_.raw(self.keys[lo:lo + n]), B_.raw(self.perm[lo:lo + n]), n, B_.f32(G[:n]), n, 0, B_.f32(self.zero), *self._hp(), st.step,
-                None, int(base))
+        self._apply(ctxh, st, self.D, self.keys[lo:lo + n], self.perm[lo:lo + n], n, G[:n], n, 0, self.zero, base)
 
     @torch.no_grad()
     def step(self, ks, os_, ys, kt, ot, yt):
@@ -1070,27 +1069,18 @@ class FusedDeepAPFStep(_Step):
         ctxh, s = B_.ctx(self.tables[0].device), B_.stream()
         B_.call('cdr_sort_ids', ctxh, s, B_.i64(ks), Bs, B_.i64(kt), Bt, self.tables[0].shape[0], B_.raw(self.keys), B_.raw(self.perm),
                 B_.raw(self.ws), self.ws.numel())
-        self._apply(ctxh, s, self.states[0], 0, Bs + Bt, self.GS, 0)
+        self._apply_rows(ctxh, self.states[0], 0, Bs + Bt, self.GS, 0)
         for d, key, oid, n in ((0, ks, os_, Bs), (1, kt, ot, Bt)):
             ost, tst = self.states[1 + 2 * d], self.states[2 + 2 * d]
             B_.call('cdr_sort_ids_two_tables', ctxh, s, B_.i64(key), n, ost.table.shape[0], B_.i64(oid), n, None, 0, tst.table.shape[0],
                     B_.raw(self.keys), B_.raw(self.perm), ctypes.byref(self._key_base), B_.raw(self.ws), self.ws.numel())
-            self._apply(ctxh, s, ost, 0, n, self.GO[d], 0)
-            self._apply(ctxh, s, tst, n, n, self.GT[d], self._key_base.value)
-        dP = self.dP[0] + self.dP[1]                                # the towers are shared by the domains
-        off = 0
-        for q in self.params:
-            q.grad = dP[off:off + q.numel()].view(q.shape)
-            off += q.numel()
-        if self.w_opt is not None:
-            self.w_opt.step()
-        else:
-            for q in self.params:
-                q.add_(q.grad + self.wd * q if self.wd else q.grad, alpha=-self.lr)
+            self._apply_rows(ctxh, ost, 0, n, self.GO[d], 0)
+            self._apply_rows(ctxh, tst, n, n, self.GT[d], self._key_base.value)
+        self._dense_update(self.dP[0] + self.dP[1])                 # the towers are shared by the domains
         return self.out16[0:1] + self.out16[8:9]
 
 
-class FusedDCDCSRMapStep(_Step):
+class FusedDCDCSRMapStep(_DenseStep):
     """DCDCSR's BOTH-phase step (dcdcsr.py:172-187): ``n`` unit ids drawn with repeats, e = maxmin(table[idx]), m = the tanh MLP of e (tanh
     after every layer, the last included), b = maxmin(bench[idx]) without a gradient, loss = MSE(m, b) as a mean over n D.  One live table
     (the target table of the overlapped unit kind) and the MLP.
@@ -1117,7 +1107,6 @@ class FusedDCDCSRMapStep(_Step):
             raise ValueError(f'FusedDCDCSRMapStep: the MLP must map the row width onto itself, got {dims}')
 
     def __init__(self, table, bench, layers, max_batch, state=None, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        from .trainer.trainer import DenseAdam
         assert table.is_cuda, 'FusedDCDCSRMapStep needs ROCm device tensors'
         layers = [tuple(l) for l in layers]
         dims = [int(layers[0][0].shape[1])] + [int(W.shape[0]) for W, _ in layers] if layers else []
@@ -1130,9 +1119,8 @@ class FusedDCDCSRMapStep(_Step):
         super().__init__(opt, lr, betas, eps, weight_decay)
         self.table, self.D, self.dims = table, dims[0], dims
         self.bench = bench
-        self.params = [q for pair in layers for q in pair]
-        self.state = state if state is not None else RowwiseState(table, self.opt)
-        self.w_opt = DenseAdam(self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.opt == OPT_ADAM else None
+        self._dense_init(q for pair in layers for q in pair)
+        self.state, = self._own_states((table,), (state,))
         dev = table.device
         self.max_batch = int(max_batch)
         self._dims_c = (ctypes.c_int * len(dims))(*dims)
@@ -1142,21 +1130,13 @@ class FusedDCDCSRMapStep(_Step):
         self.out8 = torch.zeros(8, device=dev, dtype=torch.float32)
         self.zero = torch.zeros(1, device=dev, dtype=torch.float32)             # the apply's EmbLoss coefficient: none
         self.fws = torch.empty(self._workspace_bytes(self.max_batch), device=dev, dtype=torch.uint8)
-        self.keys = torch.empty(self.max_batch, device=dev, dtype=torch.int32)
-        self.perm = torch.empty(self.max_batch, device=dev, dtype=torch.int32)
-        rows = 2 << (table.shape[0] - 1).bit_length()
-        # (the sort switches configuration at 2^18 keys: a short batch may need more scratch than a full one)
-        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (self.max_batch, min(self.max_batch, (1 << 18) - 1))), device=dev,
-                              dtype=torch.uint8)
+        self.keys, self.perm, self.ws = self._sort_buffers(self.max_batch, self._sort_rows_of(table), dev)
 
     def _states(self):
         return (self.state,)
 
     def _workspace_bytes(self, n):
-        need = ctypes.c_size_t(0)
-        B_._check(B_.load().cdr_dcdcsr_map_fwd_grad_workspace_bytes(n, len(self.dims) - 1, self._dims_c, ctypes.byref(need)),
-                  'cdr_dcdcsr_map_fwd_grad_workspace_bytes')
-        return int(need.value)
+        return self._query_bytes('cdr_dcdcsr_map_fwd_grad_workspace_bytes', n, len(self.dims) - 1, self._dims_c)
 
     def grid(self, n):
         """Workgroups cdr_dcdcsr_map_fwd_grad launches for n ids (the workspace is one packed parameter vector per workgroup)."""
@@ -1187,19 +1167,9 @@ class FusedDCDCSRMapStep(_Step):
         ctxh, s, st = B_.ctx(self.table.device), B_.stream(), self.state
         B_.call('cdr_sort_ids', ctxh, s, B_.i64(idx), n, None, 0, self.table.shape[0], B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.ws),
                 self.ws.numel())
-        st.advance()
         # one gradient row per occurrence (neg_start = n), no EmbLoss (reg_limit = 0)
-        B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
-                B_.raw(self.keys[:n]), B_.raw(self.perm[:n]), n, B_.f32(self.G[:n]), n, 0, B_.f32(self.zero), *self._hp(), st.step, None, 0)
-        off = 0
-        for q in self.params:
-            q.grad = self.dP[off:off + q.numel()].view(q.shape)
-            off += q.numel()
-        if self.w_opt is not None:
-            self.w_opt.step()
-        else:
-            for q in self.params:
-                q.add_(q.grad + self.wd * q if self.wd else q.grad, alpha=-self.lr)
+        self._apply(ctxh, st, self.D, self.keys[:n], self.perm[:n], n, self.G[:n], n, 0, self.zero, 0)
+        self._dense_update(self.dP)
         return self.out8[0]
 
 
@@ -1226,7 +1196,7 @@ class FusedFrozenSideBPRStep(_Step):
         super().__init__(opt, lr, betas, eps, weight_decay)
         self.U, self.I, self.D, self.frozen, self.gamma = user_rows, item_rows, D, frozen, gamma
         trained = item_rows if frozen == 'user' else user_rows
-        self.state = state if state is not None else RowwiseState(trained, self.opt)
+        self.state, = self._own_states((trained,), (state,))
         if self.state.table.data_ptr() != trained.data_ptr():
             raise ValueError('FusedFrozenSideBPRStep: state belongs to another table than the trained operand')
         dev = trained.device
@@ -1236,10 +1206,7 @@ class FusedFrozenSideBPRStep(_Step):
         self.out6 = torch.zeros(12, device=dev, dtype=torch.float32)
         self.zero = torch.zeros(1, device=dev, dtype=torch.float32)
         nk = 2 * Bm if frozen == 'user' else Bm
-        self.keys = torch.empty(nk, device=dev, dtype=torch.int32)
-        self.perm = torch.empty(nk, device=dev, dtype=torch.int32)
-        rows = 2 << (trained.shape[0] - 1).bit_length()
-        self.ws = torch.empty(max(_sort_workspace_bytes(n, rows) for n in (nk, min(nk, (1 << 18) - 1))), device=dev, dtype=torch.uint8)
+        self.keys, self.perm, self.ws = self._sort_buffers(nk, self._sort_rows_of(trained), dev)
 
     def _states(self):
         return (self.state,)
@@ -1261,14 +1228,12 @@ class FusedFrozenSideBPRStep(_Step):
             n, G = B, self.GU
             B_.call('cdr_sort_ids', ctxh, s, B_.i64(uid), B, None, 0, st.table.shape[0], B_.raw(self.keys), B_.raw(self.perm), B_.raw(self.ws),
                     self.ws.numel())
-        st.advance()
         # occurrences [B, 2 B) of the item list are the negatives: -GP[o - B]; no EmbLoss (reg_limit = 0)
-        B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), self.D,
-                B_.raw(self.keys[:n]), B_.raw(self.perm[:n]), n, B_.f32(G), B, 0, B_.f32(self.zero), *self._hp(), st.step, None, 0)
+        self._apply(ctxh, st, self.D, self.keys[:n], self.perm[:n], n, G, B, 0, self.zero, 0)
         return self.out6
 
 
-class SSCDRMapStep(_Step):
+class SSCDRMapStep(_DenseStep):
     """SSCDR's OVERLAP phase (sscdr.py:161-187: MSE(mapping(source_a[idx]), target_a[idx]) + lambda x triplet(normalize(target_a[idx]),
     normalize(mapping(source_b[pos])), normalize(mapping(source_b[neg])))) as an O(batch) step: the three touched tables are updated
     row-wise -- source_a and target_a on ``idx`` (one sort serves both), source_b on ``pos ++ neg`` -- and the mapping's own parameters
@@ -1278,25 +1243,31 @@ class SSCDRMapStep(_Step):
 
     def __init__(self, source_a, target_a, source_b, mapping_fn, mapping_params, margin, lamda, opt='adam', lr=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=0.0, source_a_state=None, target_a_state=None, source_b_state=None):
-        from .trainer.trainer import DenseAdam
         assert source_a.is_cuda and target_a.is_cuda and source_b.is_cuda, 'SSCDRMapStep needs ROCm device tensors'
         assert source_a.shape[1] == target_a.shape[1] == source_b.shape[1]
         super().__init__(opt, lr, betas, eps, weight_decay)
         self.SA, self.TA, self.SB = source_a, target_a, source_b
         self.D = source_a.shape[1]
         self.mapping_fn = mapping_fn
-        self.mapping_params = list(mapping_params)
         self.margin, self.lamda = float(margin), float(lamda)
-        self.sa_state = source_a_state if source_a_state is not None else RowwiseState(source_a, self.opt)
-        self.ta_state = target_a_state if target_a_state is not None else RowwiseState(target_a, self.opt)
-        self.sb_state = source_b_state if source_b_state is not None else RowwiseState(source_b, self.opt)
-        self.map_opt = DenseAdam(self.mapping_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) \
-            if self.opt == OPT_ADAM else None
+        self.sa_state, self.ta_state, self.sb_state = self._own_states((source_a, target_a, source_b),
+                                                                       (source_a_state, target_a_state, source_b_state))
+        self._dense_init(mapping_params)
+        self.mapping_params = self.params
         self.loss = torch.zeros((), device=source_a.device, dtype=torch.float32)
         self._ws = None
 
     def _states(self):
         return self.sa_state, self.ta_state, self.sb_state
+
+    @property
+    def map_opt(self):
+        """The mapping's dense Adam under the name FusedMapStep uses (one object: assigning either name replaces it)."""
+        return self.w_opt
+
+    @map_opt.setter
+    def map_opt(self, opt):
+        self.w_opt = opt
 
     def step(self, idx, pos, neg, bump=None):
         """idx / pos / neg: int64 device tensors of n ids each (any shape).  ``bump``: optional device int64 [1] advanced once (the
@@ -1329,7 +1300,7 @@ class SSCDRMapStep(_Step):
             st.advance()
         ctxh = B_.ctx(dev)
         rows = max(self.SA.shape[0], self.TA.shape[0], self.SB.shape[0])
-        need = max(_sort_workspace_bytes(n, rows), _sort_workspace_bytes(2 * n, rows))
+        need = max(self._query_bytes('cdr_sort_workspace_bytes', m, rows) for m in (n, 2 * n))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, device=dev, dtype=torch.uint8)
         keys = torch.empty(3 * n, device=dev, dtype=torch.int32)
@@ -1342,15 +1313,8 @@ class SSCDRMapStep(_Step):
         gX, gT = X3.grad.contiguous(), Tt.grad.contiguous()
         for st, k, pm, m, G in ((self.sa_state, keys[:n], perm[:n], n, gX[:n]), (self.ta_state, keys[:n], perm[:n], n, gT),
                                 (self.sb_state, keys[n:], perm[n:], 2 * n, gX[n:])):
-            B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq), D, B_.raw(k),
-                    B_.raw(pm), m, B_.f32(G), m, 0, None, *self._hp(), st.step, None, 0)
-        if self.map_opt is not None:
-            self.map_opt.step()
-        else:
-            with torch.no_grad():
-                for p in self.mapping_params:
-                    if p.grad is not None:
-                        p.add_(p.grad + self.wd * p if self.wd else p.grad, alpha=-self.lr)
+            self._apply(ctxh, st, D, k, pm, m, G, m, 0, None, 0, advance=False)
+        self._dense_update()
         return self.loss
 
 
@@ -1646,7 +1610,7 @@ class FusedMapStep(_Step):
         self.tstate.advance()
         if n:
             ctxh = B_.ctx(dev)
-            need = _sort_workspace_bytes(n, self.S.shape[0])
+            need = self._query_bytes('cdr_sort_workspace_bytes', n, self.S.shape[0])
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, device=dev, dtype=torch.uint8)
             keys = torch.empty(n, device=dev, dtype=torch.int32)
@@ -1655,8 +1619,7 @@ class FusedMapStep(_Step):
             B_.call('cdr_sort_ids', ctxh, s, B_.i64(idx), n, None, 0, self.S.shape[0], B_.raw(keys), B_.raw(perm),
                     B_.raw(self._ws), self._ws.numel())
             for st, g in ((self.sstate, src.grad), (self.tstate, tgt.grad)):
-                B_.call('cdr_rowwise_apply', ctxh, s, self.opt, B_.f32(st.table), B_.f32(st.exp_avg), B_.f32(st.exp_avg_sq),
-                        st.table.shape[1], B_.raw(keys), B_.raw(perm), n, B_.f32(g), n, 0, None, *self._hp(), st.step, None, 0)
+                self._apply(ctxh, st, st.table.shape[1], keys, perm, n, g, n, 0, None, 0, advance=False)
         if self.map_opt is not None:
             self.map_opt.step()
         else:

@@ -141,35 +141,16 @@ class CLFM(RowwiseTraining, CrossDomainRecommender):
         tables hold what ``torch.optim.Adam`` over whole tables would have left once ``fused_sync()`` has run.  One mode per model."""
         from ...fused import FusedCLFMStep, rowwise_catch_up
         exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
-        if self.__dict__.get('_dist_cfg') not in (None, False):
-            raise NotImplementedError("CLFM.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
-        try:
-            FusedCLFMStep.check_widths(self.user_embedding_size, self.source_item_embedding_size)
-        except ValueError as e:
-            raise ValueError(f'CLFM.fused_train_step: user_embedding_size = {self.user_embedding_size}, source_item_embedding_size = '
-                             f'{self.source_item_embedding_size}: {e}; use optimizer_mode=dense') from None
+        self._fused_refuse_dist('CLFM')
+        self._fused_check_widths('CLFM', FusedCLFMStep.check_widths, 'user_embedding_size = {}, source_item_embedding_size = {}',
+                                 self.user_embedding_size, self.source_item_embedding_size)
         su, si, ys, tu, ti, yt = self._pair_fields(interaction)
-        Bs, Bt = su.numel(), tu.numel()
-        if Bs == 0 or Bt == 0 or si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
-            raise ValueError(f'CLFM.fused_train_step: the {self.phase} batch needs at least one row per domain and ids and labels of equal '
-                             f'length, got {Bs} / {si.numel()} / {ys.numel()} source and {Bt} / {ti.numel()} / {yt.numel()} target entries')
-        old = self._fused_cache(exact)['steps'].get('clfm')
+        Bs, Bt = self._fused_check_pair_batch('CLFM', su, si, ys, tu, ti, yt)
+        self._fused_cache(exact)
         states = tuple(self._fused_state(n, code, exact) for n in self._TABLES)
-        ms, mt = (Bs, Bt) if old is None else (max(Bs, old.max_source), max(Bt, old.max_target))
-
-        def build():
-            step = FusedCLFMStep(*(getattr(self, n).weight.data for n in self._TABLES), self._weights(), ms, mt, self.alpha, self.reg_weight,
-                                 states=states, **hp)
-            # the weights' Adam state outlives a re-sized step object, and a checkpoint's is handed over when the first one is built
-            carry = old.w_opt.state_dict() if old is not None and old.w_opt is not None else self.__dict__.pop('_pending_weight_state', None)
-            if carry is not None and step.w_opt is not None:
-                step.w_opt.load_state_dict(carry)
-                for g in step.w_opt.param_groups:
-                    g.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-            return step
-
-        step = self._fused_step('clfm', lambda s: s.max_source >= Bs and s.max_target >= Bt and s.hp == hp, build)
-        step.hp = hp
+        ms, mt = self._fused_pair_sizes('clfm', Bs, Bt)
+        step = self._fused_weight_step('clfm', lambda s: s.max_source >= Bs and s.max_target >= Bt, lambda: FusedCLFMStep(
+            *(getattr(self, n).weight.data for n in self._TABLES), self._weights(), ms, mt, self.alpha, self.reg_weight, states=states, **hp), hp)
         ys = ys if ys.dtype == torch.float32 else ys.float()
         yt = yt if yt.dtype == torch.float32 else yt.float()
         if exact:
@@ -179,20 +160,7 @@ class CLFM(RowwiseTraining, CrossDomainRecommender):
     def _fused_phase_step(self):
         return self._fused['steps']['clfm']
 
-    def fused_optimizer_state(self):
-        """The shared per-table state, plus the dense Adam state of the three linears."""
-        out = super().fused_optimizer_state()
-        step = self.__dict__.get('_fused', {}).get('steps', {}).get('clfm')
-        if step is not None and step.w_opt is not None:
-            out['weights'] = step.w_opt.state_dict()
-        return out
-
-    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
-        """The shared per-table restore; the linears' Adam state is handed to the step when it is built."""
-        super().load_fused_optimizer_state(state, opt=opt, adam=adam)
-        if 'weights' in state:
-            self.__dict__['_pending_weight_state'] = state['weights']
-        self.__dict__.get('_fused', {}).get('steps', {}).pop('clfm', None)
+    _WEIGHT_STEP = 'clfm'                                             # (the three linears' dense Adam state: the checkpoint's 'weights')
 
     @torch.no_grad()
     def predict(self, interaction):

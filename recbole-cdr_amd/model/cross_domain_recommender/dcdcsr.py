@@ -215,17 +215,13 @@ class DCDCSR(RowwiseTraining, CrossDomainRecommender):
         unequal-length id lists, and a (phase, visit) pair ``calculate_loss`` has no loss for (ValueError)."""
         from ...fused import FusedDCDCSRMapStep, FusedFrozenSideBPRStep, rowwise_catch_up
         exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
-        if self.__dict__.get('_dist_cfg') not in (None, False):
-            raise NotImplementedError("DCDCSR.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
+        self._fused_refuse_dist('DCDCSR')
         D = self.embedding_size
         if D % 4 != 0 or D > 256:
             raise ValueError(f'DCDCSR.fused_train_step needs embedding_size % 4 == 0 and embedding_size <= 256 (one float4 per lane, '
                              f'at most 64 lanes per row), got {D}; use optimizer_mode=dense')
         dims = [D] + [int(h) for h in self.mlp_hidden_size] + [D]
-        try:
-            FusedDCDCSRMapStep.check_widths(dims)
-        except ValueError as e:
-            raise ValueError(f'DCDCSR.fused_train_step: mapping MLP widths {dims}: {e}; use optimizer_mode=dense') from None
+        self._fused_check_widths('DCDCSR', FusedDCDCSRMapStep.check_widths, 'mapping MLP widths {}', dims)
         count = self.phase2count.get(self.phase, 0)
         unit = self._unit()
 
@@ -242,19 +238,9 @@ class DCDCSR(RowwiseTraining, CrossDomainRecommender):
             old = self._fused_cache(exact)['steps'].get('map')
             st = self._fused_state(name, code, exact)
 
-            def build():
-                step = FusedDCDCSRMapStep(getattr(self, name).weight.data, self.benchmark_embedding, self._mlp_pairs(),
-                                          n if old is None else max(n, old.max_batch), state=st, **hp)
-                # the MLP's Adam state outlives a re-sized step object, and a checkpoint's is handed over when the first one is built
-                carry = old.w_opt.state_dict() if old is not None and old.w_opt is not None else self.__dict__.pop('_pending_weight_state', None)
-                if carry is not None and step.w_opt is not None:
-                    step.w_opt.load_state_dict(carry)
-                    for g in step.w_opt.param_groups:
-                        g.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-                return step
-
-            step = self._fused_step('map', lambda s: s.max_batch >= n and s.hp == hp, build)
-            step.hp = hp
+            step = self._fused_weight_step('map', lambda s: s.max_batch >= n, lambda: FusedDCDCSRMapStep(
+                getattr(self, name).weight.data, self.benchmark_embedding, self._mlp_pairs(), n if old is None else max(n, old.max_batch),
+                state=st, **hp), hp)
             sampled_index = np.random.randint(0, getattr(self, f'target_num_{unit}s'), n)        # host draw, as the reference (:175)
             idx = torch.from_numpy(sampled_index).to(st.table.device)
             catch_up(st, [idx])
@@ -293,20 +279,7 @@ class DCDCSR(RowwiseTraining, CrossDomainRecommender):
             return self._fused['steps']['frozen']
         return self._fused['steps'][('bpr', self.phase.lower())]
 
-    def fused_optimizer_state(self):
-        """The shared per-table state, plus the dense Adam state of the mapping MLP under ``'weights'``."""
-        out = super().fused_optimizer_state()
-        step = self.__dict__.get('_fused', {}).get('steps', {}).get('map')
-        if step is not None and step.w_opt is not None:
-            out['weights'] = step.w_opt.state_dict()
-        return out
-
-    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
-        """The shared per-table restore; the MLP's Adam state is handed to the map step when it is built."""
-        super().load_fused_optimizer_state(state, opt=opt, adam=adam)
-        if 'weights' in state:
-            self.__dict__['_pending_weight_state'] = state['weights']
-        self.__dict__.get('_fused', {}).get('steps', {}).pop('map', None)
+    _WEIGHT_STEP = 'map'                                              # (the mapping MLP's dense Adam state: the checkpoint's 'weights')
 
     @torch.no_grad()
     def full_sort_predict(self, interaction):

@@ -188,36 +188,17 @@ class DeepAPF(RowwiseTraining, CrossDomainRecommender):
         ``config['dist_group']``, and widths outside ``FusedDeepAPFStep.check_widths`` (use optimizer_mode=dense for those)."""
         from ...fused import FusedDeepAPFStep, rowwise_catch_up
         exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
-        if self.__dict__.get('_dist_cfg') not in (None, False):
-            raise NotImplementedError("DeepAPF.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
-        try:
-            FusedDeepAPFStep.check_widths(self.embedding_size)
-        except ValueError as e:
-            raise ValueError(f'DeepAPF.fused_train_step: embedding_size = {self.embedding_size}: {e}; use optimizer_mode=dense') from None
+        self._fused_refuse_dist('DeepAPF')
+        self._fused_check_widths('DeepAPF', FusedDeepAPFStep.check_widths, 'embedding_size = {}', self.embedding_size)
         su, si, ys, tu, ti, yt = self._pair_fields(interaction)
-        Bs, Bt = su.numel(), tu.numel()
-        if Bs == 0 or Bt == 0 or si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
-            raise ValueError(f'DeepAPF.fused_train_step: the {self.phase} batch needs at least one row per domain and ids and labels of equal '
-                             f'length, got {Bs} / {si.numel()} / {ys.numel()} source and {Bt} / {ti.numel()} / {yt.numel()} target entries')
+        Bs, Bt = self._fused_check_pair_batch('DeepAPF', su, si, ys, tu, ti, yt)
         names, _mlp, n_over, kind = self._roles()
         ks, os_, kt, ot = (su, si, tu, ti) if kind == 'user' else (si, su, ti, tu)
-        old = self._fused_cache(exact)['steps'].get('deepapf')
+        self._fused_cache(exact)
         states = tuple(self._fused_state(n, code, exact) for n in names)
-        ms, mt = (Bs, Bt) if old is None else (max(Bs, old.max_source), max(Bt, old.max_target))
-
-        def build():
-            step = FusedDeepAPFStep(*(getattr(self, n).weight.data for n in names), self._attention_params(), n_over, ms, mt, states=states,
-                                    **hp)
-            # the parameters' Adam state outlives a re-sized step object, and a checkpoint's is handed over when the first one is built
-            carry = old.w_opt.state_dict() if old is not None and old.w_opt is not None else self.__dict__.pop('_pending_weight_state', None)
-            if carry is not None and step.w_opt is not None:
-                step.w_opt.load_state_dict(carry)
-                for g in step.w_opt.param_groups:
-                    g.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-            return step
-
-        step = self._fused_step('deepapf', lambda s: s.max_source >= Bs and s.max_target >= Bt and s.hp == hp, build)
-        step.hp = hp
+        ms, mt = self._fused_pair_sizes('deepapf', Bs, Bt)
+        step = self._fused_weight_step('deepapf', lambda s: s.max_source >= Bs and s.max_target >= Bt, lambda: FusedDeepAPFStep(
+            *(getattr(self, n).weight.data for n in names), self._attention_params(), n_over, ms, mt, states=states, **hp), hp)
         ys = ys if ys.dtype == torch.float32 else ys.float()
         yt = yt if yt.dtype == torch.float32 else yt.float()
         ks, os_, kt, ot = ks.contiguous(), os_.contiguous(), kt.contiguous(), ot.contiguous()
@@ -231,17 +212,4 @@ class DeepAPF(RowwiseTraining, CrossDomainRecommender):
     def _fused_phase_step(self):
         return self._fused['steps']['deepapf']
 
-    def fused_optimizer_state(self):
-        """The shared per-table state, plus the dense Adam state of (W1, b1, w2, wp) under ``'weights'``."""
-        out = super().fused_optimizer_state()
-        step = self.__dict__.get('_fused', {}).get('steps', {}).get('deepapf')
-        if step is not None and step.w_opt is not None:
-            out['weights'] = step.w_opt.state_dict()
-        return out
-
-    def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
-        """The shared per-table restore; the parameters' Adam state is handed to the step when it is built."""
-        super().load_fused_optimizer_state(state, opt=opt, adam=adam)
-        if 'weights' in state:
-            self.__dict__['_pending_weight_state'] = state['weights']
-        self.__dict__.get('_fused', {}).get('steps', {}).pop('deepapf', None)
+    _WEIGHT_STEP = 'deepapf'                                          # ((W1, b1, w2, wp)'s dense Adam state: the checkpoint's 'weights')

@@ -172,35 +172,17 @@ class DTCDR(RowwiseTraining, CrossDomainRecommender):
         from ...fused import FusedDTCDRStep, rowwise_catch_up
         self.unfreeze_eval()                                           # the step writes the tables in place: no evaluation cache outlives it
         exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
-        if self.__dict__.get('_dist_cfg') not in (None, False):
-            raise NotImplementedError("DTCDR.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
-        try:
-            FusedDTCDRStep.check_widths(self.embedding_size, self.mlp_hidden_size)
-        except ValueError as e:
-            raise ValueError(f'DTCDR.fused_train_step: embedding_size = {self.embedding_size}, mlp_hidden_size = {self.mlp_hidden_size}: '
-                             f'{e}; use optimizer_mode=dense') from None
+        self._fused_refuse_dist('DTCDR')
+        self._fused_check_widths('DTCDR', FusedDTCDRStep.check_widths, 'embedding_size = {}, mlp_hidden_size = {}', self.embedding_size,
+                                 self.mlp_hidden_size)
         su, si, ys, tu, ti, yt = self._pair_fields(interaction)
-        Bs, Bt = su.numel(), tu.numel()
-        if Bs == 0 or Bt == 0 or si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
-            raise ValueError(f'DTCDR.fused_train_step: the {self.phase} batch needs at least one row per domain and ids and labels of equal '
-                             f'length, got {Bs} / {si.numel()} / {ys.numel()} source and {Bt} / {ti.numel()} / {yt.numel()} target entries')
-        old = self._fused_cache(exact)['steps'].get('dtcdr')
+        Bs, Bt = self._fused_check_pair_batch('DTCDR', su, si, ys, tu, ti, yt)
+        self._fused_cache(exact)
         states = tuple(self._fused_state(n, code, exact) for n in self._TABLES)
-        ms, mt = (Bs, Bt) if old is None else (max(Bs, old.max_source), max(Bt, old.max_target))
-
-        def build():
-            step = FusedDTCDRStep(*(getattr(self, n).weight.data for n in self._TABLES), self._towers(), ms, mt, self.alpha,
-                                  dropout_prob=self.dropout_prob, states=states, **hp)
-            # the towers' Adam state outlives a re-sized step object, and a checkpoint's is handed over when the first one is built
-            carry = old.w_opt.state_dict() if old is not None and old.w_opt is not None else self.__dict__.pop('_pending_weight_state', None)
-            if carry is not None and step.w_opt is not None:
-                step.w_opt.load_state_dict(carry)
-                for g in step.w_opt.param_groups:
-                    g.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-            return step
-
-        step = self._fused_step('dtcdr', lambda s: s.max_source >= Bs and s.max_target >= Bt and s.hp == hp, build)
-        step.hp = hp
+        ms, mt = self._fused_pair_sizes('dtcdr', Bs, Bt)
+        step = self._fused_weight_step('dtcdr', lambda s: s.max_source >= Bs and s.max_target >= Bt, lambda: FusedDTCDRStep(
+            *(getattr(self, n).weight.data for n in self._TABLES), self._towers(), ms, mt, self.alpha, dropout_prob=self.dropout_prob,
+            states=states, **hp), hp)
         ys = ys if ys.dtype == torch.float32 else ys.float()
         yt = yt if yt.dtype == torch.float32 else yt.float()
         seed = self._drop_seed()                                       # None in eval mode or without dropout: p = 0
@@ -213,29 +195,25 @@ class DTCDR(RowwiseTraining, CrossDomainRecommender):
     def _fused_phase_step(self):
         return self._fused['steps']['dtcdr']
 
+    _WEIGHT_STEP = 'dtcdr'                                            # (the towers' dense Adam state: the checkpoint's 'weights')
+
     def fused_optimizer_state(self):
-        """The shared per-table state, plus the dense Adam state of the towers and the state of the dropout seed (the generator
-        ``_drop_seed`` draws from and the device counter), so that a resumed run draws the masks the uninterrupted one would."""
+        """The shared state, plus the state of the dropout seed (the generator ``_drop_seed`` draws from and the device counter), so that
+        a resumed run draws the masks the uninterrupted one would."""
         out = super().fused_optimizer_state()
-        step = self.__dict__.get('_fused', {}).get('steps', {}).get('dtcdr')
-        if step is not None and step.w_opt is not None:
-            out['weights'] = step.w_opt.state_dict()
         if out and self.dropout_prob:
             st = self.__dict__.get('_drop_state')
             out['dropout'] = {'rng': torch.get_rng_state(), 'counter': None if st is None else int(st.item())}
         return out
 
     def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
-        """The shared per-table restore; the towers' Adam state is handed to the step when it is built."""
+        """The shared restore, then the dropout seed's."""
         super().load_fused_optimizer_state(state, opt=opt, adam=adam)
-        if 'weights' in state:
-            self.__dict__['_pending_weight_state'] = state['weights']
         if 'dropout' in state:
             torch.set_rng_state(state['dropout']['rng'].cpu())
             st = self.__dict__.get('_drop_state')
             if st is not None and state['dropout']['counter'] is not None:
                 st.fill_(int(state['dropout']['counter']))
-        self.__dict__.get('_fused', {}).get('steps', {}).pop('dtcdr', None)
 
     @torch.no_grad()
     def predict(self, interaction):

@@ -8,7 +8,10 @@ from ..fused import FusedBPRStep, KMajorBPRStep, RowwiseState, OPT_ADAM, OPT_SGD
 class RowwiseTraining:
     """Mixin next to ``CrossDomainRecommender``.  State: ``self._fused = {'states': {table name: RowwiseState}, 'steps': {key: step
     object}}``, created by the first accepted ``fused_train_step``.  The model supplies ``_fused_phase_step()``: the step object
-    the current phase's captured ``fused_train_step`` runs."""
+    the current phase's captured ``fused_train_step`` runs.  A model whose step also owns dense weights (CLFM, DTCDR, DeepAPF, DCDCSR)
+    names that step's key in ``_WEIGHT_STEP``: the weights' dense Adam state then travels with the step cache and the checkpoint."""
+
+    _WEIGHT_STEP = None
 
     @staticmethod
     def _fused_args(opt, adam, lr, betas, eps, weight_decay):
@@ -44,6 +47,51 @@ class RowwiseTraining:
         if step is None or not fits(step):
             step = steps[key] = build()
         return step
+
+    def _fused_weight_step(self, key, fits, make, hp):
+        """The step object with dense weights cached under ``key`` if ``fits(step)`` holds and the optimizer settings are ``hp``, else
+        ``make()``'s.  The weights' Adam state outlives a re-sized step object, and a checkpoint's (``_pending_weight_state``) is handed
+        over when the first one is built."""
+        old = self._fused['steps'].get(key)
+
+        def build():
+            step = make()
+            carry = old.w_opt.state_dict() if old is not None and old.w_opt is not None else self.__dict__.pop('_pending_weight_state', None)
+            if carry is not None and step.w_opt is not None:
+                step.w_opt.load_state_dict(carry)
+                for g in step.w_opt.param_groups:
+                    g.update(lr=hp['lr'], betas=hp['betas'], eps=hp['eps'], weight_decay=hp['weight_decay'])
+            return step
+
+        step = self._fused_step(key, lambda s: fits(s) and s.hp == hp, build)
+        step.hp = hp
+        return step
+
+    def _fused_pair_sizes(self, key, Bs, Bt):
+        """(max_source, max_target) for a two-domain step under ``key``: a rebuilt step never shrinks."""
+        old = self._fused['steps'].get(key)
+        return (Bs, Bt) if old is None else (max(Bs, old.max_source), max(Bt, old.max_target))
+
+    def _fused_refuse_dist(self, model):
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            raise NotImplementedError(f"{model}.fused_train_step does not shard its tables: config['dist_group'] is not supported (one GPU)")
+
+    @staticmethod
+    def _fused_check_widths(model, check, described, *widths):
+        """``check(*widths)`` (a step class's ``check_widths``), its refusal re-raised in the model's words: ``described`` is a format
+        of the widths (formatted only on refusal: this runs in front of every step)."""
+        try:
+            check(*widths)
+        except ValueError as e:
+            raise ValueError(f'{model}.fused_train_step: {described.format(*widths)}: {e}; use optimizer_mode=dense') from None
+
+    def _fused_check_pair_batch(self, model, su, si, ys, tu, ti, yt):
+        """(B_s, B_t) of a BOTH-phase batch: at least one row per domain, ids and labels of equal length."""
+        Bs, Bt = su.numel(), tu.numel()
+        if Bs == 0 or Bt == 0 or si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
+            raise ValueError(f'{model}.fused_train_step: the {self.phase} batch needs at least one row per domain and ids and labels of equal '
+                             f'length, got {Bs} / {si.numel()} / {ys.numel()} source and {Bt} / {ti.numel()} / {yt.numel()} target entries')
+        return Bs, Bt
 
     def _fused_domain_step(self, domain, key, cls, size, sized_by, code, exact, hp, **kw):
         """This domain's ``cls`` object on (``<domain>_user_embedding``, ``<domain>_item_embedding``) for ``size`` rows or positives,
@@ -93,16 +141,22 @@ class RowwiseTraining:
 
     def fused_optimizer_state(self):
         """Row-wise optimizer state of ``fused_train_step`` for a checkpoint: per table the moments and the update count (recbole's
-        checkpoint stores ``optimizer.state_dict()``; this is its counterpart for ``optimizer_mode='rowwise'``)."""
+        checkpoint stores ``optimizer.state_dict()``; this is its counterpart for ``optimizer_mode='rowwise'``), and under ``'weights'``
+        the dense Adam state of the ``_WEIGHT_STEP`` step's parameters."""
         cache = self.__dict__.get('_fused')
         if not cache:
             return {}
         self.fused_sync()
-        return {'tables': {k: {'step': st.step, 'exp_avg': st.exp_avg, 'exp_avg_sq': st.exp_avg_sq} for k, st in cache['states'].items()}}
+        out = {'tables': {k: {'step': st.step, 'exp_avg': st.exp_avg, 'exp_avg_sq': st.exp_avg_sq} for k, st in cache['states'].items()}}
+        step = cache['steps'].get(self._WEIGHT_STEP)
+        if step is not None and step.w_opt is not None:
+            out['weights'] = step.w_opt.state_dict()
+        return out
 
     def load_fused_optimizer_state(self, state, opt='adam', adam='lazy'):
         """Restore what ``fused_optimizer_state`` returned (before the next ``fused_train_step``).  ``adam``: the mode training goes on
-        with; in exact mode every row is current at its table's update count (the checkpoint was written flushed)."""
+        with; in exact mode every row is current at its table's update count (the checkpoint was written flushed).  The dense weights'
+        Adam state is handed to the ``_WEIGHT_STEP`` step when it is next built."""
         self._fused_cache()
         code = OPT_ADAM if opt == 'adam' else OPT_SGD
         for name, rec in state.get('tables', {}).items():
@@ -111,3 +165,7 @@ class RowwiseTraining:
             if rec['exp_avg'] is not None:
                 st.exp_avg.copy_(rec['exp_avg']); st.exp_avg_sq.copy_(rec['exp_avg_sq'])
             st.restored()
+        if self._WEIGHT_STEP is not None:
+            if 'weights' in state:
+                self.__dict__['_pending_weight_state'] = state['weights']
+            self._fused['steps'].pop(self._WEIGHT_STEP, None)

@@ -26,6 +26,6 @@ def timeit(fn, reps=30):
 import ctypes
 B_.call('cdr_sort_ids_two_tables', ctxh, B_.stream(), B_.i64(u), B, nu, B_.i64(p), B, B_.i64(n), B, ni, B_.raw(st.keys), B_.raw(st.perm),
         ctypes.byref(st._key_base), B_.raw(st.ws), st.ws_bytes)
-mu = timeit(lambda: st._apply(ctxh, st.ustate, st.keys[:B], st.perm[:B], B, st.GU, B, B, st.out6[4:5], 0))
-mi = timeit(lambda: st._apply(ctxh, st.istate, st.keys[B:3 * B], st.perm[B:3 * B], 2 * B, st.GP, B, B, st.out6[5:6], st._key_base.value))
+mu = timeit(lambda: st._apply(ctxh, st.ustate, D, st.keys[:B], st.perm[:B], B, st.GU, B, B, st.out6[4:5], 0))
+mi = timeit(lambda: st._apply(ctxh, st.istate, D, st.keys[B:3 * B], st.perm[B:3 * B], 2 * B, st.GP, B, B, st.out6[5:6], st._key_base.value))
 print(f'{os.environ.get("CDR_LIB_PATH", "default"):24s} apply users median {mu[0]:.4f} min {mu[1]:.4f} ms | items median {mi[0]:.4f} min {mi[1]:.4f} ms', flush=True)
