@@ -291,6 +291,18 @@ int cdr_adam_multi_dev(void* stream, int count, float* const* params, const floa
  * line apart behind one word; one word was enough up to ABI 53).  With it, updates of up to 512 fat workgroups run as ONE
  * launch: the kernel evaluates update number step + 1 itself and its last workgroup to finish stores the counters (and the loss total). */
 
+/* ---- config['learner'] beyond Adam (recbole Trainer.__init__ reads `learner`; recbole_cdr/properties/overall.yaml:20-21
+ * sets it; recbole's _build_optimizer builds torch.optim.<X>(params, lr=learning_rate, weight_decay=weight_decay)) -------------------
+ * The dense sweep of torch.optim.SGD (opt = CDR_OPT_SGD: no momentum; state may be NULL), torch.optim.Adagrad (CDR_OPT_ADAGRAD:
+ * lr_decay = 0; state[i] = `sum`) or torch.optim.RMSprop (CDR_OPT_RMSPROP: not centered, no momentum; state[i] = `square_avg`) over
+ * `count` parameter tensors in one launch per 24 tensors: host arrays of device pointers as for cdr_adam_multi_dev.  g += wd p first,
+ * as torch does.  `alpha` (RMSprop only) is a double so that 1 - alpha is rounded once, as torch rounds it.  IEEE sqrt and division
+ * (csrc/cdr_opt_math.h).  No bias correction, so no device step counter: capturable as it stands.  loss / loss_sum (both or neither):
+ * loss_sum[0] += loss[0] in the same launch (recbole_cdr/trainer/trainer.py:59-73 runs recbole's `total_loss += loss.item()` loop).
+ * CDR_OPT_ADAM is refused here (cdr_adam_multi_dev). */
+int cdr_opt_multi_dev(void* stream, int opt, int count, float* const* params, const float* const* grads, float* const* state,
+                      const int64_t* numel, float lr, double alpha, float eps, float weight_decay, const float* loss, float* loss_sum);
+
 /* cdr_gemm_f32 with a per-output-row scale and a pre-activation accumulate -- the CoNet cross unit
  * (conet.py:127-135):  first  C = s W^T + b           (cdr_gemm_f32, act none)
  *                      then   C = relu(C + m (.) (t H^T))   (rowscale = m, act relu, accumulate = 2)
@@ -374,6 +386,8 @@ int cdr_sort_ids_small(void* stream, int nseg, const int64_t* const* ids0, const
                        uint32_t* rank_scratch /* one uint32 per id, ZERO before the first call; left zero by every call */,
                        int64_t max_id /* an upper bound of the ids, or 0: when id and occurrence index fit 32 bits together the
                                          comparison loop works on one composite word (3x fewer instructions) */);
+/* (opt = CDR_OPT_SGD | CDR_OPT_ADAM | CDR_OPT_ADAGRAD here and in cdr_rowwise_apply_scaled; Adagrad: exp_avg NULL, the sum in exp_avg_sq,
+ * step and step_dev ignored -- see CDR_OPT_ADAGRAD) */
 int cdr_rowwise_apply_rows(cdr_ctx* ctx, void* stream, int opt, float* table, float* exp_avg, float* exp_avg_sq, int D,
                            const uint32_t* keys_sorted, const uint32_t* perm, int64_t n, const float* G, int64_t reg_limit,
                            const float* reg_coef, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
@@ -881,7 +895,9 @@ int cdr_dcdcsr_map_fwd_grad(cdr_ctx* ctx, void* stream, const float* table, cons
  * (its GU[b] / GP[b] is never written); duplicate rows go through the segmented apply as before.  Per row the arithmetic is
  * that of cdr_rowwise_apply.  keys / perm: uint32 [3B]; flags: uint8 [4B], 4-byte aligned ({user, positive, negative, -} per
  * triple); heads: uint32 [cdr_bpr_step_fused_heads_words(B)]; sort_ws as for cdr_sort_ids_two_tables(3B).  step_user /
- * step_item: the tables' update counts INCLUDING this update (Adam bias correction).  out9 as cdr_bpr_fwd_grad's.             */
+ * step_item: the tables' update counts INCLUDING this update (Adam bias correction).  out9 as cdr_bpr_fwd_grad's.
+ * opt = CDR_OPT_ADAGRAD: user_m = item_m = NULL, the sums in user_v / item_v, steps ignored (see CDR_OPT_ADAGRAD); a single row then
+ * reads and writes the row and ONE state array.                                                                                 */
 int cdr_bpr_step_fused_heads_words(int64_t B, int64_t* words);
 int cdr_bpr_step_fused(cdr_ctx* ctx, void* stream, int opt, float* user_tab, float* user_m, float* user_v, int64_t user_rows,
                        float* item_tab, float* item_m, float* item_v, int64_t item_rows, int D, const int64_t* uid,
@@ -905,7 +921,8 @@ int cdr_bpr_step_fused_dev(cdr_ctx* ctx, void* stream, int opt, float* user_tab,
  * batch are updated by the kernel that gathers them, duplicate rows through GU / GI and the segmented applies.  Replaces
  * cdr_point_fwd_grad -> cdr_sort_ids_two_tables -> cdr_rowwise_apply x 2.  loss_kind: CDR_LOSS_MSE | CDR_LOSS_BCE.  Buffers as
  * cdr_bpr_step_fused's for B rows: keys / perm [2 B], flags [4 B] (4-byte aligned), heads cdr_bpr_step_fused_heads_words(B) words,
- * GU / GI [B, D], sort workspace cdr_sort_workspace_bytes(2 B, 2 * next power of two of the larger row count). */
+ * GU / GI [B, D], sort workspace cdr_sort_workspace_bytes(2 B, 2 * next power of two of the larger row count).
+ * opt = CDR_OPT_ADAGRAD: user_m = item_m = NULL, the sums in user_v / item_v, steps ignored (see CDR_OPT_ADAGRAD). */
 int cdr_point_step_fused(cdr_ctx* ctx, void* stream, int loss_kind, int opt, float* user_tab, float* user_m, float* user_v, int64_t user_rows,
                          float* item_tab, float* item_m, float* item_v, int64_t item_rows, int D, const int64_t* uid, const int64_t* iid,
                          const float* label, int64_t B, float reg_weight, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -932,6 +949,16 @@ int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int loss_kind, int
                                   float eps, float weight_decay, int64_t* step_user_dev, int64_t* step_item_dev, float* hp_dev, float* out16,
                                   float* GU, float* GI, uint32_t* keys, uint32_t* perm, uint8_t* flags, uint32_t* heads, void* sort_ws,
                                   size_t sort_ws_bytes);
+/* The same step (cmf.py:75-99) under config['learner'] = adagrad, whose update reads no update count: opt = CDR_OPT_ADAGRAD only
+ * (user_m = item_m = NULL; user_v / item_v = the tables' sums of squared gradients; eps = torch's 1e-10): no device counters, no hp_dev.
+ * Same buffers, same out16.  CDR_OPT_SGD and CDR_OPT_ADAM are refused (their entry is the _dev form above, which keeps refusing
+ * CDR_OPT_ADAGRAD). */
+int cdr_point_step_fused_pair(cdr_ctx* ctx, void* stream, int loss_kind, int opt, float* user_tab, float* user_m, float* user_v,
+                              int64_t user_rows, float* item_tab, float* item_m, float* item_v, int64_t item_rows, int D,
+                              const int64_t* su, const int64_t* si, const float* ys, int64_t B_s, const int64_t* tu, const int64_t* ti,
+                              const float* yt, int64_t B_t, float alpha, float reg_s, float reg_t, float lr, float eps, float weight_decay,
+                              float* out16, float* GU, float* GI, uint32_t* keys, uint32_t* perm, uint8_t* flags, uint32_t* heads,
+                              void* sort_ws, size_t sort_ws_bytes);
 
 /* The same step per POSITIVE, for recbole's pointwise batch layout (TrainDataLoader._neg_sampling under data/dataloader.py:114-162): uid [S]
  * (the first S entries of the user column tiled 1 + k times), iid [S + S k] = [positives | k-major negatives], label [S + S k].  In that
@@ -1050,6 +1077,16 @@ int cdr_sort_ids(cdr_ctx* ctx, void* stream, const int64_t* ids0, int64_t n0, co
                  void* workspace, size_t workspace_bytes);
 #define CDR_OPT_SGD 0
 #define CDR_OPT_ADAM 1
+#define CDR_OPT_ADAGRAD 2
+#define CDR_OPT_RMSPROP 3 /* cdr_opt_multi_dev only: an untouched row's square_avg decays every step, so there is no lazy row-wise form */
+/* CDR_OPT_ADAGRAD (torch.optim.Adagrad, lr_decay = 0: g += wd w; s += g g; w -= lr g / (sqrt(s) + eps), IEEE sqrt and division) is taken by
+ * cdr_opt_multi_dev (the dense sweep) and by exactly these row-wise entries:
+ *   cdr_rowwise_apply, cdr_rowwise_apply_rows, cdr_rowwise_apply_scaled:  exp_avg = NULL, exp_avg_sq = the table-sized sum s;
+ *   cdr_bpr_step_fused, cdr_point_step_fused, cdr_point_step_fused_pair:  user_m = item_m = NULL, user_v / item_v = the two sums.
+ * step, step_user, step_item, step_dev, beta1 and beta2 are ignored (no bias correction); eps is torch's 1e-10.  A row the call does not
+ * touch keeps w and s bit for bit, which at weight_decay = 0 is what the dense sweep leaves it; with weight_decay != 0 only touched rows
+ * decay.  Every other entry with an `opt` argument (k-major, small-batch, _dev / _pair_dev, cdr_map_step_unique, shard, dimension-shard,
+ * lazy / exact Adam) refuses it with CDR_EINVAL. */
 int cdr_rowwise_apply(cdr_ctx* ctx, void* stream, int opt, float* table, float* exp_avg, float* exp_avg_sq, int D,
                       const uint32_t* keys_sorted, const uint32_t* perm, int64_t n,
                       const float* G, int64_t neg_start, int64_t reg_limit, const float* reg_coef,

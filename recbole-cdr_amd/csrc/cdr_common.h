@@ -272,6 +272,15 @@ static inline int cdr_lpr_for(int D) {        // lanes per row when a lane moves
         else { constexpr int O = 1; DISPATCH_LPR(lpr, __VA_ARGS__) }            \
     } while (0)
 
+// ... and with O = 2 (Adagrad: one state array) as a third arm, for the entries that accept it: cdr_rowwise_apply and its two sibling
+// forms, cdr_bpr_step_fused, cdr_point_step_fused.  Every other launch keeps DISPATCH_LPR_OPT: no Adagrad copy of its kernels is built.
+#define DISPATCH_LPR_OPT3(lpr, opt, ...)                                              \
+    do {                                                                              \
+        if ((opt) == 0) { constexpr int O = 0; DISPATCH_LPR(lpr, __VA_ARGS__) }       \
+        else if ((opt) == 1) { constexpr int O = 1; DISPATCH_LPR(lpr, __VA_ARGS__) }  \
+        else { constexpr int O = 2; DISPATCH_LPR(lpr, __VA_ARGS__) }                  \
+    } while (0)
+
 static inline int grid_for(int64_t units, int per_block) {
     int64_t g = (units + per_block - 1) / per_block;
     const int64_t cap = CDR_NUM_CU * 8;       // 2048 blocks = 8 per CU, grid-stride beyond (guide G11)

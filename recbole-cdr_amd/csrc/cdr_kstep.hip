@@ -19,6 +19,7 @@
 // two extra launches) for batches whose worst-case segment a single lane group can walk.
 #include "cdr_common.h"
 #include "cdr_adam_math.h"
+#include "cdr_opt_math.h"
 #include "cdr_loss_math.h"
 #include "cdr_ranksort.h"
 
@@ -199,7 +200,13 @@ __device__ __forceinline__ void apply_update(float* __restrict__ wp, float* __re
                                              float4 acc, float rc, const apply_hp& h) {
     float4 gr = make_float4(acc.x + rc * w.x, acc.y + rc * w.y, acc.z + rc * w.z, acc.w + rc * w.w);
     float4 wn;
-    if (OPT == 0) {
+    if constexpr (OPT == 2) {                  // Adagrad: vp is the row's sum, mp is not read (cdr_opt_math.h: the dense sweep's function)
+        float4 sm = ld4(vp);
+        if (h.wd != 0.f) { gr.x += h.wd * w.x; gr.y += h.wd * w.y; gr.z += h.wd * w.z; gr.w += h.wd * w.w; }
+        wn = make_float4(cdr_adagrad_elem(w.x, gr.x, sm.x, h.lr, h.eps, 0.f), cdr_adagrad_elem(w.y, gr.y, sm.y, h.lr, h.eps, 0.f),
+                         cdr_adagrad_elem(w.z, gr.z, sm.z, h.lr, h.eps, 0.f), cdr_adagrad_elem(w.w, gr.w, sm.w, h.lr, h.eps, 0.f));
+        st4(vp, sm);
+    } else if (OPT == 0) {
         if (h.wd != 0.f) { gr.x += h.wd * w.x; gr.y += h.wd * w.y; gr.z += h.wd * w.z; gr.w += h.wd * w.w; }
         wn = make_float4(w.x - h.lr * gr.x, w.y - h.lr * gr.y, w.z - h.lr * gr.z, w.w - h.lr * gr.w);
     } else {
@@ -267,7 +274,7 @@ __global__ __launch_bounds__(kBlock) void apply2_kernel(float* __restrict__ W, f
                     acc.x += g.x; acc.y += g.y; acc.z += g.z; acc.w += g.w;
                     cnt += (o < reg_limit) ? 1 : 0;
                 }
-                apply_update<OPT>(wp, OPT ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
+                apply_update<OPT>(wp, OPT == 1 ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
                                   w, acc, c * (float)cnt, hp);
             }
         }
@@ -361,7 +368,7 @@ __global__ __launch_bounds__(kBlock) void long_finish2_kernel(float* __restrict_
                 acc.x += g.x; acc.y += g.y; acc.z += g.z; acc.w += g.w;
                 cnt += pcnt[sg.base + kk];
             }
-            apply_update<OPT>(wp, OPT ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
+            apply_update<OPT>(wp, OPT == 1 ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
                               w, acc, c * (float)cnt, hp);
         }
     }
@@ -397,7 +404,7 @@ int apply2(cdr_ctx* ctx, hipStream_t s, int opt, float* table, float* exp_avg, f
         CDR_HIP(cdr_zero_u32(counters, 4, s));
     }
     cdr_time_scope ts(ctx, tag, s);
-    DISPATCH_LPR_OPT(lpr, opt, apply2_kernel<L, O, SRC><<<dim3(grid), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys, perm, n, G, rec, Usrc, reg_limit, reg_coef, hp, sd,
+    DISPATCH_LPR_OPT3(lpr, opt, apply2_kernel<L, O, SRC><<<dim3(grid), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys, perm, n, G, rec, Usrc, reg_limit, reg_coef, hp, sd,
                                                                                            counters, longs, pieces));
     CDR_LAUNCH_CHECK();
     if (may_have_long) {
@@ -405,7 +412,7 @@ int apply2(cdr_ctx* ctx, hipStream_t s, int opt, float* table, float* exp_avg, f
         DISPATCH_LPR(lpr, piece_sum2_kernel<L, SRC><<<dim3(gp), dim3(kBlock), 0, s>>>(D, perm, G, rec, Usrc, reg_limit, counters, pieces, partial, pcnt));
         CDR_LAUNCH_CHECK();
         const int gl = grid_for(long_cap < 4096 ? long_cap : 4096, kBlock / lpr);
-        DISPATCH_LPR_OPT(lpr, opt, long_finish2_kernel<L, O><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys, reg_coef, hp, sd, counters, longs, partial, pcnt));
+        DISPATCH_LPR_OPT3(lpr, opt, long_finish2_kernel<L, O><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys, reg_coef, hp, sd, counters, longs, partial, pcnt));
         CDR_LAUNCH_CHECK();
     }
     return CDR_OK;
@@ -451,7 +458,7 @@ extern "C" int cdr_rowwise_apply_rows(cdr_ctx* ctx, void* stream, int opt, float
                                       const float* reg_coef, float lr, float beta1, float beta2, float eps, float weight_decay,
                                       int64_t step, const int64_t* step_dev, int small) {
     CDR_CHECK_ARG(ctx && table && keys_sorted && perm && G && n > 0 && D > 0 && (D & 3) == 0);
-    CDR_CHECK_ARG(opt == 0 || (opt == 1 && exp_avg && exp_avg_sq && (step > 0 || step_dev)));
+    CDR_CHECK_ARG(opt == 0 || (opt == 1 && exp_avg && exp_avg_sq && (step > 0 || step_dev)) || (opt == CDR_OPT_ADAGRAD && !exp_avg && exp_avg_sq));
     return apply2<0>(ctx, (hipStream_t)stream, opt, table, exp_avg, exp_avg_sq, D, keys_sorted, perm, n, G, nullptr, nullptr, reg_limit,
                      reg_coef, lr, beta1, beta2, eps, weight_decay, step, step_dev, small, CDR_TAG_APPLY_UNSIGNED);
 }
@@ -461,7 +468,7 @@ extern "C" int cdr_rowwise_apply_scaled(cdr_ctx* ctx, void* stream, int opt, flo
                                         const float* src_table, int64_t reg_limit, const float* reg_coef, float lr, float beta1,
                                         float beta2, float eps, float weight_decay, int64_t step, const int64_t* step_dev, int small) {
     CDR_CHECK_ARG(ctx && table && keys_sorted && perm && item_rec_in && src_table && n > 0 && D > 0 && (D & 3) == 0);
-    CDR_CHECK_ARG(opt == 0 || (opt == 1 && exp_avg && exp_avg_sq && (step > 0 || step_dev)));
+    CDR_CHECK_ARG(opt == 0 || (opt == 1 && exp_avg && exp_avg_sq && (step > 0 || step_dev)) || (opt == CDR_OPT_ADAGRAD && !exp_avg && exp_avg_sq));
     return apply2<1>(ctx, (hipStream_t)stream, opt, table, exp_avg, exp_avg_sq, D, keys_sorted, perm, n, nullptr,
                      (const item_rec*)item_rec_in, src_table, reg_limit, reg_coef, lr, beta1, beta2, eps, weight_decay, step, step_dev,
                      small, CDR_TAG_APPLY_SIGNED);

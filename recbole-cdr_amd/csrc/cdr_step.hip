@@ -28,6 +28,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 #include "cdr_common.h"
 #include "cdr_adam_math.h"
+#include "cdr_opt_math.h"
 #include "cdr_loss_math.h"
 
 namespace {
@@ -378,7 +379,13 @@ __device__ __forceinline__ float4 apply_update(float* __restrict__ wp, float* __
                                                float4 acc, float rc, const apply_hp& h) {
     float4 gr = make_float4(acc.x + rc * w.x, acc.y + rc * w.y, acc.z + rc * w.z, acc.w + rc * w.w);
     float4 wn;
-    if (OPT == 0) {
+    if constexpr (OPT == 2) {                  // Adagrad: vp is the row's sum, mp is not read (cdr_opt_math.h: the dense sweep's function)
+        float4 sm = ld4n<(LPR >= 32)>(vp);
+        if (h.wd != 0.f) { gr.x += h.wd * w.x; gr.y += h.wd * w.y; gr.z += h.wd * w.z; gr.w += h.wd * w.w; }
+        wn = make_float4(cdr_adagrad_elem(w.x, gr.x, sm.x, h.lr, h.eps, 0.f), cdr_adagrad_elem(w.y, gr.y, sm.y, h.lr, h.eps, 0.f),
+                         cdr_adagrad_elem(w.z, gr.z, sm.z, h.lr, h.eps, 0.f), cdr_adagrad_elem(w.w, gr.w, sm.w, h.lr, h.eps, 0.f));
+        st4n<(LPR >= 32)>(vp, sm);
+    } else if (OPT == 0) {
         if (h.wd != 0.f) { gr.x += h.wd * w.x; gr.y += h.wd * w.y; gr.z += h.wd * w.z; gr.w += h.wd * w.w; }
         wn = make_float4(w.x - h.lr * gr.x, w.y - h.lr * gr.y, w.z - h.lr * gr.z, w.w - h.lr * gr.w);
     } else {
@@ -435,7 +442,7 @@ __global__ __launch_bounds__(kBlock) void rowwise_apply_kernel(float* __restrict
                     else { acc.x += g.x; acc.y += g.y; acc.z += g.z; acc.w += g.w; }
                     cnt += occ_ids ? (int)((occ_ids[o] >> 62) & 1) : ((o < reg_limit) ? 1 : 0);
                 }
-                apply_update<LPR, OPT>(wp, OPT ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
+                apply_update<LPR, OPT>(wp, OPT == 1 ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
                                   w, acc, c * (float)cnt, hp);
             }
         }
@@ -586,7 +593,7 @@ __device__ __forceinline__ void seg_long_finish_body(float* __restrict__ W, floa
                     if (k0 + j < np) { acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; acc.w += g[j].w; cnt += c[j]; }
                 }
             }
-            wnew = apply_update<LPR, OPT>(wp, OPT ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
+            wnew = apply_update<LPR, OPT>(wp, OPT == 1 ? Mo + (int64_t)row * D + 4 * ch : nullptr, OPT ? Vo + (int64_t)row * D + 4 * ch : nullptr,
                                           w, acc, c * (float)cnt, hp);
         }
         if (NC) norm_rec_store<LPR>(n2 + (int64_t)row * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wnew)), sub);
@@ -715,6 +722,9 @@ __device__ __forceinline__ float4 upd_math(float4 w, float4& m, float4& v, float
     float4 gr = make_float4(acc.x + rc * w.x, acc.y + rc * w.y, acc.z + rc * w.z, acc.w + rc * w.w);
     if (h.wd != 0.f) { gr.x += h.wd * w.x; gr.y += h.wd * w.y; gr.z += h.wd * w.z; gr.w += h.wd * w.w; }
     if (OPT == 0) return make_float4(w.x - h.lr * gr.x, w.y - h.lr * gr.y, w.z - h.lr * gr.z, w.w - h.lr * gr.w);
+    if constexpr (OPT == 2)                    // Adagrad: v is the row's sum, m is not touched (cdr_opt_math.h: the dense sweep's function)
+        return make_float4(cdr_adagrad_elem(w.x, gr.x, v.x, h.lr, h.eps, 0.f), cdr_adagrad_elem(w.y, gr.y, v.y, h.lr, h.eps, 0.f),
+                           cdr_adagrad_elem(w.z, gr.z, v.z, h.lr, h.eps, 0.f), cdr_adagrad_elem(w.w, gr.w, v.w, h.lr, h.eps, 0.f));
     m.x += (gr.x - m.x) * (1.0f - h.b1); m.y += (gr.y - m.y) * (1.0f - h.b1);
     m.z += (gr.z - m.z) * (1.0f - h.b1); m.w += (gr.w - m.w) * (1.0f - h.b1);
     v.x = h.b2 * v.x + (1.0f - h.b2) * gr.x * gr.x; v.y = h.b2 * v.y + (1.0f - h.b2) * gr.y * gr.y;
@@ -731,10 +741,12 @@ __device__ __forceinline__ float4 upd_math(float4 w, float4& m, float4& v, float
 template <int LPR, int OPT>
 __device__ __forceinline__ void row_moments(const tab_ptrs& T, int64_t off, float4& m, float4& v) {
     if constexpr (OPT == 1) { m = ld4n<(LPR >= 32)>(T.M + off); v = ld4n<(LPR >= 32)>(T.V + off); }
+    if constexpr (OPT == 2) v = ld4n<(LPR >= 32)>(T.V + off);          // Adagrad: the sum alone (T.M is NULL)
 }
 template <int LPR, int OPT>
 __device__ __forceinline__ void row_store(const tab_ptrs& T, int64_t off, float4 w, const float4& m, const float4& v) {
     if constexpr (OPT == 1) { st4n<(LPR >= 32)>(T.M + off, m); st4n<(LPR >= 32)>(T.V + off, v); }
+    if constexpr (OPT == 2) st4n<(LPR >= 32)>(T.V + off, v);
     st4n<(LPR >= 32)>(T.W + off, w);
 }
 
@@ -1104,7 +1116,9 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_apply_kernel(tab_ptrs TU, tab_
             if (fu[r]) {
                 const float4 wu = upd_math<OPT>(u[r], um[r], uv[r], gu, cu, hu);
                 // row_store, in place: the helper changed the code of the SH kernel at 64 lanes per row (Adam)
-                if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TU.M + ou[r], um[r]); st4n<(LPR >= 32)>(TU.V + ou[r], uv[r]); } st4n<(LPR >= 32)>(TU.W + ou[r], wu); }
+                if (live) { if (OPT == 1) { st4n<(LPR >= 32)>(TU.M + ou[r], um[r]); st4n<(LPR >= 32)>(TU.V + ou[r], uv[r]); }
+                            if constexpr (OPT == 2) st4n<(LPR >= 32)>(TU.V + ou[r], uv[r]);
+                            st4n<(LPR >= 32)>(TU.W + ou[r], wu); }
                 if (NC) norm_rec_store<LPR>(NU + (int64_t)iu[r] * kNormRecFloats, group_sum<LPR>(sqnorm4<LPR>(wu)), sub);
             } else if (ok) st4n<(LPR >= 32)>(GU + t * D + 4 * sub, gu);
             // ---- positive item row (EmbLoss occurrence), negative item row (gradient -g u, no EmbLoss)
@@ -2555,7 +2569,7 @@ extern "C" int cdr_rowwise_apply(cdr_ctx* ctx, void* stream, int opt, float* tab
                                  float beta2, float eps, float weight_decay, int64_t step, const int64_t* occ_ids, uint32_t key_base) {
     CDR_CHECK_ARG(table && keys_sorted && perm && G && n > 0);
     CDR_CHECK_ARG(D > 0 && (D & 3) == 0);
-    CDR_CHECK_ARG(opt == 0 || (opt == 1 && exp_avg && exp_avg_sq && step > 0));
+    CDR_CHECK_ARG(opt == 0 || (opt == 1 && exp_avg && exp_avg_sq && step > 0) || (opt == CDR_OPT_ADAGRAD && !exp_avg && exp_avg_sq));
     hipStream_t s = (hipStream_t)stream;
     // keys of a two-table sort carry the table bit: instead of subtracting it per row in the kernels, the three table
     // pointers are moved back by key_base rows here (row r of the table is then addressed as key = key_base + r)
@@ -2579,7 +2593,7 @@ extern "C" int cdr_rowwise_apply(cdr_ctx* ctx, void* stream, int opt, float* tab
         CDR_HIP(cdr_zero_u32(sc.counters, 4, s));
     }
     cdr_time_scope ts(ctx, is_signed ? CDR_TAG_APPLY_SIGNED : CDR_TAG_APPLY_UNSIGNED, s);
-    DISPATCH_LPR_OPT(lpr, opt, {
+    DISPATCH_LPR_OPT3(lpr, opt, {
         auto kern = is_signed ? rowwise_apply_kernel<L, O, true> : rowwise_apply_kernel<L, O, false>;
         kern<<<dim3(grid), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, perm, n, G, neg_start, reg_limit, reg_coef, hp, occ_ids,
                                                  sc.counters, sc.longs, sc.pieces);
@@ -2594,7 +2608,7 @@ extern "C" int cdr_rowwise_apply(cdr_ctx* ctx, void* stream, int opt, float* tab
         });
         CDR_LAUNCH_CHECK();
         const int gl = grid_for(ls.long_cap < 4096 ? ls.long_cap : 4096, kBlock / lpr);
-        DISPATCH_LPR_OPT(lpr, opt, seg_long_finish_kernel<L, O><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, reg_coef, hp, sc.counters,
+        DISPATCH_LPR_OPT3(lpr, opt, seg_long_finish_kernel<L, O><<<dim3(gl), dim3(kBlock), 0, s>>>(table, exp_avg, exp_avg_sq, D, keys_sorted, reg_coef, hp, sc.counters,
                                                                                                  sc.longs, sc.partial, sc.pcnt));
         CDR_LAUNCH_CHECK();
     }
@@ -2694,15 +2708,19 @@ int dups_plan_make(cdr_ctx* ctx, int D, const dup_host (&h)[2], dups_plan& pl) {
 
 // The two kernel pairs of apply_dups_pair: both sides update their table (every one-GPU step), or side 1 sums its segments into the
 // send buffer dup_side::out (the row-sharded step).
+// (adagrad: the pair also exists for OPT = 2 -- the one-GPU steps whose entries accept CDR_OPT_ADAGRAD)
 struct table_dups {
+    static constexpr bool adagrad = true;
     template <int L, int OPT> static constexpr auto dups = rowwise_apply_dups2_kernel<L, OPT>;
     template <int L, int OPT> static constexpr auto long_finish = seg_long_finish2_kernel<L, OPT>;
 };
 struct table_dups_nc {                          // ... and keep the tables' squared-norm records current (dup_side::n2)
+    static constexpr bool adagrad = true;
     template <int L, int OPT> static constexpr auto dups = rowwise_apply_dups2_kernel<L, OPT, true>;
     template <int L, int OPT> static constexpr auto long_finish = seg_long_finish2_kernel<L, OPT, true>;
 };
 struct shard_dups {
+    static constexpr bool adagrad = false;
     template <int L, int OPT> static constexpr auto dups = shard_dups_kernel<L, OPT>;
     template <int L, int OPT> static constexpr auto long_finish = shard_long_finish_kernel<L, OPT>;
 };
@@ -2714,7 +2732,8 @@ int apply_dups_pair(cdr_ctx* ctx, hipStream_t s, int opt, int D, const dups_plan
     const int grid = grid_for(nmax / 16 + 1, kBlock / lpr);          // four segments per lane group and round (apply_dups)
     {
         cdr_time_scope ts(ctx, CDR_TAG_APPLY_SIGNED, s);
-        DISPATCH_LPR_OPT(lpr, opt, K::template dups<L, O><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
+        if constexpr (K::adagrad) DISPATCH_LPR_OPT3(lpr, opt, K::template dups<L, O><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
+        else DISPATCH_LPR_OPT(lpr, opt, K::template dups<L, O><<<dim3(grid, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
     }
     CDR_LAUNCH_CHECK();
     if (pl.ls[0].long_cap || pl.ls[1].long_cap) {
@@ -2724,7 +2743,8 @@ int apply_dups_pair(cdr_ctx* ctx, hipStream_t s, int opt, int D, const dups_plan
         DISPATCH_LPR(lpr, seg_piece_sum2_kernel<L><<<dim3(gp, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
         CDR_LAUNCH_CHECK();
         const int gl = grid_for(lc < 4096 ? lc : 4096, kBlock / lpr);
-        DISPATCH_LPR_OPT(lpr, opt, K::template long_finish<L, O><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
+        if constexpr (K::adagrad) DISPATCH_LPR_OPT3(lpr, opt, K::template long_finish<L, O><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
+        else DISPATCH_LPR_OPT(lpr, opt, K::template long_finish<L, O><<<dim3(gl, 2), dim3(kBlock), 0, s>>>(D, pl.side[0], pl.side[1]));
         CDR_LAUNCH_CHECK();
     }
     return CDR_OK;
@@ -2815,7 +2835,7 @@ static int bpr_step_fused_impl(cdr_ctx* ctx, void* stream, int opt, float* user_
     const int grid = grid_for((B + un - 1) / un, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_BPR_FWD_APPLY, s);
-        DISPATCH_LPR_OPT(lpr, opt, {
+        DISPATCH_LPR_OPT3(lpr, opt, {
             constexpr int U2 = O == 1 ? 2 : 1;              // (the two-triple form exists for Adam only)
             auto kern = cached ? (un == 2 ? bpr_fwd_apply_kernel<L, O, U2, false, false, true> : bpr_fwd_apply_kernel<L, O, 1, false, false, true>)
                                : (un == 2 ? bpr_fwd_apply_kernel<L, O, U2> : bpr_fwd_apply_kernel<L, O, 1>);
@@ -2862,7 +2882,8 @@ extern "C" int cdr_bpr_step_fused(cdr_ctx* ctx, void* stream, int opt, float* us
                                   void* sort_ws, size_t sort_ws_bytes) {
     CDR_CHECK_ARG(ctx && user_tab && item_tab && uid && pid && nid && out9 && GU && GP && keys && perm && flags && heads && sort_ws);
     CDR_CHECK_ARG(D > 0 && (D & 3) == 0 && D <= 256 && B > 0 && 3 * B <= (int64_t)0x7FFFFFFF);
-    CDR_CHECK_ARG(opt == 0 || (opt == 1 && user_m && user_v && item_m && item_v && step_user > 0 && step_item > 0));
+    CDR_CHECK_ARG(opt == 0 || (opt == 1 && user_m && user_v && item_m && item_v && step_user > 0 && step_item > 0) ||
+                  (opt == CDR_OPT_ADAGRAD && !user_m && user_v && !item_m && item_v));       // Adagrad: the sums in user_v / item_v, no steps
     CDR_CHECK_ARG(((uintptr_t)flags & 3) == 0);
     return bpr_step_fused_impl(ctx, stream, opt, user_tab, user_m, user_v, user_rows, item_tab, item_m, item_v, item_rows, D, uid, pid, nid, B, gamma,
                                reg_weight, lr, beta1, beta2, eps, weight_decay, step_user, step_item, nullptr, nullptr, nullptr, out9, GU, GP,
@@ -2901,7 +2922,8 @@ extern "C" int cdr_point_step_fused(cdr_ctx* ctx, void* stream, int loss_kind, i
                                     void* sort_ws, size_t sort_ws_bytes) {
     CDR_CHECK_ARG(ctx && user_tab && item_tab && uid && iid && label && out9 && GU && GI && keys && perm && flags && heads && sort_ws);
     CDR_CHECK_ARG((loss_kind == CDR_LOSS_MSE || loss_kind == CDR_LOSS_BCE) && D > 0 && (D & 3) == 0 && D <= 256 && B > 0 && 2 * B <= (int64_t)0x7FFFFFFF);
-    CDR_CHECK_ARG(opt == 0 || (opt == 1 && user_m && user_v && item_m && item_v && step_user > 0 && step_item > 0));
+    CDR_CHECK_ARG(opt == 0 || (opt == 1 && user_m && user_v && item_m && item_v && step_user > 0 && step_item > 0) ||
+                  (opt == CDR_OPT_ADAGRAD && !user_m && user_v && !item_m && item_v));       // Adagrad: the sums in user_v / item_v, no steps
     CDR_CHECK_ARG(((uintptr_t)flags & 3) == 0);
     hipStream_t s = (hipStream_t)stream;
     const int lpr = cdr_lpr_for(D);
@@ -2917,7 +2939,7 @@ extern "C" int cdr_point_step_fused(cdr_ctx* ctx, void* stream, int loss_kind, i
     const int grid = grid_for(B, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-        DISPATCH_LPR_OPT(lpr, opt, point_fwd_apply_kernel<L, O><<<dim3(grid), dim3(kBlock), 0, s>>>(loss_kind, T.TU, T.TI, D, uid, iid, label, (const uint32_t*)flags, B,
+        DISPATCH_LPR_OPT3(lpr, opt, point_fwd_apply_kernel<L, O><<<dim3(grid), dim3(kBlock), 0, s>>>(loss_kind, T.TU, T.TI, D, uid, iid, label, (const uint32_t*)flags, B,
                                                                                                    1.0f / (float)B, out9 + 4, T.hu, T.hi, GU, GI, ctx->partials));
     }
     CDR_LAUNCH_CHECK();
@@ -3545,19 +3567,15 @@ __global__ __launch_bounds__(kBlock) void pair_finish_kernel(const double* __res
 
 }  // namespace
 
-extern "C" int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int loss_kind, int opt, float* user_tab, float* user_m, float* user_v,
-                                             int64_t user_rows, float* item_tab, float* item_m, float* item_v, int64_t item_rows, int D,
-                                             const int64_t* su, const int64_t* si, const float* ys, int64_t B_s, const int64_t* tu,
-                                             const int64_t* ti, const float* yt, int64_t B_t, float alpha, float reg_s, float reg_t, float lr,
-                                             float beta1, float beta2, float eps, float weight_decay, int64_t* step_user_dev,
-                                             int64_t* step_item_dev, float* hp_dev, float* out16, float* GU, float* GI, uint32_t* keys,
-                                             uint32_t* perm, uint8_t* flags, uint32_t* heads, void* sort_ws, size_t sort_ws_bytes) {
-    CDR_CHECK_ARG(ctx && user_tab && item_tab && su && si && ys && tu && ti && yt && out16 && GU && GI && keys && perm && flags && heads && sort_ws);
-    CDR_CHECK_ARG((loss_kind == CDR_LOSS_MSE || loss_kind == CDR_LOSS_BCE) && D > 0 && (D & 3) == 0 && D <= 256 && B_s >= 1 && B_t >= 1);
-    CDR_CHECK_ARG(2 * (B_s + B_t) <= (int64_t)0x7FFFFFFF && user_rows > 0 && item_rows > 0);
-    CDR_CHECK_ARG((step_user_dev == nullptr) == (step_item_dev == nullptr));
-    CDR_CHECK_ARG(opt == 0 || (opt == 1 && user_m && user_v && item_m && item_v && step_user_dev && hp_dev));
-    CDR_CHECK_ARG(((uintptr_t)flags & 3) == 0);
+// What the two entries of CMF's pair step share.  THREE: the launch also exists for CDR_OPT_ADAGRAD (cdr_point_step_fused_pair).
+template <bool THREE>
+static int point_pair_step_impl(cdr_ctx* ctx, void* stream, int loss_kind, int opt, float* user_tab, float* user_m, float* user_v,
+                                int64_t user_rows, float* item_tab, float* item_m, float* item_v, int64_t item_rows, int D,
+                                const int64_t* su, const int64_t* si, const float* ys, int64_t B_s, const int64_t* tu,
+                                const int64_t* ti, const float* yt, int64_t B_t, float alpha, float reg_s, float reg_t, float lr,
+                                float beta1, float beta2, float eps, float weight_decay, int64_t* step_user_dev,
+                                int64_t* step_item_dev, float* hp_dev, float* out16, float* GU, float* GI, uint32_t* keys,
+                                uint32_t* perm, uint8_t* flags, uint32_t* heads, void* sort_ws, size_t sort_ws_bytes) {
     hipStream_t s = (hipStream_t)stream;
     const int64_t N = B_s + B_t;
     const int lpr = cdr_lpr_for(D);
@@ -3590,7 +3608,10 @@ extern "C" int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int los
     const int grid = grid_for(N, kBlock / lpr);
     {
         cdr_time_scope ts(ctx, CDR_TAG_POINT_FWD_GRAD, s);
-        DISPATCH_LPR_OPT(lpr, opt, point_pair_fwd_apply_kernel<L, O><<<dim3(grid), dim3(kBlock), 0, s>>>(
+        if constexpr (THREE) DISPATCH_LPR_OPT3(lpr, opt, point_pair_fwd_apply_kernel<L, O><<<dim3(grid), dim3(kBlock), 0, s>>>(
+                                       loss_kind, T.TU, T.TI, D, su, si, ys, B_s, tu, ti, yt, B_t, (const uint32_t*)flags, alpha / (float)B_s, (1.0f - alpha) / (float)B_t,
+                                       out16 + 9, T.hu, T.hi, GU, GI, ctx->partials));
+        else DISPATCH_LPR_OPT(lpr, opt, point_pair_fwd_apply_kernel<L, O><<<dim3(grid), dim3(kBlock), 0, s>>>(
                                        loss_kind, T.TU, T.TI, D, su, si, ys, B_s, tu, ti, yt, B_t, (const uint32_t*)flags, alpha / (float)B_s, (1.0f - alpha) / (float)B_t,
                                        out16 + 9, T.hu, T.hi, GU, GI, ctx->partials));
     }
@@ -3601,4 +3622,41 @@ extern "C" int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int los
     return finish_and_apply_dups(ctx, s, opt, D, sides, [&](unsigned* za, unsigned* zb) {
         pair_finish_kernel<<<dim3(1), dim3(kBlock), 0, s>>>(ctx->partials, grid, B_s, B_t, alpha, reg_s, reg_t, out16, za, zb);
     });
+}
+
+extern "C" int cdr_point_step_fused_pair_dev(cdr_ctx* ctx, void* stream, int loss_kind, int opt, float* user_tab, float* user_m, float* user_v,
+                                             int64_t user_rows, float* item_tab, float* item_m, float* item_v, int64_t item_rows, int D,
+                                             const int64_t* su, const int64_t* si, const float* ys, int64_t B_s, const int64_t* tu,
+                                             const int64_t* ti, const float* yt, int64_t B_t, float alpha, float reg_s, float reg_t, float lr,
+                                             float beta1, float beta2, float eps, float weight_decay, int64_t* step_user_dev,
+                                             int64_t* step_item_dev, float* hp_dev, float* out16, float* GU, float* GI, uint32_t* keys,
+                                             uint32_t* perm, uint8_t* flags, uint32_t* heads, void* sort_ws, size_t sort_ws_bytes) {
+    CDR_CHECK_ARG(ctx && user_tab && item_tab && su && si && ys && tu && ti && yt && out16 && GU && GI && keys && perm && flags && heads && sort_ws);
+    CDR_CHECK_ARG((loss_kind == CDR_LOSS_MSE || loss_kind == CDR_LOSS_BCE) && D > 0 && (D & 3) == 0 && D <= 256 && B_s >= 1 && B_t >= 1);
+    CDR_CHECK_ARG(2 * (B_s + B_t) <= (int64_t)0x7FFFFFFF && user_rows > 0 && item_rows > 0);
+    CDR_CHECK_ARG((step_user_dev == nullptr) == (step_item_dev == nullptr));
+    CDR_CHECK_ARG(opt == 0 || (opt == 1 && user_m && user_v && item_m && item_v && step_user_dev && hp_dev));
+    CDR_CHECK_ARG(((uintptr_t)flags & 3) == 0);
+    return point_pair_step_impl<false>(ctx, stream, loss_kind, opt, user_tab, user_m, user_v, user_rows, item_tab, item_m, item_v, item_rows, D, su, si, ys, B_s,
+                                       tu, ti, yt, B_t, alpha, reg_s, reg_t, lr, beta1, beta2, eps, weight_decay, step_user_dev, step_item_dev, hp_dev,
+                                       out16, GU, GI, keys, perm, flags, heads, sort_ws, sort_ws_bytes);
+}
+
+// The same step under CDR_OPT_ADAGRAD, which reads no update count (user_m = item_m = NULL, the tables' sums of squared gradients in
+// user_v / item_v; eps = torch's 1e-10).  Buffers as cdr_point_step_fused_pair_dev's.  CDR_OPT_SGD and CDR_OPT_ADAM are refused here:
+// their entry is the _dev form.
+extern "C" int cdr_point_step_fused_pair(cdr_ctx* ctx, void* stream, int loss_kind, int opt, float* user_tab, float* user_m, float* user_v,
+                                         int64_t user_rows, float* item_tab, float* item_m, float* item_v, int64_t item_rows, int D,
+                                         const int64_t* su, const int64_t* si, const float* ys, int64_t B_s, const int64_t* tu,
+                                         const int64_t* ti, const float* yt, int64_t B_t, float alpha, float reg_s, float reg_t, float lr,
+                                         float eps, float weight_decay, float* out16, float* GU, float* GI, uint32_t* keys,
+                                         uint32_t* perm, uint8_t* flags, uint32_t* heads, void* sort_ws, size_t sort_ws_bytes) {
+    CDR_CHECK_ARG(ctx && user_tab && item_tab && su && si && ys && tu && ti && yt && out16 && GU && GI && keys && perm && flags && heads && sort_ws);
+    CDR_CHECK_ARG((loss_kind == CDR_LOSS_MSE || loss_kind == CDR_LOSS_BCE) && D > 0 && (D & 3) == 0 && D <= 256 && B_s >= 1 && B_t >= 1);
+    CDR_CHECK_ARG(2 * (B_s + B_t) <= (int64_t)0x7FFFFFFF && user_rows > 0 && item_rows > 0);
+    CDR_CHECK_ARG(opt == CDR_OPT_ADAGRAD && !user_m && user_v && !item_m && item_v);
+    CDR_CHECK_ARG(((uintptr_t)flags & 3) == 0);
+    return point_pair_step_impl<true>(ctx, stream, loss_kind, opt, user_tab, user_m, user_v, user_rows, item_tab, item_m, item_v, item_rows, D, su, si, ys, B_s,
+                                      tu, ti, yt, B_t, alpha, reg_s, reg_t, lr, 0.f, 0.f, eps, weight_decay, nullptr, nullptr, nullptr,
+                                      out16, GU, GI, keys, perm, flags, heads, sort_ws, sort_ws_bytes);
 }

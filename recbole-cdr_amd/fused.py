@@ -19,11 +19,33 @@ import torch
 
 from . import binding as B_
 
-OPT_SGD, OPT_ADAM = 0, 1
+OPT_SGD, OPT_ADAM, OPT_ADAGRAD, OPT_RMSPROP = 0, 1, 2, 3      # CDR_OPT_* of include/cdr_hip.h: THE table of this package
+OPT_NAMES = {OPT_SGD: 'sgd', OPT_ADAM: 'adam', OPT_ADAGRAD: 'adagrad', OPT_RMSPROP: 'rmsprop'}
+_OPT_CODES = {name: code for code, name in OPT_NAMES.items() if code != OPT_RMSPROP}      # what a row-wise step can be asked for
+ADAGRAD_EPS = 1e-10                                  # torch.optim.Adagrad's default (Adam's is 1e-8: pass it with opt='adagrad')
+
+
+def opt_code(opt):
+    """'sgd' | 'adam' | 'adagrad' -> the native optimizer code.  Any other name is an error (it used to mean SGD, silently).
+    Row-wise RMSprop does not exist: an untouched row's square_avg decays every step, so leaving untouched rows alone is another
+    optimizer."""
+    try:
+        return _OPT_CODES[opt]
+    except (KeyError, TypeError):
+        raise ValueError(f"opt must be one of {sorted(_OPT_CODES)}, got {opt!r}") from None
+
+
+def refuse_adagrad(who, code):
+    """For the step forms whose kernels implement SGD and Adam only (k-major, small-batch, two-launch map, sharded)."""
+    if code == OPT_ADAGRAD:
+        raise ValueError(f"{who} has no Adagrad form (opt='adagrad' is served by FusedBPRStep, FusedPointStep and the steps on the "
+                         f"general segmented apply)")
 
 
 class RowwiseState:
-    """Per-table optimizer state for the row-wise Adam (SGD needs no moments).  ``step`` counts the updates this TABLE
+    """Per-table optimizer state for the row-wise Adam (SGD needs no moments; Adagrad keeps ONE table-sized tensor, the sum of squared
+    gradients, in ``exp_avg_sq`` with ``exp_avg`` None -- no ``last``, no ring, no device step mirror is needed: a row whose gradient is
+    zero keeps its sum and its weights bit for bit, so the row-wise Adagrad IS the dense one at weight_decay = 0).  ``step`` counts the updates this TABLE
     has received -- like torch.optim.Adam's per-parameter ``state['step']`` -- so one state object can be shared by the
     step objects of several phases (SOURCE / TARGET BPR steps and the OVERLAP map step touch the same user tables).
 
@@ -55,7 +77,8 @@ class RowwiseState:
         self.table = table
         self._step = 0
         self.exp_avg = torch.zeros_like(table) if opt == OPT_ADAM else None
-        self.exp_avg_sq = torch.zeros_like(table) if opt == OPT_ADAM else None
+        self.exp_avg_sq = torch.zeros_like(table) if opt in (OPT_ADAM, OPT_ADAGRAD) else None
+        self.opt = opt
         self._step_dev = None
         self.exact = bool(exact)
         if self.exact:
@@ -209,7 +232,7 @@ class _Step:
     the steps composed of a forward, an id sort and segmented applies share: the size queries, the sort buffers, the states and the apply."""
 
     def __init__(self, opt, lr, betas, eps, weight_decay):
-        self.opt = OPT_ADAM if opt == 'adam' else OPT_SGD
+        self.opt = opt_code(opt)
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
 
     def _hp(self):
@@ -260,6 +283,15 @@ class _Step:
                 B_.raw(keys), B_.raw(perm), n, B_.f32(G), neg_start, reg_limit, None if coef is None else B_.f32(coef), *self._hp(),
                 st.step, None, int(key_base))
 
+    def _dense_optimizer(self, params):
+        """The dense optimizer of the step's own learner for its small parameters (None: plain SGD, done in torch by the caller)."""
+        from .trainer.trainer import DenseAdam, DenseAdagrad
+        if self.opt == OPT_ADAM:
+            return DenseAdam(params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.wd)
+        if self.opt == OPT_ADAGRAD:
+            return DenseAdagrad(params, lr=self.lr, eps=self.eps, weight_decay=self.wd)
+        return None
+
     def _check_pair_batch(self, source, target):
         """(B_s, B_t) of a two-domain batch: every tensor of a domain of one length, within the sizes the step was built for."""
         Bs, Bt = source[0].numel(), target[0].numel()
@@ -275,10 +307,8 @@ class _DenseStep(_Step):
     updated row-wise.  ``params`` are the parameters themselves: the step sets their ``.grad`` and updates them in place."""
 
     def _dense_init(self, params):
-        from .trainer.trainer import DenseAdam
         self.params = list(params)
-        self.w_opt = DenseAdam(self.params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.wd) \
-            if self.opt == OPT_ADAM else None
+        self.w_opt = self._dense_optimizer(self.params)
 
     def _dense_update(self, packed=None):
         """``packed``: the gradients as one vector in ``params`` order, each ``.grad`` becomes a view of it (None: the caller has set
@@ -522,6 +552,7 @@ class KMajorBPRStep(_TwoTableStep):
 
     def __init__(self, user_table, item_table, max_positives, k=1, opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, gamma=1e-10, reg_weight=0.0, user_state=None, item_state=None, fuse_singles=True):
+        refuse_adagrad('KMajorBPRStep', opt_code(opt))                           # (before the base allocates any optimizer state)
         super().__init__(user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state)
         self.k = int(k)
         self.gamma, self.reg_weight = gamma, reg_weight
@@ -1323,7 +1354,8 @@ class FusedPointPairStep(_TwoTableStep):
     loss = alpha (BCE_s + reg_source EmbLoss_s) + (1 - alpha) (BCE_t + reg_target EmbLoss_t), and ONE update per touched row from the
     sum of its two domains' contributions -- the reference's single Adam step (two FusedPointStep calls would update a row named by both
     batches twice and advance each table twice).  One native call (cdr_point_step_fused_pair_dev) with the update counts on the device:
-    capturable in a hipGraph (``replayed`` keeps the host mirrors in step)."""
+    capturable in a hipGraph (``replayed`` keeps the host mirrors in step).  opt='adagrad': the same launches through
+    cdr_point_step_fused_pair, which reads no update count (host counts; not captured)."""
 
     def __init__(self, user_table, item_table, max_source, max_target, alpha, reg_source, reg_target, opt='adam', lr=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, user_state=None, item_state=None, loss='bce'):
@@ -1354,6 +1386,16 @@ class FusedPointPairStep(_TwoTableStep):
         if si.numel() != Bs or ys.numel() != Bs or ti.numel() != Bt or yt.numel() != Bt:
             raise ValueError('FusedPointPairStep: ids and labels of a domain must have the same length')
         us, its = self.ustate, self.istate
+        if self.opt == OPT_ADAGRAD:
+            # the host-state entry: Adagrad reads no update count (the host counts still advance: checkpoints, one state per table)
+            lr, _b1, _b2, eps, wd = self._hp()
+            us.advance(); its.advance()
+            B_.call('cdr_point_step_fused_pair', B_.ctx(self.U.device), B_.stream(), self.kind, self.opt, B_.f32(us.table), None,
+                    B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), None, B_.f32(its.exp_avg_sq), its.table.shape[0],
+                    self.D, B_.i64(su), B_.i64(si), B_.f32(ys), Bs, B_.i64(tu), B_.i64(ti), B_.f32(yt), Bt, self.alpha, self.reg_source,
+                    self.reg_target, lr, eps, wd, B_.f32(self.out16), B_.f32(self.GU), B_.f32(self.GI), B_.raw(self.keys), B_.raw(self.perm),
+                    B_.raw(self.flags), B_.raw(self.heads), B_.raw(self.ws), self.ws.numel())
+            return self.out16
         adam = self.opt == OPT_ADAM
         B_.call('cdr_point_step_fused_pair_dev', B_.ctx(self.U.device), B_.stream(), self.kind, self.opt, B_.f32(us.table), B_.f32(us.exp_avg),
                 B_.f32(us.exp_avg_sq), us.table.shape[0], B_.f32(its.table), B_.f32(its.exp_avg), B_.f32(its.exp_avg_sq), its.table.shape[0],
@@ -1376,6 +1418,7 @@ class KMajorPointStep(_TwoTableStep):
     def __init__(self, user_table, item_table, max_positives, k=1, loss='mse', opt='adam', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, reg_weight=0.0, user_state=None, item_state=None):
         assert user_table.shape[1] % 4 == 0 and user_table.shape[1] <= 256 and 1 <= int(k) <= 64
+        refuse_adagrad('KMajorPointStep', opt_code(opt))
         super().__init__(user_table, item_table, opt, lr, betas, eps, weight_decay, user_state, item_state)
         self.k = int(k)
         self.kind = B_.CDR_LOSS_MSE if loss == 'mse' else B_.CDR_LOSS_BCE
@@ -1428,7 +1471,6 @@ class FusedMapStep(_Step):
 
     def __init__(self, source_table, target_table, mapping_fn, mapping_params, max_batch, opt='adam', lr=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, group=None, source_state=None, target_state=None, layers=None):
-        from .trainer.trainer import DenseAdam
         assert source_table.is_cuda and target_table.is_cuda, 'FusedMapStep needs ROCm device tensors'
         self.S, self.T = source_table, target_table
         self.mapping_fn = mapping_fn
@@ -1438,8 +1480,7 @@ class FusedMapStep(_Step):
         # state per table across phases, like the reference's single Adam instance: trainer.py:30-41)
         self.sstate = source_state if source_state is not None else RowwiseState(source_table, self.opt)
         self.tstate = target_state if target_state is not None else RowwiseState(target_table, self.opt)
-        self.map_opt = DenseAdam(self.mapping_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) \
-            if self.opt == OPT_ADAM else None
+        self.map_opt = self._dense_optimizer(self.mapping_params)                    # the dense optimizer of the same learner
         self.group = group
         self.loss = torch.zeros((), device=source_table.device, dtype=torch.float32)
         self._ws = None
@@ -1570,7 +1611,7 @@ class FusedMapStep(_Step):
         a permutation, as the reference's loader yields them): the two-launch path of csrc/cdr_mapstep.hip."""
         idx = idx.reshape(-1).contiguous()
         n_global = idx.numel()
-        if unique and self.layers is not None and n_global > 0:
+        if unique and self.layers is not None and n_global > 0 and self.opt != OPT_ADAGRAD:     # (Adagrad: the general form below)
             return self._step_unique(idx)
         if self.group is not None:
             idx, n_global = self._route(idx)

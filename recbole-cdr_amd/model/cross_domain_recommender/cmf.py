@@ -94,12 +94,12 @@ class CMF(RowwiseTraining, CrossDomainRecommender):
             rowwise_catch_up([(us, [su, tu]), (its, [si, ti])], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         return step.step(su, si, ys, tu, ti, yt)[:1]
 
-    def fused_graph_key(self, interaction, adam='lazy'):
+    def fused_graph_key(self, interaction, adam='lazy', opt='adam'):
         """Hashable tag of the launches ``fused_train_step(interaction)`` would make, or None when they must not be captured in a hipGraph.
         The step keeps its update counts on the device, so it is capturable while its two-table sort (2 (B_s + B_t) keys) stays below the
         size EMCDR.fused_graph_key refuses to capture (rocPRIM's Onesweep configuration: its temporary-storage resets do not survive a
         replay)."""
-        if self.__dict__.get('_dist_cfg') not in (None, False):
+        if self.__dict__.get('_dist_cfg') not in (None, False) or opt == 'adagrad':    # (Adagrad: host-side update counts; eager)
             return None
         if self.SOURCE_USER_ID not in interaction or self.TARGET_USER_ID not in interaction:
             return None

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from ... import binding as B_
 from ... import functional as F_
-from ...fused import FusedBPRStep, FusedMapStep, FusedPointStep, KMajorBPRStep, KMajorPointStep, rowwise_catch_up
+from ...fused import FusedBPRStep, FusedMapStep, FusedPointStep, KMajorBPRStep, KMajorPointStep, OPT_ADAGRAD, rowwise_catch_up
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
 from ..rowwise import RowwiseTraining
@@ -137,6 +137,8 @@ class EMCDR(RowwiseTraining, CrossDomainRecommender):
         exact, code, hp = self._fused_args(opt, adam, lr, betas, eps, weight_decay)
         if exact and self._dist_group() is not None:
             raise ValueError("adam='exact' is not available with config['dist_group'] (sharded tables): use adam='lazy' or one GPU")
+        if code == OPT_ADAGRAD and self._dist_group() is not None:
+            raise ValueError("opt='adagrad' is not available with config['dist_group']: the sharded steps implement SGD and Adam only")
         if self._dist_group() is not None:
             self._fused_cache()
             return self._dist_train_step(interaction, code, hp)
@@ -183,7 +185,7 @@ class EMCDR(RowwiseTraining, CrossDomainRecommender):
             pk = getattr(interaction, 'point_k', None)
             rows = user.numel()
             D_ = getattr(self, f'{domain}_user_embedding').weight.shape[1]
-            if pk is not None and 1 <= pk <= 64 and rows % (1 + pk) == 0 and rows > 8192 and D_ % 4 == 0 and D_ <= 256:
+            if code != OPT_ADAGRAD and pk is not None and 1 <= pk <= 64 and rows % (1 + pk) == 0 and rows > 8192 and D_ % 4 == 0 and D_ <= 256:
                 step = domain_step(('mfk', domain, pk), KMajorPointStep, rows // (1 + pk), 'max_positives', k=pk, loss='mse')
                 catch_up((step.ustate, [user[:rows // (1 + pk)]]), (step.istate, [item]))
                 return step.step(user, item, label)[0]
@@ -195,12 +197,12 @@ class EMCDR(RowwiseTraining, CrossDomainRecommender):
         return self._fused_bpr_domain_step(domain, getattr(interaction, 'k_major', None), user, item, neg, self.reg_weight, self.bpr_gamma,
                                            code, exact, hp)
 
-    def fused_graph_key(self, interaction, adam='lazy'):
+    def fused_graph_key(self, interaction, adam='lazy', opt='adam'):
         """Hashable tag of the launches ``fused_train_step(interaction)`` would make, or None when they must not be captured in a
         hipGraph: capturable are the per-triple BPR step (update counts on the device: cdr_bpr_step_fused_dev) and the distinct-id
         OVERLAP step; the MF steps and the per-positive forms read host-side update counts.  ``adam``: the row-wise Adam mode of
         ``fused_train_step`` (the exact mode's catch-up launch is captured with the step)."""
-        if self._dist_group() is not None:
+        if self._dist_group() is not None or opt == 'adagrad':      # (Adagrad: the steps read host-side state; eager)
             return None
         if self.phase == 'OVERLAP':
             return ('map', self.mode, adam) if getattr(self, 'overlap_ids_unique', True) and self.map_func in ('linear', 'non_linear') else None

@@ -282,7 +282,7 @@ class SSCDR(RowwiseTraining, CrossDomainRecommender):
         catch_up((step.ustate, [user]), (step.istate, [item, neg]))
         return step.step(user, item, neg)[0]
 
-    def fused_graph_key(self, interaction, adam='lazy'):
+    def fused_graph_key(self, interaction, adam='lazy', opt='adam'):
         """None for every phase: the steps read the host's update counts (and the OVERLAP step runs autograd), so the trainer launches
         them and never captures them in a hipGraph."""
         return None

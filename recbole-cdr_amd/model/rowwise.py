@@ -2,7 +2,7 @@
 ``fused_train_step``: the cache of per-table optimizer states and step objects, the checks of the (opt, adam) arguments, and the
 methods the trainer calls around the step (``fused_replayed``, ``fused_sync``, ``fused_optimizer_state``,
 ``load_fused_optimizer_state``).  Which step class a batch gets stays with the model."""
-from ..fused import FusedBPRStep, KMajorBPRStep, RowwiseState, OPT_ADAM, OPT_SGD, rowwise_bound_lag, rowwise_catch_up
+from ..fused import FusedBPRStep, KMajorBPRStep, RowwiseState, OPT_ADAGRAD, OPT_NAMES, opt_code, rowwise_bound_lag, rowwise_catch_up
 
 
 class RowwiseTraining:
@@ -22,7 +22,7 @@ class RowwiseTraining:
         exact = adam == 'exact'
         if exact and opt != 'adam':
             raise ValueError(f"adam='exact' is the reference's dense Adam: it needs opt='adam', got {opt!r}")
-        return exact, OPT_ADAM if opt == 'adam' else OPT_SGD, dict(opt=opt, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        return exact, opt_code(opt), dict(opt=opt, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)      # (an unknown opt: ValueError)
 
     def _fused_cache(self, exact=None):
         """The cache, created on first use.  ``exact`` given: the mode of this ``fused_train_step`` -- one per model."""
@@ -113,7 +113,9 @@ class RowwiseTraining:
                 rowwise_catch_up(tables, lr=hp['lr'], betas=hp['betas'], eps=hp['eps'], weight_decay=hp['weight_decay'])
 
         k, rows = k_major, user.numel()
-        if k is not None and rows % k == 0 and (k >= 2 or rows + rows // k <= 8192):
+        # (Adagrad: the per-positive kernels implement SGD and Adam only; the per-triple step below has the same loss and per-row
+        # gradients on the B = S k rows -- KMajorBPRStep's docstring)
+        if code != OPT_ADAGRAD and k is not None and rows % k == 0 and (k >= 2 or rows + rows // k <= 8192):
             step = self._fused_domain_step(domain, ('bprk', domain, k), KMajorBPRStep, rows // k, 'max_positives', code, exact, hp,
                                            reg_weight=reg_weight, k=k, gamma=gamma)
             catch_up((step.ustate, [user[:rows // k]]), (step.istate, [item[:rows // k], neg]))
@@ -148,6 +150,9 @@ class RowwiseTraining:
             return {}
         self.fused_sync()
         out = {'tables': {k: {'step': st.step, 'exp_avg': st.exp_avg, 'exp_avg_sq': st.exp_avg_sq} for k, st in cache['states'].items()}}
+        codes = {getattr(st, 'opt', None) for st in cache['states'].values()} - {None}
+        if len(codes) == 1:                                    # the learner the state belongs to: a resume under another one is refused
+            out['opt'] = OPT_NAMES[codes.pop()]
         step = cache['steps'].get(self._WEIGHT_STEP)
         if step is not None and step.w_opt is not None:
             out['weights'] = step.w_opt.state_dict()
@@ -157,13 +162,18 @@ class RowwiseTraining:
         """Restore what ``fused_optimizer_state`` returned (before the next ``fused_train_step``).  ``adam``: the mode training goes on
         with; in exact mode every row is current at its table's update count (the checkpoint was written flushed).  The dense weights'
         Adam state is handed to the ``_WEIGHT_STEP`` step when it is next built."""
+        code = opt_code(opt)
+        if state.get('opt', opt) != opt:                       # (before any state exists)
+            raise ValueError(f"the checkpoint's row-wise optimizer state was written under opt={state['opt']!r}; it cannot be resumed under "
+                             f"opt={opt!r}")
         self._fused_cache()
-        code = OPT_ADAM if opt == 'adam' else OPT_SGD
         for name, rec in state.get('tables', {}).items():
             st = self._fused_state(name, code, adam == 'exact')
             st.step = int(rec['step'])
             if rec['exp_avg'] is not None:
-                st.exp_avg.copy_(rec['exp_avg']); st.exp_avg_sq.copy_(rec['exp_avg_sq'])
+                st.exp_avg.copy_(rec['exp_avg'])
+            if rec['exp_avg_sq'] is not None:
+                st.exp_avg_sq.copy_(rec['exp_avg_sq'])
             st.restored()
         if self._WEIGHT_STEP is not None:
             if 'weights' in state:

@@ -4,7 +4,9 @@ The reference subclasses third-party ``recbole.trainer.Trainer``; the part of it
 here (optimizer built ONCE and kept across phases, ``_train_epoch`` = zero_grad -> calculate_loss ->
 (tuple => sum) -> nan check -> backward -> clip -> step, ``fit`` with eval_step / early stopping, ``evaluate`` =
 full-sort scores -> mask PAD column and history -> top-k).  Metrics are computed on device with torch.topk (plumbing);
-the dense optimizer is the native exact Adam (csrc/cdr_rows.hip ``cdr_adam_dense``).
+the dense optimizer is the one ``config['learner']`` names, as recbole's ``_build_optimizer`` builds it: the native exact Adam
+(csrc/cdr_rows.hip ``cdr_adam_multi_dev``) by default, or SGD / Adagrad / RMSprop with torch's defaults (csrc/cdr_optim.hip
+``cdr_opt_multi_dev``).
 """
 import numpy as np
 import torch
@@ -91,6 +93,149 @@ def _dense_adam_load(self, state_dict):
 DenseAdam.load_state_dict = _dense_adam_load
 
 
+LEARNERS = ('adam', 'sgd', 'adagrad', 'rmsprop')       # config['learner'] values with a native optimizer ('sparse_adam' is refused)
+
+
+class _DenseLearner(torch.optim.Optimizer):
+    """What recbole's ``_build_optimizer`` builds for ``learner`` = sgd / adagrad / rmsprop -- ``torch.optim.<X>(params, lr=..,
+    weight_decay=..)`` with torch's defaults for everything else -- on one native launch for all parameters (``cdr_opt_multi_dev``).
+    None of the three has a bias correction: the launch reads no step count, so ``step()`` is hipGraph-capturable as it stands.
+    ``state_dict()`` has torch's key names and param-group keys (``_STATE``: the state tensor; ``step``: a CPU float scalar as torch
+    keeps it), so a checkpoint loads under ``torch.optim.<X>`` and back.  ``step`` is host bookkeeping only: a replayed graph runs no
+    Python, ``on_replay`` counts its update for the parameters the captured step updated."""
+    kind, _STATE = None, None
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        self.loss_pair = None              # (loss, loss_sum) handed over before ``step()``, as for DenseAdam: added inside the update's launch
+        self._last = ()                    # the parameters the last ``step()`` updated (``on_replay``)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        import ctypes
+        from .. import binding as B_
+        last = []
+        for group in self.param_groups:
+            ps, gs, ss, ns, keep = [], [], [], [], []
+            for p in group['params']:
+                if p.grad is None:
+                    continue                      # like torch: a parameter without a gradient is skipped
+                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                keep.append(g)
+                ps.append(B_.f32(p.data)); gs.append(B_.f32(g)); ns.append(p.numel())
+                if self._STATE is not None:
+                    st = self.state[p]
+                    if not st:
+                        st['step'] = torch.tensor(0.0)
+                        st[self._STATE] = torch.zeros_like(p)
+                    if not (p.is_cuda and torch.cuda.is_current_stream_capturing()):      # (a capture records the launch: no update runs)
+                        st['step'] += 1
+                    ss.append(B_.f32(st[self._STATE]))
+                last.append(p)
+            if not ps:
+                continue
+            n = len(ps)
+            arr = lambda xs: (ctypes.c_void_p * n)(*[x.value if hasattr(x, 'value') else x for x in xs])
+            lp, self.loss_pair = self.loss_pair, None
+            B_.call('cdr_opt_multi_dev', B_.stream(), self._code(), n, arr(ps), arr(gs), arr(ss) if ss else None,
+                    (ctypes.c_int64 * n)(*ns), float(group['lr']), float(group.get('alpha', 0.0)), float(group.get('eps', 0.0)),
+                    float(group['weight_decay']), None if lp is None else B_.f32(lp[0]), None if lp is None else B_.f32(lp[1]))
+        self._last = tuple(last)
+
+    def _code(self):
+        from ..fused import OPT_NAMES                      # (the package's one table of CDR_OPT_* codes)
+        return {name: code for code, name in OPT_NAMES.items()}[self.kind]
+
+    def state_dict(self):
+        """torch.optim.Adagrad / RMSprop create ``step`` and the state tensor of EVERY parameter in ``__init__`` and their ``step()`` reads
+        them without a check; this class creates them at a parameter's first gradient.  So that a checkpoint written in between (EMCDR
+        after its SOURCE phase: the target tables have had no gradient yet) steps under torch's class, an optimizer that has updated
+        anything writes a zero state tensor and ``step`` 0 for the parameters it has not -- what torch holds for them.  One that has
+        updated nothing (the unused dense optimizer of optimizer_mode='rowwise') writes an empty state: no table-sized zeros."""
+        sd = super().state_dict()
+        if self._STATE is None or not sd['state']:
+            return sd
+        i = 0
+        for g in self.param_groups:
+            for p in g['params']:
+                if i not in sd['state']:
+                    sd['state'][i] = {'step': torch.tensor(0.0), self._STATE: torch.zeros_like(p)}
+                i += 1
+        return sd
+
+    def on_replay(self):
+        if self._STATE is not None:
+            for p in self._last:
+                self.state[p]['step'] += 1
+
+    def load_state_dict(self, state_dict):
+        """A checkpoint of this class or of ``torch.optim.<X>``; ``step`` comes back as the CPU float scalar torch keeps (a checkpoint
+        loaded with ``map_location`` hands it over on the device)."""
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            if 'step' in st:
+                st['step'] = torch.tensor(float(st['step']))
+
+
+def _refuse(name, **must):
+    for k, (got, want) in must.items():
+        if got != want:
+            raise ValueError(f'{name}: {k}={got!r} is not supported (only {want!r}: the reference builds its optimizer with torch defaults)')
+
+
+class DenseSGD(_DenseLearner):
+    """``torch.optim.SGD(params, lr, weight_decay=wd)``: no momentum.  g += wd p; p -= lr g."""
+    kind = 'sgd'
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0.0, nesterov=False):
+        _refuse('DenseSGD', momentum=(momentum, 0), dampening=(dampening, 0), nesterov=(nesterov, False))
+        super().__init__(params, dict(lr=lr, momentum=0, dampening=0, weight_decay=weight_decay, nesterov=False, maximize=False, foreach=None,
+                                      differentiable=False, fused=None))
+
+
+class DenseAdagrad(_DenseLearner):
+    """``torch.optim.Adagrad(params, lr, weight_decay=wd)``: lr_decay = 0, initial_accumulator_value = 0, eps = 1e-10.
+    g += wd p; sum += g g; p -= lr g / (sqrt(sum) + eps)."""
+    kind, _STATE = 'adagrad', 'sum'
+
+    def __init__(self, params, lr=1e-2, lr_decay=0, weight_decay=0.0, initial_accumulator_value=0, eps=1e-10):
+        _refuse('DenseAdagrad', lr_decay=(lr_decay, 0), initial_accumulator_value=(initial_accumulator_value, 0))
+        super().__init__(params, dict(lr=lr, lr_decay=0, eps=eps, weight_decay=weight_decay, initial_accumulator_value=0, foreach=None,
+                                      maximize=False, differentiable=False, fused=None))
+
+
+class DenseRMSprop(_DenseLearner):
+    """``torch.optim.RMSprop(params, lr, weight_decay=wd)``: alpha = 0.99, eps = 1e-8, not centered, no momentum.
+    g += wd p; square_avg = alpha square_avg + (1 - alpha) g g; p -= lr g / (sqrt(square_avg) + eps)."""
+    kind, _STATE = 'rmsprop', 'square_avg'
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0, centered=False):
+        _refuse('DenseRMSprop', momentum=(momentum, 0), centered=(centered, False))
+        super().__init__(params, dict(lr=lr, momentum=0, alpha=alpha, eps=eps, centered=False, weight_decay=weight_decay, capturable=False,
+                                      foreach=None, maximize=False, differentiable=False))
+
+
+def dense_optimizer(learner, params, lr, weight_decay):
+    """The native dense optimizer of ``learner`` with torch's defaults, as recbole's ``_build_optimizer`` builds it."""
+    cls = {'adam': DenseAdam, 'sgd': DenseSGD, 'adagrad': DenseAdagrad, 'rmsprop': DenseRMSprop}[learner]
+    return cls(params, lr=lr, weight_decay=weight_decay)
+
+
+def resolve_learner(config):
+    """config['learner'] -> one of LEARNERS (default 'adam', case-insensitive).  'sparse_adam' is refused: the tables are dense
+    parameters, and torch.optim.SparseAdam refuses dense gradients too.  Any other name: a warning and Adam, as recbole does."""
+    name = config['learner'] if 'learner' in config and config['learner'] is not None else 'adam'
+    name = str(name).lower()
+    if name == 'sparse_adam':
+        raise ValueError("learner='sparse_adam' is not supported: the embedding tables are dense parameters with dense gradients, which "
+                         "torch.optim.SparseAdam refuses too; use 'adam', or optimizer_mode='rowwise' for an O(batch) update")
+    if name not in LEARNERS:
+        import warnings
+        warnings.warn(f'Received unrecognized optimizer {name!r}, set default Adam optimizer', stacklevel=3)
+        return 'adam'
+    return name
+
+
 class RowAwareAdam(DenseAdam):
     """``DenseAdam`` for a model whose embedding tables take the deferred row-wise form of the SAME optimizer
     (``model.enable_deferred_adam``; lazyadam.DeferredRowAdam: exact dense-Adam results, O(batch) traffic).  ``step()`` = the
@@ -161,6 +306,7 @@ def early_stopping(value, best, cur_step, max_step, bigger=True):
 
 
 class Trainer:
+    learner = 'adam'                  # (class default, as rowwise_adam below)
     rowwise_adam = 'lazy'             # (class default: loops driven on objects built without __init__ keep the lazy row-wise Adam)
 
     def __init__(self, config, model):
@@ -183,6 +329,17 @@ class Trainer:
         # 'rowwise' : the model's O(batch) fused step (tables too large for dense gradients, e.g. BASELINE config C5)
         self.optimizer_mode = config['optimizer_mode'] if 'optimizer_mode' in config else 'dense'
         on_gpu = torch.device(self.device).type == 'cuda'
+        # config['learner'] (recbole Trainer._build_optimizer: adam | sgd | adagrad | rmsprop, torch defaults beyond lr and weight_decay;
+        # default 'adam').  Every refusal comes before any optimizer or state object exists.
+        self.learner = resolve_learner(config)
+        if self.optimizer_mode == 'rowwise' and self.learner == 'rmsprop':
+            raise ValueError("learner='rmsprop' is not available with optimizer_mode='rowwise': an untouched row's square_avg decays "
+                             "every step (square_avg *= alpha), so a lazy row-wise form that leaves untouched rows alone is not the "
+                             "optimizer asked for; use optimizer_mode='dense'")
+        if self.learner == 'adagrad' and 'dist_group' in config and config['dist_group'] not in (None, False):
+            raise ValueError("learner='adagrad' is not available with dist_group: the sharded steps implement SGD and Adam only")
+        if self.learner != 'adam' and self.optimizer_mode == 'rowwise' and 'rowwise_adam' in config and config['rowwise_adam'] == 'exact':
+            raise ValueError(f"rowwise_adam='exact' is the reference's dense Adam: it needs learner='adam', got {self.learner!r}")
         # The reference's Adam over every parameter.  A model that offers ``enable_deferred_adam`` (CoNet on its fused tower kernels)
         # gets the SAME optimizer with its embedding tables evaluated lazily per row -- bit-identical to the dense sweep
         # (lazyadam.py), O(batch) instead of O(table) traffic per step.  config['deferred_adam'] = False keeps the literal sweep;
@@ -190,7 +347,11 @@ class Trainer:
         deferred = (config['deferred_adam'] if 'deferred_adam' in config else True) and self.optimizer_mode == 'dense' and on_gpu \
             and not self.clip_grad_norm and hasattr(self.model, 'enable_deferred_adam') and getattr(self.model, 'fused_towers', True) \
             and all(p.is_cuda for p in self.model.parameters())
-        if deferred:
+        if self.learner != 'adam':
+            # built once and kept across phases, like the Adam below; the deferred row-wise form is Adam's alone (CoNet then takes its
+            # plain dense route)
+            self.optimizer = dense_optimizer(self.learner, self.model.parameters(), self.learning_rate, self.weight_decay)
+        elif deferred:
             self.optimizer = RowAwareAdam(self.model, lr=self.learning_rate, weight_decay=self.weight_decay)
         else:
             self.optimizer = DenseAdam(self.model.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay)
@@ -390,6 +551,8 @@ class Trainer:
         # full batches of a capturable phase (model.fused_graph_key): the first two run eagerly on the capture stream -- real steps, they
         # create every buffer and context the capture needs -- then {producer -> fused step -> loss total} is replayed, 4 steps per launch
         gkw = {'adam': 'exact'} if self.rowwise_adam == 'exact' else {}
+        if self.learner != 'adam':
+            gkw['opt'] = self.learner
         gkey = self.model.fused_graph_key(prod.fields, **gkw) if (self.graph_step_rowwise and hasattr(self.model, 'fused_graph_key')) else None
         gs = None
         if gkey is not None:
@@ -568,7 +731,7 @@ class Trainer:
             return
         state = {'epoch': epoch, 'cur_step': self.cur_step, 'best_valid_score': self.best_valid_score,
                  'state_dict': self.model.state_dict(), 'other_parameter': self.model.other_parameter(),
-                 'optimizer_mode': self.optimizer_mode, 'optimizer': self.optimizer.state_dict(),
+                 'optimizer_mode': self.optimizer_mode, 'optimizer': self.optimizer.state_dict(), 'learner': self.learner,
                  'phase': getattr(self.model, 'phase', None)}
         if self.optimizer_mode == 'rowwise' and hasattr(self.model, 'fused_optimizer_state'):
             state['rowwise'] = self.model.fused_optimizer_state()
@@ -586,6 +749,10 @@ class Trainer:
                 self.model.set_phase(state['phase'])
             return
         state = torch.load(path, map_location=self.device, weights_only=False)
+        mine = self.learner
+        if state.get('learner', 'adam') != mine:          # (checkpoints written before config['learner'] existed are Adam's)
+            raise ValueError(f"the checkpoint was written with learner={state.get('learner', 'adam')!r}; this trainer runs learner={mine!r} "
+                             f"(the optimizer state of one does not resume the other)")
         self.start_epoch = (state['epoch'] + 1) if state['epoch'] is not None else 0
         self.cur_step, self.best_valid_score = state['cur_step'], state['best_valid_score']
         self._graphs.clear()                       # captured steps point at the optimizer state tensors about to be replaced
@@ -597,6 +764,8 @@ class Trainer:
         if 'rowwise' in state and hasattr(self.model, 'load_fused_optimizer_state'):
             if self.rowwise_adam == 'exact':
                 self.model.load_fused_optimizer_state(state['rowwise'], adam='exact')
+            elif mine != 'adam':
+                self.model.load_fused_optimizer_state(state['rowwise'], opt=mine)
             else:
                 self.model.load_fused_optimizer_state(state['rowwise'])
 
@@ -623,7 +792,9 @@ class Trainer:
 
     def _fused_kw(self):
         """Keyword arguments of ``model.fused_train_step`` (optimizer_mode='rowwise')."""
-        kw = {'lr': self.learning_rate, 'weight_decay': self.weight_decay}
+        kw = {'opt': self.learner, 'lr': self.learning_rate, 'weight_decay': self.weight_decay}
+        if kw['opt'] == 'adagrad':
+            kw['eps'] = 1e-10                          # torch.optim.Adagrad's default (the steps' own default is Adam's 1e-8)
         if self.rowwise_adam == 'exact':
             kw['adam'] = 'exact'
         return kw
