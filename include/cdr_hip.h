@@ -244,6 +244,50 @@ int cdr_fullsort_neg_sqdist_topk_f32(void* stream, const float* user_e, int64_t 
                                      const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
                                      float* out_vals /* [U,k] */, int64_t* out_idx /* [U,k] */, void* workspace, size_t workspace_bytes);
 
+/* Rank of each ground-truth positive over the masked catalogue, without the [U, N] score matrix: what Recall / MRR / NDCG / Hit /
+ * Precision / MAP at any k and recbole's GAUC are computed from.  S is the matrix cdr_fullsort_scores_f32 (the neg_sqdist form:
+ * cdr_fullsort_neg_sqdist_f32 against the concatenated slabs) writes for the same operands.  A column is UNMASKED when it is not
+ * column 0 (with exclude_first_col), not in the user's history range (hist_indptr [U+1] / hist_cols, ascending inside a user's range,
+ * or both NULL) and its score is not NaN.  The positives are a CSR over the users: pos_indptr [U+1], pos_cols [P] ascending and
+ * distinct inside a user's range (anything else: undefined counts, never an access outside the buffers), P = pos_indptr[U], any
+ * number per user including none.  For positive p of user u at column c:
+ *   pos_score[p] = S[u, c], bit for bit;
+ *   gt[p]        = number of unmasked columns j with S[u, j] >  S[u, c];
+ *   eq[p]        = number of unmasked columns j with S[u, j] == S[u, c] (c itself included: eq >= 1);
+ *   eq_before[p] = number of those with j < c;
+ *   n_unmasked[u] = number of unmasked columns of user u.
+ * A positive that is itself masked, or whose score is NaN, gets gt = eq = eq_before = -1.  Its position in a top-k list that breaks
+ * ties towards the smaller column is 1 + gt + eq_before; its average rank is gt + (eq + 1) / 2.  Counts are added with integer
+ * atomics: bit-reproducible from run to run.  The scores are formed in column passes into the workspace by the launches the score
+ * entries use for the same columns, and counted there.  n0 + n1 < 2^31, U < 2^30; every pointer but slab0 / slab1 (one may be NULL
+ * with its n = 0), the history pair and col_sqnorm must be non-NULL, also when P = 0 (n_unmasked is then the only result); a bad
+ * argument or a workspace below *_workspace_bytes gets CDR_EINVAL with an error text and nothing is launched.
+ * Workspace: cdr_fullsort_rank_workspace_bytes(U, D, n0, n1, P); the neg_sqdist form adds ((4 * (U + n0 + n1) + 255) & ~255) bytes
+ * for the row norms (col_sqnorm: [n0 + n1] from cdr_row_sqnorm_f32 of the slabs, or NULL: computed into the workspace).            */
+int cdr_fullsort_rank_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int64_t P, size_t* bytes);
+int cdr_fullsort_rank_f32(void* stream, const float* user_e, int64_t U, int D,
+                          const float* slab0, int64_t n0, const float* slab1, int64_t n1,
+                          const int64_t* pos_indptr /* [U+1] */, const int64_t* pos_cols /* [P] */,
+                          const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                          float* pos_score /* [P] */, int32_t* gt, int32_t* eq, int32_t* eq_before /* [P] each */,
+                          int32_t* n_unmasked /* [U] */, void* workspace, size_t workspace_bytes);
+int cdr_fullsort_neg_sqdist_rank_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int64_t P, size_t* bytes);
+int cdr_fullsort_neg_sqdist_rank_f32(void* stream, const float* user_e, int64_t U, int D,
+                                     const float* slab0, int64_t n0, const float* slab1, int64_t n1, const float* col_sqnorm,
+                                     const int64_t* pos_indptr /* [U+1] */, const int64_t* pos_cols /* [P] */,
+                                     const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                                     float* pos_score /* [P] */, int32_t* gt, int32_t* eq, int32_t* eq_before /* [P] each */,
+                                     int32_t* n_unmasked /* [U] */, void* workspace, size_t workspace_bytes);
+/* The same counts over scores that are in memory: columns [col_off, col_off + N) of the catalogue as scores[U, N] with leading
+ * dimension ld >= N (the models whose score is not a contraction; one column pass of a larger matrix).  pos_score [P] is an INPUT
+ * here (the positives' scores, whichever pass holds them); the mask and pos_cols are in catalogue columns.  accumulate = 0 starts the
+ * counters (0, or -1 for a masked / NaN positive; n_unmasked = 0) and adds this block's counts, accumulate = 1 only adds: passes
+ * over disjoint column blocks in any order give the counts of the whole catalogue.  col_off + N < 2^31.                            */
+int cdr_rank_rows_f32(void* stream, const float* scores, int64_t ld, int64_t U, int64_t N, int64_t col_off,
+                      const int64_t* pos_indptr, const int64_t* pos_cols, const int64_t* hist_indptr, const int64_t* hist_cols,
+                      int exclude_first_col, const float* pos_score, int32_t* gt, int32_t* eq, int32_t* eq_before,
+                      int32_t* n_unmasked, int accumulate);
+
 /* ---- elementwise helpers used by the model mirrors --------------------------------------------------------- */
 /* d/dx of act given y = act(x): gx = gy * act'(y)  (tanh: 1-y^2, relu: y>0, sigmoid: y(1-y)) ; in place allowed */
 int cdr_act_bwd(void* stream, int act, const float* y, const float* gy, float* gx, int64_t n);

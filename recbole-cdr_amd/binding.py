@@ -244,6 +244,14 @@ _SIGNATURES = {
     'cdr_fullsort_neg_sqdist_topk_workspace_bytes': [_c_i64, _c_int, _c_i64, _c_i64, _c_int, _c_ptr],
     'cdr_fullsort_neg_sqdist_topk_f32': [_c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_int, _c_ptr, _c_ptr,
                                          _c_int, _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
+    'cdr_fullsort_rank_workspace_bytes': [_c_i64, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr],
+    'cdr_fullsort_rank_f32': [_c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int,
+                              _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
+    'cdr_fullsort_neg_sqdist_rank_workspace_bytes': [_c_i64, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr],
+    'cdr_fullsort_neg_sqdist_rank_f32': [_c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
+                                         _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
+    'cdr_rank_rows_f32': [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr,
+                          _c_ptr, _c_ptr, _c_int],
     'cdr_dedup_workspace_bytes': [_c_i64, _c_ptr],
     'cdr_dedup_sorted': [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_int, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
     'cdr_segsum_rows': [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr],

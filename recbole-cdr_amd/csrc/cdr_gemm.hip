@@ -1299,3 +1299,132 @@ extern "C" int cdr_fullsort_neg_sqdist_topk_f32(void* stream, const float* user_
     return fullsort_topk_seeded(__func__, topk_epi{rown, col_sqnorm ? col_sqnorm : coln}, stream, user_e, U, D, slab0, n0, slab1, n1, k, hist_indptr,
                                 hist_cols, exclude_first_col, out_vals, out_idx, workspace, lists);
 }
+
+// ---- rank of the ground-truth positives over the masked catalogue ------------------------------------------------------------------
+// What the evaluation metrics beyond a top-k list of <= 64 entries need (any k, MAP, GAUC) without the [U, N] matrix: the scores are formed
+// in column passes into the workspace staging by score_block -- the launches cdr_fullsort_scores_f32 (respectively
+// cdr_fullsort_neg_sqdist_f32) makes for the same columns: passes start at a multiple of 64 columns of their slab, so whole tiles and
+// the slab's tail fall to the same kernels, and the counted scores are the bits of S -- and counted by rank_rows_kernel (cdr_rank.h).  The
+// thresholds come from a first walk over the same passes (rank_gather_kernel picks pos_score out of the staging); a catalogue that fits
+// one pass is scored once.
+#include "cdr_rank.h"
+
+namespace {
+
+static int64_t rank_pass_cols(int64_t U) {
+    int64_t pass = (int64_t)(kTopkScoreBytes / sizeof(float)) / U / 64 * 64;
+    return pass < 64 ? 64 : pass;
+}
+
+static size_t rank_ws_bytes(int64_t U, const int64_t n[2]) {
+    const int64_t pass = rank_pass_cols(U);
+    int64_t cols = 0;
+    for (int i = 0; i < 2; ++i) {
+        const int64_t c = n[i] < pass ? n[i] : pass;
+        if (c > cols) cols = c;
+    }
+    return ((size_t)U * (size_t)cols * sizeof(float) + 255) & ~(size_t)255;
+}
+
+static int fullsort_rank_impl(const char* fn, const topk_epi& epi, hipStream_t s, const float* user_e, int64_t U, int D,
+                              const float* const slab[2], const int64_t n[2], const int64_t* pos_indptr, const int64_t* pos_cols,
+                              const topk_mask& mk, float* pos_score, int32_t* gt, int32_t* eq, int32_t* eq_before, int32_t* n_unmasked,
+                              float* sbuf) {
+    const int64_t pass = rank_pass_cols(U);
+    int64_t passes = 0;
+    for (int i = 0; i < 2; ++i) passes += (n[i] + pass - 1) / pass;
+    if (int rc = rank_init_launch(s, 0, U, pos_indptr, pos_cols, mk, pos_score, gt, eq, eq_before, n_unmasked)) return rc;
+    for (int walk = 0; walk < 2; ++walk) {              // walk 0: the thresholds; walk 1: the counts
+        if (walk == 1)
+            if (int rc = rank_init_launch(s, 1, U, pos_indptr, pos_cols, mk, pos_score, gt, eq, eq_before, n_unmasked)) return rc;
+        int64_t col_off = 0;
+        for (int i = 0; i < 2; ++i) {
+            for (int64_t c = 0; c < n[i]; c += pass) {
+                const int64_t cn = n[i] - c < pass ? n[i] - c : pass;
+                if (walk == 0 || passes > 1) {
+                    int rc = score_block(s, user_e, U, D, slab[i] + c * D, cn, sbuf, cn, epi.rown, epi.rown ? epi.coln + col_off + c : nullptr);
+                    if (rc) return rc;
+                }
+                int rc = walk == 0 ? rank_gather_launch(s, sbuf, cn, U, cn, col_off + c, pos_indptr, pos_cols, pos_score)
+                                   : rank_rows_launch(s, sbuf, cn, U, cn, col_off + c, pos_indptr, pos_cols, mk, pos_score, gt, eq, eq_before,
+                                                      n_unmasked);
+                if (rc) return rc;
+            }
+            col_off += n[i];
+        }
+    }
+    (void)fn;
+    return CDR_OK;
+}
+
+}  // namespace
+
+#define CDR_RANK_CHECK_COMMON()                                                                                         \
+    CDR_CHECK_ARG(user_e && workspace && U > 0 && U < ((int64_t)1 << 30) && D > 0);                                     \
+    CDR_CHECK_ARG((slab0 && n0 > 0) || (slab1 && n1 > 0));                                                              \
+    CDR_CHECK_ARG(pos_indptr && pos_cols && pos_score && gt && eq && eq_before && n_unmasked);                          \
+    CDR_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));                                                  \
+    const int64_t n[2] = {slab0 ? (n0 > 0 ? n0 : 0) : 0, slab1 ? (n1 > 0 ? n1 : 0) : 0};                                \
+    const float* const slab[2] = {slab0, slab1};                                                                        \
+    CDR_CHECK_ARG(n[0] + n[1] < ((int64_t)1 << 31))
+
+extern "C" int cdr_fullsort_rank_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int64_t P, size_t* bytes) {
+    CDR_CHECK_ARG(bytes && U > 0 && U < ((int64_t)1 << 30) && D > 0 && n0 >= 0 && n1 >= 0 && n0 + n1 > 0 && P >= 0);
+    const int64_t n[2] = {n0, n1};
+    *bytes = rank_ws_bytes(U, n);
+    return CDR_OK;
+}
+
+extern "C" int cdr_fullsort_rank_f32(void* stream, const float* user_e, int64_t U, int D, const float* slab0, int64_t n0,
+                                     const float* slab1, int64_t n1, const int64_t* pos_indptr, const int64_t* pos_cols,
+                                     const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col, float* pos_score,
+                                     int32_t* gt, int32_t* eq, int32_t* eq_before, int32_t* n_unmasked, void* workspace,
+                                     size_t workspace_bytes) {
+    CDR_RANK_CHECK_COMMON();
+    const size_t need = rank_ws_bytes(U, n);
+    if (workspace_bytes < need) { cdr_set_error("%s: workspace %zu < %zu bytes", __func__, workspace_bytes, need); return CDR_EINVAL; }
+    return fullsort_rank_impl(__func__, topk_epi{nullptr, nullptr}, (hipStream_t)stream, user_e, U, D, slab, n, pos_indptr, pos_cols,
+                              topk_mask{hist_indptr, hist_cols, exclude_first_col}, pos_score, gt, eq, eq_before, n_unmasked, (float*)workspace);
+}
+
+extern "C" int cdr_fullsort_neg_sqdist_rank_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int64_t P, size_t* bytes) {
+    CDR_CHECK_ARG(bytes && U > 0 && U < ((int64_t)1 << 30) && D > 0 && n0 >= 0 && n1 >= 0 && n0 + n1 > 0 && P >= 0);
+    const int64_t n[2] = {n0, n1};
+    *bytes = rank_ws_bytes(U, n) + sqdist_norm_bytes(U, n0 + n1);
+    return CDR_OK;
+}
+
+extern "C" int cdr_fullsort_neg_sqdist_rank_f32(void* stream, const float* user_e, int64_t U, int D, const float* slab0, int64_t n0,
+                                                const float* slab1, int64_t n1, const float* col_sqnorm, const int64_t* pos_indptr,
+                                                const int64_t* pos_cols, const int64_t* hist_indptr, const int64_t* hist_cols,
+                                                int exclude_first_col, float* pos_score, int32_t* gt, int32_t* eq, int32_t* eq_before,
+                                                int32_t* n_unmasked, void* workspace, size_t workspace_bytes) {
+    CDR_RANK_CHECK_COMMON();
+    const size_t staging = rank_ws_bytes(U, n), need = staging + sqdist_norm_bytes(U, n[0] + n[1]);
+    if (workspace_bytes < need) { cdr_set_error("%s: workspace %zu < %zu bytes", __func__, workspace_bytes, need); return CDR_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    float* rown = (float*)((char*)workspace + staging);
+    float* coln = rown + U;
+    if (int rc = row_sqnorm_launch(s, user_e, U, D, rown)) return rc;
+    if (!col_sqnorm) {
+        if (n[0] > 0) { if (int rc = row_sqnorm_launch(s, slab0, n[0], D, coln)) return rc; }
+        if (n[1] > 0) { if (int rc = row_sqnorm_launch(s, slab1, n[1], D, coln + n[0])) return rc; }
+    }
+    return fullsort_rank_impl(__func__, topk_epi{rown, col_sqnorm ? col_sqnorm : coln}, s, user_e, U, D, slab, n, pos_indptr, pos_cols,
+                              topk_mask{hist_indptr, hist_cols, exclude_first_col}, pos_score, gt, eq, eq_before, n_unmasked, (float*)workspace);
+}
+#undef CDR_RANK_CHECK_COMMON
+
+extern "C" int cdr_rank_rows_f32(void* stream, const float* scores, int64_t ld, int64_t U, int64_t N, int64_t col_off,
+                                 const int64_t* pos_indptr, const int64_t* pos_cols, const int64_t* hist_indptr, const int64_t* hist_cols,
+                                 int exclude_first_col, const float* pos_score, int32_t* gt, int32_t* eq, int32_t* eq_before,
+                                 int32_t* n_unmasked, int accumulate) {
+    CDR_CHECK_ARG(scores && U > 0 && N > 0 && ld >= N && col_off >= 0 && col_off + N < ((int64_t)1 << 31));
+    CDR_CHECK_ARG(pos_indptr && pos_cols && pos_score && gt && eq && eq_before && n_unmasked);
+    CDR_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));
+    hipStream_t s = (hipStream_t)stream;
+    const topk_mask mk{hist_indptr, hist_cols, exclude_first_col};
+    if (!accumulate)
+        if (int rc = rank_init_launch(s, 1, U, pos_indptr, pos_cols, mk, const_cast<float*>(pos_score), gt, eq, eq_before, n_unmasked)) return rc;
+    return rank_rows_launch(s, scores, ld, U, N, col_off, pos_indptr, pos_cols, mk, pos_score, gt, eq, eq_before, n_unmasked);
+}

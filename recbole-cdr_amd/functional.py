@@ -874,6 +874,96 @@ def fullsort_neg_sqdist_topk(user_e, slab0, slab1=None, k=10, hist_indptr=None, 
     return (vals[:U], idx[:U]) if rows != U else (vals, idx)
 
 
+def _rank_outputs(dev, U, P):
+    """(pos_score, gt, eq, eq_before, n_unmasked); one spare element so that P = 0 still hands the entries real buffers"""
+    return (torch.empty(P + 1, device=dev, dtype=torch.float32), torch.empty(P + 1, device=dev, dtype=torch.int32),
+            torch.empty(P + 1, device=dev, dtype=torch.int32), torch.empty(P + 1, device=dev, dtype=torch.int32),
+            torch.empty(U, device=dev, dtype=torch.int32))
+
+
+def _rank_positives(pos_indptr, pos_cols, U):
+    assert pos_indptr.dtype == torch.int64 and pos_cols.dtype == torch.int64 and pos_indptr.numel() == U + 1
+    P = pos_cols.numel()
+    return P, (pos_cols if P else pos_cols.new_zeros(1))
+
+
+def _fullsort_rank(entry, user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols, exclude_first_col, col_sqnorm):
+    _dev_check(user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols, col_sqnorm)
+    user_e = user_e.detach().contiguous()
+    U, D = user_e.shape
+    n0 = slab0.shape[0] if slab0 is not None else 0
+    n1 = slab1.shape[0] if slab1 is not None else 0
+    dev = user_e.device
+    P, cols = _rank_positives(pos_indptr, pos_cols, U)
+    need = ctypes.c_size_t(0)
+    B_._check(getattr(B_.load(), entry + '_workspace_bytes')(U, D, n0, n1, P, ctypes.byref(need)), entry + '_workspace_bytes')
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _topk_ws.get(key)                  # (the top-k forms': one per device and stream, it only grows)
+    if ws is None or ws.numel() < need.value:
+        ws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
+        _topk_ws[key] = ws
+    score, gt, eq, eqb, nun = _rank_outputs(dev, U, P)
+    head = (B_.stream(), B_.f32(user_e), U, D, B_.f32(slab0.detach()) if n0 else None, n0, B_.f32(slab1.detach()) if n1 else None, n1)
+    if entry == 'cdr_fullsort_neg_sqdist_rank':
+        if col_sqnorm is not None:
+            assert col_sqnorm.dtype == torch.float32 and col_sqnorm.numel() == n0 + n1
+        head = head + (B_.f32(col_sqnorm),)
+    B_.call(entry + '_f32', *head, B_.i64(pos_indptr), B_.i64(cols), B_.i64(hist_indptr), B_.i64(hist_cols),
+            1 if exclude_first_col else 0, B_.f32(score), B_.raw(gt), B_.raw(eq), B_.raw(eqb), B_.raw(nun), B_.raw(ws), ws.numel())
+    return score[:P], gt[:P], eq[:P], eqb[:P], nun
+
+
+def fullsort_rank(user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr=None, hist_cols=None, exclude_first_col=True):
+    """Rank of each ground-truth positive over the masked catalogue without the [U, N] matrix (cdr_fullsort_rank_f32).  The positives are
+    a CSR over the users (``pos_indptr`` [U+1], ``pos_cols`` [P] ascending and distinct inside a user's range), the mask is
+    ``fullsort_topk``'s.  Returns ``(pos_score [P] float32, gt, eq, eq_before [P] int32, n_unmasked [U] int32)``: ``pos_score`` bit-equal
+    to the positives' entries of ``fullsort_scores(user_e, slab0, slab1)``; the numbers of unmasked (not PAD, not history, not NaN)
+    columns scoring above / equal to the positive (itself included) / equal and left of it; the user's number of unmasked columns.  A
+    masked or NaN positive gets -1 three times.  Top-k position with ties to the smaller column: ``1 + gt + eq_before``; average rank:
+    ``gt + (eq + 1) / 2``."""
+    return _fullsort_rank('cdr_fullsort_rank', user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols, exclude_first_col, None)
+
+
+def fullsort_neg_sqdist_rank(user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr=None, hist_cols=None, exclude_first_col=True,
+                             col_sqnorm=None):
+    """``fullsort_rank`` over SSCDR's distances, ``fullsort_neg_sqdist(user_e, cat(slab0, slab1))`` (cdr_fullsort_neg_sqdist_rank_f32).
+    ``col_sqnorm``: ``row_sqnorm`` of the concatenated slabs when the caller keeps it; computed per call otherwise (the same bits)."""
+    return _fullsort_rank('cdr_fullsort_neg_sqdist_rank', user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols,
+                          exclude_first_col, col_sqnorm)
+
+
+def rank_rows(scores, pos_indptr, pos_cols, hist_indptr=None, hist_cols=None, exclude_first_col=True, pos_score=None, col_off=0, out=None,
+              accumulate=False):
+    """The counts of ``fullsort_rank`` over scores that are in memory (cdr_rank_rows_f32): ``scores`` [U, N] (rows may be strided:
+    ``scores.stride(0) >= N``) holds columns ``[col_off, col_off + N)`` of the catalogue; ``pos_cols`` and the mask are in catalogue
+    columns.  ``pos_score`` [P]: the positives' scores (default: gathered from ``scores``, which then has to hold every positive's
+    column).  ``out`` = the ``(gt, eq, eq_before, n_unmasked)`` of an earlier call with ``accumulate=True`` adds this block's counts to
+    them: passes over disjoint column blocks give the whole catalogue's counts.  Returns ``(pos_score, gt, eq, eq_before, n_unmasked)``."""
+    _dev_check(scores, pos_indptr, pos_cols, hist_indptr, hist_cols, pos_score)
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.stride(1) == 1
+    U, N = scores.shape
+    ld = scores.stride(0) if U > 1 else max(scores.stride(0), N)
+    assert ld >= N
+    dev = scores.device
+    P, cols = _rank_positives(pos_indptr, pos_cols, U)
+    if pos_score is None:
+        rows = torch.repeat_interleave(torch.arange(U, device=dev), pos_indptr[1:] - pos_indptr[:-1])
+        pos_score = scores[rows, pos_cols - col_off]
+    pos_score = pos_score.detach().contiguous()
+    assert pos_score.dtype == torch.float32 and pos_score.numel() == P
+    if out is None:
+        assert not accumulate, 'accumulate=True continues the counters of an earlier call: pass them as out'
+        _, gt, eq, eqb, nun = _rank_outputs(dev, U, P)
+    else:
+        gt, eq, eqb, nun = (t if t.numel() else t.new_zeros(1) for t in out)
+    # (as_strided views keep the rows' stride; the entry reads U rows of N floats, ld apart, from the first element)
+    B_._alive.append(scores)
+    B_.call('cdr_rank_rows_f32', B_.stream(), B_._c_ptr(scores.data_ptr()), ld, U, N, int(col_off), B_.i64(pos_indptr), B_.i64(cols),
+            B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(pos_score if P else pos_score.new_zeros(1)),
+            B_.raw(gt), B_.raw(eq), B_.raw(eqb), B_.raw(nun), 1 if accumulate else 0)
+    return pos_score, gt[:P], eq[:P], eqb[:P], nun
+
+
 # ---------------------------------------------------------------------------------------------------- CoNet pieces
 class GatherConcat2(Function):
     """cat([A[ida], B[idb]], dim=1) in one buffer (conet.py:106-111) with the dense scatter-add backward."""

@@ -170,6 +170,12 @@ class BiTGCF(CrossDomainRecommender):
         return F_.fullsort_scores(u, restore_item_e[:self.target_num_items]).view(-1)
 
     @torch.no_grad()
+    def _full_sort_operands(self, interaction):
+        """(user_e, slab0, slab1) of ``full_sort_predict``'s contraction (``full_sort_rank`` scores them in column passes)."""
+        restore_user_e, restore_item_e = self.get_restore_e()
+        return F_.gather_rows(restore_user_e, interaction[self.TARGET_USER_ID]), restore_item_e[:self.target_num_items], None
+
+    @torch.no_grad()
     def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
         """(values, columns) [U,k] of ``full_sort_predict`` after recbole's evaluation mask, without the [U, N] matrix."""
         restore_user_e, restore_item_e = self.get_restore_e()

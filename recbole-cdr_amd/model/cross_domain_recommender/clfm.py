@@ -173,6 +173,12 @@ class CLFM(RowwiseTraining, CrossDomainRecommender):
         return F_.fullsort_scores(fac, self.target_item_embedding.weight[:self.target_num_items]).view(-1)
 
     @torch.no_grad()
+    def _full_sort_operands(self, interaction):
+        """(user factors, slab0, slab1) of ``full_sort_predict``'s contraction (``full_sort_rank`` scores them in column passes)."""
+        user_e = F_.gather_rows(self.target_user_embedding.weight, interaction[self.TARGET_USER_ID])
+        return self._factors(user_e, 'target'), self.target_item_embedding.weight[:self.target_num_items], None
+
+    @torch.no_grad()
     def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
         """Evaluation without the [U, N] matrix: (values [U,k], columns [U,k]) of ``full_sort_predict`` after the evaluation mask (column 0
         and the per-user history columns, CSR with ascending columns), on the dot-product kernel's fused mask + top-k (F_.fullsort_topk;

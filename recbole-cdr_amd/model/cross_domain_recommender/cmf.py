@@ -122,6 +122,12 @@ class CMF(RowwiseTraining, CrossDomainRecommender):
         return score.view(-1)
 
     @torch.no_grad()
+    def _full_sort_operands(self, interaction):
+        """(user_e, slab0, slab1) of ``full_sort_predict``'s contraction (``full_sort_rank`` scores them in column passes)."""
+        user_e = F_.gather_rows(self.user_embedding.weight, interaction[self.TARGET_USER_ID])
+        return user_e, self.item_embedding.weight[:self.target_num_items], None
+
+    @torch.no_grad()
     def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
         """(values, columns) [U,k] of ``full_sort_predict`` after recbole's evaluation mask, without the [U, N] matrix."""
         user_e = F_.gather_rows(self.user_embedding.weight, interaction[self.TARGET_USER_ID])

@@ -292,6 +292,18 @@ class DCDCSR(RowwiseTraining, CrossDomainRecommender):
         return F_.fullsort_scores(user_e, I[:self.target_num_items])
 
     @torch.no_grad()
+    def _full_sort_operands(self, interaction):
+        """(user_e, slab0, slab1) of ``full_sort_predict``'s contraction in its three table cases (``full_sort_rank`` scores them in
+        column passes)."""
+        U, I, tag = self._tables()
+        user_e = F_.gather_rows(U, interaction[getattr(self, f'{tag}_USER_ID')])
+        if tag == 'SOURCE':
+            return user_e, I[:self.overlapped_num_items], I[self.target_num_items:]
+        if I is self.affine_embedding:
+            return user_e, I, None
+        return user_e, I[:self.target_num_items], None
+
+    @torch.no_grad()
     def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
         """Evaluation without the [U, N] matrix: (values [U,k], columns [U,k]) of ``full_sort_predict`` after the evaluation mask (column 0
         and the per-user history columns, CSR with ascending columns) -- the same three table cases, on the dot-product kernel's fused

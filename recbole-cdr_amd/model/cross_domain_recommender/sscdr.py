@@ -421,6 +421,18 @@ class SSCDR(RowwiseTraining, CrossDomainRecommender):
         s0, s1 = (cache['items'], None) if cache is not None else self._item_slabs()
         return self._full_sort_users(interaction), s0, s1
 
+    def _rank_distance_form(self):
+        return True
+
+    def _rank_col_sqnorm(self):
+        """``full_sort_rank``: the column norms of the cached item operand, formed once per evaluation bracket (None outside one)."""
+        cache = self._eval_item_cache()
+        if cache is None:
+            return None
+        if cache['sqnorm'] is None:
+            cache['sqnorm'] = F_.row_sqnorm(cache['items'])
+        return cache['sqnorm']
+
     @torch.no_grad()
     def full_sort_predict(self, interaction):
         ue, s0, s1 = self._full_sort_operands(interaction)

@@ -6,6 +6,7 @@ Same constructor contract ``(config, dataset)``, same attribute names, same ``se
 is not a dependency of this package.
 """
 import numpy as np
+import torch
 import torch.nn as nn
 from torch.nn.init import xavier_normal_, constant_
 
@@ -76,6 +77,65 @@ class CrossDomainRecommender(nn.Module):
 
     def full_sort_predict(self, interaction):
         raise NotImplementedError
+
+    # [U, N] floats one ``rank_rows`` pass may hold when the scores are not a contraction (64 M = 256 MB: the staging of the native passes)
+    RANK_ROWS_MAX_SCORES = 64 << 20
+
+    def _rank_distance_form(self):
+        """True when ``_full_sort_operands`` are scored by the distance (SSCDR), not the dot product."""
+        return False
+
+    def _rank_col_sqnorm(self):
+        return None
+
+    @torch.no_grad()
+    def full_sort_rank(self, interaction, pos_indptr, pos_cols, hist_indptr=None, hist_cols=None, predict_fallback=None):
+        """``(pos_score [P], gt, eq, eq_before [P] int32, n_unmasked [U] int32)`` of the ground-truth positives (a CSR over the
+        interaction's users, ascending distinct columns) over ``full_sort_predict`` after the evaluation mask (column 0 and the per-user
+        history CSR): the contract of ``functional.fullsort_rank``; what ``Trainer.evaluate`` derives any ``topk``, MAP and GAUC from.
+        A model whose score is a contraction (``_full_sort_operands``) never forms the [U, N] matrix; the others score chunks of users
+        with ``full_sort_predict`` -- ``predict_fallback(interaction, n_user)`` where that raises NotImplementedError -- and count with
+        ``functional.rank_rows``."""
+        from .. import functional as F_
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            raise NotImplementedError(f"{type(self).__name__}.full_sort_rank does not shard its tables: config['dist_group'] is not "
+                                      f"supported (one GPU)")
+        if hasattr(self, '_full_sort_operands'):
+            user_e, slab0, slab1 = self._full_sort_operands(interaction)
+            slab0 = slab0 if slab0 is not None and slab0.shape[0] else None
+            slab1 = slab1 if slab1 is not None and slab1.shape[0] else None
+            if self._rank_distance_form():
+                return F_.fullsort_neg_sqdist_rank(user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols,
+                                                   col_sqnorm=self._rank_col_sqnorm())
+            return F_.fullsort_rank(user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols)
+        n_user = len(interaction)
+        dev = pos_cols.device
+        P = pos_cols.numel()
+        score = torch.empty(P, device=dev, dtype=torch.float32)
+        out = tuple(torch.empty(n, device=dev, dtype=torch.int32) for n in (P, P, P, n_user))
+        counts = (pos_indptr[1:] - pos_indptr[:-1])
+        step = None
+        s = 0
+        while s < n_user:
+            e = n_user if step is None else min(s + step, n_user)
+            part = interaction if (s, e) == (0, n_user) else interaction[s:e]
+            try:
+                scores = self.full_sort_predict(part).view(e - s, -1)
+            except NotImplementedError:
+                if predict_fallback is None:
+                    raise
+                scores = predict_fallback(part, e - s)
+            if step is None and n_user * scores.shape[1] > self.RANK_ROWS_MAX_SCORES and n_user > 1:
+                step = max(self.RANK_ROWS_MAX_SCORES // scores.shape[1], 1)      # (this first block was too tall: redo it in chunks)
+                continue
+            scores = scores.float().contiguous()
+            p0, p1 = (int(pos_indptr[s]), int(pos_indptr[e])) if (s, e) != (0, n_user) else (0, P)
+            rows = torch.repeat_interleave(torch.arange(e - s, device=dev), counts[s:e])
+            score[p0:p1] = scores[rows, pos_cols[p0:p1]]
+            F_.rank_rows(scores, pos_indptr[s:e + 1].contiguous(), pos_cols, hist_indptr[s:e + 1].contiguous() if hist_indptr is not None
+                         else None, hist_cols, pos_score=score, out=(out[0], out[1], out[2], out[3][s:e]))
+            s = e
+        return (score,) + out
 
     def other_parameter(self):
         if hasattr(self, 'other_parameter_name'):

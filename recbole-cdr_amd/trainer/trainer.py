@@ -305,7 +305,115 @@ def early_stopping(value, best, cur_step, max_step, bigger=True):
     return best, cur_step, stop_flag, update_flag
 
 
+DEFAULT_METRICS = ('recall', 'hit', 'precision', 'mrr', 'ndcg')     # what evaluate returned before config['metrics'] was read
+TOPK_METRICS = ('recall', 'mrr', 'ndcg', 'hit', 'precision', 'map')  # keys name@k
+VALUE_METRICS = ('auc', 'mae', 'rmse', 'logloss')
+NON_ACCURACY_METRICS = ('itemcoverage', 'averagepopularity', 'shannonentropy', 'giniindex', 'tailpercentage')
+FUSED_TOPK_MAX = 64                   # the fused mask + top-k kernels keep a list in one wave: k <= 64
+
+
+def resolve_metrics(config):
+    """config['metrics'] as recbole reads it (a name or a list of names, any letter case) -> tuple of lower-case names, or None when the
+    key is absent (evaluate then returns what it always did).  Refused here, before anything is built: recbole's value metrics (they need
+    the labeled evaluation mode), its non-accuracy metrics (they need the training set's item counts), unknown names."""
+    if 'metrics' not in config or config['metrics'] is None:
+        return None
+    names = config['metrics']
+    names = [names] if isinstance(names, str) else list(names)
+    out = []
+    for n in names:
+        m = str(n).lower()
+        if m in VALUE_METRICS:
+            raise ValueError(f"metrics: {n!r} is a value metric: it needs recbole's labeled evaluation mode, which this trainer does not "
+                             f"have (full-sort ranking only)")
+        if m in NON_ACCURACY_METRICS:
+            raise ValueError(f"metrics: {n!r} is a non-accuracy metric: it needs the training set's item counts, which evaluate() is not "
+                             f"given")
+        if m not in TOPK_METRICS and m != 'gauc':
+            raise ValueError(f"metrics: unknown metric {n!r}; supported: {', '.join(TOPK_METRICS)} (keys name@k) and gauc")
+        if m not in out:
+            out.append(m)
+    if not out:
+        raise ValueError('metrics: the list is empty')
+    return tuple(out)
+
+
+def resolve_eval_route(config, metrics):
+    route = config['eval_route'] if 'eval_route' in config and config['eval_route'] is not None else 'auto'
+    if route not in ('auto', 'topk', 'rank'):
+        raise ValueError(f"eval_route must be 'auto', 'topk' or 'rank', got {route!r}")
+    if route == 'topk' and metrics is not None and 'gauc' in metrics:
+        raise ValueError("eval_route='topk' cannot answer gauc: a top-k list does not hold the rank of every positive over the whole "
+                         "catalogue; use eval_route='rank' or 'auto'")
+    return route
+
+
+def metrics_from_hits(hit, n_pos, topk, names=DEFAULT_METRICS):
+    """{name@k: value} from the hit matrix [U, kmax] (hit[u, j] = 1 where position j of user u's ranking is a ground-truth positive) and
+    the positives per user ``n_pos`` [U] (clamped to >= 1 by the caller): recbole's Recall / Hit / Precision / MRR / NDCG / MAP, averaged
+    over the users.  The one copy of this arithmetic: both evaluation routes end here."""
+    kmax = hit.shape[1]
+    result = {}
+    ranks = torch.arange(1, kmax + 1, device=hit.device, dtype=torch.float32)
+    for k in topk:
+        h = hit[:, :k]
+        for name in names:
+            if name == 'recall':
+                value = (h.sum(1) / n_pos).mean()
+            elif name == 'hit':
+                value = (h.sum(1) > 0).float().mean()
+            elif name == 'precision':
+                value = (h.sum(1) / k).mean()
+            elif name == 'mrr':
+                value = (h * (1.0 / ranks[:k])).max(1).values.mean()
+            elif name == 'ndcg':
+                dcg = (h / torch.log2(ranks[:k] + 1)).sum(1)
+                ideal = torch.cumsum(1.0 / torch.log2(ranks[:k] + 1), 0)
+                idcg = ideal[(n_pos.clamp(max=k).long() - 1)]
+                value = (dcg / idcg).mean()
+            elif name == 'map':
+                # recbole MAP: the mean of precision@j over the hit positions j <= k, divided by min(n_pos, k)
+                pre = torch.cumsum(h, 1) / ranks[:k]
+                value = ((pre * h).sum(1) / n_pos.clamp(max=k)).mean()
+            else:
+                continue                                   # (gauc has no @k: gauc_from_counts)
+            result[f'{name}@{k}'] = float(value)
+    return result
+
+
+def gauc_from_counts(pos_len, user_len, rank_sum):
+    """recbole's GAUC in float64 from per-user integers: ``pos_len`` positives, ``user_len`` unmasked items (positives included),
+    ``rank_sum`` = the sum of the positives' average ranks gt + (eq + 1) / 2 (descending order, 1 = best, ties share the mean position).
+    pair = (user_len + 1) pos_len - pos_len (pos_len + 1) / 2 - rank_sum counts the (positive, negative) pairs in the right order, ties
+    half; auc_u = pair / (neg pos_len); users without positives or without negatives are dropped; the mean is pos_len-weighted."""
+    pos_len, user_len, rank_sum = pos_len.double(), user_len.double(), rank_sum.double()
+    neg = user_len - pos_len
+    keep = (pos_len > 0) & (neg > 0)
+    if not bool(keep.any()):
+        return float('nan')
+    pos_len, neg, user_len, rank_sum = pos_len[keep], neg[keep], user_len[keep], rank_sum[keep]
+    pair = (user_len + 1) * pos_len - pos_len * (pos_len + 1) / 2 - rank_sum
+    return float((pair / (neg * pos_len) * pos_len).sum() / pos_len.sum())
+
+
+def rank_counts_reference(scores, pos_rows, pos_cols):
+    """The counts of ``functional.fullsort_rank`` in plain torch over a materialised, already masked matrix (masked entries NaN): what the
+    trainer uses where there is no device to run the kernel on (``device: cpu``)."""
+    valid = ~torch.isnan(scores)
+    t = scores[pos_rows, pos_cols]
+    rows, ok = scores[pos_rows], valid[pos_rows]
+    col = torch.arange(scores.shape[1], device=scores.device).unsqueeze(0)
+    gt = ((rows > t.unsqueeze(1)) & ok).sum(1)
+    same = (rows == t.unsqueeze(1)) & ok
+    eq, eqb = same.sum(1), (same & (col < pos_cols.unsqueeze(1))).sum(1)
+    bad = torch.isnan(t)
+    gt, eq, eqb = (torch.where(bad, torch.full_like(x, -1), x).to(torch.int32) for x in (gt, eq, eqb))
+    return t, gt, eq, eqb, valid.sum(1).to(torch.int32)
+
+
 class Trainer:
+    metrics = None                    # (class defaults: objects built without __init__ evaluate as before)
+    eval_route = 'auto'
     learner = 'adam'                  # (class default, as rowwise_adam below)
     rowwise_adam = 'lazy'             # (class default: loops driven on objects built without __init__ keep the lazy row-wise Adam)
 
@@ -319,6 +427,11 @@ class Trainer:
         self.valid_metric = (config['valid_metric'] if 'valid_metric' in config else 'MRR@10').lower()
         self.valid_metric_bigger = config['valid_metric_bigger'] if 'valid_metric_bigger' in config else True
         self.topk = config['topk'] if 'topk' in config else [10]
+        # config['metrics'] (absent: recall / hit / precision / mrr / ndcg, as always) and config['eval_route']: 'auto' keeps the model's
+        # mask + top-k route whenever it can answer (no gauc, and max(topk) <= 64 or the route is unfused), 'rank' derives every metric
+        # from the rank of each positive over the masked catalogue (model.full_sort_rank: any k, MAP, GAUC), 'topk' insists on the lists
+        self.metrics = resolve_metrics(config)
+        self.eval_route = resolve_eval_route(config, self.metrics)
         self.device = config['device']
         self.weight_decay = config['weight_decay'] if 'weight_decay' in config else 0.0
         self.start_epoch, self.cur_step = 0, 0
@@ -641,7 +754,8 @@ class Trainer:
     @torch.no_grad()
     def evaluate(self, eval_data):
         """eval_data yields (interaction, history_index (rows, cols) or None, positive_u, positive_i) like recbole's
-        FullSortEvalDataLoader; returns {metric@k: value} for recall / mrr / ndcg / hit / precision."""
+        FullSortEvalDataLoader; returns {metric@k: value} for config['metrics'] (default recall / mrr / ndcg / hit / precision; also map, and
+        gauc under the key 'gauc') at every k of config['topk']."""
         self._fused_sync()
         self.model.eval()
         kmax = max(self.topk)
@@ -680,6 +794,9 @@ class Trainer:
         return torch.cat(out).view(n_user, N).float()
 
     def _evaluate_batches(self, eval_data, fused, kmax):
+        names = self.metrics if self.metrics is not None else DEFAULT_METRICS
+        if self._takes_rank_route(fused, kmax):
+            return self._evaluate_batches_by_rank(eval_data, kmax, names)
         hits, pos_len = [], []
         for interaction, history_index, positive_u, positive_i in eval_data:
             interaction = interaction.to(self.device)
@@ -700,21 +817,83 @@ class Trainer:
             pos[positive_u, positive_i] = True
             hits.append(torch.gather(pos, 1, topk_idx).float())
             pos_len.append(pos.sum(1).float())
-        hit = torch.cat(hits)
-        n_pos = torch.cat(pos_len).clamp(min=1)
-        result = {}
-        ranks = torch.arange(1, kmax + 1, device=hit.device, dtype=torch.float32)
-        for k in self.topk:
-            h = hit[:, :k]
-            result[f'recall@{k}'] = float((h.sum(1) / n_pos).mean())
-            result[f'hit@{k}'] = float((h.sum(1) > 0).float().mean())
-            result[f'precision@{k}'] = float((h.sum(1) / k).mean())
-            first = (h * (1.0 / ranks[:k])).max(1).values
-            result[f'mrr@{k}'] = float(first.mean())
-            dcg = (h / torch.log2(ranks[:k] + 1)).sum(1)
-            ideal = torch.cumsum(1.0 / torch.log2(ranks[:k] + 1), 0)
-            idcg = ideal[(n_pos.clamp(max=k).long() - 1)]
-            result[f'ndcg@{k}'] = float((dcg / idcg).mean())
+        return metrics_from_hits(torch.cat(hits), torch.cat(pos_len).clamp(min=1), self.topk, names)
+
+    def _takes_rank_route(self, fused, kmax):
+        gauc = self.metrics is not None and 'gauc' in self.metrics
+        if self.eval_route == 'rank':
+            return True
+        if self.eval_route == 'topk':
+            if fused and kmax > FUSED_TOPK_MAX:
+                raise ValueError(f"eval_route='topk': the fused mask + top-k holds k <= {FUSED_TOPK_MAX}, topk asks for {kmax}; use "
+                                 f"eval_route='rank' or 'auto', or fused_topk=False")
+            return False
+        return gauc or (fused and kmax > FUSED_TOPK_MAX)
+
+    @staticmethod
+    def _csr(rows, cols, n_user):
+        """(indptr [n_user + 1], cols ascending and distinct inside each user's range) of (row, column) pairs, by one sort of the keys"""
+        span = int(cols.max()) + 1 if cols.numel() else 1
+        key = torch.unique(rows * span + cols)                       # (sorted)
+        indptr = torch.zeros(n_user + 1, device=rows.device, dtype=torch.int64)
+        indptr[1:] = torch.cumsum(torch.bincount(key // span, minlength=n_user), 0)
+        return indptr, (key % span).contiguous()
+
+    def _rank_counts(self, interaction, n_user, history_index, positive_u, positive_i):
+        """(user of each positive [P], gt, eq, eq_before [P], n_unmasked [U], positives per user [U]) of one batch: the model's
+        ``full_sort_rank`` on a GPU; a torch restatement over the materialised matrix where there is none (plumbing, as the unfused
+        route)."""
+        dev = self.device
+        pu = torch.as_tensor(positive_u, device=dev, dtype=torch.int64)
+        pi = torch.as_tensor(positive_i, device=dev, dtype=torch.int64)
+        pindptr, pcols = self._csr(pu, pi, n_user)
+        npos = pindptr[1:] - pindptr[:-1]
+        prow = torch.repeat_interleave(torch.arange(n_user, device=dev), npos)
+        hindptr = hcols = hrows = None
+        if history_index is not None:
+            hr, hc = (torch.as_tensor(t, device=dev, dtype=torch.int64) for t in history_index)
+            if hc.numel():
+                hindptr, hcols = self._csr(hr, hc, n_user)
+                hrows = hr
+        if torch.device(dev).type == 'cuda':
+            _score, gt, eq, eqb, nun = self.model.full_sort_rank(interaction, pindptr, pcols, hist_indptr=hindptr, hist_cols=hcols,
+                                                                 predict_fallback=self._predict_all_pairs)
+        else:
+            try:
+                scores = self.model.full_sort_predict(interaction).view(n_user, -1).float().clone()
+            except NotImplementedError:
+                scores = self._predict_all_pairs(interaction, n_user)
+            scores[:, 0] = float('nan')
+            if hrows is not None:
+                scores[history_index] = float('nan')
+            _score, gt, eq, eqb, nun = rank_counts_reference(scores, prow, pcols)
+        if bool((gt < 0).any()):
+            p = int(torch.nonzero(gt < 0)[0])
+            raise ValueError(f'evaluate: the positive item {int(pcols[p])} of user row {int(prow[p])} of this batch is masked (PAD column or '
+                             f'in the user\'s history) or has a NaN score: the rank route does not rank such a positive')
+        return prow, gt, eq, eqb, nun, npos
+
+    def _evaluate_batches_by_rank(self, eval_data, kmax, names):
+        """Every metric from the rank of each positive over the masked catalogue: a positive at top-k position r = 1 + gt + eq_before
+        (ties to the smaller column) is a hit at position r of the list for every k >= r -- the same hit matrix the top-k route builds,
+        for any kmax; GAUC from the average ranks gt + (eq + 1) / 2."""
+        hits, pos_len, user_len, rank_sum = [], [], [], []
+        for interaction, history_index, positive_u, positive_i in eval_data:
+            interaction = interaction.to(self.device)
+            n_user = len(interaction)
+            prow, gt, eq, eqb, nun, npos = self._rank_counts(interaction, n_user, history_index, positive_u, positive_i)
+            at = gt.long() + eqb.long()
+            hit = torch.zeros(n_user, kmax, device=gt.device, dtype=torch.float32)
+            sel = at < kmax
+            hit[prow[sel], at[sel]] = 1.0
+            hits.append(hit); pos_len.append(npos)
+            user_len.append(nun.long())
+            rank_sum.append(torch.zeros(n_user, device=gt.device, dtype=torch.float64).index_add_(
+                0, prow, gt.double() + (eq.double() + 1) / 2))
+        n_pos = torch.cat(pos_len)
+        result = metrics_from_hits(torch.cat(hits), n_pos.float().clamp(min=1), self.topk, names)
+        if 'gauc' in names:
+            result['gauc'] = gauc_from_counts(n_pos, torch.cat(user_len), torch.cat(rank_sum))
         return result
 
     def save_checkpoint(self, path, epoch=None):
