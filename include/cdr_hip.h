@@ -288,6 +288,32 @@ int cdr_rank_rows_f32(void* stream, const float* scores, int64_t ld, int64_t U, 
                       int exclude_first_col, const float* pos_score, int32_t* gt, int32_t* eq, int32_t* eq_before,
                       int32_t* n_unmasked, int accumulate);
 
+/* Sampled-candidate evaluation (eval_args mode uniN / popN): what recbole_cdr/data/utils.py:149-151 hands to recbole's
+ * NegSampleEvalDataLoader and Trainer._neg_sample_batch_eval (third-party) -- predict on every expanded (user, candidate) pair, scattered
+ * into a [U, tot_item_num] matrix of -inf -- without the pairs and without the matrix.  The candidates of U users are a CSR: cand_indptr
+ * [U+1], cand_cols [C] ascending and distinct inside a user's range, C = cand_indptr[U]; cand_row [C] is the user row of each entry.
+ * Columns address the rows of slab0 [n0, D] followed by slab1 [n1, D] (one may be NULL with its n = 0), as in cdr_fullsort_scores_f32;
+ * n0 + n1 < 2^31.  Row and column values are not checked.
+ *   form 0: scores[q] = sum_d user_e[cand_row[q], d] * item(cand_cols[q])[d]
+ *   form 1: scores[q] = -sum_d (user_e[cand_row[q], d] - item(cand_cols[q])[d])^2      (the distance as sscdr.py:127-128 forms it)
+ * One launch, flat over the candidates; 16-byte loads when D % 4 == 0, 4-byte loads otherwise.  U = 0 or C = 0: nothing is launched. */
+int cdr_candidate_scores_f32(void* stream, const float* user_e, int64_t U, int D,
+                             const float* slab0, int64_t n0, const float* slab1, int64_t n1,
+                             const int64_t* cand_row /* [C] */, const int64_t* cand_cols /* [C] */, int64_t C, int form,
+                             float* scores /* [C] */);
+/* The counts of cdr_rank_rows_f32 over those ragged rows.  The positives are a CSR over the same users (pos_indptr [U+1], pos_cols [P]).
+ * For positive p of user u at column c, with t = the score of c in u's candidate range (binary search):
+ *   pos_score[p] = t, bit for bit;  gt / eq / eq_before[p] = the number of u's candidates scoring above t / equal to t (c itself
+ *   included) / equal to t at a smaller column;  n_cand[u] = the number of u's candidates whose score is not NaN (written for every
+ *   user, with or without positives).
+ * A NaN candidate is counted nowhere.  A positive that is absent from its user's range, or whose score is NaN, gets gt = eq = eq_before
+ * = -1 and pos_score = NaN.  Integer atomics: bit-reproducible.  One workgroup per (user, block of 8,192 candidates).  A NULL output is
+ * CDR_EINVAL before anything is launched; U = 0, C = 0 or P = 0: nothing is launched and no output is written.  U < 2^30.            */
+int cdr_candidate_rank_f32(void* stream, int64_t U, const int64_t* cand_indptr /* [U+1] */, const int64_t* cand_cols /* [C] */,
+                           const float* scores /* [C] */, int64_t C, const int64_t* pos_indptr /* [U+1] */,
+                           const int64_t* pos_cols /* [P] */, int64_t P, float* pos_score /* [P] */,
+                           int32_t* gt, int32_t* eq, int32_t* eq_before /* [P] each */, int32_t* n_cand /* [U] */);
+
 /* ---- elementwise helpers used by the model mirrors --------------------------------------------------------- */
 /* d/dx of act given y = act(x): gx = gy * act'(y)  (tanh: 1-y^2, relu: y>0, sigmoid: y(1-y)) ; in place allowed */
 int cdr_act_bwd(void* stream, int act, const float* y, const float* gy, float* gx, int64_t n);

@@ -9,6 +9,9 @@
 // the user's ascending history that falls into the block (two binary searches per workgroup, not one per column); the positives are taken
 // kRankBatch at a time with their thresholds in registers, so LDS holds the same few hundred bytes whatever the user's number of
 // positives is.  A NaN threshold (padding, masked or NaN positives) compares false against everything and counts nothing.
+//
+// The walk itself (rank_walk) takes its scores through a small source type, so the ragged candidate rows of sampled evaluation
+// (cdr_candidate.hip: a flat score list with its column list, nothing masked) are counted by the same code as the matrix's rows.
 #pragma once
 #include "cdr_common.h"
 #include "cdr_topk.h"
@@ -64,6 +67,89 @@ __global__ __launch_bounds__(256) void rank_gather_kernel(const float* __restric
     }
 }
 
+// Where the walk below takes a block's scores from.  The matrix form: row `row` of the score matrix, columns [c0, c1) of this pass, the
+// evaluation mask as the block's bitmap.
+struct rank_src_rows {
+    const float* __restrict__ row;
+    const unsigned* maskw;
+    int64_t c0, col_off;
+    topk_mask mk;
+    __device__ __forceinline__ float value(int64_t c) const {
+        const int lc = (int)(c - c0);
+        float v = row[c];
+        if ((maskw[lc >> 5] >> (lc & 31)) & 1u) v = __int_as_float(0x7fc00000);
+        return v;
+    }
+    __device__ __forceinline__ int col(int64_t c) const { return (int)(col_off + c); }
+    __device__ __forceinline__ bool hidden(int64_t u, int c) const { return topk_masked(mk, u, c); }
+};
+
+// The walk of one workgroup (256 threads) over the entries [c0, c1) of `src` for the positives [p0, p1) of user u: the positives are taken
+// kRankBatch at a time with their thresholds in registers; the counts of a batch are joined in LDS and ADDED to gt / eq / eqb, the number
+// of non-NaN entries (first batch only) to n_unmasked[u].  thr_s, col_s [kRankBatch] and cnt [3 kRankBatch + 1] are the caller's LDS.
+template <class Src>
+__device__ __forceinline__ void rank_walk(const Src& src, int64_t u, int64_t c0, int64_t c1, int64_t p0, int64_t p1,
+                                          const int64_t* __restrict__ pos_cols, const float* __restrict__ pos_score, int* __restrict__ gt,
+                                          int* __restrict__ eq, int* __restrict__ eqb, int* __restrict__ n_unmasked, float* thr_s, int* col_s,
+                                          int* cnt) {
+    const int tid = threadIdx.x;
+    bool first = true;                                               // a user without positives still gets n_unmasked
+    for (int64_t pb = p0; first || pb < p1; pb += kRankBatch) {
+        __syncthreads();                                             // the mask stands; the last batch's counters were read
+        if (tid < kRankBatch) {
+            const int64_t p = pb + tid;
+            float t = __int_as_float(0x7fc00000);
+            int64_t c = -1;
+            if (p < p1) {
+                c = pos_cols[p];
+                t = pos_score[p];
+                if (c < 0 || c >= ((int64_t)1 << 31) || src.hidden(u, (int)c)) t = __int_as_float(0x7fc00000);
+            }
+            thr_s[tid] = t;
+            col_s[tid] = (int)c;
+        }
+        if (tid < 3 * kRankBatch + 1) cnt[tid] = 0;
+        __syncthreads();
+        float t[kRankBatch];
+        int pc[kRankBatch], g[kRankBatch], e[kRankBatch], b[kRankBatch];
+#pragma unroll
+        for (int j = 0; j < kRankBatch; ++j) { t[j] = thr_s[j]; pc[j] = col_s[j]; g[j] = e[j] = b[j] = 0; }
+        int nu = 0;
+        for (int64_t c = c0 + tid; c < c1; c += 256) {
+            const float v = src.value(c);
+            nu += v == v ? 1 : 0;
+            bool any_eq = false;
+#pragma unroll
+            for (int j = 0; j < kRankBatch; ++j) { g[j] += v > t[j] ? 1 : 0; any_eq |= v == t[j]; }
+            if (any_eq) {
+                const int col = src.col(c);
+#pragma unroll
+                for (int j = 0; j < kRankBatch; ++j) {
+                    const bool q = v == t[j];
+                    e[j] += q ? 1 : 0;
+                    b[j] += q && col < pc[j] ? 1 : 0;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kRankBatch; ++j) {
+            if (g[j]) atomicAdd(&cnt[3 * j], g[j]);
+            if (e[j]) atomicAdd(&cnt[3 * j + 1], e[j]);
+            if (b[j]) atomicAdd(&cnt[3 * j + 2], b[j]);
+        }
+        if (first && nu) atomicAdd(&cnt[3 * kRankBatch], nu);
+        __syncthreads();
+        if (tid < kRankBatch && pb + tid < p1) {
+            const int64_t p = pb + tid;
+            if (cnt[3 * tid]) atomicAdd(&gt[p], cnt[3 * tid]);
+            if (cnt[3 * tid + 1]) atomicAdd(&eq[p], cnt[3 * tid + 1]);
+            if (cnt[3 * tid + 2]) atomicAdd(&eqb[p], cnt[3 * tid + 2]);
+        }
+        if (first && tid == 0 && cnt[3 * kRankBatch]) atomicAdd(&n_unmasked[u], cnt[3 * kRankBatch]);
+        first = false;
+    }
+}
+
 __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict__ scores, int64_t ld, int64_t U, int64_t n, int64_t col_off,
                                                         const int64_t* __restrict__ pos_indptr, const int64_t* __restrict__ pos_cols,
                                                         topk_mask mk, const float* __restrict__ pos_score, int* __restrict__ gt,
@@ -78,7 +164,6 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict_
         const int64_t u = w / n_chunks;
         const int64_t c0 = (w % n_chunks) * kRankCols, c1 = c0 + kRankCols < n ? c0 + kRankCols : n;
         const int64_t g0 = col_off + c0, g1 = col_off + c1;               // the block's global columns
-        const float* row = scores + u * ld;
         __syncthreads();                                                 // the previous block's LDS reads are over
         for (int i = tid; i < kRankMaskWords; i += 256) maskw[i] = 0u;
         __syncthreads();
@@ -92,64 +177,8 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict_
                 atomicOr(&maskw[(c - g0) >> 5], 1u << ((c - g0) & 31));
             }
         }
-        const int64_t p0 = pos_indptr[u], p1 = pos_indptr[u + 1];
-        bool first = true;                                               // a user without positives still gets n_unmasked
-        for (int64_t pb = p0; first || pb < p1; pb += kRankBatch) {
-            __syncthreads();                                             // the mask stands; the last batch's counters were read
-            if (tid < kRankBatch) {
-                const int64_t p = pb + tid;
-                float t = __int_as_float(0x7fc00000);
-                int64_t c = -1;
-                if (p < p1) {
-                    c = pos_cols[p];
-                    t = pos_score[p];
-                    if (c < 0 || c >= ((int64_t)1 << 31) || topk_masked(mk, u, (int)c)) t = __int_as_float(0x7fc00000);
-                }
-                thr_s[tid] = t;
-                col_s[tid] = (int)c;
-            }
-            if (tid < 3 * kRankBatch + 1) cnt[tid] = 0;
-            __syncthreads();
-            float t[kRankBatch];
-            int pc[kRankBatch], g[kRankBatch], e[kRankBatch], b[kRankBatch];
-#pragma unroll
-            for (int j = 0; j < kRankBatch; ++j) { t[j] = thr_s[j]; pc[j] = col_s[j]; g[j] = e[j] = b[j] = 0; }
-            int nu = 0;
-            for (int64_t c = c0 + tid; c < c1; c += 256) {
-                const int lc = (int)(c - c0);
-                float v = row[c];
-                if ((maskw[lc >> 5] >> (lc & 31)) & 1u) v = __int_as_float(0x7fc00000);
-                nu += v == v ? 1 : 0;
-                bool any_eq = false;
-#pragma unroll
-                for (int j = 0; j < kRankBatch; ++j) { g[j] += v > t[j] ? 1 : 0; any_eq |= v == t[j]; }
-                if (any_eq) {
-                    const int col = (int)(col_off + c);
-#pragma unroll
-                    for (int j = 0; j < kRankBatch; ++j) {
-                        const bool q = v == t[j];
-                        e[j] += q ? 1 : 0;
-                        b[j] += q && col < pc[j] ? 1 : 0;
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < kRankBatch; ++j) {
-                if (g[j]) atomicAdd(&cnt[3 * j], g[j]);
-                if (e[j]) atomicAdd(&cnt[3 * j + 1], e[j]);
-                if (b[j]) atomicAdd(&cnt[3 * j + 2], b[j]);
-            }
-            if (first && nu) atomicAdd(&cnt[3 * kRankBatch], nu);
-            __syncthreads();
-            if (tid < kRankBatch && pb + tid < p1) {
-                const int64_t p = pb + tid;
-                if (cnt[3 * tid]) atomicAdd(&gt[p], cnt[3 * tid]);
-                if (cnt[3 * tid + 1]) atomicAdd(&eq[p], cnt[3 * tid + 1]);
-                if (cnt[3 * tid + 2]) atomicAdd(&eqb[p], cnt[3 * tid + 2]);
-            }
-            if (first && tid == 0 && cnt[3 * kRankBatch]) atomicAdd(&n_unmasked[u], cnt[3 * kRankBatch]);
-            first = false;
-        }
+        rank_walk(rank_src_rows{scores + u * ld, maskw, c0, col_off, mk}, u, c0, c1, pos_indptr[u], pos_indptr[u + 1], pos_cols, pos_score, gt,
+                  eq, eqb, n_unmasked, thr_s, col_s, cnt);
     }
 }
 

@@ -288,3 +288,136 @@ class FullSortEvalLoader:
             e0, e1, h0, h1 = self._ev_ptr[b], self._ev_ptr[b + 1], self._hi_ptr[b], self._hi_ptr[b + 1]
             yield (Interaction({self.uid_field: us}), (self._hi[0][h0:h1], self._hi[1][h0:h1]),
                    self._ev[0][e0:e1], self._ev[1][e0:e1])
+
+
+class NegSampleEvalLoader:
+    """Sampled-candidate evaluation batches: recbole 1.0.1's ``NegSampleEvalDataLoader`` with strategy ``'by'`` (third-party; what
+    recbole_cdr/data/utils.py:131-153 returns for ``eval_args: {mode: uniN | popN}``) without the pair expansion.
+
+    Evaluated users: the distinct users of ``eval_pairs``, ascending; a user's positives: its distinct items.  On every pass over the
+    loader each positive ``p`` of user ``u`` draws ``sample_by`` negatives, ``sampler(users_of_positives [P], items [P], sample_by)`` ->
+    k-major ``[P * sample_by]`` (the ``sampler.DeviceNegSampler`` call; any callable of that shape will do, on any device).  A user's
+    candidate set is its positives together with ALL of its negatives as DISTINCT items -- the reference scatters the scores into a row of
+    the [U, N] matrix, so a negative drawn twice is one column.  ``resample=True`` is recbole's behaviour; ``False`` draws once and reuses
+    the candidates on later passes, so that validation curves are comparable between epochs.
+
+    Yields ``(Interaction{uid_field: users [U]}, (cand_indptr [U+1], cand_cols [C]), positive_u [P], positive_i [P])``: the candidates as
+    a CSR over the batch's users, ascending and distinct inside a user's range (one device sort of ``user_row * span + item`` keys);
+    ``positive_u`` are batch rows.  That is the information of recbole's ``(interaction [C], row_idx, positive_u, positive_i)``;
+    ``expand(batch)`` returns that form.  ``eval_mode = 'sampled'`` is what ``Trainer.evaluate`` dispatches on.
+
+    Batch cut: recbole's rule by default -- the largest number of users whose ``P_u * (1 + sample_by)``, taken in descending order, fit
+    into ``eval_batch_size``, at least one -- or ``users_per_batch`` / ``rebatch(n)`` as on ``FullSortEvalLoader``; per-user results do
+    not depend on the cut.
+
+    Precondition: the sampler's used pairs must include the evaluated pairs themselves (recbole's evaluation samplers use train + valid,
+    then + test); otherwise a drawn negative can coincide with a positive, and the user's set is one candidate short."""
+
+    eval_mode = 'sampled'
+
+    def __init__(self, uid_field, iid_field, eval_pairs, sampler, sample_by, eval_batch_size, device, users_per_batch=None, resample=True):
+        import numpy as np
+        self.uid_field, self.iid_field, self.device = uid_field, iid_field, device
+        self.sampler, self.sample_by, self.resample = sampler, int(sample_by), bool(resample)
+        if self.sample_by < 1:
+            raise ValueError(f'sample_by must be a positive integer, got {sample_by!r}')
+        ev_t = (torch.as_tensor(np.asarray(eval_pairs, dtype=np.int64) if not torch.is_tensor(eval_pairs) else eval_pairs).to(device)
+                .reshape(-1, 2))
+        mul = (int(ev_t[:, 1].max()) if ev_t.numel() else 0) + 1
+        ev_key = torch.unique(ev_t[:, 0] * mul + ev_t[:, 1])                              # sorted by (user, item), duplicates dropped
+        self._ev_u, self._ev_i = (ev_key // mul).contiguous(), (ev_key % mul).contiguous()
+        self._users_t = torch.unique(self._ev_u)
+        self.users = self._users_t.cpu().numpy()
+        self._rank = torch.searchsorted(self._users_t, self._ev_u)                         # row of each positive's user among the evaluated users
+        n_pos = torch.bincount(self._rank, minlength=self._users_t.numel())
+        self._pos_ptr = torch.zeros(self._users_t.numel() + 1, device=device, dtype=torch.int64)
+        self._pos_ptr[1:] = torch.cumsum(n_pos, 0)
+        self._cand = None                                                                  # (global cand_indptr, cand_cols) of the last draw
+        self.draws = 0
+        step = int(users_per_batch) if users_per_batch else self.recbole_step((n_pos * (1 + self.sample_by)).tolist(), eval_batch_size)
+        self.rebatch(step)
+
+    @staticmethod
+    def recbole_step(sizes, eval_batch_size):
+        """Users per batch by ``NegSampleEvalDataLoader._init_batch_size_and_step``: ``sizes`` (pairs per user, positives and negatives) in
+        descending order, as many from the front as fit into ``eval_batch_size``; the first always counts."""
+        sizes = sorted((int(s) for s in sizes), reverse=True)
+        if not sizes:
+            return 1
+        num, total = 1, sizes[0]
+        for s in sizes[1:]:
+            if total + s > eval_batch_size:
+                break
+            num, total = num + 1, total + s
+        return num
+
+    def rebatch(self, users_per_batch):
+        """Cut the same evaluated users into batches of ``users_per_batch`` (candidates are kept per user: the cut changes no result)."""
+        self.step = max(int(users_per_batch), 1)
+        return self
+
+    def __len__(self):
+        return (len(self.users) + self.step - 1) // self.step
+
+    def _draw(self):
+        """One draw for every positive -> the candidate CSR over ALL evaluated users."""
+        n_user, P, k = self._users_t.numel(), self._ev_u.numel(), self.sample_by
+        neg = torch.as_tensor(self.sampler(self._ev_u, self._ev_i, k)).to(self.device).to(torch.int64).reshape(-1)
+        if neg.numel() != P * k:
+            raise ValueError(f'the sampler returned {neg.numel()} items for {P} positives x {k}')
+        if hasattr(self.sampler, 'check_failures'):
+            self.sampler.check_failures()
+        self.draws += 1
+        items = torch.cat([self._ev_i, neg])
+        rows = torch.cat([self._rank, self._rank.repeat(k)])                               # k-major: negative j of positive p sits at j * P + p
+        span = (int(items.max()) if items.numel() else 0) + 1
+        key = torch.unique(rows * span + items)                                            # ONE sort: ascending and distinct inside a user
+        indptr = torch.zeros(n_user + 1, device=self.device, dtype=torch.int64)
+        indptr[1:] = torch.cumsum(torch.bincount(key // span, minlength=n_user), 0)
+        self._cand = (indptr, (key % span).contiguous())
+
+    def __iter__(self):
+        if self.resample or self._cand is None:
+            self._draw()
+        gptr, gcols = self._cand
+        n_user = self._users_t.numel()
+        starts = torch.arange(0, n_user + self.step, self.step, device=self.device).clamp_(max=n_user)[:len(self) + 1]
+        cb, pb = gptr[starts].tolist(), self._pos_ptr[starts].tolist()                     # (one host read of the batch boundaries per pass)
+        for b in range(len(self)):
+            s, e = b * self.step, min((b + 1) * self.step, n_user)
+            yield (Interaction({self.uid_field: self._users_t[s:e]}), ((gptr[s:e + 1] - cb[b]).contiguous(), gcols[cb[b]:cb[b + 1]]),
+                   self._rank[pb[b]:pb[b + 1]] - s, self._ev_i[pb[b]:pb[b + 1]])
+
+    def expand(self, batch):
+        """recbole's form of a batch: ``(interaction [C] of (user, candidate item) pairs, row_idx [C], positive_u, positive_i)``."""
+        interaction, (cand_indptr, cand_cols), positive_u, positive_i = batch
+        users = interaction[self.uid_field]
+        row_idx = torch.repeat_interleave(torch.arange(users.numel(), device=users.device), cand_indptr[1:] - cand_indptr[:-1])
+        return Interaction({self.uid_field: users[row_idx], self.iid_field: cand_cols}), row_idx, positive_u, positive_i
+
+
+def eval_loader_for(config, domain, dataset, uid_field, iid_field, eval_pairs, history_pairs, device, users_per_batch=None, seed=2022,
+                    resample=True):
+    """The evaluation loader of one domain, as recbole_cdr/data/utils.py:131-153 (``get_dataloader``) picks it: ``domain='source'`` is
+    always the full-sort loader with ``revoke``; ``domain='target'`` is the loader of ``config['eval_args']['mode']``
+    (``trainer.resolve_eval_mode``): ``FullSortEvalLoader``, or for uniN / popN a ``NegSampleEvalLoader`` over a ``DeviceNegSampler`` of
+    that distribution whose used pairs are history + evaluated pairs.  ``history_pairs``: the (user, item) pairs an evaluated user must
+    not be recommended (train, and valid when testing)."""
+    import numpy as np
+    from ..trainer.trainer import resolve_eval_mode
+    batch = int(config['eval_batch_size']) if 'eval_batch_size' in config else 4096
+    OI, TOI = dataset.num_overlap_item, dataset.num_target_only_item
+    if domain == 'source':
+        return FullSortEvalLoader(uid_field, eval_pairs, history_pairs, dataset.num_total_item - TOI, batch, device, revoke=(OI, TOI),
+                                  users_per_batch=users_per_batch)
+    if domain != 'target':
+        raise ValueError(f"domain must be 'source' or 'target', got {domain!r}")
+    strategy, sample_by, distribution = resolve_eval_mode(config)
+    if strategy == 'full':
+        return FullSortEvalLoader(uid_field, eval_pairs, history_pairs, OI + TOI, batch, device, users_per_batch=users_per_batch)
+    from ..sampler import DeviceNegSampler
+    as_np = lambda p: (p.cpu().numpy() if torch.is_tensor(p) else np.asarray(p)).astype(np.int64).reshape(-1, 2)
+    used = np.concatenate([as_np(history_pairs), as_np(eval_pairs)]) if len(history_pairs) else as_np(eval_pairs)
+    sampler = DeviceNegSampler(dataset, 'target', used, device, seed=seed, distribution=distribution)
+    return NegSampleEvalLoader(uid_field, iid_field, eval_pairs, sampler, sample_by, batch, device, users_per_batch=users_per_batch,
+                               resample=resample)

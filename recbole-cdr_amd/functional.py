@@ -964,6 +964,96 @@ def rank_rows(scores, pos_indptr, pos_cols, hist_indptr=None, hist_cols=None, ex
     return pos_score, gt[:P], eq[:P], eqb[:P], nun
 
 
+def candidate_scores(user_e, slab0, slab1, cand_indptr, cand_cols, distance=False):
+    """Scores [C] of a ragged candidate list (cdr_candidate_scores_f32): user row u against the item rows of its candidate columns
+    ``cand_cols[cand_indptr[u]:cand_indptr[u+1]]``, columns addressing ``slab0`` followed by ``slab1`` (either may be None) as in
+    ``fullsort_scores``.  The dot product, or with ``distance`` SSCDR's ``-sum (u - i)^2``.  One row gather, flat over the candidates:
+    neither the (user, item) pairs nor a [U, N] matrix are formed.  Column values are not checked (the evaluation loader guarantees them)."""
+    _dev_check(user_e, slab0, slab1, cand_indptr, cand_cols)
+    user_e = user_e.detach().contiguous()
+    U, D = user_e.shape
+    assert cand_indptr.dtype == torch.int64 and cand_cols.dtype == torch.int64 and cand_indptr.numel() == U + 1
+    n0 = slab0.shape[0] if slab0 is not None else 0
+    n1 = slab1.shape[0] if slab1 is not None else 0
+    C = cand_cols.numel()
+    scores = torch.empty(C, device=user_e.device, dtype=torch.float32)
+    if C == 0 or U == 0:
+        return scores
+    cand_row = torch.repeat_interleave(torch.arange(U, device=user_e.device), cand_indptr[1:] - cand_indptr[:-1], output_size=C)
+    B_.call('cdr_candidate_scores_f32', B_.stream(), B_.f32(user_e), U, D, B_.f32(slab0.detach().contiguous()) if n0 else None, n0,
+            B_.f32(slab1.detach().contiguous()) if n1 else None, n1, B_.i64(cand_row), B_.i64(cand_cols.contiguous()), C,
+            1 if distance else 0, B_.f32(scores))
+    return scores
+
+
+def candidate_rank(cand_indptr, cand_cols, scores, pos_indptr, pos_cols):
+    """``fullsort_rank``'s counts over ragged candidate rows (cdr_candidate_rank_f32): the candidates are a CSR over the users
+    (``cand_indptr`` [U+1], ``cand_cols`` [C] ascending and distinct inside a user's range) with ``scores`` [C], the positives a CSR over the
+    same users.  Returns ``(pos_score [P] float32, gt, eq, eq_before [P] int32, n_cand [U] int32)``: the positive's score (found by binary
+    search in its user's range), the user's candidates scoring above / equal to it (itself included) / equal and at a smaller column, and
+    the user's candidates whose score is not NaN.  A positive that is not among its user's candidates, or whose score is NaN, gets -1
+    three times and a NaN ``pos_score``."""
+    _dev_check(cand_indptr, cand_cols, scores, pos_indptr, pos_cols)
+    U = cand_indptr.numel() - 1
+    assert cand_indptr.dtype == torch.int64 and cand_cols.dtype == torch.int64 and scores.dtype == torch.float32
+    assert scores.numel() == cand_cols.numel()
+    P, cols = _rank_positives(pos_indptr, pos_cols, U)
+    C = cand_cols.numel()
+    dev = scores.device
+    if U == 0 or C == 0 or P == 0:
+        # nothing to rank (the entry launches nothing): no positive has a candidate range to be found in
+        nun = torch.zeros(U, device=dev, dtype=torch.int32)
+        if C:
+            rows = torch.repeat_interleave(torch.arange(U, device=dev), cand_indptr[1:] - cand_indptr[:-1], output_size=C)
+            nun = torch.zeros(U, device=dev, dtype=torch.int64).index_add_(0, rows, (~torch.isnan(scores)).long()).to(torch.int32)
+        minus = torch.full((P,), -1, device=dev, dtype=torch.int32)
+        return torch.full((P,), float('nan'), device=dev), minus, minus.clone(), minus.clone(), nun
+    score, gt, eq, eqb, nun = _rank_outputs(dev, U, P)
+    B_.call('cdr_candidate_rank_f32', B_.stream(), U, B_.i64(cand_indptr.contiguous()), B_.i64(cand_cols.contiguous()),
+            B_.f32(scores.detach().contiguous()), C, B_.i64(pos_indptr.contiguous()), B_.i64(cols.contiguous()), P, B_.f32(score), B_.raw(gt),
+            B_.raw(eq), B_.raw(eqb), B_.raw(nun))
+    return score[:P], gt[:P], eq[:P], eqb[:P], nun
+
+
+def candidate_rank_reference(cand_indptr, cand_cols, scores, pos_indptr, pos_cols):
+    """``candidate_rank`` in plain torch, on any device: what the trainer uses where there is no device to run the kernel on
+    (``device: cpu``) -- plumbing, like ``trainer.rank_counts_reference``.  One [P, longest range] comparison block."""
+    dev = scores.device
+    U = cand_indptr.numel() - 1
+    P = pos_cols.numel()
+    n = cand_indptr[1:] - cand_indptr[:-1]
+    crow = torch.repeat_interleave(torch.arange(U, device=dev), n)
+    valid = ~torch.isnan(scores)
+    nun = torch.zeros(U, device=dev, dtype=torch.int64).index_add_(0, crow, valid.long()).to(torch.int32)
+    if P == 0:
+        e = torch.zeros(0, device=dev, dtype=torch.int32)
+        return torch.zeros(0, device=dev, dtype=torch.float32), e, e.clone(), e.clone(), nun
+    prow = torch.repeat_interleave(torch.arange(U, device=dev), pos_indptr[1:] - pos_indptr[:-1])
+    width = max(int(n.max()), 1)
+    at = cand_indptr[prow].unsqueeze(1) + torch.arange(width, device=dev).unsqueeze(0)            # [P, width] flat candidate positions
+    inside = at < cand_indptr[prow + 1].unsqueeze(1)
+    at = at.clamp(max=max(scores.numel() - 1, 0))
+    if scores.numel() == 0:
+        inside = torch.zeros_like(inside)
+        s = torch.zeros(P, width, device=dev)
+        c = torch.zeros(P, width, device=dev, dtype=torch.int64)
+        ok = inside
+    else:
+        s, c = scores[at], cand_cols[at]
+        ok = inside & valid[at]
+    mine = inside & (c == pos_cols.unsqueeze(1))
+    found = mine.any(1)
+    t = s[torch.arange(P, device=dev), mine.int().argmax(1)].float()
+    t = torch.where(found, t, torch.full_like(t, float('nan')))
+    tt = t.unsqueeze(1)
+    gt = ((s > tt) & ok).sum(1)
+    same = (s == tt) & ok
+    eq, eqb = same.sum(1), (same & (c < pos_cols.unsqueeze(1))).sum(1)
+    bad = torch.isnan(t)
+    gt, eq, eqb = (torch.where(bad, torch.full_like(x, -1), x).to(torch.int32) for x in (gt, eq, eqb))
+    return t.float(), gt, eq, eqb, nun
+
+
 # ---------------------------------------------------------------------------------------------------- CoNet pieces
 class GatherConcat2(Function):
     """cat([A[ida], B[idb]], dim=1) in one buffer (conet.py:106-111) with the dense scatter-add backward."""

@@ -175,6 +175,11 @@ class BiTGCF(CrossDomainRecommender):
         restore_user_e, restore_item_e = self.get_restore_e()
         return F_.gather_rows(restore_user_e, interaction[self.TARGET_USER_ID]), restore_item_e[:self.target_num_items], None
 
+    def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
+        """Sampled-candidate evaluation on the row-gather kernel: ``predict`` is the plain dot of the propagated rows (bitgcf.py:252-262 of
+        the reference), the operands of ``_full_sort_operands`` (the cached propagation: one per evaluation, not one per chunk of pairs)."""
+        return self._candidate_scores_native(interaction, cand_indptr, cand_cols)
+
     @torch.no_grad()
     def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
         """(values, columns) [U,k] of ``full_sort_predict`` after recbole's evaluation mask, without the [U, N] matrix."""

@@ -162,6 +162,8 @@ class CLFM(RowwiseTraining, CrossDomainRecommender):
 
     _WEIGHT_STEP = 'clfm'                                             # (the three linears' dense Adam state: the checkpoint's 'weights')
 
+    # (sampled-candidate evaluation keeps the base class's ``candidate_scores``: ``predict`` applies a sigmoid -- clfm.py:100 of the
+    # reference, as CMF's -- and two candidates whose probabilities saturate to the same float tie, which the raw dot would rank apart)
     @torch.no_grad()
     def predict(self, interaction):
         return self.target_forward(interaction[self.TARGET_USER_ID], interaction[self.TARGET_ITEM_ID])

@@ -303,6 +303,11 @@ class DCDCSR(RowwiseTraining, CrossDomainRecommender):
             return user_e, I, None
         return user_e, I[:self.target_num_items], None
 
+    def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
+        """Sampled-candidate evaluation on the row-gather kernel: ``predict`` is the plain dot of the phase's two tables (dcdcsr.py:249-280
+        of the reference), the operands of ``_full_sort_operands``."""
+        return self._candidate_scores_native(interaction, cand_indptr, cand_cols)
+
     @torch.no_grad()
     def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
         """Evaluation without the [U, N] matrix: (values [U,k], columns [U,k]) of ``full_sort_predict`` after the evaluation mask (column 0

@@ -491,6 +491,12 @@ class EMCDR(RowwiseTraining, CrossDomainRecommender):
         user_e = F_.gather_rows(self.target_user_embedding.weight, user)
         return user_e, self.apply_mapping(self.source_item_embedding.weight[:OI]), self.target_item_embedding.weight[OI:TI]
 
+    def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
+        """Sampled-candidate evaluation on the row-gather kernel: ``predict`` is the plain dot in every phase and both overlap modes
+        (emcdr.py:178-206 of the reference), of the operands of ``_full_sort_operands`` (OVERLAP: the mapping MLP runs once per user, or
+        once per shared item row, not once per pair)."""
+        return self._candidate_scores_native(interaction, cand_indptr, cand_cols)
+
     @torch.no_grad()
     def full_sort_predict(self, interaction):
         self._whole_tables_only('full_sort_predict')

@@ -433,6 +433,12 @@ class SSCDR(RowwiseTraining, CrossDomainRecommender):
             cache['sqnorm'] = F_.row_sqnorm(cache['items'])
         return cache['sqnorm']
 
+    def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
+        """Sampled-candidate evaluation on the row-gather kernel in its distance form: ``predict`` is -sum (u - i)^2 over the normalised
+        rows (sscdr.py:127-128, 197-226 of the reference), the operands of ``_full_sort_operands`` (inside an evaluation bracket the cached
+        normalised item buffer; the mapping MLP runs once per user, not once per pair)."""
+        return self._candidate_scores_native(interaction, cand_indptr, cand_cols)
+
     @torch.no_grad()
     def full_sort_predict(self, interaction):
         ue, s0, s1 = self._full_sort_operands(interaction)

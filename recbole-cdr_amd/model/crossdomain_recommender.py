@@ -137,6 +137,47 @@ class CrossDomainRecommender(nn.Module):
             s = e
         return (score,) + out
 
+    def _candidate_guard(self):
+        if self.__dict__.get('_dist_cfg') not in (None, False):
+            raise NotImplementedError(f"{type(self).__name__}.candidate_scores does not shard its tables: config['dist_group'] is not "
+                                      f"supported (one GPU)")
+
+    @torch.no_grad()
+    def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
+        """Scores [C] of a ragged candidate list -- the users of ``interaction`` [U] against the columns
+        ``cand_cols[cand_indptr[u]:cand_indptr[u+1]]`` -- as ``predict`` gives them: sampled-candidate evaluation (eval_args mode uniN /
+        popN) ranks ``predict``'s values, as recbole's ``Trainer._neg_sample_batch_eval`` does.  This is the definition of the route and
+        works for every model: the list is expanded to (user, item) pairs and ``predict`` runs in chunks of ``chunk`` pairs (the way
+        ``Trainer._predict_all_pairs`` chunks).  The columns are those of ``full_sort_predict`` in the model's phase: target item ids, and
+        in a SOURCE phase the source loader's revoked columns (ids from ``overlapped_num_items`` on shifted down by the target-only count).
+        A model whose ``predict`` is the same function of ``_full_sort_operands`` as ``functional.candidate_scores`` computes overrides this
+        with ``_candidate_scores_native``."""
+        self._candidate_guard()
+        C = cand_cols.numel()
+        dev = cand_cols.device
+        if C == 0:
+            return torch.empty(0, device=dev, dtype=torch.float32)
+        cand_row = torch.repeat_interleave(torch.arange(len(interaction), device=dev), cand_indptr[1:] - cand_indptr[:-1], output_size=C)
+        pairs = interaction.index_select(cand_row)
+        if getattr(self, 'phase', None) == 'SOURCE':
+            OI, TI = self.overlapped_num_items, self.target_num_items
+            pairs.update({self.SOURCE_ITEM_ID: torch.where(cand_cols < OI, cand_cols, cand_cols + (TI - OI))})
+        else:
+            pairs.update({self.TARGET_ITEM_ID: cand_cols})
+        step = max(int(chunk), 1)
+        return torch.cat([self.predict(pairs[s:s + step]).reshape(-1) for s in range(0, C, step)]).float()
+
+    @torch.no_grad()
+    def _candidate_scores_native(self, interaction, cand_indptr, cand_cols):
+        """``candidate_scores`` on the row-gather kernel: the user operand of ``_full_sort_operands`` is formed once per user (EMCDR's and
+        SSCDR's mapping MLP runs U times, not once per pair) and each candidate reads one item row."""
+        from .. import functional as F_
+        self._candidate_guard()
+        user_e, slab0, slab1 = self._full_sort_operands(interaction)
+        slab0 = slab0 if slab0 is not None and slab0.shape[0] else None
+        slab1 = slab1 if slab1 is not None and slab1.shape[0] else None
+        return F_.candidate_scores(user_e, slab0, slab1, cand_indptr, cand_cols, distance=self._rank_distance_form())
+
     def other_parameter(self):
         if hasattr(self, 'other_parameter_name'):
             return {key: getattr(self, key) for key in self.other_parameter_name}

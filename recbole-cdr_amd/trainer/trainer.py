@@ -338,7 +338,25 @@ def resolve_metrics(config):
     return tuple(out)
 
 
+def resolve_eval_mode(config):
+    """config['eval_args']['mode'] as recbole's ``Config._set_eval_neg_sample_args`` reads it -> (strategy, sample_by, distribution):
+    absent or 'full' -> ('full', None, 'uniform'); 'uniN' -> ('by', N, 'uniform'); 'popN' -> ('by', N, 'popularity'), N a positive integer.
+    Case-sensitive, as recbole is ('Uni5' is refused).  'labeled' and everything else raise ValueError, before anything is built."""
+    args = config['eval_args'] if 'eval_args' in config and config['eval_args'] is not None else {}
+    mode = args['mode'] if 'mode' in args and args['mode'] is not None else 'full'
+    if mode == 'full':
+        return 'full', None, 'uniform'
+    if mode == 'labeled':
+        raise ValueError("the mode [labeled] in eval_args is not provided: labeled evaluation and the value metrics (auc, mae, rmse, "
+                         "logloss) need label-carrying evaluation data and training without negative sampling; use full, uniN or popN")
+    if isinstance(mode, str) and mode[:3] in ('uni', 'pop') and mode[3:].isascii() and mode[3:].isdigit() and int(mode[3:]) > 0:
+        return 'by', int(mode[3:]), 'uniform' if mode[:3] == 'uni' else 'popularity'
+    raise ValueError(f'the mode [{mode}] in eval_args is not supported.')
+
+
 def resolve_eval_route(config, metrics):
+    """config['eval_route'] ('auto' | 'topk' | 'rank'): which of the two FULL-SORT routes a full-sort loader takes.  It does not concern a
+    sampled-candidate loader (``eval_mode = 'sampled'``), which always ranks its positives inside the candidate lists."""
     route = config['eval_route'] if 'eval_route' in config and config['eval_route'] is not None else 'auto'
     if route not in ('auto', 'topk', 'rank'):
         raise ValueError(f"eval_route must be 'auto', 'topk' or 'rank', got {route!r}")
@@ -432,6 +450,9 @@ class Trainer:
         # from the rank of each positive over the masked catalogue (model.full_sort_rank: any k, MAP, GAUC), 'topk' insists on the lists
         self.metrics = resolve_metrics(config)
         self.eval_route = resolve_eval_route(config, self.metrics)
+        # config['eval_args']['mode'] (full | uniN | popN): which evaluation loader data.dataloader.eval_loader_for builds for the target
+        # domain; evaluate() itself dispatches on the loader it is handed.  A mode that is not provided is refused here
+        self.eval_mode = resolve_eval_mode(config)
         self.device = config['device']
         self.weight_decay = config['weight_decay'] if 'weight_decay' in config else 0.0
         self.start_epoch, self.cur_step = 0, 0
@@ -755,17 +776,21 @@ class Trainer:
     def evaluate(self, eval_data):
         """eval_data yields (interaction, history_index (rows, cols) or None, positive_u, positive_i) like recbole's
         FullSortEvalDataLoader; returns {metric@k: value} for config['metrics'] (default recall / mrr / ndcg / hit / precision; also map, and
-        gauc under the key 'gauc') at every k of config['topk']."""
+        gauc under the key 'gauc') at every k of config['topk'].  A loader whose ``eval_mode`` is 'sampled' (``NegSampleEvalLoader``, eval_args
+        mode uniN / popN) yields (interaction, (cand_indptr, cand_cols), positive_u, positive_i) instead and every positive is ranked inside
+        its user's candidate list (``_evaluate_sampled_batches``)."""
         self._fused_sync()
         self.model.eval()
         kmax = max(self.topk)
-        fused = self.fused_topk and hasattr(self.model, 'full_sort_topk')
+        # dispatch per loader, on its own attribute: a (source full-sort, target sampled) pair of valid loaders evaluates each its way
+        sampled = getattr(eval_data, 'eval_mode', 'full') == 'sampled'
+        fused = self.fused_topk and hasattr(self.model, 'full_sort_topk') and not sampled
         # recbole cuts the evaluated users so that the [U, N] score matrix fits eval_batch_size entries (ONE user per call over a 10 M-item
         # catalogue at the default 4,096).  The fused mask + top-k path never forms that matrix, so it re-cuts a loader that allows it
         # into throughput-sized batches (config['eval_users_per_batch'], default 1,024; 0 keeps recbole's cut): same users, same metrics
         want = int(self.config['eval_users_per_batch']) if 'eval_users_per_batch' in self.config else 1024
         restore = None
-        if fused and want > 0 and hasattr(eval_data, 'rebatch') and getattr(eval_data, 'step', want) < want:
+        if (fused or sampled) and want > 0 and hasattr(eval_data, 'rebatch') and getattr(eval_data, 'step', want) < want:
             restore = eval_data.step                      # (the caller's cut comes back afterwards: another consumer may need [U, N] to fit)
             eval_data.rebatch(want)
         # the model's evaluation-mode caches (CoNet: the item half of layer 1, the packed one-user call) live exactly as long as this loop:
@@ -774,6 +799,8 @@ class Trainer:
         if frozen:
             self.model.freeze_for_eval()
         try:
+            if sampled:
+                return self._evaluate_sampled_batches(eval_data, kmax)
             return self._evaluate_batches(eval_data, fused, kmax)
         finally:
             if frozen:
@@ -877,24 +904,62 @@ class Trainer:
         """Every metric from the rank of each positive over the masked catalogue: a positive at top-k position r = 1 + gt + eq_before
         (ties to the smaller column) is a hit at position r of the list for every k >= r -- the same hit matrix the top-k route builds,
         for any kmax; GAUC from the average ranks gt + (eq + 1) / 2."""
-        hits, pos_len, user_len, rank_sum = [], [], [], []
+        acc = ([], [], [], [])
         for interaction, history_index, positive_u, positive_i in eval_data:
             interaction = interaction.to(self.device)
             n_user = len(interaction)
-            prow, gt, eq, eqb, nun, npos = self._rank_counts(interaction, n_user, history_index, positive_u, positive_i)
-            at = gt.long() + eqb.long()
-            hit = torch.zeros(n_user, kmax, device=gt.device, dtype=torch.float32)
-            sel = at < kmax
-            hit[prow[sel], at[sel]] = 1.0
-            hits.append(hit); pos_len.append(npos)
-            user_len.append(nun.long())
-            rank_sum.append(torch.zeros(n_user, device=gt.device, dtype=torch.float64).index_add_(
-                0, prow, gt.double() + (eq.double() + 1) / 2))
+            self._rank_batch_tail(acc, n_user, kmax, *self._rank_counts(interaction, n_user, history_index, positive_u, positive_i))
+        return self._rank_result(acc, names)
+
+    @staticmethod
+    def _rank_batch_tail(acc, n_user, kmax, prow, gt, eq, eqb, nun, npos):
+        """One batch's (hit matrix, positives per user, ranked items per user, sum of average ranks per user) from its rank counts,
+        appended to ``acc``: the one copy both rank routes (full-sort and sampled candidates) end in."""
+        at = gt.long() + eqb.long()
+        hit = torch.zeros(n_user, kmax, device=gt.device, dtype=torch.float32)
+        sel = at < kmax
+        hit[prow[sel], at[sel]] = 1.0
+        acc[0].append(hit); acc[1].append(npos)
+        acc[2].append(nun.long())
+        acc[3].append(torch.zeros(n_user, device=gt.device, dtype=torch.float64).index_add_(
+            0, prow, gt.double() + (eq.double() + 1) / 2))
+
+    def _rank_result(self, acc, names):
+        hits, pos_len, user_len, rank_sum = acc
         n_pos = torch.cat(pos_len)
         result = metrics_from_hits(torch.cat(hits), n_pos.float().clamp(min=1), self.topk, names)
         if 'gauc' in names:
             result['gauc'] = gauc_from_counts(n_pos, torch.cat(user_len), torch.cat(rank_sum))
         return result
+
+    def _evaluate_sampled_batches(self, eval_data, kmax):
+        """Sampled-candidate evaluation (a ``NegSampleEvalLoader``): per batch the model's ``candidate_scores`` over the ragged candidate
+        lists, then the rank of every positive inside its user's list (``functional.candidate_rank``; its torch restatement on
+        ``device: cpu``), then the rank route's arithmetic.  ``n_unmasked`` is the user's distinct candidate count: what recbole's
+        collector sees in a row of -inf with the candidates' scores scattered in."""
+        from .. import functional as F_
+        names = self.metrics if self.metrics is not None else DEFAULT_METRICS
+        chunk = int(self.config['eval_batch_size']) if 'eval_batch_size' in self.config else 4096
+        on_gpu = torch.device(self.device).type == 'cuda'
+        acc = ([], [], [], [])
+        for interaction, (cand_indptr, cand_cols), positive_u, positive_i in eval_data:
+            interaction = interaction.to(self.device)
+            n_user = len(interaction)
+            cand_indptr, cand_cols = cand_indptr.to(self.device), cand_cols.to(self.device)
+            pu = torch.as_tensor(positive_u, device=self.device, dtype=torch.int64)
+            pi = torch.as_tensor(positive_i, device=self.device, dtype=torch.int64)
+            pindptr, pcols = self._csr(pu, pi, n_user)
+            npos = pindptr[1:] - pindptr[:-1]
+            prow = torch.repeat_interleave(torch.arange(n_user, device=pu.device), npos)
+            scores = self.model.candidate_scores(interaction, cand_indptr, cand_cols, chunk).float().contiguous()
+            rank = F_.candidate_rank if on_gpu else F_.candidate_rank_reference
+            _score, gt, eq, eqb, nun = rank(cand_indptr, cand_cols, scores, pindptr, pcols)
+            if bool((gt < 0).any()):
+                p = int(torch.nonzero(gt < 0)[0])
+                raise ValueError(f'evaluate: the positive item {int(pcols[p])} of user row {int(prow[p])} of this batch is not among the '
+                                 f'user\'s candidates or has a NaN score: the rank route does not rank such a positive')
+            self._rank_batch_tail(acc, n_user, kmax, prow, gt, eq, eqb, nun, npos)
+        return self._rank_result(acc, names)
 
     def save_checkpoint(self, path, epoch=None):
         """recbole ``Trainer._save_checkpoint``: config-free subset -- epoch, early-stopping state, model ``state_dict``,
