@@ -259,8 +259,9 @@ __global__ __launch_bounds__(kBlock) void sscdr_map_loss_kernel(const float* __r
             const float u2 = (active && d2 > 0.f) ? (av - mn[c] / nq + eps) / d2 : 0.f;
             const float gs = cs * (ms[c] - t[c]);
             G3[r * D + c] = gs;
-            G3[(n + r) * D + c] = sq_norm_bwd(mp[c], -cu * u1, lp, dpp);
-            G3[(2 * n + r) * D + c] = sq_norm_bwd(mn[c], cu * u2, lq, dq);
+            // (+ 0.0f: a closed hinge, or lambda = 0, leaves -cu * 0 = -0.0 in some elements; such a row's gradient is +0.0 throughout)
+            G3[(n + r) * D + c] = sq_norm_bwd(mp[c], -cu * u1, lp, dpp) + 0.0f;
+            G3[(2 * n + r) * D + c] = sq_norm_bwd(mn[c], cu * u2, lq, dq) + 0.0f;
             GT[r * D + c] = -gs + sq_norm_bwd(t[c], cu * (u1 - u2), lt, da);
         }
     }
