@@ -761,22 +761,39 @@ def select_mapped(mapped, weight, ids, n_overlap):
     return out
 
 
-def fullsort_scores(user_e, slab0, slab1=None, out=None):
-    """scores[U, n0+n1] = user_e @ cat(slab0, slab1)^T without the cat copy; slabs are contiguous row ranges."""
-    _dev_check(user_e, slab0, slab1)
+def _fullsort_head(user_e, slab0, slab1):
+    """What the entries that score ``user_e`` against ``cat(slab0, slab1)`` share: ``(user_e detached and contiguous, U, D, n0, n1, head)``
+    with ``head`` their leading arguments ``(stream, user_e, U, D, slab0, n0, slab1, n1)``; a slab that is None or has no rows goes in
+    as NULL with 0 rows."""
     user_e = user_e.detach().contiguous()
     U, D = user_e.shape
     n0 = slab0.shape[0] if slab0 is not None else 0
     n1 = slab1.shape[0] if slab1 is not None else 0
+    head = (B_.stream(), B_.f32(user_e), U, D, B_.f32(slab0.detach()) if n0 else None, n0, B_.f32(slab1.detach()) if n1 else None, n1)
+    return user_e, U, D, n0, n1, head
+
+
+def _grown_workspace(cache, key, dev, need):
+    """The byte buffer ``cache`` keeps per ``key`` + (device, current stream): at least ``need`` bytes, and it only grows."""
+    key = key + (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = cache[key] = torch.empty(int(need), device=dev, dtype=torch.uint8)
+    return ws
+
+
+def fullsort_scores(user_e, slab0, slab1=None, out=None):
+    """scores[U, n0+n1] = user_e @ cat(slab0, slab1)^T without the cat copy; slabs are contiguous row ranges."""
+    _dev_check(user_e, slab0, slab1)
+    user_e, U, D, n0, n1, head = _fullsort_head(user_e, slab0, slab1)
     if out is None:
         out = torch.empty(U, n0 + n1, device=user_e.device, dtype=torch.float32)
     assert out.is_contiguous() and tuple(out.shape) == (U, n0 + n1)
-    B_.call('cdr_fullsort_scores_f32', B_.stream(), B_.f32(user_e), U, D,
-            B_.f32(slab0.detach()) if n0 else None, n0, B_.f32(slab1.detach()) if n1 else None, n1, B_.f32(out))
+    B_.call('cdr_fullsort_scores_f32', *head, B_.f32(out))
     return out
 
 
-_topk_ws = {}
+_topk_ws = {}           # one workspace per (device, stream) for the dot-product top-k, the distance top-k and the two rank entries
 
 
 def fullsort_topk(user_e, slab0, slab1=None, k=10, hist_indptr=None, hist_cols=None, exclude_first_col=True):
@@ -784,23 +801,15 @@ def fullsort_topk(user_e, slab0, slab1=None, k=10, hist_indptr=None, hist_cols=N
     mask -- column 0 (PAD) and, per user, the ascending columns ``hist_cols[hist_indptr[u]:hist_indptr[u+1]]`` -- without
     materialising the [U, N] matrix when U > 32 and D is 64 or 128 (cdr_fullsort_topk_f32)."""
     _dev_check(user_e, slab0, slab1, hist_indptr, hist_cols)
-    user_e = user_e.detach().contiguous()
-    U, D = user_e.shape
-    n0 = slab0.shape[0] if slab0 is not None else 0
-    n1 = slab1.shape[0] if slab1 is not None else 0
+    user_e, U, D, n0, n1, head = _fullsort_head(user_e, slab0, slab1)
     dev = user_e.device
     need = ctypes.c_size_t(0)
     B_._check(B_.load().cdr_fullsort_topk_workspace_bytes(U, D, n0, n1, int(k), ctypes.byref(need)),
               'cdr_fullsort_topk_workspace_bytes')
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _topk_ws.get(key)
-    if ws is None or ws.numel() < need.value:
-        ws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
-        _topk_ws[key] = ws
+    ws = _grown_workspace(_topk_ws, (), dev, need.value)
     vals = torch.empty(U, k, device=dev, dtype=torch.float32)
     idx = torch.empty(U, k, device=dev, dtype=torch.int64)
-    B_.call('cdr_fullsort_topk_f32', B_.stream(), B_.f32(user_e), U, D, B_.f32(slab0.detach()) if n0 else None, n0,
-            B_.f32(slab1.detach()) if n1 else None, n1, int(k), B_.i64(hist_indptr), B_.i64(hist_cols),
+    B_.call('cdr_fullsort_topk_f32', *head, int(k), B_.i64(hist_indptr), B_.i64(hist_cols),
             1 if exclude_first_col else 0, B_.f32(vals), B_.i64(idx), B_.raw(ws), ws.numel())
     return vals, idx
 
@@ -843,33 +852,24 @@ def fullsort_neg_sqdist_topk(user_e, slab0, slab1=None, k=10, hist_indptr=None, 
     entries; (-inf, -1) pads a row with fewer than k columns left.  ``col_sqnorm``: ``row_sqnorm`` of the concatenated slabs when the caller
     keeps it (an evaluation's item operand does not change between user batches); computed per call otherwise."""
     _dev_check(user_e, slab0, slab1, hist_indptr, hist_cols, col_sqnorm)
-    user_e = user_e.detach().contiguous()
-    U, D = user_e.shape
-    n0 = slab0.shape[0] if slab0 is not None else 0
-    n1 = slab1.shape[0] if slab1 is not None else 0
-    dev = user_e.device
-    if col_sqnorm is not None:
-        assert col_sqnorm.dtype == torch.float32 and col_sqnorm.numel() == n0 + n1
-    rows = U
+    U = user_e.shape[0]
     if U <= 8:
         # The entry has no form for these few rows (the dot-product plan streams a GEMV there and sizes no score staging).  Nine rows
         # take the unfused passes -- the distance GEMM's 32-row tile either way -- and the padding rows are cut off again.
-        rows = 9
-        user_e = torch.cat([user_e, user_e.new_zeros(rows - U, D)])
+        user_e = torch.cat([user_e.detach(), user_e.new_zeros(9 - U, user_e.shape[1])])
         if hist_indptr is not None:
-            hist_indptr = torch.cat([hist_indptr, hist_indptr[-1:].expand(rows - U)])
+            hist_indptr = torch.cat([hist_indptr, hist_indptr[-1:].expand(9 - U)])
+    user_e, rows, D, n0, n1, head = _fullsort_head(user_e, slab0, slab1)
+    dev = user_e.device
+    if col_sqnorm is not None:
+        assert col_sqnorm.dtype == torch.float32 and col_sqnorm.numel() == n0 + n1
     need = ctypes.c_size_t(0)
     B_._check(B_.load().cdr_fullsort_neg_sqdist_topk_workspace_bytes(rows, D, n0, n1, int(k), ctypes.byref(need)),
               'cdr_fullsort_neg_sqdist_topk_workspace_bytes')
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _topk_ws.get(key)                  # (the dot-product form's: one per device and stream, it only grows)
-    if ws is None or ws.numel() < need.value:
-        ws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
-        _topk_ws[key] = ws
+    ws = _grown_workspace(_topk_ws, (), dev, need.value)
     vals = torch.empty(rows, k, device=dev, dtype=torch.float32)
     idx = torch.empty(rows, k, device=dev, dtype=torch.int64)
-    B_.call('cdr_fullsort_neg_sqdist_topk_f32', B_.stream(), B_.f32(user_e), rows, D, B_.f32(slab0.detach()) if n0 else None, n0,
-            B_.f32(slab1.detach()) if n1 else None, n1, B_.f32(col_sqnorm), int(k), B_.i64(hist_indptr), B_.i64(hist_cols),
+    B_.call('cdr_fullsort_neg_sqdist_topk_f32', *head, B_.f32(col_sqnorm), int(k), B_.i64(hist_indptr), B_.i64(hist_cols),
             1 if exclude_first_col else 0, B_.f32(vals), B_.i64(idx), B_.raw(ws), ws.numel())
     return (vals[:U], idx[:U]) if rows != U else (vals, idx)
 
@@ -889,21 +889,13 @@ def _rank_positives(pos_indptr, pos_cols, U):
 
 def _fullsort_rank(entry, user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols, exclude_first_col, col_sqnorm):
     _dev_check(user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols, col_sqnorm)
-    user_e = user_e.detach().contiguous()
-    U, D = user_e.shape
-    n0 = slab0.shape[0] if slab0 is not None else 0
-    n1 = slab1.shape[0] if slab1 is not None else 0
+    user_e, U, D, n0, n1, head = _fullsort_head(user_e, slab0, slab1)
     dev = user_e.device
     P, cols = _rank_positives(pos_indptr, pos_cols, U)
     need = ctypes.c_size_t(0)
     B_._check(getattr(B_.load(), entry + '_workspace_bytes')(U, D, n0, n1, P, ctypes.byref(need)), entry + '_workspace_bytes')
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _topk_ws.get(key)                  # (the top-k forms': one per device and stream, it only grows)
-    if ws is None or ws.numel() < need.value:
-        ws = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
-        _topk_ws[key] = ws
+    ws = _grown_workspace(_topk_ws, (), dev, need.value)
     score, gt, eq, eqb, nun = _rank_outputs(dev, U, P)
-    head = (B_.stream(), B_.f32(user_e), U, D, B_.f32(slab0.detach()) if n0 else None, n0, B_.f32(slab1.detach()) if n1 else None, n1)
     if entry == 'cdr_fullsort_neg_sqdist_rank':
         if col_sqnorm is not None:
             assert col_sqnorm.dtype == torch.float32 and col_sqnorm.numel() == n0 + n1
@@ -970,19 +962,15 @@ def candidate_scores(user_e, slab0, slab1, cand_indptr, cand_cols, distance=Fals
     ``fullsort_scores``.  The dot product, or with ``distance`` SSCDR's ``-sum (u - i)^2``.  One row gather, flat over the candidates:
     neither the (user, item) pairs nor a [U, N] matrix are formed.  Column values are not checked (the evaluation loader guarantees them)."""
     _dev_check(user_e, slab0, slab1, cand_indptr, cand_cols)
-    user_e = user_e.detach().contiguous()
-    U, D = user_e.shape
+    U = user_e.shape[0]
     assert cand_indptr.dtype == torch.int64 and cand_cols.dtype == torch.int64 and cand_indptr.numel() == U + 1
-    n0 = slab0.shape[0] if slab0 is not None else 0
-    n1 = slab1.shape[0] if slab1 is not None else 0
     C = cand_cols.numel()
     scores = torch.empty(C, device=user_e.device, dtype=torch.float32)
     if C == 0 or U == 0:
         return scores
     cand_row = torch.repeat_interleave(torch.arange(U, device=user_e.device), cand_indptr[1:] - cand_indptr[:-1], output_size=C)
-    B_.call('cdr_candidate_scores_f32', B_.stream(), B_.f32(user_e), U, D, B_.f32(slab0.detach().contiguous()) if n0 else None, n0,
-            B_.f32(slab1.detach().contiguous()) if n1 else None, n1, B_.i64(cand_row), B_.i64(cand_cols.contiguous()), C,
-            1 if distance else 0, B_.f32(scores))
+    head = _fullsort_head(user_e, *(s.contiguous() if s is not None else None for s in (slab0, slab1)))[-1]
+    B_.call('cdr_candidate_scores_f32', *head, B_.i64(cand_row), B_.i64(cand_cols.contiguous()), C, 1 if distance else 0, B_.f32(scores))
     return scores
 
 
@@ -1274,11 +1262,7 @@ def _stripe_topk_call(entry, dev, U, N, k, args, hist_indptr, hist_cols, exclude
     except RuntimeError:
         B_._alive.clear()
         raise
-    key = (entry, dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    wsp = _stripe_topk_ws.get(key)
-    if wsp is None or wsp.numel() < need.value:
-        wsp = torch.empty(int(need.value), device=dev, dtype=torch.uint8)
-        _stripe_topk_ws[key] = wsp
+    wsp = _grown_workspace(_stripe_topk_ws, (entry,), dev, need.value)
     vals = torch.empty(U, k, device=dev, dtype=torch.float32)
     idx = torch.empty(U, k, device=dev, dtype=torch.int64)
     B_.call(entry, *args, int(k), B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals), B_.i64(idx),

@@ -18,6 +18,7 @@ import torch.nn as nn
 from ... import binding as B_
 from ... import functional as F_
 from ...utils import InputType
+from ..contraction import ContractionScoring
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
 
 
@@ -41,7 +42,7 @@ def _csr_norm_adj(pairs, n_users, n_items, device):
     return F_.CSRGraph(indptr, col[order].contiguous(), val[order].contiguous(), n)
 
 
-class BiTGCF(CrossDomainRecommender):
+class BiTGCF(ContractionScoring, CrossDomainRecommender):
     input_type = InputType.POINTWISE
 
     def __init__(self, config, dataset):
@@ -164,29 +165,15 @@ class BiTGCF(CrossDomainRecommender):
         return scores
 
     @torch.no_grad()
-    def full_sort_predict(self, interaction):
-        restore_user_e, restore_item_e = self.get_restore_e()
-        u = F_.gather_rows(restore_user_e, interaction[self.TARGET_USER_ID])
-        return F_.fullsort_scores(u, restore_item_e[:self.target_num_items]).view(-1)
-
-    @torch.no_grad()
     def _full_sort_operands(self, interaction):
-        """(user_e, slab0, slab1) of ``full_sort_predict``'s contraction (``full_sort_rank`` scores them in column passes)."""
+        """(user_e, slab0, slab1) of the all-items contraction over the cached propagation: what ``ContractionScoring`` derives
+        ``full_sort_predict`` / ``full_sort_topk`` / ``full_sort_rank`` from."""
         restore_user_e, restore_item_e = self.get_restore_e()
         return F_.gather_rows(restore_user_e, interaction[self.TARGET_USER_ID]), restore_item_e[:self.target_num_items], None
 
-    def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
-        """Sampled-candidate evaluation on the row-gather kernel: ``predict`` is the plain dot of the propagated rows (bitgcf.py:252-262 of
-        the reference), the operands of ``_full_sort_operands`` (the cached propagation: one per evaluation, not one per chunk of pairs)."""
-        return self._candidate_scores_native(interaction, cand_indptr, cand_cols)
-
-    @torch.no_grad()
-    def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
-        """(values, columns) [U,k] of ``full_sort_predict`` after recbole's evaluation mask, without the [U, N] matrix."""
-        restore_user_e, restore_item_e = self.get_restore_e()
-        u = F_.gather_rows(restore_user_e, interaction[self.TARGET_USER_ID])
-        return F_.fullsort_topk(u, restore_item_e[:self.target_num_items], None, k=k, hist_indptr=hist_indptr,
-                                hist_cols=hist_cols, exclude_first_col=True)
+    # Sampled-candidate evaluation on the row-gather kernel: ``predict`` is the plain dot of the propagated rows (bitgcf.py:252-262 of the
+    # reference), the operands of ``_full_sort_operands`` (the cached propagation: one per evaluation, not one per chunk of pairs).
+    candidate_scores = ContractionScoring.candidate_scores_from_operands
 
     def on_train_steps(self):
         # a replayed step runs no Python: the trainer calls this after replays so that the next evaluation propagates the TRAINED tables

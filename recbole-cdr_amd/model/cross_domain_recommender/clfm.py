@@ -15,10 +15,11 @@ from ... import binding as B_
 from ... import functional as F_
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
+from ..contraction import ContractionScoring
 from ..rowwise import RowwiseTraining
 
 
-class CLFM(RowwiseTraining, CrossDomainRecommender):
+class CLFM(RowwiseTraining, ContractionScoring, CrossDomainRecommender):
     input_type = InputType.POINTWISE
 
     def __init__(self, config, dataset):
@@ -169,22 +170,8 @@ class CLFM(RowwiseTraining, CrossDomainRecommender):
         return self.target_forward(interaction[self.TARGET_USER_ID], interaction[self.TARGET_ITEM_ID])
 
     @torch.no_grad()
-    def full_sort_predict(self, interaction):
-        user_e = F_.gather_rows(self.target_user_embedding.weight, interaction[self.TARGET_USER_ID])
-        fac = self._factors(user_e, 'target')
-        return F_.fullsort_scores(fac, self.target_item_embedding.weight[:self.target_num_items]).view(-1)
-
-    @torch.no_grad()
     def _full_sort_operands(self, interaction):
-        """(user factors, slab0, slab1) of ``full_sort_predict``'s contraction (``full_sort_rank`` scores them in column passes)."""
+        """(user factors, slab0, slab1) of the all-items contraction: what ``ContractionScoring`` derives ``full_sort_predict`` /
+        ``full_sort_topk`` / ``full_sort_rank`` from."""
         user_e = F_.gather_rows(self.target_user_embedding.weight, interaction[self.TARGET_USER_ID])
         return self._factors(user_e, 'target'), self.target_item_embedding.weight[:self.target_num_items], None
-
-    @torch.no_grad()
-    def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
-        """Evaluation without the [U, N] matrix: (values [U,k], columns [U,k]) of ``full_sort_predict`` after the evaluation mask (column 0
-        and the per-user history columns, CSR with ascending columns), on the dot-product kernel's fused mask + top-k (F_.fullsort_topk;
-        values bit-equal to the unfused scores)."""
-        user_e = F_.gather_rows(self.target_user_embedding.weight, interaction[self.TARGET_USER_ID])
-        return F_.fullsort_topk(self._factors(user_e, 'target'), self.target_item_embedding.weight[:self.target_num_items], None, k=k,
-                                hist_indptr=hist_indptr, hist_cols=hist_cols, exclude_first_col=True)

@@ -13,10 +13,11 @@ from ... import functional as F_
 from ...fused import FusedPointPairStep, rowwise_catch_up
 from ...utils import InputType
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
+from ..contraction import ContractionScoring
 from ..rowwise import RowwiseTraining
 
 
-class CMF(RowwiseTraining, CrossDomainRecommender):
+class CMF(RowwiseTraining, ContractionScoring, CrossDomainRecommender):
     input_type = InputType.POINTWISE
 
     def __init__(self, config, dataset):
@@ -116,20 +117,8 @@ class CMF(RowwiseTraining, CrossDomainRecommender):
         return self.forward(interaction[self.TARGET_USER_ID], interaction[self.TARGET_ITEM_ID])
 
     @torch.no_grad()
-    def full_sort_predict(self, interaction):
-        user_e = F_.gather_rows(self.user_embedding.weight, interaction[self.TARGET_USER_ID])
-        score = F_.fullsort_scores(user_e, self.item_embedding.weight[:self.target_num_items])
-        return score.view(-1)
-
-    @torch.no_grad()
     def _full_sort_operands(self, interaction):
-        """(user_e, slab0, slab1) of ``full_sort_predict``'s contraction (``full_sort_rank`` scores them in column passes)."""
+        """(user_e, slab0, slab1) of the all-items contraction: what ``ContractionScoring`` derives ``full_sort_predict`` / ``full_sort_topk``
+        / ``full_sort_rank`` from."""
         user_e = F_.gather_rows(self.user_embedding.weight, interaction[self.TARGET_USER_ID])
         return user_e, self.item_embedding.weight[:self.target_num_items], None
-
-    @torch.no_grad()
-    def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
-        """(values, columns) [U,k] of ``full_sort_predict`` after recbole's evaluation mask, without the [U, N] matrix."""
-        user_e = F_.gather_rows(self.user_embedding.weight, interaction[self.TARGET_USER_ID])
-        return F_.fullsort_topk(user_e, self.item_embedding.weight[:self.target_num_items], None, k=k,
-                                hist_indptr=hist_indptr, hist_cols=hist_cols, exclude_first_col=True)

@@ -24,12 +24,13 @@ import torch.nn as nn
 from ... import binding as B_
 from ... import functional as F_
 from ...utils import InputType
+from ..contraction import ContractionScoring
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
 from ..rowwise import RowwiseTraining
 from .sscdr import MLPLayers
 
 
-class DCDCSR(RowwiseTraining, CrossDomainRecommender):
+class DCDCSR(RowwiseTraining, ContractionScoring, CrossDomainRecommender):
     input_type = InputType.PAIRWISE
 
     def __init__(self, config, dataset):
@@ -281,20 +282,12 @@ class DCDCSR(RowwiseTraining, CrossDomainRecommender):
 
     _WEIGHT_STEP = 'map'                                              # (the mapping MLP's dense Adam state: the checkpoint's 'weights')
 
-    @torch.no_grad()
-    def full_sort_predict(self, interaction):
-        U, I, tag = self._tables()
-        user_e = F_.gather_rows(U, interaction[getattr(self, f'{tag}_USER_ID')])
-        if tag == 'SOURCE':
-            return F_.fullsort_scores(user_e, I[:self.overlapped_num_items], I[self.target_num_items:])
-        if I is self.affine_embedding:
-            return F_.fullsort_scores(user_e, I)
-        return F_.fullsort_scores(user_e, I[:self.target_num_items])
+    _FULL_SORT_FLAT = False                                           # (``full_sort_predict`` returns [U, N]: dcdcsr.py:244 of the reference)
 
     @torch.no_grad()
     def _full_sort_operands(self, interaction):
-        """(user_e, slab0, slab1) of ``full_sort_predict``'s contraction in its three table cases (``full_sort_rank`` scores them in
-        column passes)."""
+        """(user_e, slab0, slab1) of the all-items contraction in its three table cases: what ``ContractionScoring`` derives
+        ``full_sort_predict`` / ``full_sort_topk`` / ``full_sort_rank`` from."""
         U, I, tag = self._tables()
         user_e = F_.gather_rows(U, interaction[getattr(self, f'{tag}_USER_ID')])
         if tag == 'SOURCE':
@@ -303,25 +296,9 @@ class DCDCSR(RowwiseTraining, CrossDomainRecommender):
             return user_e, I, None
         return user_e, I[:self.target_num_items], None
 
-    def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
-        """Sampled-candidate evaluation on the row-gather kernel: ``predict`` is the plain dot of the phase's two tables (dcdcsr.py:249-280
-        of the reference), the operands of ``_full_sort_operands``."""
-        return self._candidate_scores_native(interaction, cand_indptr, cand_cols)
-
-    @torch.no_grad()
-    def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
-        """Evaluation without the [U, N] matrix: (values [U,k], columns [U,k]) of ``full_sort_predict`` after the evaluation mask (column 0
-        and the per-user history columns, CSR with ascending columns) -- the same three table cases, on the dot-product kernel's fused
-        mask + top-k (F_.fullsort_topk, as EMCDR's: values bit-equal to the unfused scores, no catalogue threshold of its own)."""
-        U, I, tag = self._tables()
-        user_e = F_.gather_rows(U, interaction[getattr(self, f'{tag}_USER_ID')])
-        if tag == 'SOURCE':
-            slab0, slab1 = I[:self.overlapped_num_items], I[self.target_num_items:]
-        elif I is self.affine_embedding:
-            slab0, slab1 = I, None
-        else:
-            slab0, slab1 = I[:self.target_num_items], None
-        return F_.fullsort_topk(user_e, slab0, slab1, k=k, hist_indptr=hist_indptr, hist_cols=hist_cols, exclude_first_col=True)
+    # Sampled-candidate evaluation on the row-gather kernel: ``predict`` is the plain dot of the phase's two tables (dcdcsr.py:249-280 of the
+    # reference), the operands of ``_full_sort_operands``.
+    candidate_scores = ContractionScoring.candidate_scores_from_operands
 
     @torch.no_grad()
     def predict(self, interaction):

@@ -14,11 +14,12 @@ from ... import binding as B_
 from ... import functional as F_
 from ...fused import FusedBPRStep, FusedMapStep, FusedPointStep, KMajorBPRStep, KMajorPointStep, OPT_ADAGRAD, rowwise_catch_up
 from ...utils import InputType
+from ..contraction import ContractionScoring
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
 from ..rowwise import RowwiseTraining
 
 
-class EMCDR(RowwiseTraining, CrossDomainRecommender):
+class EMCDR(RowwiseTraining, ContractionScoring, CrossDomainRecommender):
 
     def __init__(self, config, dataset):
         super().__init__(config, dataset)
@@ -491,24 +492,19 @@ class EMCDR(RowwiseTraining, CrossDomainRecommender):
         user_e = F_.gather_rows(self.target_user_embedding.weight, user)
         return user_e, self.apply_mapping(self.source_item_embedding.weight[:OI]), self.target_item_embedding.weight[OI:TI]
 
-    def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
-        """Sampled-candidate evaluation on the row-gather kernel: ``predict`` is the plain dot in every phase and both overlap modes
-        (emcdr.py:178-206 of the reference), of the operands of ``_full_sort_operands`` (OVERLAP: the mapping MLP runs once per user, or
-        once per shared item row, not once per pair)."""
-        return self._candidate_scores_native(interaction, cand_indptr, cand_cols)
+    # Sampled-candidate evaluation on the row-gather kernel: ``predict`` is the plain dot in every phase and both overlap modes
+    # (emcdr.py:178-206 of the reference), of the operands of ``_full_sort_operands`` (OVERLAP: the mapping MLP runs once per user, or once
+    # per shared item row, not once per pair).
+    candidate_scores = ContractionScoring.candidate_scores_from_operands
 
     @torch.no_grad()
     def full_sort_predict(self, interaction):
         self._whole_tables_only('full_sort_predict')
-        user_e, slab0, slab1 = self._full_sort_operands(interaction)
-        return F_.fullsort_scores(user_e, slab0 if slab0.shape[0] else None, slab1).view(-1)
+        return super().full_sort_predict(interaction)
 
     @torch.no_grad()
     def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
-        """Evaluation without the [U, N] matrix: (values [U,k], columns [U,k]) of ``full_sort_predict`` after recbole's
-        mask (column 0 and the per-user history columns, CSR with ascending columns) -- what ``Trainer.evaluate`` needs."""
+        """``ContractionScoring.full_sort_topk``; over row shards when a dist group is set (``_dist_full_sort_topk``)."""
         if self._dist_group() is not None:
             return self._dist_full_sort_topk(interaction, k, hist_indptr, hist_cols)
-        user_e, slab0, slab1 = self._full_sort_operands(interaction)
-        return F_.fullsort_topk(user_e, slab0 if slab0.shape[0] else None, slab1, k=k, hist_indptr=hist_indptr,
-                                hist_cols=hist_cols, exclude_first_col=True)
+        return super().full_sort_topk(interaction, k, hist_indptr, hist_cols)

@@ -23,6 +23,7 @@ import torch.nn as nn
 from ... import binding as B_
 from ... import functional as F_
 from ...utils import InputType
+from ..contraction import ContractionScoring
 from ..crossdomain_recommender import CrossDomainRecommender, xavier_normal_initialization
 from ..rowwise import RowwiseTraining
 
@@ -45,7 +46,7 @@ class MLPLayers(nn.Module):
         return x
 
 
-class SSCDR(RowwiseTraining, CrossDomainRecommender):
+class SSCDR(RowwiseTraining, ContractionScoring, CrossDomainRecommender):
     input_type = InputType.PAIRWISE
 
     def __init__(self, config, dataset):
@@ -396,7 +397,7 @@ class SSCDR(RowwiseTraining, CrossDomainRecommender):
 
     def _eval_item_cache(self):
         """Inside an evaluation bracket: {'items': the normalised item operand as one buffer, 'sqnorm': its squared row norms, formed when
-        ``full_sort_topk`` first asks}.  None outside."""
+        ``_rank_col_sqnorm`` first asks}.  None outside."""
         if self.training or not self.__dict__.get('_eval_frozen', False):
             return None
         cache = self.__dict__.get('_eval_items')
@@ -425,7 +426,8 @@ class SSCDR(RowwiseTraining, CrossDomainRecommender):
         return True
 
     def _rank_col_sqnorm(self):
-        """``full_sort_rank``: the column norms of the cached item operand, formed once per evaluation bracket (None outside one)."""
+        """``full_sort_rank`` and ``full_sort_topk``: the column norms of the cached item operand, formed once per evaluation bracket by
+        whichever asks first (None outside one)."""
         cache = self._eval_item_cache()
         if cache is None:
             return None
@@ -433,11 +435,10 @@ class SSCDR(RowwiseTraining, CrossDomainRecommender):
             cache['sqnorm'] = F_.row_sqnorm(cache['items'])
         return cache['sqnorm']
 
-    def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
-        """Sampled-candidate evaluation on the row-gather kernel in its distance form: ``predict`` is -sum (u - i)^2 over the normalised
-        rows (sscdr.py:127-128, 197-226 of the reference), the operands of ``_full_sort_operands`` (inside an evaluation bracket the cached
-        normalised item buffer; the mapping MLP runs once per user, not once per pair)."""
-        return self._candidate_scores_native(interaction, cand_indptr, cand_cols)
+    # Sampled-candidate evaluation on the row-gather kernel in its distance form: ``predict`` is -sum (u - i)^2 over the normalised rows
+    # (sscdr.py:127-128, 197-226 of the reference), the operands of ``_full_sort_operands`` (inside an evaluation bracket the cached
+    # normalised item buffer; the mapping MLP runs once per user, not once per pair).
+    candidate_scores = ContractionScoring.candidate_scores_from_operands
 
     @torch.no_grad()
     def full_sort_predict(self, interaction):
@@ -455,11 +456,5 @@ class SSCDR(RowwiseTraining, CrossDomainRecommender):
         if N < self.__dict__.get('fullsort_topk_min_items', F_.SQDIST_TOPK_MIN_ITEMS):
             uid = interaction[self.SOURCE_USER_ID if self.phase == 'SOURCE' else self.TARGET_USER_ID]
             return F_.masked_topk(self.full_sort_predict(interaction).view(uid.numel(), -1), k, hist_indptr, hist_cols)
-        ue, s0, s1 = self._full_sort_operands(interaction)
-        cache = self._eval_item_cache()
-        sq = None
-        if cache is not None:
-            if cache['sqnorm'] is None:
-                cache['sqnorm'] = F_.row_sqnorm(cache['items'])
-            sq = cache['sqnorm']
-        return F_.fullsort_neg_sqdist_topk(ue, s0, s1, k=k, hist_indptr=hist_indptr, hist_cols=hist_cols, col_sqnorm=sq)
+        return F_.fullsort_neg_sqdist_topk(*self._scored_operands(interaction), k=k, hist_indptr=hist_indptr, hist_cols=hist_cols,
+                                           col_sqnorm=self._rank_col_sqnorm())

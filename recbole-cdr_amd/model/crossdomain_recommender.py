@@ -81,33 +81,16 @@ class CrossDomainRecommender(nn.Module):
     # [U, N] floats one ``rank_rows`` pass may hold when the scores are not a contraction (64 M = 256 MB: the staging of the native passes)
     RANK_ROWS_MAX_SCORES = 64 << 20
 
-    def _rank_distance_form(self):
-        """True when ``_full_sort_operands`` are scored by the distance (SSCDR), not the dot product."""
-        return False
-
-    def _rank_col_sqnorm(self):
-        return None
-
     @torch.no_grad()
     def full_sort_rank(self, interaction, pos_indptr, pos_cols, hist_indptr=None, hist_cols=None, predict_fallback=None):
         """``(pos_score [P], gt, eq, eq_before [P] int32, n_unmasked [U] int32)`` of the ground-truth positives (a CSR over the
         interaction's users, ascending distinct columns) over ``full_sort_predict`` after the evaluation mask (column 0 and the per-user
         history CSR): the contract of ``functional.fullsort_rank``; what ``Trainer.evaluate`` derives any ``topk``, MAP and GAUC from.
-        A model whose score is a contraction (``_full_sort_operands``) never forms the [U, N] matrix; the others score chunks of users
-        with ``full_sort_predict`` -- ``predict_fallback(interaction, n_user)`` where that raises NotImplementedError -- and count with
-        ``functional.rank_rows``."""
+        A model whose score is a contraction never forms the [U, N] matrix (``contraction.ContractionScoring.full_sort_rank``); this
+        default scores chunks of users with ``full_sort_predict`` -- ``predict_fallback(interaction, n_user)`` where that raises
+        NotImplementedError -- and counts with ``functional.rank_rows``."""
         from .. import functional as F_
-        if self.__dict__.get('_dist_cfg') not in (None, False):
-            raise NotImplementedError(f"{type(self).__name__}.full_sort_rank does not shard its tables: config['dist_group'] is not "
-                                      f"supported (one GPU)")
-        if hasattr(self, '_full_sort_operands'):
-            user_e, slab0, slab1 = self._full_sort_operands(interaction)
-            slab0 = slab0 if slab0 is not None and slab0.shape[0] else None
-            slab1 = slab1 if slab1 is not None and slab1.shape[0] else None
-            if self._rank_distance_form():
-                return F_.fullsort_neg_sqdist_rank(user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols,
-                                                   col_sqnorm=self._rank_col_sqnorm())
-            return F_.fullsort_rank(user_e, slab0, slab1, pos_indptr, pos_cols, hist_indptr, hist_cols)
+        self._one_gpu_only('full_sort_rank')
         n_user = len(interaction)
         dev = pos_cols.device
         P = pos_cols.numel()
@@ -137,10 +120,13 @@ class CrossDomainRecommender(nn.Module):
             s = e
         return (score,) + out
 
-    def _candidate_guard(self):
+    def _one_gpu_only(self, what):
         if self.__dict__.get('_dist_cfg') not in (None, False):
-            raise NotImplementedError(f"{type(self).__name__}.candidate_scores does not shard its tables: config['dist_group'] is not "
+            raise NotImplementedError(f"{type(self).__name__}.{what} does not shard its tables: config['dist_group'] is not "
                                       f"supported (one GPU)")
+
+    def _candidate_guard(self):
+        CrossDomainRecommender._one_gpu_only(self, 'candidate_scores')
 
     @torch.no_grad()
     def candidate_scores(self, interaction, cand_indptr, cand_cols, chunk=4096):
@@ -151,7 +137,7 @@ class CrossDomainRecommender(nn.Module):
         ``Trainer._predict_all_pairs`` chunks).  The columns are those of ``full_sort_predict`` in the model's phase: target item ids, and
         in a SOURCE phase the source loader's revoked columns (ids from ``overlapped_num_items`` on shifted down by the target-only count).
         A model whose ``predict`` is the same function of ``_full_sort_operands`` as ``functional.candidate_scores`` computes overrides this
-        with ``_candidate_scores_native``."""
+        with ``contraction.ContractionScoring.candidate_scores_from_operands``."""
         self._candidate_guard()
         C = cand_cols.numel()
         dev = cand_cols.device
@@ -166,17 +152,6 @@ class CrossDomainRecommender(nn.Module):
             pairs.update({self.TARGET_ITEM_ID: cand_cols})
         step = max(int(chunk), 1)
         return torch.cat([self.predict(pairs[s:s + step]).reshape(-1) for s in range(0, C, step)]).float()
-
-    @torch.no_grad()
-    def _candidate_scores_native(self, interaction, cand_indptr, cand_cols):
-        """``candidate_scores`` on the row-gather kernel: the user operand of ``_full_sort_operands`` is formed once per user (EMCDR's and
-        SSCDR's mapping MLP runs U times, not once per pair) and each candidate reads one item row."""
-        from .. import functional as F_
-        self._candidate_guard()
-        user_e, slab0, slab1 = self._full_sort_operands(interaction)
-        slab0 = slab0 if slab0 is not None and slab0.shape[0] else None
-        slab1 = slab1 if slab1 is not None and slab1.shape[0] else None
-        return F_.candidate_scores(user_e, slab0, slab1, cand_indptr, cand_cols, distance=self._rank_distance_form())
 
     def other_parameter(self):
         if hasattr(self, 'other_parameter_name'):

@@ -866,16 +866,20 @@ class Trainer:
         indptr[1:] = torch.cumsum(torch.bincount(key // span, minlength=n_user), 0)
         return indptr, (key % span).contiguous()
 
+    def _positives_csr(self, positive_u, positive_i, n_user):
+        """(indptr [n_user + 1], columns [P], positives per user [n_user], user row of each positive [P]) of a batch's ground truth"""
+        pu = torch.as_tensor(positive_u, device=self.device, dtype=torch.int64)
+        pi = torch.as_tensor(positive_i, device=self.device, dtype=torch.int64)
+        pindptr, pcols = self._csr(pu, pi, n_user)
+        npos = pindptr[1:] - pindptr[:-1]
+        return pindptr, pcols, npos, torch.repeat_interleave(torch.arange(n_user, device=pu.device), npos)
+
     def _rank_counts(self, interaction, n_user, history_index, positive_u, positive_i):
         """(user of each positive [P], gt, eq, eq_before [P], n_unmasked [U], positives per user [U]) of one batch: the model's
         ``full_sort_rank`` on a GPU; a torch restatement over the materialised matrix where there is none (plumbing, as the unfused
         route)."""
         dev = self.device
-        pu = torch.as_tensor(positive_u, device=dev, dtype=torch.int64)
-        pi = torch.as_tensor(positive_i, device=dev, dtype=torch.int64)
-        pindptr, pcols = self._csr(pu, pi, n_user)
-        npos = pindptr[1:] - pindptr[:-1]
-        prow = torch.repeat_interleave(torch.arange(n_user, device=dev), npos)
+        pindptr, pcols, npos, prow = self._positives_csr(positive_u, positive_i, n_user)
         hindptr = hcols = hrows = None
         if history_index is not None:
             hr, hc = (torch.as_tensor(t, device=dev, dtype=torch.int64) for t in history_index)
@@ -946,11 +950,7 @@ class Trainer:
             interaction = interaction.to(self.device)
             n_user = len(interaction)
             cand_indptr, cand_cols = cand_indptr.to(self.device), cand_cols.to(self.device)
-            pu = torch.as_tensor(positive_u, device=self.device, dtype=torch.int64)
-            pi = torch.as_tensor(positive_i, device=self.device, dtype=torch.int64)
-            pindptr, pcols = self._csr(pu, pi, n_user)
-            npos = pindptr[1:] - pindptr[:-1]
-            prow = torch.repeat_interleave(torch.arange(n_user, device=pu.device), npos)
+            pindptr, pcols, npos, prow = self._positives_csr(positive_u, positive_i, n_user)
             scores = self.model.candidate_scores(interaction, cand_indptr, cand_cols, chunk).float().contiguous()
             rank = F_.candidate_rank if on_gpu else F_.candidate_rank_reference
             _score, gt, eq, eqb, nun = rank(cand_indptr, cand_cols, scores, pindptr, pcols)

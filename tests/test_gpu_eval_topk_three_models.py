@@ -1,5 +1,7 @@
 """SSCDR, CLFM and DCDCSR evaluate through ``full_sort_topk`` like the other seven models: for every phase / mode case their
-``full_sort_predict`` distinguishes, the fused mask + top-k returns the bits of ``torch.topk`` over the masked ``full_sort_predict``;
+``full_sort_predict`` distinguishes, the fused mask + top-k returns the bits of ``torch.topk`` over the masked ``full_sort_predict``
+-- and so it does for the other contraction models, EMCDR (every phase, both overlap modes), CMF and BiTGCF, and for all six
+``full_sort_rank`` returns the positives' bits of ``full_sort_predict`` and the counts of ``trainer.rank_counts_reference`` over it;
 ``Trainer.evaluate`` returns the same metrics on both routes; SSCDR's evaluation bracket normalises its item table once and leaves nothing
 behind.  Small models: 501 target items, 70 users of width 64 (the fused kernel itself runs), a non-empty history."""
 import pickle
@@ -84,7 +86,31 @@ def _assert_topk_equals_masked_predict(model, interaction, seed=0):
     assert got_v.shape == (U, K) and got_i.dtype == torch.int64
     assert torch.equal(got_v, want_v), (got_v - want_v).abs().max()
     assert torch.equal(torch.gather(scores, 1, got_i), want_v)
+    _assert_rank_equals_counts_over_masked_predict(model, interaction, scores, best, got_i, indptr, hist, g)
     return N
+
+
+def _assert_rank_equals_counts_over_masked_predict(model, interaction, masked, best, top, hist_indptr, hist_cols, g):
+    """``full_sort_rank`` under the same history: ``pos_score`` is the bits of the positives' entries of ``full_sort_predict``, the counts
+    are ``trainer.rank_counts_reference`` over the same matrix with the masked entries NaN.  Positives per user: the best and the k-th
+    unmasked column, three random ones, and the best column of all -- which the history masks (-1 three times)."""
+    from recbole_cdr_amd.trainer.trainer import rank_counts_reference
+    U, N = masked.shape
+    pos = torch.cat([top[:, :1], top[:, K - 1:], best[:, :1], torch.randint(0, N, (U, 3), device=DEV, generator=g)], 1)
+    cols = [torch.unique(pos[u]) for u in range(U)]
+    pindptr = torch.zeros(U + 1, dtype=torch.int64, device=DEV)
+    pindptr[1:] = torch.cumsum(torch.tensor([c.numel() for c in cols], device=DEV), 0)
+    pcols = torch.cat(cols)
+    prow = torch.repeat_interleave(torch.arange(U, device=DEV), pindptr[1:] - pindptr[:-1])
+    full = model.full_sort_predict(interaction).view(U, -1)
+    nan = torch.where(masked == NEG_INF, torch.full_like(masked, float('nan')), masked)
+    assert bool((nan[prow, pcols] != nan[prow, pcols]).any()) and bool((masked != NEG_INF)[:, 1:].any(1).all())
+    score, gt, eq, eqb, nun = model.full_sort_rank(interaction, pindptr, pcols, hist_indptr=hist_indptr, hist_cols=hist_cols)
+    assert torch.equal(score.view(torch.int32), full[prow, pcols].view(torch.int32))
+    _, *want = rank_counts_reference(nan, prow, pcols)
+    for name, a, b in zip(('gt', 'eq', 'eq_before', 'n_unmasked'), (gt, eq, eqb, nun), want):
+        assert a.dtype == b.dtype == torch.int32 and torch.equal(a, b), (name, int((a != b).sum()))
+    assert bool((gt[pcols == top[prow, 0]] == 0).all())                             # the best unmasked column has nothing above it
 
 
 @pytest.mark.parametrize('mode', ['overlap_users', 'overlap_items'])
@@ -135,6 +161,31 @@ def test_dcdcsr_full_sort_topk_equals_topk_of_masked_predict_in_its_three_table_
     assert _assert_topk_equals_masked_predict(model, _interaction(model, ids)) == ids.target_num_items
     model.set_phase('TARGET')                                                    # the second visit builds affine_embedding
     assert model.affine_embedding is not None
+    assert _assert_topk_equals_masked_predict(model, _interaction(model, ids)) == ids.target_num_items
+
+
+@pytest.mark.parametrize('mode', ['overlap_users', 'overlap_items'])
+@pytest.mark.parametrize('phase', ['SOURCE', 'TARGET', 'OVERLAP'])
+def test_emcdr_full_sort_topk_equals_topk_of_masked_predict(phase, mode):
+    """SOURCE and OVERLAP / overlap_items score two row ranges, OVERLAP a mapped operand; with one shared item (overlap_users) the first
+    range of SOURCE is the PAD row alone."""
+    import test_gpu_candidate_eval as cand
+    model, _, n_cols, _, _, _ = cand._emcdr_case(phase, mode)
+    ids = _ids(mode)
+    assert _assert_topk_equals_masked_predict(model, _interaction(model, ids, source=phase == 'SOURCE')) == n_cols
+    assert n_cols == (ids.OI + ids.SOI if phase == 'SOURCE' else ids.target_num_items)
+
+
+def test_cmf_full_sort_topk_equals_topk_of_masked_predict():
+    import test_gpu_candidate_eval as cand
+    ids, model = cand._default_route_model('CMF', cmf_width=D)
+    assert _assert_topk_equals_masked_predict(model, _interaction(model, ids)) == ids.target_num_items
+
+
+def test_bitgcf_full_sort_topk_equals_topk_of_masked_predict():
+    import test_gpu_candidate_eval as cand
+    ids, model = cand._bitgcf_model(n_layers=1)                                  # rows of 2 x 32 floats
+    assert model.get_restore_e()[0].shape[1] == D
     assert _assert_topk_equals_masked_predict(model, _interaction(model, ids)) == ids.target_num_items
 
 

@@ -69,6 +69,16 @@ def test_the_three_models_evaluate_through_full_sort_topk(name):
     assert callable(getattr(cls, 'full_sort_topk')) and callable(getattr(cls, 'full_sort_predict'))
 
 
+@pytest.mark.parametrize('name', ['CMF', 'CLFM', 'BiTGCF', 'DCDCSR'])
+def test_a_contraction_model_states_its_operands_and_inherits_the_routes(name):
+    """These four score the plain dot of ``_full_sort_operands``: the routes come from ``ContractionScoring``, not from copies per model."""
+    from recbole_cdr_amd.model.contraction import ContractionScoring
+    cls = get_model(name)
+    assert '_full_sort_operands' in vars(cls)
+    assert 'full_sort_predict' not in vars(cls) and 'full_sort_topk' not in vars(cls)
+    assert cls.full_sort_predict is ContractionScoring.full_sort_predict and cls.full_sort_topk is ContractionScoring.full_sort_topk
+
+
 def test_sscdr_brackets_an_evaluation():
     cls = get_model('SSCDR')
     assert callable(getattr(cls, 'freeze_for_eval')) and callable(getattr(cls, 'unfreeze_eval'))
