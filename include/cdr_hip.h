@@ -288,6 +288,42 @@ int cdr_rank_rows_f32(void* stream, const float* scores, int64_t ld, int64_t U, 
                       int exclude_first_col, const float* pos_score, int32_t* gt, int32_t* eq, int32_t* eq_before,
                       int32_t* n_unmasked, int accumulate);
 
+/* Mask + top-k lists beyond the fused entries' k <= 64 (1 <= k <= 1024) without the [U, N] score matrix: candidate lists for a
+ * re-ranker, recbole's topk: [10, 50, 100] as lists (recbole Trainer._full_sort_batch_eval's two masks, then Collector's torch.topk).
+ * S is the matrix cdr_fullsort_scores_f32 (the neg_sqdist form: cdr_fullsort_neg_sqdist_f32 against the concatenated slabs) writes for
+ * the same operands.  A column is UNMASKED when it is not column 0 (with exclude_first_col), not in the user's history range
+ * (hist_indptr [U+1] / hist_cols, ascending inside a user's range, or both NULL) and its score is neither NaN nor -inf; +inf is an
+ * ordinary score.  out_vals [U, k] / out_idx [U, k] are the first k unmasked columns of each user in the TOTAL order "score descending,
+ * then column ascending" -- torch.sort(descending, stable) of the masked matrix -- with values bit-equal to S and (-inf, -1) behind
+ * the last entry of a user with fewer than k unmasked columns.  The order is total: the result does not depend on launch geometry,
+ * pass order or run, and it is the order of cdr_fullsort_rank_f32: a positive with 1 + gt + eq_before = r <= k is out_idx[u, r - 1].
+ * The scores are formed in column passes into the workspace by the launches the score entries use for the same columns (as the rank
+ * entries form them; ONE walk, a catalogue that fits one pass is scored once) and selected there (csrc/cdr_topk_wide.h).
+ * 1 <= k <= 1024, U < 2^30, n0 + n1 < 2^31; a bad argument or a workspace below *_workspace_bytes gets CDR_EINVAL with an error text
+ * and nothing is launched.  Workspace: the pass staging (at most 256 MiB + 256 bytes) plus the partial lists (8 k bytes per user and
+ * column stripe; stripes <= max(1, ceil(1024 / U))); the neg_sqdist form adds ((4 * (U + n0 + n1) + 255) & ~255) bytes for the row
+ * norms (col_sqnorm: [n0 + n1] from cdr_row_sqnorm_f32 of the slabs, or NULL: computed into the workspace).                        */
+int cdr_fullsort_topk_wide_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int k, size_t* bytes);
+int cdr_fullsort_topk_wide_f32(void* stream, const float* user_e, int64_t U, int D,
+                               const float* slab0, int64_t n0, const float* slab1, int64_t n1, int k,
+                               const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                               float* out_vals /* [U,k] */, int64_t* out_idx /* [U,k] */, void* workspace, size_t workspace_bytes);
+int cdr_fullsort_neg_sqdist_topk_wide_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int k, size_t* bytes);
+int cdr_fullsort_neg_sqdist_topk_wide_f32(void* stream, const float* user_e, int64_t U, int D,
+                                          const float* slab0, int64_t n0, const float* slab1, int64_t n1,
+                                          const float* col_sqnorm, int k,
+                                          const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                                          float* out_vals /* [U,k] */, int64_t* out_idx /* [U,k] */, void* workspace, size_t workspace_bytes);
+/* The same lists over scores that are in memory: columns [col_off, col_off + N) of the catalogue as scores[U, N] with leading
+ * dimension ld >= N (the models whose score is not a contraction; one column pass of a larger matrix); the mask and idx are in
+ * catalogue columns.  accumulate = 0 writes this block's lists to vals / idx, accumulate = 1 merges them into the lists vals / idx
+ * hold from earlier calls: calls over disjoint column blocks in any order give the lists of the whole catalogue.  col_off + N < 2^31.
+ * Workspace (the partial lists): cdr_topk_rows_workspace_bytes(U, N, k).                                                             */
+int cdr_topk_rows_workspace_bytes(int64_t U, int64_t N, int k, size_t* bytes);
+int cdr_topk_rows_f32(void* stream, const float* scores, int64_t ld, int64_t U, int64_t N, int64_t col_off, int k,
+                      const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                      float* vals /* [U,k] */, int64_t* idx /* [U,k] */, int accumulate, void* workspace, size_t workspace_bytes);
+
 /* Sampled-candidate evaluation (eval_args mode uniN / popN): what recbole_cdr/data/utils.py:149-151 hands to recbole's
  * NegSampleEvalDataLoader and Trainer._neg_sample_batch_eval (third-party) -- predict on every expanded (user, candidate) pair, scattered
  * into a [U, tot_item_num] matrix of -inf -- without the pairs and without the matrix.  The candidates of U users are a CSR: cand_indptr

@@ -253,6 +253,15 @@ _SIGNATURES = {
     'cdr_rank_rows_f32': [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr,
                           _c_ptr, _c_ptr, _c_int],
     'cdr_candidate_scores_f32': [_c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr],
+    'cdr_fullsort_topk_wide_workspace_bytes': [_c_i64, _c_int, _c_i64, _c_i64, _c_int, _c_ptr],
+    'cdr_fullsort_topk_wide_f32': [_c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_int, _c_ptr, _c_ptr, _c_int,
+                                   _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
+    'cdr_fullsort_neg_sqdist_topk_wide_workspace_bytes': [_c_i64, _c_int, _c_i64, _c_i64, _c_int, _c_ptr],
+    'cdr_fullsort_neg_sqdist_topk_wide_f32': [_c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_int, _c_ptr,
+                                              _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, ctypes.c_size_t],
+    'cdr_topk_rows_workspace_bytes': [_c_i64, _c_i64, _c_int, _c_ptr],
+    'cdr_topk_rows_f32': [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_int, _c_ptr,
+                          ctypes.c_size_t],
     'cdr_candidate_rank_f32': [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                _c_ptr],
     'cdr_dedup_workspace_bytes': [_c_i64, _c_ptr],

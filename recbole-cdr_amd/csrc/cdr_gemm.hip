@@ -1428,3 +1428,121 @@ extern "C" int cdr_rank_rows_f32(void* stream, const float* scores, int64_t ld, 
         if (int rc = rank_init_launch(s, 1, U, pos_indptr, pos_cols, mk, const_cast<float*>(pos_score), gt, eq, eq_before, n_unmasked)) return rc;
     return rank_rows_launch(s, scores, ld, U, N, col_off, pos_indptr, pos_cols, mk, pos_score, gt, eq, eq_before, n_unmasked);
 }
+
+// ---- mask + top-k lists beyond one wave (k <= 1024) over the masked catalogue -------------------------------------------------------
+// The rank route's walk with a selection in place of the count: the same column passes through score_block into the same staging (so the
+// listed values are the bits of S), each pass selected by wide_topk_launch (cdr_topk_wide.h) and merged into the running lists in
+// out_vals / out_idx, whose last entry is the next pass's starting threshold.  One walk: nothing has to be known before it.
+#include "cdr_topk_wide.h"
+
+namespace {
+
+// the columns of the longest pass (what rank_ws_bytes sizes the staging for)
+static int64_t wide_pass_max(int64_t U, const int64_t n[2]) {
+    const int64_t pass = rank_pass_cols(U);
+    int64_t cols = 0;
+    for (int i = 0; i < 2; ++i) {
+        const int64_t c = n[i] < pass ? n[i] : pass;
+        if (c > cols) cols = c;
+    }
+    return cols;
+}
+
+static int fullsort_topk_wide_impl(const topk_epi& epi, hipStream_t s, const float* user_e, int64_t U, int D, const float* const slab[2],
+                                   const int64_t n[2], int k, const topk_mask& mk, float* out_vals, int64_t* out_idx, float* sbuf,
+                                   unsigned long long* part) {
+    const int64_t pass = rank_pass_cols(U);
+    int64_t col_off = 0;
+    int accumulate = 0;
+    for (int i = 0; i < 2; ++i) {
+        for (int64_t c = 0; c < n[i]; c += pass) {
+            const int64_t cn = n[i] - c < pass ? n[i] - c : pass;
+            if (int rc = score_block(s, user_e, U, D, slab[i] + c * D, cn, sbuf, cn, epi.rown, epi.rown ? epi.coln + col_off + c : nullptr)) return rc;
+            if (int rc = wide_topk_launch(s, sbuf, cn, U, cn, col_off + c, k, mk, out_vals, out_idx, accumulate, part)) return rc;
+            accumulate = 1;
+        }
+        col_off += n[i];
+    }
+    return CDR_OK;
+}
+
+}  // namespace
+
+#define CDR_WIDE_CHECK_SIZES()                                                                                          \
+    CDR_CHECK_ARG(bytes && U > 0 && U < ((int64_t)1 << 30) && D > 0 && k >= 1 && k <= kWideMaxK);                       \
+    CDR_CHECK_ARG(n0 >= 0 && n1 >= 0 && n0 + n1 > 0 && n0 + n1 < ((int64_t)1 << 31));                                   \
+    const int64_t n[2] = {n0, n1}
+
+#define CDR_WIDE_CHECK_COMMON()                                                                                         \
+    CDR_CHECK_ARG(user_e && out_vals && out_idx && workspace && U > 0 && U < ((int64_t)1 << 30) && D > 0);              \
+    CDR_CHECK_ARG(k >= 1 && k <= kWideMaxK);                                                                            \
+    CDR_CHECK_ARG((slab0 && n0 > 0) || (slab1 && n1 > 0));                                                              \
+    CDR_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));                                                  \
+    const int64_t n[2] = {slab0 ? (n0 > 0 ? n0 : 0) : 0, slab1 ? (n1 > 0 ? n1 : 0) : 0};                                \
+    const float* const slab[2] = {slab0, slab1};                                                                        \
+    CDR_CHECK_ARG(n[0] + n[1] < ((int64_t)1 << 31))
+
+extern "C" int cdr_fullsort_topk_wide_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int k, size_t* bytes) {
+    CDR_WIDE_CHECK_SIZES();
+    *bytes = rank_ws_bytes(U, n) + wide_part_bytes(U, wide_pass_max(U, n), k);
+    return CDR_OK;
+}
+
+extern "C" int cdr_fullsort_topk_wide_f32(void* stream, const float* user_e, int64_t U, int D, const float* slab0, int64_t n0,
+                                          const float* slab1, int64_t n1, int k, const int64_t* hist_indptr, const int64_t* hist_cols,
+                                          int exclude_first_col, float* out_vals, int64_t* out_idx, void* workspace,
+                                          size_t workspace_bytes) {
+    CDR_WIDE_CHECK_COMMON();
+    const size_t staging = rank_ws_bytes(U, n), need = staging + wide_part_bytes(U, wide_pass_max(U, n), k);
+    if (workspace_bytes < need) { cdr_set_error("%s: workspace %zu < %zu bytes", __func__, workspace_bytes, need); return CDR_EINVAL; }
+    return fullsort_topk_wide_impl(topk_epi{nullptr, nullptr}, (hipStream_t)stream, user_e, U, D, slab, n, k,
+                                   topk_mask{hist_indptr, hist_cols, exclude_first_col}, out_vals, out_idx, (float*)workspace,
+                                   (unsigned long long*)((char*)workspace + staging));
+}
+
+extern "C" int cdr_fullsort_neg_sqdist_topk_wide_workspace_bytes(int64_t U, int D, int64_t n0, int64_t n1, int k, size_t* bytes) {
+    CDR_WIDE_CHECK_SIZES();
+    *bytes = rank_ws_bytes(U, n) + wide_part_bytes(U, wide_pass_max(U, n), k) + sqdist_norm_bytes(U, n0 + n1);
+    return CDR_OK;
+}
+
+extern "C" int cdr_fullsort_neg_sqdist_topk_wide_f32(void* stream, const float* user_e, int64_t U, int D, const float* slab0, int64_t n0,
+                                                     const float* slab1, int64_t n1, const float* col_sqnorm, int k,
+                                                     const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col,
+                                                     float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes) {
+    CDR_WIDE_CHECK_COMMON();
+    const size_t staging = rank_ws_bytes(U, n), lists = wide_part_bytes(U, wide_pass_max(U, n), k);
+    const size_t need = staging + lists + sqdist_norm_bytes(U, n[0] + n[1]);
+    if (workspace_bytes < need) { cdr_set_error("%s: workspace %zu < %zu bytes", __func__, workspace_bytes, need); return CDR_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    float* rown = (float*)((char*)workspace + staging + lists);
+    float* coln = rown + U;
+    if (int rc = row_sqnorm_launch(s, user_e, U, D, rown)) return rc;
+    if (!col_sqnorm) {
+        if (n[0] > 0) { if (int rc = row_sqnorm_launch(s, slab0, n[0], D, coln)) return rc; }
+        if (n[1] > 0) { if (int rc = row_sqnorm_launch(s, slab1, n[1], D, coln + n[0])) return rc; }
+    }
+    return fullsort_topk_wide_impl(topk_epi{rown, col_sqnorm ? col_sqnorm : coln}, s, user_e, U, D, slab, n, k,
+                                   topk_mask{hist_indptr, hist_cols, exclude_first_col}, out_vals, out_idx, (float*)workspace,
+                                   (unsigned long long*)((char*)workspace + staging));
+}
+#undef CDR_WIDE_CHECK_SIZES
+#undef CDR_WIDE_CHECK_COMMON
+
+extern "C" int cdr_topk_rows_workspace_bytes(int64_t U, int64_t N, int k, size_t* bytes) {
+    CDR_CHECK_ARG(bytes && U > 0 && U < ((int64_t)1 << 30) && N > 0 && N < ((int64_t)1 << 31) && k >= 1 && k <= kWideMaxK);
+    *bytes = wide_part_bytes(U, N, k);
+    return CDR_OK;
+}
+
+extern "C" int cdr_topk_rows_f32(void* stream, const float* scores, int64_t ld, int64_t U, int64_t N, int64_t col_off, int k,
+                                 const int64_t* hist_indptr, const int64_t* hist_cols, int exclude_first_col, float* vals, int64_t* idx,
+                                 int accumulate, void* workspace, size_t workspace_bytes) {
+    CDR_CHECK_ARG(scores && vals && idx && workspace && U > 0 && U < ((int64_t)1 << 30) && N > 0 && ld >= N);
+    CDR_CHECK_ARG(k >= 1 && k <= kWideMaxK && col_off >= 0 && col_off + N < ((int64_t)1 << 31));
+    CDR_CHECK_ARG((hist_indptr == nullptr) == (hist_cols == nullptr));
+    const size_t need = wide_part_bytes(U, N, k);
+    if (workspace_bytes < need) { cdr_set_error("%s: workspace %zu < %zu bytes", __func__, workspace_bytes, need); return CDR_EINVAL; }
+    return wide_topk_launch((hipStream_t)stream, scores, ld, U, N, col_off, k, topk_mask{hist_indptr, hist_cols, exclude_first_col}, vals,
+                            idx, accumulate ? 1 : 0, (unsigned long long*)workspace);
+}

@@ -31,6 +31,25 @@ __device__ __forceinline__ int64_t rank_lower_bound(const int64_t* __restrict__ 
     return lo;
 }
 
+// The evaluation mask of user u over the global columns [g0, g1), g1 - g0 <= kRankCols, as a bitmap in the workgroup's LDS (bit c - g0
+// set: column c is masked).  Called by all 256 threads; the bitmap is complete after the caller's next __syncthreads().
+__device__ __forceinline__ void rank_build_mask(unsigned* maskw, const topk_mask& mk, int64_t u, int64_t g0, int64_t g1) {
+    const int tid = threadIdx.x;
+    __syncthreads();                                                     // the previous block's LDS reads are over
+    for (int i = tid; i < kRankMaskWords; i += 256) maskw[i] = 0u;
+    __syncthreads();
+    if (mk.exclude_col0 && g0 == 0 && tid == 0) atomicOr(&maskw[0], 1u);
+    if (mk.indptr) {
+        const int64_t h1 = mk.indptr[u + 1];
+        for (int64_t h = rank_lower_bound(mk.cols, mk.indptr[u], h1, g0) + tid; h < h1; h += 256) {
+            const int64_t c = mk.cols[h];
+            if (c >= g1) break;
+            if (c < g0) continue;                                        // (a history that is not ascending: never outside the bitmap)
+            atomicOr(&maskw[(c - g0) >> 5], 1u << ((c - g0) & 31));
+        }
+    }
+}
+
 // stage 0: pos_score[p] = NaN (a positive whose column no pass covers stays flagged).  stage 1: the counters start at 0, at -1 for the
 // positives that are masked or whose score is NaN, and n_unmasked at 0.  One wave per user.
 __global__ __launch_bounds__(256) void rank_init_kernel(int stage, int64_t U, const int64_t* __restrict__ pos_indptr,
@@ -164,19 +183,7 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict_
         const int64_t u = w / n_chunks;
         const int64_t c0 = (w % n_chunks) * kRankCols, c1 = c0 + kRankCols < n ? c0 + kRankCols : n;
         const int64_t g0 = col_off + c0, g1 = col_off + c1;               // the block's global columns
-        __syncthreads();                                                 // the previous block's LDS reads are over
-        for (int i = tid; i < kRankMaskWords; i += 256) maskw[i] = 0u;
-        __syncthreads();
-        if (mk.exclude_col0 && g0 == 0 && tid == 0) atomicOr(&maskw[0], 1u);
-        if (mk.indptr) {
-            const int64_t h1 = mk.indptr[u + 1];
-            for (int64_t h = rank_lower_bound(mk.cols, mk.indptr[u], h1, g0) + tid; h < h1; h += 256) {
-                const int64_t c = mk.cols[h];
-                if (c >= g1) break;
-                if (c < g0) continue;                                    // (a history that is not ascending: never outside the bitmap)
-                atomicOr(&maskw[(c - g0) >> 5], 1u << ((c - g0) & 31));
-            }
-        }
+        rank_build_mask(maskw, mk, u, g0, g1);
         rank_walk(rank_src_rows{scores + u * ld, maskw, c0, col_off, mk}, u, c0, c1, pos_indptr[u], pos_indptr[u + 1], pos_cols, pos_score, gt,
                   eq, eqb, n_unmasked, thr_s, col_s, cnt);
     }

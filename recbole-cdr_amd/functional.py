@@ -874,6 +874,93 @@ def fullsort_neg_sqdist_topk(user_e, slab0, slab1=None, k=10, hist_indptr=None, 
     return (vals[:U], idx[:U]) if rows != U else (vals, idx)
 
 
+# Widest list of the fused mask + top-k entries (a user's list is one wave: csrc/cdr_topk.h), and of the wide route behind them
+# (csrc/cdr_topk_wide.h).  A model's ``full_sort_topk`` takes the wide route for FUSED_TOPK_MAX < k <= WIDE_TOPK_MAX.
+FUSED_TOPK_MAX = 64
+WIDE_TOPK_MAX = 1024
+
+
+def _wide_outputs(dev, U, k):
+    return torch.empty(U, k, device=dev, dtype=torch.float32), torch.empty(U, k, device=dev, dtype=torch.int64)
+
+
+def _wide_hist(U, hist_indptr, hist_cols):
+    if (hist_indptr is None) != (hist_cols is None):
+        raise ValueError('hist_indptr and hist_cols go together: both or neither')
+    if hist_indptr is not None:
+        assert hist_indptr.dtype == torch.int64 and hist_cols.dtype == torch.int64 and hist_indptr.numel() == U + 1
+        if hist_cols.numel() == 0:
+            hist_cols = hist_cols.new_zeros(1)           # (a real buffer behind the pointer; no range reaches it)
+    return hist_indptr, hist_cols
+
+
+def _fullsort_topk_wide(entry, user_e, slab0, slab1, k, hist_indptr, hist_cols, exclude_first_col, col_sqnorm):
+    _dev_check(user_e, slab0, slab1, hist_indptr, hist_cols, col_sqnorm)
+    k = int(k)
+    user_e, U, D, n0, n1, head = _fullsort_head(user_e, slab0, slab1)
+    hist_indptr, hist_cols = _wide_hist(U, hist_indptr, hist_cols)
+    dev = user_e.device
+    need = ctypes.c_size_t(0)
+    B_._check(getattr(B_.load(), entry + '_workspace_bytes')(U, D, n0, n1, k, ctypes.byref(need)), entry + '_workspace_bytes')
+    ws = _grown_workspace(_topk_ws, (), dev, need.value)
+    vals, idx = _wide_outputs(dev, U, k)
+    if entry == 'cdr_fullsort_neg_sqdist_topk_wide':
+        if col_sqnorm is not None:
+            assert col_sqnorm.dtype == torch.float32 and col_sqnorm.numel() == n0 + n1
+        head = head + (B_.f32(col_sqnorm),)
+    B_.call(entry + '_f32', *head, k, B_.i64(hist_indptr), B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals), B_.i64(idx),
+            B_.raw(ws), ws.numel())
+    return vals, idx
+
+
+def fullsort_topk_wide(user_e, slab0, slab1=None, k=100, hist_indptr=None, hist_cols=None, exclude_first_col=True):
+    """``fullsort_topk`` for lists of up to ``WIDE_TOPK_MAX`` = 1,024 entries, never holding more than the staging of one column pass
+    (cdr_fullsort_topk_wide_f32): ``(values [U,k] float32, columns [U,k] int64)``, per user the first k unmasked columns of
+    ``fullsort_scores(user_e, slab0, slab1)`` in the total order score descending, then column ascending -- ``torch.sort(descending=True,
+    stable=True)`` of the masked matrix.  Unmasked: not column 0 (``exclude_first_col``), not in the user's ascending history columns,
+    score neither NaN nor -inf.  Values are bit-equal to the matrix's entries; (-inf, -1) pads a row with fewer than k unmasked
+    columns.  The order is ``fullsort_rank``'s: a positive with ``1 + gt + eq_before = r <= k`` sits at ``idx[u, r - 1]``."""
+    return _fullsort_topk_wide('cdr_fullsort_topk_wide', user_e, slab0, slab1, k, hist_indptr, hist_cols, exclude_first_col, None)
+
+
+def fullsort_neg_sqdist_topk_wide(user_e, slab0, slab1=None, k=100, hist_indptr=None, hist_cols=None, exclude_first_col=True,
+                                  col_sqnorm=None):
+    """``fullsort_topk_wide`` over SSCDR's distances, ``fullsort_neg_sqdist(user_e, cat(slab0, slab1))``
+    (cdr_fullsort_neg_sqdist_topk_wide_f32).  ``col_sqnorm``: ``row_sqnorm`` of the concatenated slabs when the caller keeps it;
+    computed per call otherwise (the same bits)."""
+    return _fullsort_topk_wide('cdr_fullsort_neg_sqdist_topk_wide', user_e, slab0, slab1, k, hist_indptr, hist_cols, exclude_first_col,
+                               col_sqnorm)
+
+
+def topk_rows(scores, k, hist_indptr=None, hist_cols=None, exclude_first_col=True, col_off=0, out=None, accumulate=False):
+    """The lists of ``fullsort_topk_wide`` over scores that are in memory (cdr_topk_rows_f32): ``scores`` [U, N] (rows may be strided:
+    ``scores.stride(0) >= N``) holds columns ``[col_off, col_off + N)`` of the catalogue; the mask and the returned columns are catalogue
+    columns.  ``out`` = the ``(vals, idx)`` of an earlier call with ``accumulate=True`` merges this block's lists into them: calls over
+    disjoint column blocks, in any order, give the whole catalogue's lists.  ``scores`` is only read.  Returns ``(vals, idx)``."""
+    _dev_check(scores, hist_indptr, hist_cols)
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.stride(1) == 1
+    k = int(k)
+    U, N = scores.shape
+    ld = scores.stride(0) if U > 1 else max(scores.stride(0), N)
+    assert ld >= N
+    dev = scores.device
+    hist_indptr, hist_cols = _wide_hist(U, hist_indptr, hist_cols)
+    need = ctypes.c_size_t(0)
+    B_._check(B_.load().cdr_topk_rows_workspace_bytes(U, N, k, ctypes.byref(need)), 'cdr_topk_rows_workspace_bytes')
+    ws = _grown_workspace(_topk_ws, (), dev, need.value)
+    if out is None:
+        assert not accumulate, 'accumulate=True continues the lists of an earlier call: pass them as out'
+        vals, idx = _wide_outputs(dev, U, k)
+    else:
+        vals, idx = out
+        assert vals.dtype == torch.float32 and idx.dtype == torch.int64 and vals.is_contiguous() and idx.is_contiguous()
+        assert tuple(vals.shape) == (U, k) and tuple(idx.shape) == (U, k)
+    B_._alive.append(scores)
+    B_.call('cdr_topk_rows_f32', B_.stream(), B_._c_ptr(scores.data_ptr()), ld, U, N, int(col_off), k, B_.i64(hist_indptr),
+            B_.i64(hist_cols), 1 if exclude_first_col else 0, B_.f32(vals), B_.i64(idx), 1 if accumulate else 0, B_.raw(ws), ws.numel())
+    return vals, idx
+
+
 def _rank_outputs(dev, U, P):
     """(pos_score, gt, eq, eq_before, n_unmasked); one spare element so that P = 0 still hands the entries real buffers"""
     return (torch.empty(P + 1, device=dev, dtype=torch.float32), torch.empty(P + 1, device=dev, dtype=torch.int32),

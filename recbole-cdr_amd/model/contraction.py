@@ -35,9 +35,22 @@ class ContractionScoring:
     def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
         """Evaluation without the [U, N] matrix: (values [U,k], columns [U,k]) of ``full_sort_predict`` after recbole's mask (column 0 and
         the per-user history columns, CSR with ascending columns) on the scoring kernel's fused mask + top-k (``F_.fullsort_topk``: values
-        bit-equal to the unfused scores, no catalogue threshold) -- what ``Trainer.evaluate`` needs."""
+        bit-equal to the unfused scores, no catalogue threshold) -- what ``Trainer.evaluate`` needs.  Lists beyond its 64 entries:
+        ``full_sort_topk_wide``."""
+        if k > F_.FUSED_TOPK_MAX:
+            return self.full_sort_topk_wide(interaction, k, hist_indptr, hist_cols)
         return F_.fullsort_topk(*self._scored_operands(interaction), k=k, hist_indptr=hist_indptr, hist_cols=hist_cols,
                                 exclude_first_col=True)
+
+    @torch.no_grad()
+    def full_sort_topk_wide(self, interaction, k, hist_indptr=None, hist_cols=None, predict_fallback=None):
+        """``CrossDomainRecommender.full_sort_topk_wide`` without the [U, N] matrix: the operands are scored in column passes and selected
+        there (``F_.fullsort_topk_wide``; SSCDR: the distance form with the column norms of its evaluation bracket)."""
+        self._one_gpu_only('full_sort_topk_wide')
+        user_e, slab0, slab1 = self._scored_operands(interaction)
+        if self._rank_distance_form():
+            return F_.fullsort_neg_sqdist_topk_wide(user_e, slab0, slab1, k, hist_indptr, hist_cols, col_sqnorm=self._rank_col_sqnorm())
+        return F_.fullsort_topk_wide(user_e, slab0, slab1, k, hist_indptr, hist_cols)
 
     @torch.no_grad()
     def full_sort_rank(self, interaction, pos_indptr, pos_cols, hist_indptr=None, hist_cols=None, predict_fallback=None):

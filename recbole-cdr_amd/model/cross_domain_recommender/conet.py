@@ -250,6 +250,8 @@ class CoNet(CrossDomainRecommender):
         (F_.conet_fullsort_topk; values bit-equal to the unfused scores).  A tower outside that kernel's range, or ``fullsort_fused = False``,
         and a catalogue below ``F_.TOWER_TOPK_MIN_ITEMS`` (where the unfused route measures faster; ``self.fullsort_topk_min_items`` overrides)
         take ``full_sort_predict`` + mask + ``torch.topk``: the method always exists and always agrees with the unfused path."""
+        if k > F_.FUSED_TOPK_MAX:                # beyond the fused kernels' lists: the wide route, whatever the catalogue size
+            return self.full_sort_topk_wide(interaction, k, hist_indptr, hist_cols)
         D = self.latent_dim
         lin1, lo = self.target_crossunit_linear[0], self.target_outputunit[0]
         W1 = lin1.weight

@@ -300,6 +300,8 @@ class DTCDR(RowwiseTraining, CrossDomainRecommender):
         [U, N] matrix where the kernel takes the tower and the catalogue has at least ``F_.TOWER_TOPK_MIN_ITEMS`` items (below it the unfused
         route measures faster; ``self.fullsort_topk_min_items`` overrides) -- values bit-equal to the unfused scores; mask + ``torch.topk``
         of ``full_sort_predict`` otherwise."""
+        if k > F_.FUSED_TOPK_MAX:                # beyond the fused kernels' lists: the wide route, whatever the catalogue size
+            return self.full_sort_topk_wide(interaction, k, hist_indptr, hist_cols)
         uid = interaction[self.TARGET_USER_ID]
         lins = [m for m in self.target_mlp_layers.mlp_layers if isinstance(m, nn.Linear)]
         if not self._fullsort_kernel_ok(lins[1:]) or \

@@ -506,5 +506,8 @@ class EMCDR(RowwiseTraining, ContractionScoring, CrossDomainRecommender):
     def full_sort_topk(self, interaction, k, hist_indptr=None, hist_cols=None):
         """``ContractionScoring.full_sort_topk``; over row shards when a dist group is set (``_dist_full_sort_topk``)."""
         if self._dist_group() is not None:
+            if k > F_.FUSED_TOPK_MAX:
+                raise NotImplementedError(f"EMCDR.full_sort_topk over row shards (config['dist_group']) lists at most "
+                                          f"{F_.FUSED_TOPK_MAX} items per user, not k = {k}")
             return self._dist_full_sort_topk(interaction, k, hist_indptr, hist_cols)
         return super().full_sort_topk(interaction, k, hist_indptr, hist_cols)

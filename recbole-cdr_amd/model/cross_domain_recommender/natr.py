@@ -215,6 +215,8 @@ class NATR(CrossDomainRecommender):
         """(values [U,k], item ids [U,k]) of ``full_sort_predict`` after the evaluation mask (PAD column, per-user history CSR): the fused
         launch from ``F_.NATR_TOPK_MIN_ITEMS`` target items on (``self.fullsort_topk_min_items`` overrides) -- values bit-equal to the
         unfused scores; mask + ``torch.topk`` of ``full_sort_predict`` below it and for widths outside the kernel's range."""
+        if k > F_.FUSED_TOPK_MAX:                # beyond the fused kernels' lists: the wide route, whatever the catalogue size
+            return self.full_sort_topk_wide(interaction, k, hist_indptr, hist_cols)
         uid = interaction[self.TARGET_USER_ID].reshape(-1)
         N = int(self.target_num_items)
         if not F_.natr_fullsort_supported(self.target_embedding_size) or \

@@ -451,6 +451,8 @@ class SSCDR(RowwiseTraining, ContractionScoring, CrossDomainRecommender):
         ``F_.SQDIST_TOPK_MIN_ITEMS`` items on (``self.fullsort_topk_min_items`` overrides) without the [U, N] matrix and without the cat of
         the item ranges: the scoring kernel's distance epilogue under the fused mask + top-k (F_.fullsort_neg_sqdist_topk; values bit-equal
         to the unfused scores).  Below it ``full_sort_predict`` + mask + ``torch.topk``."""
+        if k > F_.FUSED_TOPK_MAX:                # beyond the fused kernels' lists: the wide route, whatever the catalogue size
+            return self.full_sort_topk_wide(interaction, k, hist_indptr, hist_cols)
         OI, TI = self.overlapped_num_items, self.target_num_items
         N = OI + self.total_num_items - TI if self.phase == 'SOURCE' else TI
         if N < self.__dict__.get('fullsort_topk_min_items', F_.SQDIST_TOPK_MIN_ITEMS):

@@ -120,6 +120,40 @@ class CrossDomainRecommender(nn.Module):
             s = e
         return (score,) + out
 
+    @torch.no_grad()
+    def full_sort_topk_wide(self, interaction, k, hist_indptr=None, hist_cols=None, predict_fallback=None):
+        """``(values [U,k] float32, columns [U,k] int64)`` for lists beyond the fused kernels' 64 entries (``1 <= k <=
+        functional.WIDE_TOPK_MAX``): per user the first k unmasked columns of ``full_sort_predict`` after the evaluation mask (column 0 and
+        the per-user history CSR) in the order score descending, then column ascending; (-inf, -1) pads a short row -- the contract of
+        ``functional.fullsort_topk_wide``, and the tie rule of ``full_sort_rank``.  A model whose score is a contraction never forms the
+        [U, N] matrix (``contraction.ContractionScoring.full_sort_topk_wide``); this default scores chunks of users with
+        ``full_sort_predict`` -- ``predict_fallback(interaction, n_user)`` where that raises NotImplementedError -- of at most
+        ``RANK_ROWS_MAX_SCORES`` scores and selects with ``functional.topk_rows``."""
+        from .. import functional as F_
+        self._one_gpu_only('full_sort_topk_wide')
+        n_user = len(interaction)
+        vals = idx = None
+        step = None
+        s = 0
+        while s < n_user:
+            e = n_user if step is None else min(s + step, n_user)
+            part = interaction if (s, e) == (0, n_user) else interaction[s:e]
+            try:
+                scores = self.full_sort_predict(part).view(e - s, -1)
+            except NotImplementedError:
+                if predict_fallback is None:
+                    raise
+                scores = predict_fallback(part, e - s)
+            if step is None and n_user * scores.shape[1] > self.RANK_ROWS_MAX_SCORES and n_user > 1:
+                step = max(self.RANK_ROWS_MAX_SCORES // scores.shape[1], 1)      # (this first block was too tall: redo it in chunks)
+                continue
+            if vals is None:
+                vals, idx = F_._wide_outputs(scores.device, n_user, int(k))
+            F_.topk_rows(scores.float().contiguous(), k, hist_indptr[s:e + 1].contiguous() if hist_indptr is not None else None, hist_cols,
+                         out=(vals[s:e], idx[s:e]))
+            s = e
+        return vals, idx
+
     def _one_gpu_only(self, what):
         if self.__dict__.get('_dist_cfg') not in (None, False):
             raise NotImplementedError(f"{type(self).__name__}.{what} does not shard its tables: config['dist_group'] is not "

@@ -310,6 +310,7 @@ TOPK_METRICS = ('recall', 'mrr', 'ndcg', 'hit', 'precision', 'map')  # keys name
 VALUE_METRICS = ('auc', 'mae', 'rmse', 'logloss')
 NON_ACCURACY_METRICS = ('itemcoverage', 'averagepopularity', 'shannonentropy', 'giniindex', 'tailpercentage')
 FUSED_TOPK_MAX = 64                   # the fused mask + top-k kernels keep a list in one wave: k <= 64
+WIDE_TOPK_MAX = 1024                  # the wide mask + top-k behind them (model.full_sort_topk_wide): k <= 1024
 
 
 def resolve_metrics(config):
@@ -448,6 +449,7 @@ class Trainer:
         # config['metrics'] (absent: recall / hit / precision / mrr / ndcg, as always) and config['eval_route']: 'auto' keeps the model's
         # mask + top-k route whenever it can answer (no gauc, and max(topk) <= 64 or the route is unfused), 'rank' derives every metric
         # from the rank of each positive over the masked catalogue (model.full_sort_rank: any k, MAP, GAUC), 'topk' insists on the lists
+        # (max(topk) <= 1024; above 64 on a GPU they come from model.full_sort_topk_wide)
         self.metrics = resolve_metrics(config)
         self.eval_route = resolve_eval_route(config, self.metrics)
         # config['eval_args']['mode'] (full | uniN | popN): which evaluation loader data.dataloader.eval_loader_for builds for the target
@@ -747,9 +749,10 @@ class Trainer:
             out.k_major = km
         return out
 
-    def _topk_hits(self, interaction, n_user, history_index, positive_u, positive_i, kmax):
+    def _topk_hits(self, interaction, n_user, history_index, positive_u, positive_i, kmax, wide=False):
         """Hit matrix [U, kmax] and positives per user from the model's fused mask + top-k (no [U, N] score matrix): the
-        history (rows, cols) pairs become a CSR with ascending columns, positives are matched by sorted (user, item) keys."""
+        history (rows, cols) pairs become a CSR with ascending columns, positives are matched by sorted (user, item) keys.  ``wide``: the
+        list comes from ``full_sort_topk_wide`` (kmax > 64; every model has it, those with ``predict`` only through ``_predict_all_pairs``)."""
         dev = self.device
         N = int(self.model.target_num_items) if hasattr(self.model, 'target_num_items') else None
         indptr = cols = None
@@ -762,7 +765,11 @@ class Trainer:
             indptr[1:] = torch.cumsum(torch.bincount(key // span, minlength=n_user), 0)
             if cols.numel() == 0:
                 indptr = cols = None
-        _vals, idx = self.model.full_sort_topk(interaction, kmax, hist_indptr=indptr, hist_cols=cols)
+        if wide:
+            _vals, idx = self.model.full_sort_topk_wide(interaction, kmax, hist_indptr=indptr, hist_cols=cols,
+                                                        predict_fallback=self._predict_all_pairs)
+        else:
+            _vals, idx = self.model.full_sort_topk(interaction, kmax, hist_indptr=indptr, hist_cols=cols)
         pu = torch.as_tensor(positive_u, device=dev, dtype=torch.int64)
         pi = torch.as_tensor(positive_i, device=dev, dtype=torch.int64)
         span = max(int(idx.max()) + 1, int(pi.max()) + 1 if pi.numel() else 1, N or 1)
@@ -824,12 +831,16 @@ class Trainer:
         names = self.metrics if self.metrics is not None else DEFAULT_METRICS
         if self._takes_rank_route(fused, kmax):
             return self._evaluate_batches_by_rank(eval_data, kmax, names)
+        # eval_route='topk' beyond the fused kernels' 64 entries: on a GPU the list comes from the wide mask + top-k, for every model (a
+        # model without full_sort_topk included: its scores go through the selection in chunks, not as one [U, N] matrix)
+        wide = (self.eval_route == 'topk' and self.fused_topk and FUSED_TOPK_MAX < kmax <= WIDE_TOPK_MAX
+                and torch.device(self.device).type == 'cuda' and hasattr(self.model, 'full_sort_topk_wide'))
         hits, pos_len = [], []
         for interaction, history_index, positive_u, positive_i in eval_data:
             interaction = interaction.to(self.device)
             n_user = len(interaction)
-            if fused:
-                h, npos = self._topk_hits(interaction, n_user, history_index, positive_u, positive_i, kmax)
+            if fused or wide:
+                h, npos = self._topk_hits(interaction, n_user, history_index, positive_u, positive_i, kmax, wide=wide)
                 hits.append(h); pos_len.append(npos)
                 continue
             try:
@@ -851,8 +862,8 @@ class Trainer:
         if self.eval_route == 'rank':
             return True
         if self.eval_route == 'topk':
-            if fused and kmax > FUSED_TOPK_MAX:
-                raise ValueError(f"eval_route='topk': the fused mask + top-k holds k <= {FUSED_TOPK_MAX}, topk asks for {kmax}; use "
+            if fused and kmax > WIDE_TOPK_MAX:
+                raise ValueError(f"eval_route='topk': the mask + top-k lists hold k <= {WIDE_TOPK_MAX}, topk asks for {kmax}; use "
                                  f"eval_route='rank' or 'auto', or fused_topk=False")
             return False
         return gauc or (fused and kmax > FUSED_TOPK_MAX)
