@@ -350,6 +350,25 @@ int cdr_candidate_rank_f32(void* stream, int64_t U, const int64_t* cand_indptr /
                            const int64_t* pos_cols /* [P] */, int64_t P, float* pos_score /* [P] */,
                            int32_t* gt, int32_t* eq, int32_t* eq_before /* [P] each */, int32_t* n_cand /* [U] */);
 
+/* Non-accuracy metrics from the top-k lists: the accumulation that recbole/evaluator/metrics.py ItemCoverage, AveragePopularity,
+ * ShannonEntropy, GiniIndex and TailPercentage (third-party) take from the collector's rec.items matrix and dataset.item_counter on the
+ * host -- a Counter over every recommended item, two gathers of [U, k] -- folded batch by batch into integers on the device.
+ * idx [U, kmax] with leading dimension ld >= kmax holds one batch's lists (the out_idx of the top-k entries above); an entry < 0 is a pad
+ * and counts nowhere.  pos_bucket [kmax] (device) is the bucket of each list position, 0 <= pos_bucket[j] < n_bucket: the distinct values
+ * of topk, ascending, cut the positions into buckets, and the count inside the first k positions is the sum over the buckets up to k's
+ * (taken by the caller).  For every entry item = idx[u, j] with 0 <= item < N:
+ *   rec_count[pos_bucket[j], item] += 1;   col_pop[j] += item_count[item];   col_tail[j] += tail[item]  (tail and col_tail both NULL: skipped).
+ * An entry >= N (or a bucket outside [0, n_bucket)) is skipped and counted in n_bad[0]: nothing is indexed with an unchecked value.
+ * The call ADDS to the buffers (zeroed by the caller before the first batch).  Integer atomics only -- per-workgroup LDS sums, then one
+ * 64-bit global add per column and workgroup; one 4-byte global add per entry for the histogram -- so the buffers are bit-reproducible
+ * and independent of launch geometry and batch cut.  1 <= kmax <= 1024, U < 2^30, 1 <= N < 2^31, 1 <= n_bucket <= kmax; a NULL required
+ * pointer or a bad size gets CDR_EINVAL with an error text before anything is launched; U = 0 launches nothing.                      */
+int cdr_list_stats_accumulate(void* stream, const int64_t* idx, int64_t ld, int64_t U, int kmax,
+                              const int32_t* pos_bucket /* [kmax], device */, int n_bucket, int64_t N,
+                              const int64_t* item_count /* [N] */, const uint8_t* tail /* [N] or NULL */,
+                              int32_t* rec_count /* [n_bucket, N] */, int64_t* col_pop /* [kmax] */,
+                              int64_t* col_tail /* [kmax] or NULL */, int64_t* n_bad /* [1] */);
+
 /* ---- elementwise helpers used by the model mirrors --------------------------------------------------------- */
 /* d/dx of act given y = act(x): gx = gy * act'(y)  (tanh: 1-y^2, relu: y>0, sigmoid: y(1-y)) ; in place allowed */
 int cdr_act_bwd(void* stream, int act, const float* y, const float* gy, float* gx, int64_t n);

@@ -1129,6 +1129,107 @@ def candidate_rank_reference(cand_indptr, cand_cols, scores, pos_indptr, pos_col
     return t.float(), gt, eq, eqb, nun
 
 
+LIST_STATS_MAX_K = 1024
+LIST_METRICS = ('itemcoverage', 'averagepopularity', 'shannonentropy', 'giniindex', 'tailpercentage')
+
+
+class ListStats:
+    """recbole's non-accuracy metrics (ItemCoverage, AveragePopularity, ShannonEntropy, GiniIndex, TailPercentage; recbole 1.0.1
+    evaluator/metrics.py, third-party) from the top-k lists of one evaluation, batch after batch, without the lists leaving the device.
+    ``item_counts`` int64 [N]: the training-set count of every column (``data.train_item_counts``); ``topk``: the k values (any order,
+    duplicates allowed); ``tail_mask`` bool [N] (``data.tail_items``): needed by tailpercentage alone.  The buffers -- per (bucket of
+    list positions, item) how often the item was recommended, per position the summed counts and tail flags -- are allocated and
+    zeroed here once; ``add`` folds a batch in, ``result`` turns them into {name@k: float}."""
+
+    def __init__(self, item_counts, topk, tail_mask=None):
+        counts = torch.as_tensor(item_counts)
+        if counts.dim() != 1 or counts.numel() == 0 or counts.dtype.is_floating_point or counts.dtype == torch.bool:
+            raise ValueError('ListStats: item_counts must be a non-empty 1-D integer vector')
+        self.ks = sorted({int(k) for k in topk})
+        if not self.ks or self.ks[0] < 1 or self.ks[-1] > LIST_STATS_MAX_K:
+            raise ValueError(f'ListStats: every topk value must be in [1, {LIST_STATS_MAX_K}], got {list(topk)}')
+        dev = counts.device
+        self.item_counts = counts.to(torch.int64).contiguous()
+        self.N, self.kmax, self.topk = counts.numel(), self.ks[-1], [int(k) for k in topk]
+        # bucket b holds the positions [ks[b - 1], ks[b]): the count inside the first ks[b] positions is the sum over the buckets 0..b
+        self.pos_bucket = torch.searchsorted(torch.tensor(self.ks), torch.arange(self.kmax), right=True).to(device=dev, dtype=torch.int32)
+        self.tail = None
+        if tail_mask is not None:
+            if tail_mask.shape != counts.shape:
+                raise ValueError('ListStats: tail_mask must have the shape of item_counts')
+            self.tail = tail_mask.to(device=dev, dtype=torch.uint8).contiguous()
+        self.rec_count = torch.zeros(len(self.ks), self.N, device=dev, dtype=torch.int32)
+        self.col_pop = torch.zeros(self.kmax, device=dev, dtype=torch.int64)
+        self.col_tail = torch.zeros(self.kmax, device=dev, dtype=torch.int64) if self.tail is not None else None
+        self.n_bad = torch.zeros(1, device=dev, dtype=torch.int64)
+
+    def add(self, idx, vals=None):
+        """Fold the lists ``idx`` int64 [U, >= kmax] in (their first kmax positions).  An entry -1 is a pad; with ``vals`` (the lists'
+        scores, as ``torch.topk`` of a masked matrix returns them) an entry whose value is -inf is one too.  One native launch on a GPU,
+        ``add_reference`` where there is no device to run it on (``device: cpu``)."""
+        assert idx.dtype == torch.int64 and idx.dim() == 2 and idx.shape[1] >= self.kmax and idx.device == self.item_counts.device
+        if vals is not None:
+            idx = torch.where(vals == -float('inf'), torch.full_like(idx, -1), idx)
+        if idx.shape[0] == 0:
+            return
+        if not idx.is_cuda:
+            return self.add_reference(idx)
+        if idx.stride(1) != 1 or idx.stride(0) < self.kmax:
+            idx = idx.contiguous()
+        B_.call('cdr_list_stats_accumulate', B_.stream(), B_._c_ptr(idx.data_ptr()), idx.stride(0), idx.shape[0], self.kmax,
+                B_.raw(self.pos_bucket), len(self.ks), self.N, B_.i64(self.item_counts), B_.raw(self.tail), B_.raw(self.rec_count),
+                B_.i64(self.col_pop), B_.i64(self.col_tail), B_.i64(self.n_bad))
+
+    def add_reference(self, idx):
+        """``cdr_list_stats_accumulate`` in plain torch, on any device (plumbing, like ``candidate_rank_reference``)."""
+        sub = idx[:, :self.kmax]
+        ok = (sub >= 0) & (sub < self.N)
+        self.n_bad += (sub >= self.N).sum()
+        safe = sub.clamp(0, self.N - 1)
+        flat = (self.pos_bucket.long().unsqueeze(0) * self.N + safe)[ok]
+        self.rec_count.view(-1).index_add_(0, flat, torch.ones_like(flat, dtype=torch.int32))
+        self.col_pop += (self.item_counts[safe] * ok).sum(0)
+        if self.tail is not None:
+            self.col_tail += (self.tail[safe].long() * ok).sum(0)
+
+    def result(self, n_users, names=LIST_METRICS):
+        """{name@k: Python float} for every k of ``topk`` over the ``n_users`` users whose lists were added, in float64 on the device: the
+        one copy of this arithmetic (recbole's formulas, the division of the entropy by the number of recommended items included).
+        T_k = n_users * k whatever the pads.  Raises ValueError when an added entry was >= the count vector's length."""
+        names = [str(n).lower() for n in names]
+        bad = int(self.n_bad)
+        if bad:
+            raise ValueError(f'ListStats: {bad} list entries are item ids >= {self.N}, the length of the item count vector: the counts '
+                             f'must span the column space of the lists')
+        if 'tailpercentage' in names and self.col_tail is None:
+            raise ValueError('ListStats: tailpercentage needs tail_mask (data.tail_items)')
+        keys, vals = [], []
+        c = torch.zeros(self.N, device=self.rec_count.device, dtype=torch.int64)
+        pos = torch.arange(1, self.N + 1, device=c.device, dtype=torch.float64)
+        for b, k in enumerate(self.ks):
+            c += self.rec_count[b]
+            T = float(n_users) * k
+            R = (c > 0).sum().double()
+            for name in names:
+                if name == 'itemcoverage':
+                    value = R                   # (divided by N on the host below: a device division by a scalar multiplies by 1 / N)
+                elif name == 'averagepopularity':
+                    value = self.col_pop[:k].sum().double() / T
+                elif name == 'tailpercentage':
+                    value = self.col_tail[:k].sum().double() / T
+                elif name == 'shannonentropy':
+                    p = c.double() / T
+                    value = torch.where(c > 0, -p * torch.log(p), torch.zeros_like(p)).sum() / R
+                elif name == 'giniindex':
+                    # the positive counts ascending at the positions N - R + 1 .. N: the zeros in front of them add nothing
+                    value = ((2 * pos - self.N - 1) * torch.sort(c).values.double()).sum() / T / self.N
+                else:
+                    continue
+                keys.append(f'{name}@{k}'); vals.append(value)
+        vals = torch.stack(vals).tolist() if vals else []
+        return {key: v / self.N if key.startswith('itemcoverage@') else v for key, v in zip(keys, vals)}
+
+
 # ---------------------------------------------------------------------------------------------------- CoNet pieces
 class GatherConcat2(Function):
     """cat([A[ida], B[idb]], dim=1) in one buffer (conet.py:106-111) with the dense scatter-add backward."""

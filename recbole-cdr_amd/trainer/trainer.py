@@ -308,6 +308,10 @@ def early_stopping(value, best, cur_step, max_step, bigger=True):
 DEFAULT_METRICS = ('recall', 'hit', 'precision', 'mrr', 'ndcg')     # what evaluate returned before config['metrics'] was read
 TOPK_METRICS = ('recall', 'mrr', 'ndcg', 'hit', 'precision', 'map')  # keys name@k
 VALUE_METRICS = ('auc', 'mae', 'rmse', 'logloss')
+# recbole's non-accuracy metrics (keys name@k): the only ones that need to know WHICH items are in the lists, so they are answered by the
+# list route alone -- the lists of the mask + top-k kernels (k <= 1024) folded on the device by functional.ListStats, batch after batch --
+# and they need the training set's item counts over the evaluated loader's column space: config['item_counts'] (data.train_item_counts of
+# the target domain's training pairs), or the loader's own ``item_counts`` attribute.  tailpercentage reads config['tail_ratio'] (0.1).
 NON_ACCURACY_METRICS = ('itemcoverage', 'averagepopularity', 'shannonentropy', 'giniindex', 'tailpercentage')
 FUSED_TOPK_MAX = 64                   # the fused mask + top-k kernels keep a list in one wave: k <= 64
 WIDE_TOPK_MAX = 1024                  # the wide mask + top-k behind them (model.full_sort_topk_wide): k <= 1024
@@ -316,7 +320,8 @@ WIDE_TOPK_MAX = 1024                  # the wide mask + top-k behind them (model
 def resolve_metrics(config):
     """config['metrics'] as recbole reads it (a name or a list of names, any letter case) -> tuple of lower-case names, or None when the
     key is absent (evaluate then returns what it always did).  Refused here, before anything is built: recbole's value metrics (they need
-    the labeled evaluation mode), its non-accuracy metrics (they need the training set's item counts), unknown names."""
+    the labeled evaluation mode), its non-accuracy metrics unless config['item_counts'] is given (they need the training set's item
+    counts), unknown names."""
     if 'metrics' not in config or config['metrics'] is None:
         return None
     names = config['metrics']
@@ -327,11 +332,12 @@ def resolve_metrics(config):
         if m in VALUE_METRICS:
             raise ValueError(f"metrics: {n!r} is a value metric: it needs recbole's labeled evaluation mode, which this trainer does not "
                              f"have (full-sort ranking only)")
-        if m in NON_ACCURACY_METRICS:
+        if m in NON_ACCURACY_METRICS and ('item_counts' not in config or config['item_counts'] is None):
             raise ValueError(f"metrics: {n!r} is a non-accuracy metric: it needs the training set's item counts, which evaluate() is not "
-                             f"given")
-        if m not in TOPK_METRICS and m != 'gauc':
-            raise ValueError(f"metrics: unknown metric {n!r}; supported: {', '.join(TOPK_METRICS)} (keys name@k) and gauc")
+                             f"given: set config['item_counts'] (data.train_item_counts of the target domain's training pairs)")
+        if m not in TOPK_METRICS and m not in NON_ACCURACY_METRICS and m != 'gauc':
+            raise ValueError(f"metrics: unknown metric {n!r}; supported: {', '.join(TOPK_METRICS + NON_ACCURACY_METRICS)} (keys name@k) "
+                             f"and gauc")
         if m not in out:
             out.append(m)
     if not out:
@@ -432,6 +438,7 @@ def rank_counts_reference(scores, pos_rows, pos_cols):
 
 class Trainer:
     metrics = None                    # (class defaults: objects built without __init__ evaluate as before)
+    list_metrics = ()
     eval_route = 'auto'
     learner = 'adam'                  # (class default, as rowwise_adam below)
     rowwise_adam = 'lazy'             # (class default: loops driven on objects built without __init__ keep the lazy row-wise Adam)
@@ -456,6 +463,11 @@ class Trainer:
         # domain; evaluate() itself dispatches on the loader it is handed.  A mode that is not provided is refused here
         self.eval_mode = resolve_eval_mode(config)
         self.device = config['device']
+        # the non-accuracy metrics among config['metrics'] (NON_ACCURACY_METRICS): what they cannot be combined with is refused here
+        self.list_metrics = tuple(m for m in (self.metrics or ()) if m in NON_ACCURACY_METRICS)
+        self.item_counts = None
+        if self.list_metrics:
+            self.item_counts = self._check_list_metrics(config)
         self.weight_decay = config['weight_decay'] if 'weight_decay' in config else 0.0
         self.start_epoch, self.cur_step = 0, 0
         self.best_valid_score = -np.inf if self.valid_metric_bigger else np.inf
@@ -548,6 +560,42 @@ class Trainer:
             warnings.warn('parallel_domains: the SOURCE and TARGET phases of a parallel stage run WITHOUT validation, early stopping, '
                           'best_valid_score updates and callback_fn (evaluation needs every rank); later phases evaluate as usual',
                           stacklevel=2)
+
+    def _check_list_metrics(self, config):
+        """The refusals of the non-accuracy metrics; returns config['item_counts'] as an int64 vector on the trainer's device."""
+        what = f"metrics {', '.join(self.list_metrics)}"
+        if self.eval_route == 'rank':
+            raise ValueError(f"{what}: eval_route='rank' holds no list -- the rank of a positive does not say which items were recommended; "
+                             f"use eval_route='auto' or 'topk'")
+        if max(self.topk) > WIDE_TOPK_MAX:
+            raise ValueError(f"{what}: the mask + top-k lists hold k <= {WIDE_TOPK_MAX}, topk asks for {max(self.topk)}")
+        if self.eval_mode[0] != 'full':
+            raise ValueError(f"{what}: eval_args mode {config['eval_args']['mode']!r} ranks the positives inside sampled candidate lists, "
+                             f"whose positions are not recommendations over the catalogue; use mode 'full'")
+        if 'dist_group' in config and config['dist_group'] not in (None, False):
+            raise ValueError(f"{what}: not available with dist_group (the lists are counted on one GPU only, as on the rank route)")
+        return self._as_item_counts(config['item_counts'])
+
+    def _as_item_counts(self, counts):
+        counts = torch.as_tensor(counts)
+        if counts.dim() != 1 or counts.numel() == 0 or counts.dtype.is_floating_point or counts.dtype == torch.bool:
+            raise ValueError("item_counts must be a non-empty 1-D integer tensor or array: the training-set count of every column of the "
+                             "evaluated loader (data.train_item_counts)")
+        return counts.to(device=self.device, dtype=torch.int64)
+
+    def _list_stats_for(self, eval_data):
+        """The ``functional.ListStats`` of one evaluate call when a non-accuracy metric is asked (None otherwise): the loader's own
+        ``item_counts`` ahead of config['item_counts'], the tail set of config['tail_ratio'] when tailpercentage is asked."""
+        if not self.list_metrics:
+            return None
+        from .. import functional as F_
+        from ..data.popularity import tail_items
+        own = getattr(eval_data, 'item_counts', None)
+        counts = self._as_item_counts(own) if own is not None else self.item_counts
+        tail = None
+        if 'tailpercentage' in self.list_metrics:
+            tail = tail_items(counts, self.config['tail_ratio'] if 'tail_ratio' in self.config else None)
+        return F_.ListStats(counts, self.topk, tail_mask=tail)
 
     # ---- dense mode, one hipGraph replay per step --------------------------------------------------------------------------------
     def _graph_for(self, key, example=None, producer=None):
@@ -749,12 +797,11 @@ class Trainer:
             out.k_major = km
         return out
 
-    def _topk_hits(self, interaction, n_user, history_index, positive_u, positive_i, kmax, wide=False):
-        """Hit matrix [U, kmax] and positives per user from the model's fused mask + top-k (no [U, N] score matrix): the
-        history (rows, cols) pairs become a CSR with ascending columns, positives are matched by sorted (user, item) keys.  ``wide``: the
-        list comes from ``full_sort_topk_wide`` (kmax > 64; every model has it, those with ``predict`` only through ``_predict_all_pairs``)."""
+    def _topk_lists(self, interaction, n_user, history_index, kmax, wide=False):
+        """idx [U, kmax] of the model's fused mask + top-k (no [U, N] score matrix), pads -1: the history (rows, cols) pairs become a CSR
+        with ascending columns.  ``wide``: the list comes from ``full_sort_topk_wide`` (kmax > 64; every model has it, those with
+        ``predict`` only through ``_predict_all_pairs``)."""
         dev = self.device
-        N = int(self.model.target_num_items) if hasattr(self.model, 'target_num_items') else None
         indptr = cols = None
         if history_index is not None:
             rows, hc = (torch.as_tensor(t, device=dev, dtype=torch.int64) for t in history_index)
@@ -770,6 +817,16 @@ class Trainer:
                                                         predict_fallback=self._predict_all_pairs)
         else:
             _vals, idx = self.model.full_sort_topk(interaction, kmax, hist_indptr=indptr, hist_cols=cols)
+        return idx
+
+    def _topk_hits(self, interaction, n_user, history_index, positive_u, positive_i, kmax, wide=False, stats=None):
+        """Hit matrix [U, kmax] and positives per user from ``_topk_lists``: positives are matched by sorted (user, item) keys.  The lists
+        are handed on to ``stats`` (``functional.ListStats``): no second top-k call for the non-accuracy metrics."""
+        dev = self.device
+        N = int(self.model.target_num_items) if hasattr(self.model, 'target_num_items') else None
+        idx = self._topk_lists(interaction, n_user, history_index, kmax, wide=wide)
+        if stats is not None:
+            stats.add(idx)
         pu = torch.as_tensor(positive_u, device=dev, dtype=torch.int64)
         pi = torch.as_tensor(positive_i, device=dev, dtype=torch.int64)
         span = max(int(idx.max()) + 1, int(pi.max()) + 1 if pi.numel() else 1, N or 1)
@@ -792,6 +849,9 @@ class Trainer:
         # dispatch per loader, on its own attribute: a (source full-sort, target sampled) pair of valid loaders evaluates each its way
         sampled = getattr(eval_data, 'eval_mode', 'full') == 'sampled'
         fused = self.fused_topk and hasattr(self.model, 'full_sort_topk') and not sampled
+        if sampled and self.list_metrics:
+            raise ValueError(f"evaluate: metrics {', '.join(self.list_metrics)} cannot be answered on a sampled-candidate loader (its lists "
+                             f"are positions inside a sample); hand evaluate a full-sort loader")
         # recbole cuts the evaluated users so that the [U, N] score matrix fits eval_batch_size entries (ONE user per call over a 10 M-item
         # catalogue at the default 4,096).  The fused mask + top-k path never forms that matrix, so it re-cuts a loader that allows it
         # into throughput-sized batches (config['eval_users_per_batch'], default 1,024; 0 keeps recbole's cut): same users, same metrics
@@ -829,36 +889,65 @@ class Trainer:
 
     def _evaluate_batches(self, eval_data, fused, kmax):
         names = self.metrics if self.metrics is not None else DEFAULT_METRICS
+        # the non-accuracy metrics: the lists of every batch are folded into ``stats`` on the device, the arithmetic comes at the end
+        stats = self._list_stats_for(eval_data)
+        wide = self._takes_wide_lists(kmax)
         if self._takes_rank_route(fused, kmax):
-            return self._evaluate_batches_by_rank(eval_data, kmax, names)
-        # eval_route='topk' beyond the fused kernels' 64 entries: on a GPU the list comes from the wide mask + top-k, for every model (a
-        # model without full_sort_topk included: its scores go through the selection in chunks, not as one [U, N] matrix)
-        wide = (self.eval_route == 'topk' and self.fused_topk and FUSED_TOPK_MAX < kmax <= WIDE_TOPK_MAX
+            # (with ``stats``: gauc is asked too -- the rank route answers the accuracy metrics and gauc, one list call per batch feeds stats)
+            lists = (lambda *batch: self._count_lists(stats, fused, wide, kmax, *batch)) if stats is not None else None
+            result, n_users = self._evaluate_batches_by_rank(eval_data, kmax, names, lists)
+        else:
+            hits, pos_len = [], []
+            for interaction, history_index, positive_u, positive_i in eval_data:
+                interaction = interaction.to(self.device)
+                n_user = len(interaction)
+                if fused or wide:
+                    h, npos = self._topk_hits(interaction, n_user, history_index, positive_u, positive_i, kmax, wide=wide, stats=stats)
+                    hits.append(h); pos_len.append(npos)
+                    continue
+                scores = self._masked_scores(interaction, n_user, history_index)
+                topk_vals, topk_idx = torch.topk(scores, kmax, dim=-1)
+                if stats is not None:
+                    stats.add(topk_idx, topk_vals)                 # (a masked entry comes back with value -inf: a pad)
+                pos = torch.zeros_like(scores, dtype=torch.bool)
+                pos[positive_u, positive_i] = True
+                hits.append(torch.gather(pos, 1, topk_idx).float())
+                pos_len.append(pos.sum(1).float())
+            hits = torch.cat(hits)
+            result, n_users = metrics_from_hits(hits, torch.cat(pos_len).clamp(min=1), self.topk, names), hits.shape[0]
+        if stats is not None:
+            result.update(stats.result(n_users, self.list_metrics))
+        return result
+
+    def _masked_scores(self, interaction, n_user, history_index):
+        """The [U, N] matrix of the unfused route, PAD column and history at -inf."""
+        try:
+            scores = self.model.full_sort_predict(interaction).view(n_user, -1)
+        except NotImplementedError:
+            scores = self._predict_all_pairs(interaction, n_user)
+        scores[:, 0] = -np.inf
+        if history_index is not None:
+            scores[history_index] = -np.inf
+        return scores
+
+    def _takes_wide_lists(self, kmax):
+        """Lists beyond the fused kernels' 64 entries -- eval_route='topk', or a non-accuracy metric under 'auto': on a GPU they come from
+        the wide mask + top-k, for every model (a model without full_sort_topk included: its scores go through the selection in chunks,
+        not as one [U, N] matrix)."""
+        return ((self.eval_route == 'topk' or bool(self.list_metrics)) and self.fused_topk and FUSED_TOPK_MAX < kmax <= WIDE_TOPK_MAX
                 and torch.device(self.device).type == 'cuda' and hasattr(self.model, 'full_sort_topk_wide'))
-        hits, pos_len = [], []
-        for interaction, history_index, positive_u, positive_i in eval_data:
-            interaction = interaction.to(self.device)
-            n_user = len(interaction)
-            if fused or wide:
-                h, npos = self._topk_hits(interaction, n_user, history_index, positive_u, positive_i, kmax, wide=wide)
-                hits.append(h); pos_len.append(npos)
-                continue
-            try:
-                scores = self.model.full_sort_predict(interaction).view(n_user, -1)
-            except NotImplementedError:
-                scores = self._predict_all_pairs(interaction, n_user)
-            scores[:, 0] = -np.inf
-            if history_index is not None:
-                scores[history_index] = -np.inf
-            _, topk_idx = torch.topk(scores, kmax, dim=-1)
-            pos = torch.zeros_like(scores, dtype=torch.bool)
-            pos[positive_u, positive_i] = True
-            hits.append(torch.gather(pos, 1, topk_idx).float())
-            pos_len.append(pos.sum(1).float())
-        return metrics_from_hits(torch.cat(hits), torch.cat(pos_len).clamp(min=1), self.topk, names)
+
+    def _count_lists(self, stats, fused, wide, kmax, interaction, n_user, history_index):
+        """One batch's lists by the list route (fused, wide, or torch.topk of the masked matrix where the route is unfused), into ``stats``."""
+        if wide or (fused and kmax <= FUSED_TOPK_MAX):
+            return stats.add(self._topk_lists(interaction, n_user, history_index, kmax, wide=wide))
+        vals, idx = torch.topk(self._masked_scores(interaction, n_user, history_index), kmax, dim=-1)
+        stats.add(idx, vals)
 
     def _takes_rank_route(self, fused, kmax):
         gauc = self.metrics is not None and 'gauc' in self.metrics
+        if self.list_metrics:
+            return gauc                       # the list route answers everything but gauc (k <= 1024: checked at construction)
         if self.eval_route == 'rank':
             return True
         if self.eval_route == 'topk':
@@ -915,16 +1004,21 @@ class Trainer:
                              f'in the user\'s history) or has a NaN score: the rank route does not rank such a positive')
         return prow, gt, eq, eqb, nun, npos
 
-    def _evaluate_batches_by_rank(self, eval_data, kmax, names):
+    def _evaluate_batches_by_rank(self, eval_data, kmax, names, lists=None):
         """Every metric from the rank of each positive over the masked catalogue: a positive at top-k position r = 1 + gt + eq_before
         (ties to the smaller column) is a hit at position r of the list for every k >= r -- the same hit matrix the top-k route builds,
-        for any kmax; GAUC from the average ranks gt + (eq + 1) / 2."""
+        for any kmax; GAUC from the average ranks gt + (eq + 1) / 2.  ``lists(interaction, n_user, history_index)`` is called once per
+        batch when a non-accuracy metric rides along.  Returns (result, evaluated users)."""
         acc = ([], [], [], [])
+        n_users = 0
         for interaction, history_index, positive_u, positive_i in eval_data:
             interaction = interaction.to(self.device)
             n_user = len(interaction)
+            n_users += n_user
             self._rank_batch_tail(acc, n_user, kmax, *self._rank_counts(interaction, n_user, history_index, positive_u, positive_i))
-        return self._rank_result(acc, names)
+            if lists is not None:
+                lists(interaction, n_user, history_index)
+        return self._rank_result(acc, names), n_users
 
     @staticmethod
     def _rank_batch_tail(acc, n_user, kmax, prow, gt, eq, eqb, nun, npos):
