@@ -400,7 +400,7 @@ def eval_loader_for(config, domain, dataset, uid_field, iid_field, eval_pairs, h
                     resample=True, item_counts=None):
     """The evaluation loader of one domain, as recbole_cdr/data/utils.py:131-153 (``get_dataloader``) picks it: ``domain='source'`` is
     always the full-sort loader with ``revoke``; ``domain='target'`` is the loader of ``config['eval_args']['mode']``
-    (``trainer.resolve_eval_mode``): ``FullSortEvalLoader``, or for uniN / popN a ``NegSampleEvalLoader`` over a ``DeviceNegSampler`` of
+    (``eval_config.resolve_eval_mode``): ``FullSortEvalLoader``, or for uniN / popN a ``NegSampleEvalLoader`` over a ``DeviceNegSampler`` of
     that distribution whose used pairs are history + evaluated pairs.  ``history_pairs``: the (user, item) pairs an evaluated user must
     not be recommended (train, and valid when testing).  ``item_counts`` (``data.train_item_counts`` over the loader's column space)
     becomes the loader's ``item_counts`` attribute: the counts the trainer's non-accuracy metrics use for this loader, ahead of
@@ -413,7 +413,7 @@ def eval_loader_for(config, domain, dataset, uid_field, iid_field, eval_pairs, h
 
 def _eval_loader_for(config, domain, dataset, uid_field, iid_field, eval_pairs, history_pairs, device, users_per_batch, seed, resample):
     import numpy as np
-    from ..trainer.trainer import resolve_eval_mode
+    from ..eval_config import resolve_eval_mode
     batch = int(config['eval_batch_size']) if 'eval_batch_size' in config else 4096
     OI, TOI = dataset.num_overlap_item, dataset.num_target_only_item
     if domain == 'source':

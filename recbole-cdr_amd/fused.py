@@ -285,7 +285,7 @@ class _Step:
 
     def _dense_optimizer(self, params):
         """The dense optimizer of the step's own learner for its small parameters (None: plain SGD, done in torch by the caller)."""
-        from .trainer.trainer import DenseAdam, DenseAdagrad
+        from .optim import DenseAdam, DenseAdagrad
         if self.opt == OPT_ADAM:
             return DenseAdam(params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.wd)
         if self.opt == OPT_ADAGRAD:

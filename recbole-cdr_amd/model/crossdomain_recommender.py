@@ -81,6 +81,28 @@ class CrossDomainRecommender(nn.Module):
     # [U, N] floats one ``rank_rows`` pass may hold when the scores are not a contraction (64 M = 256 MB: the staging of the native passes)
     RANK_ROWS_MAX_SCORES = 64 << 20
 
+    def _score_chunks(self, interaction, predict_fallback):
+        """Yields ``(s, e, scores [e - s, N])`` over blocks of users that tile [0, len(interaction)) in order: ``full_sort_predict`` --
+        ``predict_fallback(part, e - s)`` where that raises NotImplementedError -- of all users at once first, and of chunks of at most
+        ``RANK_ROWS_MAX_SCORES`` scores when that first block turns out too tall."""
+        n_user = len(interaction)
+        step = None
+        s = 0
+        while s < n_user:
+            e = n_user if step is None else min(s + step, n_user)
+            part = interaction if (s, e) == (0, n_user) else interaction[s:e]
+            try:
+                scores = self.full_sort_predict(part).view(e - s, -1)
+            except NotImplementedError:
+                if predict_fallback is None:
+                    raise
+                scores = predict_fallback(part, e - s)
+            if step is None and n_user * scores.shape[1] > self.RANK_ROWS_MAX_SCORES and n_user > 1:
+                step = max(self.RANK_ROWS_MAX_SCORES // scores.shape[1], 1)      # (this first block was too tall: redo it in chunks)
+                continue
+            yield s, e, scores
+            s = e
+
     @torch.no_grad()
     def full_sort_rank(self, interaction, pos_indptr, pos_cols, hist_indptr=None, hist_cols=None, predict_fallback=None):
         """``(pos_score [P], gt, eq, eq_before [P] int32, n_unmasked [U] int32)`` of the ground-truth positives (a CSR over the
@@ -97,27 +119,13 @@ class CrossDomainRecommender(nn.Module):
         score = torch.empty(P, device=dev, dtype=torch.float32)
         out = tuple(torch.empty(n, device=dev, dtype=torch.int32) for n in (P, P, P, n_user))
         counts = (pos_indptr[1:] - pos_indptr[:-1])
-        step = None
-        s = 0
-        while s < n_user:
-            e = n_user if step is None else min(s + step, n_user)
-            part = interaction if (s, e) == (0, n_user) else interaction[s:e]
-            try:
-                scores = self.full_sort_predict(part).view(e - s, -1)
-            except NotImplementedError:
-                if predict_fallback is None:
-                    raise
-                scores = predict_fallback(part, e - s)
-            if step is None and n_user * scores.shape[1] > self.RANK_ROWS_MAX_SCORES and n_user > 1:
-                step = max(self.RANK_ROWS_MAX_SCORES // scores.shape[1], 1)      # (this first block was too tall: redo it in chunks)
-                continue
+        for s, e, scores in self._score_chunks(interaction, predict_fallback):
             scores = scores.float().contiguous()
             p0, p1 = (int(pos_indptr[s]), int(pos_indptr[e])) if (s, e) != (0, n_user) else (0, P)
             rows = torch.repeat_interleave(torch.arange(e - s, device=dev), counts[s:e])
             score[p0:p1] = scores[rows, pos_cols[p0:p1]]
             F_.rank_rows(scores, pos_indptr[s:e + 1].contiguous(), pos_cols, hist_indptr[s:e + 1].contiguous() if hist_indptr is not None
                          else None, hist_cols, pos_score=score, out=(out[0], out[1], out[2], out[3][s:e]))
-            s = e
         return (score,) + out
 
     @torch.no_grad()
@@ -133,25 +141,11 @@ class CrossDomainRecommender(nn.Module):
         self._one_gpu_only('full_sort_topk_wide')
         n_user = len(interaction)
         vals = idx = None
-        step = None
-        s = 0
-        while s < n_user:
-            e = n_user if step is None else min(s + step, n_user)
-            part = interaction if (s, e) == (0, n_user) else interaction[s:e]
-            try:
-                scores = self.full_sort_predict(part).view(e - s, -1)
-            except NotImplementedError:
-                if predict_fallback is None:
-                    raise
-                scores = predict_fallback(part, e - s)
-            if step is None and n_user * scores.shape[1] > self.RANK_ROWS_MAX_SCORES and n_user > 1:
-                step = max(self.RANK_ROWS_MAX_SCORES // scores.shape[1], 1)      # (this first block was too tall: redo it in chunks)
-                continue
+        for s, e, scores in self._score_chunks(interaction, predict_fallback):
             if vals is None:
                 vals, idx = F_._wide_outputs(scores.device, n_user, int(k))
             F_.topk_rows(scores.float().contiguous(), k, hist_indptr[s:e + 1].contiguous() if hist_indptr is not None else None, hist_cols,
                          out=(vals[s:e], idx[s:e]))
-            s = e
         return vals, idx
 
     def _one_gpu_only(self, what):

@@ -124,7 +124,7 @@ def parent_arms(N):
     from oracle.common import IdSpace
     from recbole_cdr_amd.data.interaction import Interaction
     from recbole_cdr_amd.model.cross_domain_recommender.natr import NATR
-    from recbole_cdr_amd.trainer.trainer import Trainer
+    from recbole_cdr_amd.trainer.evaluation import Evaluation
     U, D, L = 64, 64, 50
     for mode, ids in (('overlap_items', IdSpace(OU=1, TOU=99, SOU=22, OI=N // 2, TOI=N - N // 2, SOI=16)),
                       ('overlap_users', IdSpace(OU=40, TOU=60, SOU=35, OI=1, TOI=N - 1, SOI=70))):
@@ -144,7 +144,7 @@ def parent_arms(N):
         inter = Interaction({'target_user_id': torch.arange(1, U + 1, device=dev)})
         cols = torch.sort(torch.randint(1, N, (U, H), device=dev), dim=1).values.reshape(-1)
         indptr = torch.arange(0, U * H + 1, H, device=dev, dtype=torch.int64)
-        chunked = lambda n: Trainer(base_config(dev, eval_batch_size=n, graph_step=False, topk=[K], **kw), model)._predict_all_pairs(inter, U)
+        chunked = lambda n: Evaluation(base_config(dev, eval_batch_size=n, topk=[K], **kw), model)._predict_all_pairs(inter, U)
         arms = {'predict chunks of 4,096': lambda: chunked(4096), 'predict chunks of 1 << 20': lambda: chunked(1 << 20),
                 'full_sort_predict': lambda: model.full_sort_predict(inter),
                 'full_sort_topk (fused)': lambda: model.full_sort_topk(inter, K, hist_indptr=indptr, hist_cols=cols)}
